@@ -337,6 +337,35 @@ def emit_line(out):
     os.open(os.devnull, os.O_WRONLY)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write every array of `arrays` ({name: ndarray}) as out_dir/<name>.npy in float32 (the planes are u8,
+    so the values are exact), all files together within `budget` bytes.  An array larger than its share is written as a
+    fixed sample, flattened: the flat array cut into n equal blocks, one element per block at an offset drawn from a
+    generator of seed 0 -- the same elements in every run with the same arguments.  Returns what was written, for the line."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = (budget - 4096 * len(arrays)) // max(1, len(arrays))        # (4 KiB per file for the .npy header)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        rec = {"file": f"{name}.npy", "shape": list(a.shape), "source_dtype": str(a.dtype)}
+        n_max = share // 4
+        if a.size > n_max:
+            flat = a.reshape(-1)
+            block = -(-flat.size // n_max)
+            n = flat.size // block
+            idx = np.arange(n, dtype=np.int64) * block + np.random.default_rng(0).integers(0, block, n)
+            a = flat[idx]
+            rec["sample"] = f"{n} of {flat.size} elements: one per block of {block} of the flattened array, offsets seeded (0)"
+        np.save(d / rec["file"], a.astype(np.float32))
+        written[name] = rec
+    return written
+
+
 
 def parse_args():
     ap = argparse.ArgumentParser()
@@ -418,7 +447,14 @@ def parse_args():
     ap.add_argument("--hang-stripe-rank", type=int, default=-1, help=argparse.SUPPRESS)    # test hook: this rank never enters the stripe leg (its watchdog's test)
     ap.add_argument("--shared-gpu", action="store_true",
                     help="smoke-test aid: every rank uses GPU 0 (1-GPU box, use with --backend gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/output.npy (float32, "
+                         "all ranks' planes in rank order; a fixed, seeded sample when it exceeds 64 MB).  The inputs are the "
+                         "same in every run with the same arguments, so two builds can be compared output for output.")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def worker(args):
@@ -687,6 +723,21 @@ def worker(args):
             parts = [torch.zeros_like(t) for _ in range(world)]
             dist.all_gather(parts, t)
             crcs = [int(v) for p in parts for v in p]
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path received from its last step: one rank's planes (the stitched plane of a striped
+        # run), or every rank's in rank order -- the same array as one rank with --frames F x N
+        if dist is not None and stripe:
+            full = plane[None]
+        elif dist is not None:
+            t = torch.from_numpy(np.ascontiguousarray(res))
+            parts = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(parts, t)
+            full = torch.cat(parts).numpy()
+        else:
+            full = res
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"output": full})
 
     # The OTHER half of the metric ("MPix/s AND ms/image at 1/2/4/8"): ms per image at N > 1 is ONE plane row-striped over the
     # ranks (BASELINE configs[3]).  The driver's one command per N is the frames workload above; this leg rides on it, after
@@ -767,6 +818,8 @@ def worker(args):
                                    "H2D + kernel + D2H of neighbouring frames overlapped on two lanes" if F > 1 else ": row bands")}
         if pmc_ref:
             out["pmc_reference"] = pmc_ref
+        if dumped:
+            out["dumped_outputs"] = dumped
         if world > 1:
             out["degraded"] = bool(degraded)
             out["distributed"] = {"control_plane": "gloo", "rccl_world": rccl_world,
@@ -1089,8 +1142,11 @@ def worker_cxx(args):
     if stripe:
         res = np.concatenate([t.cpu().numpy() for t in d_out], axis=0)
         crcs = [zlib.crc32(res.tobytes())]
+        res = res[None]
     else:
-        crcs = [zlib.crc32(np.ascontiguousarray(t[f].cpu().numpy()).tobytes()) for t in d_out for f in range(F)]
+        res = np.concatenate([t.cpu().numpy() for t in d_out], axis=0)
+        crcs = [zlib.crc32(np.ascontiguousarray(res[k]).tobytes()) for k in range(res.shape[0])]
+    dumped = dump_outputs(args.dump_outputs, {"output": res}) if args.dump_outputs else None
     pix_per_step = W * H if stripe else W * H * F * n
     rows0 = (S.stripe_rows(H, n, 0)[1] - S.stripe_rows(H, n, 0)[0]) if stripe else H * F
     achieved = S.FLOP_PER_PIXEL * W * rows0 / (kern[0] * 1e-3) / 1e12
@@ -1123,6 +1179,8 @@ def worker_cxx(args):
         # a link refused peer access: the rows crossed host memory -- not the configs[3] transport; say so like the Python path
         out["degraded"] = True
         out["degraded_why"] = "; ".join(sorted({c._lib.srcnn_last_error(c._h).decode() for c in ctxs if c.halo_transport() == 3}))
+    if dumped:
+        out["dumped_outputs"] = dumped
     emit_line(out)
     for c in ctxs:
         c.close()
