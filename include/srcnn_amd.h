@@ -204,6 +204,34 @@ int srcnn_set_weights(srcnn_ctx *ctx,
                       const float *kernel11, const float *bias11,
                       const float *kernel55, float bias55);
 
+/* The 9-3-5 and 9-5-5 SRCNN models (Dong et al., TPAMI 2016): the same layers 1 and 3 (f1 = 9, n1 = 64, n2 = 32, f3 = 5) with
+ * an f2 x f2 layer 2, f2 = 1, 3 or 5.
+ *   kernel2 [32][64][f2][f2] (out, in, kh, kw: PyTorch's conv2.weight; for f2 = 1 the reference's kernel11), bias2 [32];
+ *   the other tables as in srcnn_set_weights.  Blob form: b1 | W1 | b2 | W2 | b3 | W3 with W2 holding 2048 f2^2 floats
+ *   (8,129 / 24,513 / 57,281 floats).
+ * Semantics: cross-correlation like torch.nn.functional.conv2d; ReLU after layers 1 and 2; EVERY layer replicate-pads its
+ * own input (layer 2 pads the 64-channel layer-1 map by (f2 - 1) / 2), so an output pixel sees a radius of 6 + (f2 - 1) / 2.
+ * f2 = 1 is srcnn_set_weights, bit for bit in every mode.  For f2 > 1:
+ *   - only SRCNN_MODE_MFMA has arithmetic (float32 v_mfma_f32_32x32x2_f32; summation order in srcnn_spatial_kernels.hip): in any other
+ *     mode the whole-path calls return SRCNN_ERR_STATE and srcnn_last_error() says why;
+ *   - srcnn_forward_y, srcnn_forward_y_dev (any n_frames, frame pitches, d_preclamp), srcnn_forward_y_frames,
+ *     srcnn_process_bgr and srcnn_process_bgr_dev run the model;
+ *   - row stripes (srcnn_forward_y_rows_dev), halo buffers (_rows_halo_dev), the several-GPU calls (striped, lanes, multi),
+ *     srcnn_forward_y_unfused_dev, srcnn_conv99x11_dev and srcnn_conv55_dev return SRCNN_ERR_STATE: they run the 9-1-5 path;
+ *   - a per-filter call that loads weights (srcnn_conv99x11, srcnn_conv55 and their _to_dev / _from_dev forms) ENDS the model:
+ *     the context is back on the 9-1-5 tables holding only the layers loaded from then on, srcnn_get_model_f2() returns 1,
+ *     and the next whole-path call returns SRCNN_ERR_STATE until a full model is loaded again.  srcnn_conv99 / srcnn_conv11
+ *     take their own weights and leave the model as it is;
+ *   - workspace: the context keeps the 64- and 32-channel maps of one row band (384 B per pixel), bands sized so that the
+ *     two stay within 512 MiB (at least 16 rows per band); each band recomputes the 2 + (f2 - 1) / 2 rows it shares with
+ *     its neighbours. */
+int srcnn_set_model(srcnn_ctx *ctx, int f2,
+                    const float *kernel99, const float *bias99,
+                    const float *kernel2, const float *bias2,
+                    const float *kernel55, float bias55);
+/* f2 of the loaded model: 1 after srcnn_set_weights (which always puts the context back on the 9-1-5 path), 3 or 5. */
+int srcnn_get_model_f2(const srcnn_ctx *ctx);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

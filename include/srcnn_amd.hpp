@@ -102,6 +102,14 @@ public:
     int kernel_variant() const { return srcnn_kernel_variant(get()); }
     // A cautious deployment pins the hazard-safe kernels (same bytes, ~3 % slower): srcnn_set_kernel_variant
     void pin_safe_kernels(bool on = true) { check(srcnn_set_kernel_variant(get(), on ? 1 : 0)); }
+    // A 9-1-5, 9-3-5 or 9-5-5 model (srcnn_set_model): kernel2 is [32][64][f2][f2] (PyTorch's conv2.weight), f2 = 1, 3 or 5.
+    // f2 > 1 runs in SRCNN_MODE_MFMA through srcnn_forward_y* and srcnn_process_bgr*; model_f2() is the loaded model's f2.
+    void set_model(int f2, const float kernel99[64][9][9], const float bias99[64], const float *kernel2, const float bias2[32],
+                   const float kernel55[32][5][5], float bias55)
+    {
+        check(srcnn_set_model(get(), f2, &kernel99[0][0][0], bias99, kernel2, bias2, &kernel55[0][0][0], bias55));
+    }
+    int model_f2() const { return srcnn_get_model_f2(get()); }
 
 private:
     struct Handle {

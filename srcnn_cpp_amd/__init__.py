@@ -27,6 +27,7 @@ import numpy as np
 
 __all__ = [
     "Context", "SrcnnError", "forward_y_striped_frames", "load_library", "library_path", "tuning_library_path", "use_library", "load_weights", "split_weights",
+    "load_model", "split_model", "model_from_state_dict", "MODEL_SIZES",
     "Convolution99", "Convolution11", "Convolution55", "Convolution99x11", "default_context",
     "MODE_MFMA", "MODE_EXACT", "MODE_SPLIT16", "MODE_REFBYTES", "MODE_REFBYTES16", "FLOP_PER_PIXEL",
     "ERR_INVALID", "ERR_HIP", "ERR_NOMEM", "ERR_NODEVICE", "ERR_STATE",
@@ -43,6 +44,8 @@ MODE_SPLIT16 = 2
 MODE_REFBYTES = 3          # float32 MFMA + exact fix-up of the pixels next to a truncation boundary: the reference's bytes
 MODE_REFBYTES16 = 4        # opt-in: the same behind the split-f16 kernel
 N_WEIGHTS = 8129
+# blob sizes of the 9-f2-5 models (srcnn_set_model): b1|W1|b2|W2|b3|W3 with W2 holding 2048 * f2^2 floats
+MODEL_SIZES = {8129: 1, 24513: 3, 57281: 5}
 # 2 x (64*81 + 32*64 + 32*25) MAC per output pixel
 FLOP_PER_PIXEL = 16064
 
@@ -114,6 +117,8 @@ def load_library() -> C.CDLL:
         "srcnn_conv55": ([vp, _f32pp, sz, _u8p, sz, i, i, _f32p, C.c_float], i),
         "srcnn_conv99x11": ([vp, _u8p, sz, _f32pp, sz, i, i, _f32p, _f32p, _f32p, _f32p], i),
         "srcnn_set_weights": ([vp, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float], i),
+        "srcnn_set_model": ([vp, i, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float], i),
+        "srcnn_get_model_f2": ([vp], i),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_y_frames": ([vp, C.POINTER(_u8p), sz, C.POINTER(_u8p), sz, i, i, i], i),
         "srcnn_forward_y_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
@@ -172,6 +177,7 @@ ABI_SYMBOLS = (
     "srcnn_dev_download", "srcnn_dev_upload", "srcnn_ipc_export", "srcnn_ipc_open", "srcnn_ipc_close", "srcnn_query_plan", "srcnn_fixup_stats", "srcnn_set_fixup_strict", "srcnn_set_fixup_margin", "srcnn_set_fixup_local", "srcnn_fixup_local_stats", "srcnn_set_seam_deferral", "srcnn_flush", "srcnn_scaled_size", "srcnn_bgr2ycrcb", "srcnn_ycrcb2bgr",
     "srcnn_resize_cubic", "srcnn_process_bgr", "srcnn_process_bgr_dev",
     "srcnn_stripe_rows", "srcnn_forward_y_frames_multi", "srcnn_forward_y_lanes_dev", "srcnn_forward_y_striped", "srcnn_forward_y_striped_frames", "srcnn_forward_y_striped_dev",
+    "srcnn_set_model", "srcnn_get_model_f2",
 )
 
 
@@ -189,6 +195,59 @@ def split_weights(blob: np.ndarray):
     blob = np.ascontiguousarray(blob, dtype=np.float32)
     return (blob[64:5248].reshape(64, 9, 9), blob[0:64], blob[5280:7328].reshape(32, 64),
             blob[5248:5280], blob[7329:8129].reshape(32, 5, 5), float(blob[7328]))
+
+
+def split_model(blob: np.ndarray):
+    """A 9-1-5, 9-3-5 or 9-5-5 blob (8,129 / 24,513 / 57,281 floats, b1|W1|b2|W2|b3|W3) ->
+    (w1[64,9,9], b1[64], w2, b2[32], w3[32,5,5], b3) with w2 [32,64] for f2 = 1, else [32,64,f2,f2]."""
+    blob = np.ascontiguousarray(blob, dtype=np.float32).ravel()
+    f2 = MODEL_SIZES.get(blob.size)
+    if f2 is None:
+        raise ValueError(f"model blob has {blob.size} floats, expected one of {sorted(MODEL_SIZES)}")
+    if f2 == 1:
+        return split_weights(blob)
+    n2 = 2048 * f2 * f2
+    o3 = 5280 + n2
+    return (blob[64:5248].reshape(64, 9, 9), blob[0:64], blob[5280:o3].reshape(32, 64, f2, f2),
+            blob[5248:5280], blob[o3 + 1:o3 + 801].reshape(32, 5, 5), float(blob[o3]))
+
+
+def load_model(path) -> np.ndarray:
+    """A 9-1-5, 9-3-5 or 9-5-5 model blob from a file (float32 little-endian, b1|W1|b2|W2|b3|W3)."""
+    blob = np.fromfile(str(path), dtype="<f4")
+    if blob.size not in MODEL_SIZES:
+        raise ValueError(f"model blob has {blob.size} floats, expected one of {sorted(MODEL_SIZES)}")
+    return blob
+
+
+def model_from_state_dict(sd, input_scale: float = 255.0):
+    """A PyTorch SRCNN state dict -> (w1, b1, w2, b2, w3, b3) for Context.set_model.
+
+    Reads conv1.weight (64,1,9,9), conv1.bias, conv2.weight (32,64,f2,f2) with f2 = 1, 3 or 5, conv2.bias,
+    conv3.weight (1,32,5,5) and conv3.bias.  The library runs on 0..255 luma; a model trained on [0, 1] inputs
+    (input_scale = 255, the default) gets its three biases multiplied by input_scale, which maps it exactly onto
+    0..255 because ReLU is positively homogeneous (pass 1.0 for a model trained on 0..255).
+
+    The library replicate-pads the input of every layer.  Models trained with zero padding (nn.Conv2d's
+    padding=...) or without padding give different values near the image borders (within 6 + (f2 - 1) / 2 pixels).
+    """
+    def arr(key, shape=None):
+        if key not in sd:
+            raise KeyError(f"state dict has no {key!r}")
+        v = sd[key]
+        v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        v = np.asarray(v, dtype=np.float64)
+        if shape is not None and v.shape != shape:
+            raise ValueError(f"{key}: shape {v.shape}, expected {shape}")
+        return v
+    w2 = arr("conv2.weight")
+    if w2.ndim != 4 or w2.shape[:2] != (32, 64) or w2.shape[2] != w2.shape[3] or w2.shape[2] not in (1, 3, 5):
+        raise ValueError(f"conv2.weight: shape {w2.shape}, expected (32, 64, f2, f2) with f2 in 1, 3, 5")
+    s = float(input_scale)
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    return (f32(arr("conv1.weight", (64, 1, 9, 9)).reshape(64, 9, 9)), f32(arr("conv1.bias", (64,)) * s),
+            f32(w2 if w2.shape[2] > 1 else w2.reshape(32, 64)), f32(arr("conv2.bias", (32,)) * s),
+            f32(arr("conv3.weight", (1, 32, 5, 5)).reshape(32, 5, 5)), float(arr("conv3.bias", (1,))[0] * s))
 
 
 def _plane(a, dtype, name, writable=False):
@@ -292,6 +351,27 @@ class Context:
 
     def set_weights_blob(self, blob):
         self.set_weights(*split_weights(blob))
+
+    def set_model(self, w1, b1, w2, b2, w3, b3):
+        """A 9-1-5, 9-3-5 or 9-5-5 model (srcnn_set_model): f2 from w2's shape, (32, 64) or (32, 64, f2, f2)."""
+        shape = tuple(np.shape(w2))
+        if shape == (32, 64):
+            f2 = 1
+        elif len(shape) == 4 and shape[:2] == (32, 64) and shape[2] == shape[3] and shape[2] in (1, 3, 5):
+            f2 = shape[2]
+        else:
+            raise ValueError(f"kernel2: shape {shape}, expected (32, 64) or (32, 64, f2, f2) with f2 in 1, 3, 5")
+        w1, b1 = _wt(w1, 5184, "kernel99"), _wt(b1, 64, "bias99")
+        w2, b2 = _wt(w2, 2048 * f2 * f2, "kernel2"), _wt(b2, 32, "bias2")
+        w3 = _wt(w3, 800, "kernel55")
+        self._check(self._lib.srcnn_set_model(self._h, f2, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(w3), float(b3)))
+
+    def set_model_blob(self, blob):
+        self.set_model(*split_model(blob))
+
+    def model_f2(self) -> int:
+        """f2 of the loaded model: 1 (9-1-5, also after set_weights), 3 or 5."""
+        return int(self._lib.srcnn_get_model_f2(self._h))
 
     def query_plan(self, width, height, n_frames=1):
         out = (C.c_int * 6)()

@@ -47,14 +47,18 @@ UNITS = [
     # the resize's vertical pass is OpenCV's float32 multiply-then-add (every product and sum rounded on its own):
     # __fmul_rn / __fadd_rn are plain * and + in HIP's headers, so contraction must be off here too
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # layers 1-2 of the 9-3-5 / 9-5-5 models (srcnn_set_model)
+    ("srcnn_spatial_kernels.hip", []),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),
     ("srcnn_launch.cpp", ["-x", "hip"]),
     ("srcnn_host.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_table(): OpenCV's float arithmetic, nothing contracted
     ("srcnn_multi.cpp", ["-x", "hip"]),
+    ("srcnn_spatial.cpp", ["-x", "hip"]),
 ]
-HOST_UNITS = {"srcnn_api.cpp", "srcnn_model.cpp", "srcnn_plan.cpp", "srcnn_launch.cpp", "srcnn_host.cpp", "srcnn_multi.cpp"}
+HOST_UNITS = {"srcnn_api.cpp", "srcnn_model.cpp", "srcnn_plan.cpp", "srcnn_launch.cpp", "srcnn_host.cpp", "srcnn_multi.cpp",
+              "srcnn_spatial.cpp"}
 
 
 def kernel_sources_fingerprint() -> str:

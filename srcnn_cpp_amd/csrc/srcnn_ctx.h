@@ -169,6 +169,13 @@ struct srcnn_ctx {
     srcnn::host::DevBuf wfrag16; // split-f16 fragments (SRCNN_MODE_SPLIT16), S16_TABLE_BYTES
     bool split16_ok = false;   // the uploaded weights fit the f16 ranges of that mode (split16_range_ok)
     srcnn::host::DevBuf wraw;    // b1|W1|b2|W2|b3|W3 in convdata.h order (exact kernels)
+    // a 9-3-5 / 9-5-5 model (srcnn_set_model, srcnn_spatial.cpp): f2 > 1 runs layers 1-2 from sp_frag (spatial_table_floats())
+    // and layer 3 from wfrag / b3, which srcnn_set_model loads with W2 = 0; the two maps of one row band, and the event behind
+    // the last launch that used them (so that launches on another stream -- the frame lanes -- wait before reusing them)
+    int f2 = 1;
+    srcnn::host::DevBuf sp_frag, sp_map64, sp_map32;
+    hipEvent_t sp_done = nullptr;
+    hipStream_t sp_stream = nullptr;
     // staging for the host-buffer entry points
     srcnn::host::DevBuf in_u8, out_u8, pre_f32, planes, plane1, kern, sink;
     // seam scratch (srcnn_kernels.h) is written by one launch and read by the seam kernel behind it: one buffer per
@@ -320,6 +327,16 @@ int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11);
 int use_layer3(srcnn_ctx *c, const float *kernel, float bias);
 inline bool has_model(const srcnn_ctx *c) { return c->has_l12 && c->has_l3; }
+void drop_spatial_model(srcnn_ctx *c);
+
+// the entry points that run the 9-1-5 path only (row stripes, halo buffers, several GPUs, unfused, per-layer device calls)
+int refuse_spatial(srcnn_ctx *c, const char *what);
+// The whole path of an f2 > 1 model on device planes (srcnn_forward_y_dev with srcnn_get_model_f2() > 1), defined in
+// srcnn_spatial.cpp, which sets this pointer when the library loads: the units above reach the spatial path only through it.
+using ForwardSpatialFn = int (*)(srcnn_ctx *c, const uint8_t *src, size_t src_stride, size_t src_frame_pitch, uint8_t *dst,
+                                 size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre);
+extern ForwardSpatialFn forward_spatial;
+constexpr size_t kSpatialWorkBytes = (size_t)512 << 20;     // bound of the two band maps (include/srcnn_amd.h, srcnn_set_model)
 extern const char *const kNoModel;
 
 // ---- srcnn_plan.cpp ----

@@ -251,6 +251,21 @@ hipError_t launch_conv55_exact(const float *planes, long stride, long pitch, lon
                                int w, int h, int n_frames, const float *d_kernel800, float bias,
                                hipStream_t st);
 
+// ---- layers 1-2 of the 9-3-5 / 9-5-5 models (srcnn_spatial_kernels.hip; srcnn_set_model) ----
+// Fragment table of a spatial model, floats: [SPATIAL_NFRAG_L1][64] layer 1 (fragment t * 41 + s, lane l: channel 32t + (l & 31),
+// tap 2s + (l >> 5), 81 = b1), then layer 2 [8 chunks][f2 * f2 taps][4 pairs][64] (lane l: output channel l & 31, input
+// channel 8 chunk + 2 pair + (l >> 5)), then b2 [32].  Unscaled: the maps hold the model's own values.
+constexpr int SPATIAL_NFRAG_L1 = 82;
+__host__ __device__ constexpr size_t spatial_table_floats(int f2) { return (size_t)SPATIAL_NFRAG_L1 * 64 + (size_t)f2 * f2 * 2048 + 32; }
+size_t spatial_l2_lds_bytes(int f2);
+// 64 planar maps (plane pitch mpitch, row stride W) of image rows [m0, m1)
+hipError_t launch_spatial_l1(const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag, float *map,
+                             long mpitch, hipStream_t st);
+// 32 planar maps (row stride W) of rows [o0, o1) from the 64 maps of rows [m0, m1) (which must hold rows o0 - r2 .. o1 + r2 - 1,
+// clamped to the image)
+hipError_t launch_spatial_l2(int f2, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                             const float *frag, const float *bias, float *out, long opitch, hipStream_t st);
+
 // ---- pipeline steps around the conv path (srcnn_pipeline.hip) ---------------
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);
 hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8_t *planes, long pstride,

@@ -240,8 +240,29 @@ const char *const kNoModel = "the model is not loaded: srcnn_set_weights not cal
 // The per-call tables of the reference surface (src/srcnn.cpp:609, :627: the same const arrays on every call).
 // Layers 1-2 of the model are replaced, layer 3 of any loaded model is kept (and the other way round for layer 3);
 // tables equal to the uploaded ones are not packed or uploaded again.
+ForwardSpatialFn forward_spatial = nullptr;
+
+int refuse_spatial(srcnn_ctx *c, const char *what)
+{
+    return fail(c, SRCNN_ERR_STATE, "%s runs the 9-1-5 model only: the context holds a 9-%d-5 model (srcnn_set_model); "
+                                    "use srcnn_forward_y_dev / srcnn_forward_y / srcnn_forward_y_frames / srcnn_process_bgr*",
+                what, c->f2);
+}
+
+// A per-filter call that loads weights under a 9-3-5 / 9-5-5 model ends that model (include/srcnn_amd.h, srcnn_set_model):
+// the context goes back to the 9-1-5 tables holding only the layers loaded from then on, so a whole-path call returns
+// SRCNN_ERR_STATE until srcnn_set_model / srcnn_set_weights (or the per-filter calls have loaded all three layers).
+void drop_spatial_model(srcnn_ctx *c)
+{
+    if (c->f2 == 1) return;
+    c->f2 = 1;
+    c->has_l12 = c->has_l3 = false;
+    std::fill(c->host_raw.begin(), c->host_raw.end(), 0.f);
+}
+
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11)
 {
+    drop_spatial_model(c);
     const float *hr = c->host_raw.data();
     const bool same = c->has_l12 && !std::memcmp(hr, bias99, 64 * 4) && !std::memcmp(hr + 64, kernel99, 5184 * 4) &&
                       !std::memcmp(hr + 5248, bias11, 32 * 4) && !std::memcmp(hr + 5280, kernel11, 2048 * 4);
@@ -253,6 +274,7 @@ int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const
 }
 int use_layer3(srcnn_ctx *c, const float *kernel, float bias)
 {
+    drop_spatial_model(c);
     const float *hr = c->host_raw.data();
     if (c->has_l3 && hr[7328] == bias && !std::memcmp(hr + 7329, kernel, 800 * 4)) return SRCNN_OK;
     const std::vector<float> raw(c->host_raw);               // upload_weights rewrites host_raw
@@ -273,6 +295,7 @@ int srcnn_set_weights(srcnn_ctx *c, const float *k99, const float *b99, const fl
     int rc = SRCNN_OK;
     (void)rc;
     if (!k99 || !b99 || !k11 || !b11 || !k55) return fail(c, SRCNN_ERR_INVALID, "null weight table");
+    c->f2 = 1;                  // back on the 9-1-5 path (srcnn_set_model)
     // a caller that passes its const tables on every call (the reference does, src/srcnn.cpp:609,627) packs and uploads once
     const float *hr = c->host_raw.data();
     if (c->has_l12 && c->has_l3 && hr[7328] == b55 && !std::memcmp(hr, b99, 64 * 4) && !std::memcmp(hr + 64, k99, 5184 * 4) &&

@@ -1,0 +1,86 @@
+"""Time the 9-3-5 and 9-5-5 models (srcnn_set_model) on one GPU: device-resident planes, HIP events around each call of
+srcnn_forward_y_dev on the context's stream, warm-up calls excluded.  Reports ms per plane, MPix/s and the fraction of the
+f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81 + 32*64*f2^2 + 32*25).
+
+    python tools/model_bench.py [--f2 3 5] [--sizes 3840x2160 1920x1080] [--steps 20] [--warmup 3] [--json out.json]
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch  # noqa: F401  -- before the HIP library: one HIP runtime for both
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import numpy as np  # noqa: E402
+
+import srcnn_cpp_amd as S  # noqa: E402
+from srcnn_cpp_amd.synth import synth_luma  # noqa: E402
+
+PEAK_TFLOPS = 157.3
+
+
+def flop_per_pixel(f2):
+    return 2 * (64 * 81 + 32 * 64 * f2 * f2 + 32 * 25)
+
+
+def model(f2, seed=0):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0, 0.03, (64, 9, 9)).astype(np.float32), rng.normal(0, 1, 64).astype(np.float32),
+            rng.normal(0, 0.08 / f2, (32, 64, f2, f2)).astype(np.float32), rng.normal(0, 1, 32).astype(np.float32),
+            rng.normal(0, 0.02, (32, 5, 5)).astype(np.float32), 60.0)
+
+
+def time_plane(ctx, w, h, steps, warmup):
+    d_src = torch.from_numpy(synth_luma(w, h)).cuda()
+    d_dst = torch.empty_like(d_src)
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    try:
+        for _ in range(warmup):
+            ctx.forward_y_dev(d_src.data_ptr(), w, 0, d_dst.data_ptr(), w, 0, w, h, 1)
+        ctx.synchronize()
+        ms = []
+        for _ in range(steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            ctx.forward_y_dev(d_src.data_ptr(), w, 0, d_dst.data_ptr(), w, 0, w, h, 1)
+            b.record(stream)
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+    finally:
+        ctx.set_stream(0)
+    return float(np.median(ms)), float(np.min(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--f2", type=int, nargs="+", default=[3, 5])
+    ap.add_argument("--sizes", nargs="+", default=["3840x2160", "1920x1080"])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    rows = []
+    with S.Context(0) as ctx:
+        for f2 in args.f2:
+            ctx.set_model(*model(f2))
+            for size in args.sizes:
+                w, h = map(int, size.split("x"))
+                med, best = time_plane(ctx, w, h, args.steps, args.warmup)
+                px = w * h
+                tflops = flop_per_pixel(f2) * px / (med * 1e-3) / 1e12
+                row = dict(model=f"9-{f2}-5", width=w, height=h, ms_per_plane=round(med, 3), ms_min=round(best, 3),
+                           mpix_per_s=round(px / (med * 1e-3) / 1e6, 1), flop_per_pixel=flop_per_pixel(f2),
+                           tflops=round(tflops, 2), fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps,
+                           warmup=args.warmup)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(json.dumps(rows, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -93,7 +93,7 @@ void help(const Options &o)
     std::printf("    _options_:\n\n");
     std::printf("        --scale=( ratio: 0.1 to .. ) : scaling by ratio.\n");
     std::printf("        --noverbose                  : turns off all verbose\n");
-    std::printf("        --weights=FILE               : 8129-float model blob (convdata.h order)\n");
+    std::printf("        --weights=FILE               : model blob, b1|W1|b2|W2|b3|W3: 8129 (9-1-5), 24513 (9-3-5) or 57281 (9-5-5) floats\n");
     std::printf("        --help                       : this help\n\n");
 }
 
@@ -114,13 +114,20 @@ bool load_weights(const Options &o, const char *argv0, std::vector<float> &blob)
     cand.push_back(dir + "/../srcnn_cpp_amd/data/srcnn915_weights.f32");
     cand.push_back(dir + "/srcnn915_weights.f32");
     cand.push_back("srcnn_cpp_amd/data/srcnn915_weights.f32");
+    // a 9-1-5, 9-3-5 or 9-5-5 blob (include/srcnn_amd.h, srcnn_set_model): 8,129 / 24,513 / 57,281 floats; a file of any other
+    // size named by --weights= is an error, not a reason to fall back on the shipped model
     for (const auto &p : cand) {
         FILE *f = std::fopen(p.c_str(), "rb");
         if (!f) continue;
-        blob.resize(8129);
-        const bool ok = std::fread(blob.data(), 4, 8129, f) == 8129;
+        std::vector<float> buf(57281 + 1);
+        const size_t n = std::fread(buf.data(), 4, buf.size(), f);
         std::fclose(f);
-        if (ok) return true;
+        if (n == 8129 || n == 24513 || n == 57281) {
+            buf.resize(n);
+            blob.swap(buf);
+            return true;
+        }
+        if (p == o.weights) return false;
     }
     return false;
 }
@@ -200,8 +207,9 @@ int main(int argc, char **argv)
         std::printf("- GPU failure : no usable gfx950 device (error %d); there is no CPU fallback\n", rc);
         return -1;
     }
-    const float *b1 = w.data(), *w1 = b1 + 64, *b2 = w1 + 5184, *w2 = b2 + 32, *w3 = w2 + 2048 + 1;
-    rc = srcnn_set_weights(ctx, w1, b1, w2, b2, w3, w[7328]);
+    const int f2 = w.size() == 8129 ? 1 : (w.size() == 24513 ? 3 : 5);
+    const float *b1 = w.data(), *w1 = b1 + 64, *b2 = w1 + 5184, *w2 = b2 + 32, *w3 = w2 + 2048 * f2 * f2 + 1;
+    rc = f2 == 1 ? srcnn_set_weights(ctx, w1, b1, w2, b2, w3, w3[-1]) : srcnn_set_model(ctx, f2, w1, b1, w2, b2, w3, w3[-1]);
     if (rc == SRCNN_OK && o.refbytes) rc = srcnn_set_mode(ctx, SRCNN_MODE_REFBYTES);
     ph.mark("srcnn_set_weights (pack + upload)");
     std::vector<unsigned char> out((size_t)ow * oh * 3);
