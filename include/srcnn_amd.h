@@ -210,7 +210,8 @@ int srcnn_set_weights(srcnn_ctx *ctx,
  *   the other tables as in srcnn_set_weights.  Blob form: b1 | W1 | b2 | W2 | b3 | W3 with W2 holding 2048 f2^2 floats
  *   (8,129 / 24,513 / 57,281 floats).
  * Semantics: cross-correlation like torch.nn.functional.conv2d; ReLU after layers 1 and 2; EVERY layer replicate-pads its
- * own input (layer 2 pads the 64-channel layer-1 map by (f2 - 1) / 2), so an output pixel sees a radius of 6 + (f2 - 1) / 2.
+ * own input (layer 2 pads the 64-channel layer-1 map by (f2 - 1) / 2; srcnn_set_padding selects zero padding instead), so an
+ * output pixel sees a radius of 6 + (f2 - 1) / 2.
  * f2 = 1 is srcnn_set_weights, bit for bit in every mode.  For f2 > 1:
  *   - only SRCNN_MODE_MFMA has arithmetic (float32 v_mfma_f32_32x32x2_f32; summation order in srcnn_spatial_kernels.hip): in any other
  *     mode the whole-path calls return SRCNN_ERR_STATE and srcnn_last_error() says why;
@@ -231,6 +232,23 @@ int srcnn_set_model(srcnn_ctx *ctx, int f2,
                     const float *kernel55, float bias55);
 /* f2 of the loaded model: 1 after srcnn_set_weights (which always puts the context back on the 9-1-5 path), 3 or 5. */
 int srcnn_get_model_f2(const srcnn_ctx *ctx);
+
+/* Padding of every layer's input, a setting of the CONTEXT (not of the model): it survives model loads and applies to whatever
+ * srcnn_set_weights / srcnn_set_model loaded, before or after the call.
+ *   SRCNN_PAD_REPLICATE (the default): every layer replicate-pads its own input, as the reference does.
+ *   SRCNN_PAD_ZERO: every layer zero-pads its own input -- torch.nn.functional.conv2d(x, w, b, padding=k // 2), i.e. a PyTorch
+ *     nn.Conv2d(..., padding=k // 2) with its default padding_mode "zeros": luma outside the image is 0, and so are the layer-1
+ *     and layer-2 maps outside it.  Rows inside the image are never padded, also where two row bands meet.  For f2 = 1, 3
+ *     and 5, in SRCNN_MODE_MFMA only, srcnn_forward_y, srcnn_forward_y_dev, srcnn_forward_y_frames and srcnn_process_bgr(_dev)
+ *     run the model on the banded path of srcnn_set_model (three launches per band, layer 3 by its own zero-padding kernel).
+ *     Every other mode, every other entry point (row stripes, halo buffers, the several-GPU calls, unfused,
+ *     srcnn_conv99x11_dev, srcnn_conv55_dev) and the per-filter calls (srcnn_conv99, _conv11, _conv55, _conv99x11 and their
+ *     _to_dev / _from_dev forms) return SRCNN_ERR_STATE, as do the whole-path calls when the loaded layers came from per-filter
+ *     calls; the context stays usable.
+ * srcnn_set_padding returns SRCNN_ERR_INVALID for any other value; srcnn_get_padding returns the setting. */
+enum { SRCNN_PAD_REPLICATE = 0, SRCNN_PAD_ZERO = 1 };
+int srcnn_set_padding(srcnn_ctx *ctx, int padding);
+int srcnn_get_padding(const srcnn_ctx *ctx);
 
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be

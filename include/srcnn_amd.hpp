@@ -110,6 +110,10 @@ public:
         check(srcnn_set_model(get(), f2, &kernel99[0][0][0], bias99, kernel2, bias2, &kernel55[0][0][0], bias55));
     }
     int model_f2() const { return srcnn_get_model_f2(get()); }
+    // SRCNN_PAD_REPLICATE (the default) or SRCNN_PAD_ZERO (srcnn_set_padding): zero padding matches a PyTorch model built with
+    // nn.Conv2d(..., padding=k // 2) and runs in SRCNN_MODE_MFMA through srcnn_forward_y* and srcnn_process_bgr*.
+    void set_padding(int padding) { check(srcnn_set_padding(get(), padding)); }
+    int padding() const { return srcnn_get_padding(get()); }
 
 private:
     struct Handle {

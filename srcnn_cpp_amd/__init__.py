@@ -27,7 +27,7 @@ import numpy as np
 
 __all__ = [
     "Context", "SrcnnError", "forward_y_striped_frames", "load_library", "library_path", "tuning_library_path", "use_library", "load_weights", "split_weights",
-    "load_model", "split_model", "model_from_state_dict", "MODEL_SIZES",
+    "load_model", "split_model", "model_from_state_dict", "model_from_module", "MODEL_SIZES", "PAD_REPLICATE", "PAD_ZERO",
     "Convolution99", "Convolution11", "Convolution55", "Convolution99x11", "default_context",
     "MODE_MFMA", "MODE_EXACT", "MODE_SPLIT16", "MODE_REFBYTES", "MODE_REFBYTES16", "FLOP_PER_PIXEL",
     "ERR_INVALID", "ERR_HIP", "ERR_NOMEM", "ERR_NODEVICE", "ERR_STATE",
@@ -46,6 +46,10 @@ MODE_REFBYTES16 = 4        # opt-in: the same behind the split-f16 kernel
 N_WEIGHTS = 8129
 # blob sizes of the 9-f2-5 models (srcnn_set_model): b1|W1|b2|W2|b3|W3 with W2 holding 2048 * f2^2 floats
 MODEL_SIZES = {8129: 1, 24513: 3, 57281: 5}
+# padding of every layer's input (srcnn_set_padding): replicate (the default, as the reference) or zero (PyTorch's nn.Conv2d default)
+PAD_REPLICATE = 0
+PAD_ZERO = 1
+_PADDINGS = {"replicate": PAD_REPLICATE, "zero": PAD_ZERO}
 # 2 x (64*81 + 32*64 + 32*25) MAC per output pixel
 FLOP_PER_PIXEL = 16064
 
@@ -119,6 +123,8 @@ def load_library() -> C.CDLL:
         "srcnn_set_weights": ([vp, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float], i),
         "srcnn_set_model": ([vp, i, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float], i),
         "srcnn_get_model_f2": ([vp], i),
+        "srcnn_set_padding": ([vp, i], i),
+        "srcnn_get_padding": ([vp], i),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_y_frames": ([vp, C.POINTER(_u8p), sz, C.POINTER(_u8p), sz, i, i, i], i),
         "srcnn_forward_y_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
@@ -177,7 +183,7 @@ ABI_SYMBOLS = (
     "srcnn_dev_download", "srcnn_dev_upload", "srcnn_ipc_export", "srcnn_ipc_open", "srcnn_ipc_close", "srcnn_query_plan", "srcnn_fixup_stats", "srcnn_set_fixup_strict", "srcnn_set_fixup_margin", "srcnn_set_fixup_local", "srcnn_fixup_local_stats", "srcnn_set_seam_deferral", "srcnn_flush", "srcnn_scaled_size", "srcnn_bgr2ycrcb", "srcnn_ycrcb2bgr",
     "srcnn_resize_cubic", "srcnn_process_bgr", "srcnn_process_bgr_dev",
     "srcnn_stripe_rows", "srcnn_forward_y_frames_multi", "srcnn_forward_y_lanes_dev", "srcnn_forward_y_striped", "srcnn_forward_y_striped_frames", "srcnn_forward_y_striped_dev",
-    "srcnn_set_model", "srcnn_get_model_f2",
+    "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
 )
 
 
@@ -228,8 +234,10 @@ def model_from_state_dict(sd, input_scale: float = 255.0):
     (input_scale = 255, the default) gets its three biases multiplied by input_scale, which maps it exactly onto
     0..255 because ReLU is positively homogeneous (pass 1.0 for a model trained on 0..255).
 
-    The library replicate-pads the input of every layer.  Models trained with zero padding (nn.Conv2d's
-    padding=...) or without padding give different values near the image borders (within 6 + (f2 - 1) / 2 pixels).
+    A state dict does not say how the layers pad their input.  A model built with nn.Conv2d(..., padding=k // 2) and the
+    default padding_mode "zeros" -- the usual PyTorch SRCNN -- needs Context.set_padding("zero"); "replicate" (the
+    context's default) is for models trained with padding_mode="replicate".  model_from_module reads the padding from an
+    nn.Module.
     """
     def arr(key, shape=None):
         if key not in sd:
@@ -248,6 +256,40 @@ def model_from_state_dict(sd, input_scale: float = 255.0):
     return (f32(arr("conv1.weight", (64, 1, 9, 9)).reshape(64, 9, 9)), f32(arr("conv1.bias", (64,)) * s),
             f32(w2 if w2.shape[2] > 1 else w2.reshape(32, 64)), f32(arr("conv2.bias", (32,)) * s),
             f32(arr("conv3.weight", (1, 32, 5, 5)).reshape(32, 5, 5)), float(arr("conv3.bias", (1,))[0] * s))
+
+
+def model_from_module(module, input_scale: float = 255.0):
+    """A PyTorch SRCNN nn.Module with conv1, conv2 and conv3 -> (model, padding) for Context.set_model and Context.set_padding.
+
+    model is model_from_state_dict(module.state_dict(), input_scale); padding is "zero" or "replicate", read from each conv's
+    padding and padding_mode.  Every layer must pad by k // 2 in one mode: ValueError for an unpadded layer (0 or "valid"),
+    for "reflect" or "circular", and for layers whose modes differ.
+    """
+    modes = set()
+    for name in ("conv1", "conv2", "conv3"):
+        conv = getattr(module, name, None)
+        if conv is None:
+            raise ValueError(f"module has no {name}")
+        k = tuple(conv.kernel_size)
+        pad = conv.padding
+        if isinstance(pad, str):
+            if pad == "valid":
+                raise ValueError(f"{name}: padding='valid' (unpadded layers are not supported)")
+            pad = tuple(kk // 2 for kk in k)          # "same" with an odd kernel
+        pad = tuple(pad) if isinstance(pad, (tuple, list)) else (pad, pad)
+        if pad != tuple(kk // 2 for kk in k):
+            raise ValueError(f"{name}: padding {pad} for kernel {k}, expected {tuple(kk // 2 for kk in k)}"
+                             + (" (unpadded layers are not supported)" if pad == (0, 0) else ""))
+        mode = conv.padding_mode
+        if mode == "zeros":
+            modes.add("zero")
+        elif mode == "replicate":
+            modes.add("replicate")
+        else:
+            raise ValueError(f"{name}: padding_mode={mode!r} (only 'zeros' and 'replicate' are supported)")
+    if len(modes) != 1:
+        raise ValueError(f"the layers mix padding modes {sorted(modes)}: one mode for all three layers is supported")
+    return model_from_state_dict(module.state_dict(), input_scale), modes.pop()
 
 
 def _plane(a, dtype, name, writable=False):
@@ -372,6 +414,20 @@ class Context:
     def model_f2(self) -> int:
         """f2 of the loaded model: 1 (9-1-5, also after set_weights), 3 or 5."""
         return int(self._lib.srcnn_get_model_f2(self._h))
+
+    def set_padding(self, padding):
+        """"zero" (PyTorch's nn.Conv2d(..., padding=k // 2)) or "replicate" (the default), or PAD_ZERO / PAD_REPLICATE
+        (srcnn_set_padding).  A setting of the context: it applies to the model loaded before or after it."""
+        if isinstance(padding, str):
+            if padding not in _PADDINGS:
+                raise ValueError(f"padding {padding!r}: expected 'zero' or 'replicate'")
+            padding = _PADDINGS[padding]
+        self._check(self._lib.srcnn_set_padding(self._h, int(padding)))
+
+    def padding(self) -> str:
+        """"replicate" or "zero" (srcnn_get_padding)."""
+        v = int(self._lib.srcnn_get_padding(self._h))
+        return {PAD_REPLICATE: "replicate", PAD_ZERO: "zero"}[v]
 
     def query_plan(self, width, height, n_frames=1):
         out = (C.c_int * 6)()

@@ -176,6 +176,14 @@ struct srcnn_ctx {
     srcnn::host::DevBuf sp_frag, sp_map64, sp_map32;
     hipEvent_t sp_done = nullptr;
     hipStream_t sp_stream = nullptr;
+    // SRCNN_PAD_ZERO (srcnn_set_padding): every model runs the banded path above with the zero-padding kernels.  whole_model:
+    // the tables came from srcnn_set_weights / srcnn_set_model, not from per-filter calls.  zp_f2: the f2 for which zp_frag
+    // (layer-3 fragments, SPATIAL_NFRAG_L3Z) -- and for f2 = 1 sp_frag -- were packed from host_raw, 0 = not since the last
+    // upload_weights; the replicate path never packs them
+    int padding = SRCNN_PAD_REPLICATE;
+    bool whole_model = false;
+    int zp_f2 = 0;
+    srcnn::host::DevBuf zp_frag;
     // staging for the host-buffer entry points
     srcnn::host::DevBuf in_u8, out_u8, pre_f32, planes, plane1, kern, sink;
     // seam scratch (srcnn_kernels.h) is written by one launch and read by the seam kernel behind it: one buffer per
@@ -329,7 +337,8 @@ int use_layer3(srcnn_ctx *c, const float *kernel, float bias);
 inline bool has_model(const srcnn_ctx *c) { return c->has_l12 && c->has_l3; }
 void drop_spatial_model(srcnn_ctx *c);
 
-// the entry points that run the 9-1-5 path only (row stripes, halo buffers, several GPUs, unfused, per-layer device calls)
+// the entry points that run the 9-1-5 path with replicate padding only (row stripes, halo buffers, several GPUs, unfused,
+// per-layer device calls; under SRCNN_PAD_ZERO also the per-filter calls): the message names the model or the padding
 int refuse_spatial(srcnn_ctx *c, const char *what);
 // The whole path of an f2 > 1 model on device planes (srcnn_forward_y_dev with srcnn_get_model_f2() > 1), defined in
 // srcnn_spatial.cpp, which sets this pointer when the library loads: the units above reach the spatial path only through it.

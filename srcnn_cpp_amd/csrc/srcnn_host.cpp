@@ -302,7 +302,8 @@ int srcnn_forward_y(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uint8_t
     // bands of >= 1024 rows: shorter ones lose more in their launches than the overlap wins (measured: 3840x2160 1.35 ms
     // in one piece, 1.27 in two bands, 1.28 in four, 1.40 in eight; 7680x4320 5.20 -> 4.44 in four)
     int n_bands = env_bands ? std::atoi(env_bands) : ((long)width * height >= (4L << 20) ? std::min(8, height / 1024) : 1);
-    if (c->mode == SRCNN_MODE_EXACT || preclamp || n_bands < 1 || c->f2 > 1) n_bands = 1;   // (bands: row stripes, 9-1-5 only)
+    if (c->mode == SRCNN_MODE_EXACT || preclamp || n_bands < 1 || c->f2 > 1 || c->padding == SRCNN_PAD_ZERO)
+        n_bands = 1;        // (bands: row stripes, the replicate-padded 9-1-5 model only)
     n_bands = std::min(n_bands, std::max(1, height / 64));
     if (n_bands == 1) {
         HIP_TRY(c, hipMemcpy2DAsync(d_in, width, src, src_stride, width, height, hipMemcpyHostToDevice, c->stream));
@@ -449,6 +450,7 @@ int srcnn_conv99(srcnn_ctx *c, const uint8_t *src, size_t src_stride, float *dst
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv99");
     if (bad_plane(src, src_stride, width, height) || bad_plane(dst, dst_stride, width, height) || !kernel)
         return fail(c, SRCNN_ERR_INVALID, "conv99: bad arguments");
     const size_t n = (size_t)width * height;
@@ -472,6 +474,7 @@ int srcnn_conv11(srcnn_ctx *c, const float *const *src, size_t src_stride, float
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv11");
     if (!src || src_stride < (size_t)width || bad_plane(dst, dst_stride, width, height) || !kernel)
         return fail(c, SRCNN_ERR_INVALID, "conv11: bad arguments");
     for (int k = 0; k < 64; ++k)

@@ -258,13 +258,21 @@ hipError_t launch_conv55_exact(const float *planes, long stride, long pitch, lon
 constexpr int SPATIAL_NFRAG_L1 = 82;
 __host__ __device__ constexpr size_t spatial_table_floats(int f2) { return (size_t)SPATIAL_NFRAG_L1 * 64 + (size_t)f2 * f2 * 2048 + 32; }
 size_t spatial_l2_lds_bytes(int f2);
-// 64 planar maps (plane pitch mpitch, row stride W) of image rows [m0, m1)
-hipError_t launch_spatial_l1(const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag, float *map,
-                             long mpitch, hipStream_t st);
+// 64 planar maps (plane pitch mpitch, row stride W) of image rows [m0, m1); zero: luma outside the image is 0 (SRCNN_PAD_ZERO),
+// else replicated
+hipError_t launch_spatial_l1(bool zero, const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag,
+                             float *map, long mpitch, hipStream_t st);
 // 32 planar maps (row stride W) of rows [o0, o1) from the 64 maps of rows [m0, m1) (which must hold rows o0 - r2 .. o1 + r2 - 1,
-// clamped to the image)
-hipError_t launch_spatial_l2(int f2, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+// clamped to the image); zero: the map outside the image is 0 (f2 = 1, 3, 5), else replicated (f2 = 3, 5)
+hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
                              const float *frag, const float *bias, float *out, long opitch, hipStream_t st);
+// Layer 3 under zero padding: u8 rows [b0, b1) of dst (row stride dstride, image rows; pre: the value before truncation, same
+// offsets, or null) from the 32 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch), which must hold every image
+// row of [b0 - 2, b1 + 2).  frag: SPATIAL_NFRAG_L3Z A fragments [16 k-steps][64 lanes] (lane l: W3[2s + (l >> 5)][tap of
+// l3_row_tap(l & 31)], 0 for the unused rows).
+constexpr int SPATIAL_NFRAG_L3Z = 16;
+hipError_t launch_spatial_l3z(const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, const float *frag,
+                              float b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
 
 // ---- pipeline steps around the conv path (srcnn_pipeline.hip) ---------------
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);

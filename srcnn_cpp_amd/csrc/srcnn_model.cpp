@@ -216,6 +216,7 @@ int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float
         for (int t = 0; t < 81; ++t) raw[10177 + t * 64 + ch] = w1[ch * 81 + t];
     std::vector<uint8_t> frag16(S16_TABLE_BYTES);
     pack_fragments16(w1, b1, w2, b2, w3, frag16.data());
+    c->zp_f2 = 0;                // the zero-padding tables are packed from host_raw again when next needed (srcnn_spatial.cpp)
     int rc;
     if ((rc = reserve(c, c->wfrag, frag.size() * 4))) return rc;
     if ((rc = reserve(c, c->wfrag16, frag16.size()))) return rc;
@@ -244,6 +245,11 @@ ForwardSpatialFn forward_spatial = nullptr;
 
 int refuse_spatial(srcnn_ctx *c, const char *what)
 {
+    if (c->padding == SRCNN_PAD_ZERO)
+        return fail(c, SRCNN_ERR_STATE, "%s has replicate padding only: the context is set to SRCNN_PAD_ZERO (srcnn_set_padding); "
+                                        "use srcnn_forward_y_dev / srcnn_forward_y / srcnn_forward_y_frames / srcnn_process_bgr* "
+                                        "in SRCNN_MODE_MFMA, or srcnn_set_padding(SRCNN_PAD_REPLICATE)",
+                    what);
     return fail(c, SRCNN_ERR_STATE, "%s runs the 9-1-5 model only: the context holds a 9-%d-5 model (srcnn_set_model); "
                                     "use srcnn_forward_y_dev / srcnn_forward_y / srcnn_forward_y_frames / srcnn_process_bgr*",
                 what, c->f2);
@@ -262,6 +268,7 @@ void drop_spatial_model(srcnn_ctx *c)
 
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11)
 {
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "a per-filter call");
     drop_spatial_model(c);
     const float *hr = c->host_raw.data();
     const bool same = c->has_l12 && !std::memcmp(hr, bias99, 64 * 4) && !std::memcmp(hr + 64, kernel99, 5184 * 4) &&
@@ -269,16 +276,19 @@ int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const
     if (same) return SRCNN_OK;
     const std::vector<float> w3(hr + 7329, hr + 8129);      // upload_weights rewrites host_raw
     const int rc = upload_weights(c, kernel99, bias99, kernel11, bias11, w3.data(), c->b3);
+    c->whole_model = false;
     if (rc == SRCNN_OK) c->has_l12 = true;
     return rc;
 }
 int use_layer3(srcnn_ctx *c, const float *kernel, float bias)
 {
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "a per-filter call");
     drop_spatial_model(c);
     const float *hr = c->host_raw.data();
     if (c->has_l3 && hr[7328] == bias && !std::memcmp(hr + 7329, kernel, 800 * 4)) return SRCNN_OK;
     const std::vector<float> raw(c->host_raw);               // upload_weights rewrites host_raw
     const int rc = upload_weights(c, raw.data() + 64, raw.data(), raw.data() + 5280, raw.data() + 5248, kernel, bias);
+    c->whole_model = false;
     if (rc == SRCNN_OK) c->has_l3 = true;
     return rc;
 }
@@ -299,10 +309,13 @@ int srcnn_set_weights(srcnn_ctx *c, const float *k99, const float *b99, const fl
     // a caller that passes its const tables on every call (the reference does, src/srcnn.cpp:609,627) packs and uploads once
     const float *hr = c->host_raw.data();
     if (c->has_l12 && c->has_l3 && hr[7328] == b55 && !std::memcmp(hr, b99, 64 * 4) && !std::memcmp(hr + 64, k99, 5184 * 4) &&
-        !std::memcmp(hr + 5248, b11, 32 * 4) && !std::memcmp(hr + 5280, k11, 2048 * 4) && !std::memcmp(hr + 7329, k55, 800 * 4))
+        !std::memcmp(hr + 5248, b11, 32 * 4) && !std::memcmp(hr + 5280, k11, 2048 * 4) && !std::memcmp(hr + 7329, k55, 800 * 4)) {
+        c->whole_model = true;
         return SRCNN_OK;
+    }
     if ((rc = upload_weights(c, k99, b99, k11, b11, k55, b55))) return rc;
     c->has_l12 = c->has_l3 = true;
+    c->whole_model = true;
     return SRCNN_OK;
 }
 

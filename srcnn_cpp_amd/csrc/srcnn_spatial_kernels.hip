@@ -1,4 +1,5 @@
-// srcnn_spatial_kernels.hip -- layers 1 and 2 of the 9-3-5 / 9-5-5 SRCNN models (srcnn_set_model, f2 = 3 or 5) for gfx950.
+// srcnn_spatial_kernels.hip -- layers 1 and 2 of the 9-3-5 / 9-5-5 SRCNN models (srcnn_set_model, f2 = 3 or 5), and the banded
+// path of every model under zero padding (srcnn_set_padding), for gfx950.
 //
 // A spatial layer 2 (32 x 64 x f2 x f2) is 10 or 28 times the work of the 9-1-5 model's 1x1 layer and needs an f2 x f2 window
 // of the 64-channel layer-1 map, which at 256 B per pixel does not fit beside the strip kernels' rings in LDS.  The path is
@@ -10,7 +11,10 @@
 //
 // Both kernels use v_mfma_f32_32x32x2_f32 with the weights as the A operand (output channel on the accumulator ROW) and one
 // pixel per lane as the B operand; accumulator register r of lane-half h holds output channel acc_row(r, h), lane & 31 the pixel.
-// Each layer replicate-pads ITS OWN input: layer 1 clamps luma coordinates, layer 2 clamps layer-1 map coordinates.
+// Each layer pads ITS OWN input.  Replicate padding (the default, ZERO = false): layer 1 clamps luma coordinates, layer 2 clamps
+// layer-1 map coordinates, and layer 3 is MODE_L3.  Zero padding (srcnn_set_padding(SRCNN_PAD_ZERO), ZERO = true; also for
+// f2 = 1): layers 1 and 2 stage 0 for every luma / map value outside the image, and layer 3 is spatial_l3z_kernel below,
+// because MODE_L3 builds the replicate border into its column offsets and vertical chains.
 //
 // Summation order (each MFMA is a 2-term fmaf chain, srcnn_mfma.hip):
 //   layer 1, channel c:  0 + w1[c][0] y0 + w1[c][1] y1 + ... + w1[c][80] y80 + b1[c]   (taps row-major, the bias tap last)
@@ -31,6 +35,7 @@ __device__ __forceinline__ int sclamp(int v, int lo, int hi) { return v < lo ? l
 constexpr int SL1_COLS = 128, SL1_ROWS = 8;
 constexpr int SL1_YP = SL1_COLS + 8, SL1_YR = SL1_ROWS + 8;
 
+template <bool ZERO>
 __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restrict__ src, long sstride, int W, int H,
                                                          int m0, int m1, const float *__restrict__ frag,
                                                          float *__restrict__ map, long mpitch)
@@ -42,7 +47,10 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restri
     for (int e = tid; e < SL1_YR * SL1_YP; e += 256) {
         const int rr = e / SL1_YP, cc = e - rr * SL1_YP;
         const int yy = sclamp(y0 - 4 + rr, 0, H - 1), xx = sclamp(x0 - 4 + cc, 0, W - 1);
-        ys[e] = (float)src[(long)yy * sstride + xx];
+        const float v = (float)src[(long)yy * sstride + xx];
+        // ZERO: 0 where the load was clamped, by a multiply: a select lets the compiler branch around the load (measured slower)
+        if constexpr (ZERO) ys[e] = v * ((yy == y0 - 4 + rr && xx == x0 - 4 + cc) ? 1.f : 0.f);
+        else ys[e] = v;
     }
     for (int e = tid; e < SPATIAL_NFRAG_L1 * 64; e += 256) as[e] = frag[e];
     __syncthreads();
@@ -85,7 +93,7 @@ size_t spatial_l2_lds_bytes(int f2)
     return ((size_t)SL2_CC * sl2_ps((f2 - 1) / 2) + (size_t)f2 * f2 * (SL2_CC / 2) * 64) * sizeof(float);
 }
 
-template <int F2>
+template <int F2, bool ZERO>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void spatial_l2_kernel(const float *__restrict__ map, long mpitch, int m0, int m1,
                                                          int W, int H, int o0, int o1, const float *__restrict__ frag,
                                                          const float *__restrict__ bias, float *__restrict__ out, long opitch)
@@ -110,7 +118,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
             const int c = e / (WR * WC), rem = e - c * (WR * WC), rr = rem / WC, cc = rem - rr * WC;
             // image row, replicate-clamped, then kept inside the rows the map holds (only rows that are not stored differ)
             const int yy = sclamp(sclamp(y0 - R + rr, 0, H - 1), m0, m1 - 1), xx = sclamp(x0 - R + cc, 0, W - 1);
-            xs[c * PS + rr * SL2_XP + cc] = map[(long)(SL2_CC * chunk + c) * mpitch + (long)(yy - m0) * W + xx];
+            const float v = map[(long)(SL2_CC * chunk + c) * mpitch + (long)(yy - m0) * W + xx];
+            if constexpr (ZERO) {   // 0 outside the image: the replicate load times 0 (as in layer 1: no branch around the load)
+                const int iy = y0 - R + rr, ix = x0 - R + cc;
+                xs[c * PS + rr * SL2_XP + cc] = v * ((iy >= 0 && iy < H && ix >= 0 && ix < W) ? 1.f : 0.f);
+            } else {
+                xs[c * PS + rr * SL2_XP + cc] = v;
+            }
         }
         const float4 *fa = reinterpret_cast<const float4 *>(frag + (size_t)chunk * NA);
         for (int e = tid; e < NA / 4; e += 256) reinterpret_cast<float4 *>(as)[e] = fa[e];
@@ -140,29 +154,141 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     }
 }
 
-hipError_t launch_spatial_l1(const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag, float *map,
-                             long mpitch, hipStream_t st)
+// ---- layer 3 under zero padding ---------------------------------------------------------------------------------------
+// Workgroup: 4 waves, a strip of SL3_COLS = 128 map columns (image columns 124 bx - 2 ..), of which the middle SL3_OUT = 124
+// are output, and a segment of SL3_SEG output rows; wave w owns map columns 32w .. 32w + 31 and walks the map rows
+// y0 - 2 .. y1 + 1.  Per map row 16 MFMAs give the 25 tap partials T[tap] = sum_c W3[c][tap] F_c (A: W3 with the rows of
+// l3_row_tap(); B: the 32 channels of the lane's pixel; the partials of a pixel outside the image are set to 0), so register
+// 5s + m of lane-half h holds tap (m, n = s (h = 0) or 3 + s (h = 1)).  Each wave keeps SL3_AHEAD map rows of loads in
+// flight (the kernel is bound by the 128 B per pixel it reads).  The 5 tap rows are summed down register chains, m ascending; the finished
+// per-tap-column sums V_n cross lanes through a double-buffered LDS row, and
+//   out(y, x) = (V_0(x - 2) + V_1(x - 1) + V_2(x) + V_3(x + 1) + V_4(x + 2)) + b3,  truncated, clamped to 0..255
+// (the epilogue of MODE_L3).  Zero padding needs no clamp in the sums: a feature outside the image contributes T = 0.
+// The map rows outside the band that the image holds are inside [o0, o1) (srcnn_spatial.cpp); the tiles are handed out
+// XCD by XCD (block b runs on XCD b % 8), so horizontally neighbouring strips share their halo columns in one L2.
+constexpr int SL3_COLS = 128, SL3_OUT = SL3_COLS - 4, SL3_SEG = 16, SL3_XCDS = 8;
+constexpr int SL3_AHEAD = 4;        // map rows in flight per wave: a ring of SL3_AHEAD x 16 registers
+
+template <bool PRE>
+__global__ __launch_bounds__(256) void spatial_l3z_kernel(const float *__restrict__ map, long mpitch, int o0, int o1, int W,
+                                                          int H, int b0, int b1, int nx, int n_tiles,
+                                                          const float *__restrict__ frag, float b3, uint8_t *__restrict__ dst,
+                                                          long dstride, float *__restrict__ pre)
+{
+    __shared__ float vt[2][5][SL3_COLS];
+    const int per = (n_tiles + SL3_XCDS - 1) / SL3_XCDS;
+    const int tile = (int)(blockIdx.x % SL3_XCDS) * per + (int)(blockIdx.x / SL3_XCDS);
+    if (tile >= n_tiles) return;                   // uniform over the workgroup
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, kk = lane >> 5;
+    const int ty = tile / nx, tx = tile - ty * nx;
+    const int c = 32 * wave + j, x = tx * SL3_OUT - 2 + c;
+    const int y0 = b0 + ty * SL3_SEG, y1 = min(b1, y0 + SL3_SEG), r_end = y1 + 2;
+    const bool col_ok = x >= 0 && x < W;
+    float a[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) a[s] = frag[s * 64 + lane];
+    // channels 2s + kk of map row r at the lane's column, from a clamped (always valid) address: no branch between the loads;
+    // the rows and columns outside the image are zeroed in the tap partials instead
+    const float *colp = map + (long)kk * mpitch + sclamp(x, 0, W - 1);
+    auto load = [&](int r, float *v) {
+        const float *p = colp + (long)(sclamp(r, o0, o1 - 1) - o0) * W;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v[s] = p[(long)(2 * s) * mpitch];
+    };
+    float xr[SL3_AHEAD][16], ch[3][4];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ch[s][k] = 0.f;
+#pragma unroll
+    for (int d = 0; d < SL3_AHEAD; ++d)
+        if (y0 - 2 + d < r_end) load(y0 - 2 + d, xr[d]);
+    for (int rb = y0 - 2; rb < r_end; rb += SL3_AHEAD) {
+#pragma unroll
+        for (int d = 0; d < SL3_AHEAD; ++d) {
+            const int r = rb + d;
+            if (r >= r_end) break;                 // uniform over the workgroup
+            f32x16 t = {0};
+#pragma unroll
+            for (int s = 0; s < 16; ++s) t = SMFMA(a[s], xr[d][s], t);
+            if (r + SL3_AHEAD < r_end) load(r + SL3_AHEAD, xr[d]);
+            const bool ok = col_ok && r >= 0 && r < H;   // zero padding: a feature outside the image contributes nothing
+            float v[3];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {              // ch[s][k]: tap rows 0 .. k of output row r + 1 - k
+                v[s] = ch[s][3] + (ok ? t[5 * s + 4] : 0.f);
+                ch[s][3] = ch[s][2] + (ok ? t[5 * s + 3] : 0.f);
+                ch[s][2] = ch[s][1] + (ok ? t[5 * s + 2] : 0.f);
+                ch[s][1] = ch[s][0] + (ok ? t[5 * s + 1] : 0.f);
+                ch[s][0] = ok ? t[5 * s] : 0.f;
+            }
+            const int y = r - 2;
+            if (y >= y0) {                             // uniform over the workgroup
+                float *vr = &vt[r & 1][0][0];
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    const int n = kk ? 3 + s : s;
+                    if (n < 5) vr[n * SL3_COLS + c] = v[s];
+                }
+                __syncthreads();
+                if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
+                    const float sum = (((vr[c - 2] + vr[SL3_COLS + c - 1]) + vr[2 * SL3_COLS + c]) + vr[3 * SL3_COLS + c + 1]) +
+                                      vr[4 * SL3_COLS + c + 2];
+                    const float val = sum + b3;
+                    const long o = (long)y * dstride + x;
+                    dst[o] = (uint8_t)sclamp((int)val, 0, 255);
+                    if constexpr (PRE) pre[o] = val;
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_spatial_l1(bool zero, const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag,
+                             float *map, long mpitch, hipStream_t st)
 {
     const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
-    hipLaunchKernelGGL(spatial_l1_kernel, grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
+    if (zero) hipLaunchKernelGGL(spatial_l1_kernel<true>, grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
+    else hipLaunchKernelGGL(spatial_l1_kernel<false>, grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
     return hipGetLastError();
 }
 
-hipError_t launch_spatial_l2(int f2, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+template <int F2, bool ZERO>
+static void launch_l2(dim3 grid, size_t lds, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                      const float *frag, const float *bias, float *out, long opitch, hipStream_t st)
+{
+    // (the 9-5-5 kernel's 70 KB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l2_kernel<F2, ZERO>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    hipLaunchKernelGGL((spatial_l2_kernel<F2, ZERO>), grid, dim3(256), lds, st, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out,
+                       opitch);
+}
+
+hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
                              const float *frag, const float *bias, float *out, long opitch, hipStream_t st)
 {
     const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS));
     const size_t lds = spatial_l2_lds_bytes(f2);
-    // (the 9-5-5 kernel's 70 KB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
-    if (f2 == 3) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l2_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(spatial_l2_kernel<3>, grid, dim3(256), lds, st, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch);
-    } else if (f2 == 5) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l2_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(spatial_l2_kernel<5>, grid, dim3(256), lds, st, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    if (f2 == 3 && !zero) launch_l2<3, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    else if (f2 == 5 && !zero) launch_l2<5, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    else if (f2 == 1 && zero) launch_l2<1, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    else if (f2 == 3 && zero) launch_l2<3, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    else if (f2 == 5 && zero) launch_l2<5, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    else return hipErrorInvalidValue;          // (f2 = 1 under replicate padding is the strip kernels' model)
+    return hipGetLastError();
+}
+
+hipError_t launch_spatial_l3z(const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, const float *frag,
+                              float b3, uint8_t *dst, long dstride, float *pre, hipStream_t st)
+{
+    const int nx = (W + SL3_OUT - 1) / SL3_OUT, ny = (b1 - b0 + SL3_SEG - 1) / SL3_SEG, n_tiles = nx * ny;
+    const dim3 grid((unsigned)(SL3_XCDS * ((n_tiles + SL3_XCDS - 1) / SL3_XCDS)));
+    if (pre)
+        hipLaunchKernelGGL(spatial_l3z_kernel<true>, grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag,
+                           b3, dst, dstride, pre);
+    else
+        hipLaunchKernelGGL(spatial_l3z_kernel<false>, grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag,
+                           b3, dst, dstride, pre);
     return hipGetLastError();
 }
 

@@ -1,8 +1,11 @@
-"""Time the 9-3-5 and 9-5-5 models (srcnn_set_model) on one GPU: device-resident planes, HIP events around each call of
+"""Time the 9-1-5, 9-3-5 and 9-5-5 models (srcnn_set_model) on one GPU: device-resident planes, HIP events around each call of
 srcnn_forward_y_dev on the context's stream, warm-up calls excluded.  Reports ms per plane, MPix/s and the fraction of the
 f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81 + 32*64*f2^2 + 32*25).
 
-    python tools/model_bench.py [--f2 3 5] [--sizes 3840x2160 1920x1080] [--steps 20] [--warmup 3] [--json out.json]
+    python tools/model_bench.py [--f2 1 3 5] [--padding replicate|zero|both] [--sizes 3840x2160 1920x1080] [--steps 20]
+                                [--warmup 3] [--json out.json]
+
+--padding both times each model and size with replicate padding, then with zero padding (srcnn_set_padding), in one process.
 """
 import argparse
 import json
@@ -56,27 +59,31 @@ def time_plane(ctx, w, h, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--f2", type=int, nargs="+", default=[3, 5])
+    ap.add_argument("--f2", type=int, nargs="+", default=[3, 5], choices=[1, 3, 5])
+    ap.add_argument("--padding", choices=["replicate", "zero", "both"], default="replicate")
     ap.add_argument("--sizes", nargs="+", default=["3840x2160", "1920x1080"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    paddings = ["replicate", "zero"] if args.padding == "both" else [args.padding]
     rows = []
     with S.Context(0) as ctx:
         for f2 in args.f2:
             ctx.set_model(*model(f2))
             for size in args.sizes:
                 w, h = map(int, size.split("x"))
-                med, best = time_plane(ctx, w, h, args.steps, args.warmup)
-                px = w * h
-                tflops = flop_per_pixel(f2) * px / (med * 1e-3) / 1e12
-                row = dict(model=f"9-{f2}-5", width=w, height=h, ms_per_plane=round(med, 3), ms_min=round(best, 3),
-                           mpix_per_s=round(px / (med * 1e-3) / 1e6, 1), flop_per_pixel=flop_per_pixel(f2),
-                           tflops=round(tflops, 2), fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps,
-                           warmup=args.warmup)
-                rows.append(row)
-                print(json.dumps(row), flush=True)
+                for padding in paddings:
+                    ctx.set_padding(padding)
+                    med, best = time_plane(ctx, w, h, args.steps, args.warmup)
+                    px = w * h
+                    tflops = flop_per_pixel(f2) * px / (med * 1e-3) / 1e12
+                    row = dict(model=f"9-{f2}-5", padding=padding, width=w, height=h, ms_per_plane=round(med, 3),
+                               ms_min=round(best, 3), mpix_per_s=round(px / (med * 1e-3) / 1e6, 1),
+                               flop_per_pixel=flop_per_pixel(f2), tflops=round(tflops, 2),
+                               fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps, warmup=args.warmup)
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
     if args.json:
         Path(args.json).parent.mkdir(parents=True, exist_ok=True)
         Path(args.json).write_text(json.dumps(rows, indent=1) + "\n")

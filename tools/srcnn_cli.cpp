@@ -2,7 +2,8 @@
 // (reference: parseArgs / printTitle / printHelp /
 // pthreadcall / main, src/srcnn.cpp:331-731), running the pipeline on the GPU.
 //
-//   srcnn_amd [--scale=F] [--noverbose] [--help] [--weights=FILE] [--timing] [--refbytes] source [output]
+//   srcnn_amd [--scale=F] [--noverbose] [--help] [--weights=FILE] [--padding=zero|replicate] [--timing] [--refbytes]
+//             source [output]
 //
 // Same argument rules as the reference: --scale= must be > 0 (default 2.0,
 // src/srcnn.cpp:40,359-370); first free argument = source, second = output;
@@ -38,7 +39,8 @@ namespace {
 struct Options {
     float scale = 2.0f;
     bool verbose = true, help = false, copy = false, timing = false, refbytes = false;
-    std::string me, src, dst, weights;
+    int padding = SRCNN_PAD_REPLICATE;
+    std::string me, src, dst, weights, error;
 };
 
 bool starts_with(const std::string &s, const char *p) { return s.rfind(p, 0) == 0; }
@@ -65,6 +67,11 @@ bool parse(int argc, char **argv, Options &o)
             o.refbytes = true;
         } else if (starts_with(a, "--weights=")) {
             o.weights = a.substr(10);
+        } else if (starts_with(a, "--padding=")) {
+            const std::string v = a.substr(10);
+            if (v == "zero") o.padding = SRCNN_PAD_ZERO;
+            else if (v == "replicate") o.padding = SRCNN_PAD_REPLICATE;
+            else o.error = "--padding=" + v + " : expected zero or replicate";
         } else if (o.src.empty()) {
             o.src = a;
         } else if (o.dst.empty()) {
@@ -94,6 +101,7 @@ void help(const Options &o)
     std::printf("        --scale=( ratio: 0.1 to .. ) : scaling by ratio.\n");
     std::printf("        --noverbose                  : turns off all verbose\n");
     std::printf("        --weights=FILE               : model blob, b1|W1|b2|W2|b3|W3: 8129 (9-1-5), 24513 (9-3-5) or 57281 (9-5-5) floats\n");
+    std::printf("        --padding=zero|replicate     : padding of every layer's input (default replicate; zero = PyTorch's nn.Conv2d)\n");
     std::printf("        --help                       : this help\n\n");
 }
 
@@ -172,6 +180,12 @@ int main(int argc, char **argv)
         std::fflush(stdout);
         return 0;
     }
+    if (o.error.empty() && o.padding == SRCNN_PAD_ZERO && o.refbytes)
+        o.error = "--padding=zero and --refbytes : the reference's bytes are those of replicate padding";
+    if (!o.error.empty()) {
+        std::printf("- argument error : %s\n", o.error.c_str());
+        return -1;
+    }
     if (o.verbose) {
         title(o);
         std::printf("\n- Scale multiply ratio : %.2f\n", o.scale);
@@ -211,6 +225,7 @@ int main(int argc, char **argv)
     const float *b1 = w.data(), *w1 = b1 + 64, *b2 = w1 + 5184, *w2 = b2 + 32, *w3 = w2 + 2048 * f2 * f2 + 1;
     rc = f2 == 1 ? srcnn_set_weights(ctx, w1, b1, w2, b2, w3, w3[-1]) : srcnn_set_model(ctx, f2, w1, b1, w2, b2, w3, w3[-1]);
     if (rc == SRCNN_OK && o.refbytes) rc = srcnn_set_mode(ctx, SRCNN_MODE_REFBYTES);
+    if (rc == SRCNN_OK) rc = srcnn_set_padding(ctx, o.padding);
     ph.mark("srcnn_set_weights (pack + upload)");
     std::vector<unsigned char> out((size_t)ow * oh * 3);
     // (No warm-up call: the reference runs ONE picture per process, so the timed region below is the context's first call and
