@@ -250,6 +250,42 @@ enum { SRCNN_PAD_REPLICATE = 0, SRCNN_PAD_ZERO = 1 };
 int srcnn_set_padding(srcnn_ctx *ctx, int padding);
 int srcnn_get_padding(const srcnn_ctx *ctx);
 
+/* Colour SRCNN models (Dong et al., TPAMI 2016, section 4.4): a 9-f2-5 model (f2 = 1, 3 or 5) with 3 input and 3 output
+ * channels that super-resolves every channel of an image of interleaved 3-byte pixels.
+ *   kernel1 [64][3][9][9], bias1 [64]; kernel2 [32][64][f2][f2], bias2 [32] as in srcnn_set_model; kernel3 [3][32][5][5],
+ *   bias3 [3] (PyTorch's convN.weight / convN.bias of an nn.Conv2d SRCNN with num_channels = 3).  Blob form:
+ *   b1 | W1 | b2 | W2 | b3[3] | W3 (20,099 / 36,483 / 69,251 floats).
+ * Semantics: cross-correlation, ReLU after layers 1 and 2, every layer pads its own input as srcnn_set_padding says
+ * (replicate by default, or zero); output channel c is (int)(layer 3 + bias3[c]) clamped to 0..255.  Model channel i reads
+ * byte i of each input pixel and writes byte i of each output pixel: for a BGR image channel 0 is B, so the weights carry
+ * the channel order.
+ *   - only SRCNN_MODE_MFMA has arithmetic (summation order in srcnn_color_kernels.hip); other modes return SRCNN_ERR_STATE;
+ *   - srcnn_forward_color and srcnn_forward_color_dev run the model.  A row holds 3 * width bytes; strides and frame
+ *     pitches are in bytes and a stride is at least 3 * width.  The pre-clamp values (may be NULL) have the layout of the
+ *     output, in floats: preclamp_stride floats per row, and for srcnn_forward_color_dev the dst stride and frame pitch;
+ *   - srcnn_process_bgr and srcnn_process_bgr_dev resize all three channels with the bicubic arithmetic of the 1-channel
+ *     pipeline and run the model on the result (no YCrCb conversion);
+ *   - every entry point that runs a 1-channel model (srcnn_forward_y*, row stripes, halo buffers, the several-GPU calls,
+ *     srcnn_forward_y_unfused_dev, srcnn_conv99x11_dev, srcnn_conv55_dev) returns SRCNN_ERR_STATE, and srcnn_last_error()
+ *     names the colour model;
+ *   - srcnn_set_weights, srcnn_set_model or a per-filter call that loads weights ENDS the model, as for srcnn_set_model;
+ *     srcnn_get_model_channels() then returns 1.  With a 1-channel model loaded srcnn_forward_color* return SRCNN_ERR_STATE;
+ *   - workspace: the band maps of srcnn_set_model (within 512 MiB), and the host-buffer form stages the image on the device. */
+int srcnn_set_model_color(srcnn_ctx *ctx, int f2,
+                          const float *kernel1 /*[64][3][9][9]*/, const float *bias1 /*[64]*/,
+                          const float *kernel2 /*[32][64][f2][f2]*/, const float *bias2 /*[32]*/,
+                          const float *kernel3 /*[3][32][5][5]*/, const float *bias3 /*[3]*/);
+/* Channels of the loaded model: 3 after srcnn_set_model_color, else 1. */
+int srcnn_get_model_channels(const srcnn_ctx *ctx);
+int srcnn_forward_color(srcnn_ctx *ctx, const uint8_t *src, size_t src_stride,
+                        uint8_t *dst, size_t dst_stride, int width, int height,
+                        float *preclamp /*may be NULL: [h][3w], preclamp_stride floats*/, size_t preclamp_stride);
+/* Same on device memory, asynchronous on the context's stream: n_frames images, frame pitches in bytes. */
+int srcnn_forward_color_dev(srcnn_ctx *ctx,
+                            const uint8_t *d_src, size_t src_stride, size_t src_frame_pitch,
+                            uint8_t *d_dst, size_t dst_stride, size_t dst_frame_pitch,
+                            int width, int height, int n_frames, float *d_preclamp /*may be NULL; dst strides*/);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

@@ -114,6 +114,20 @@ public:
     // nn.Conv2d(..., padding=k // 2) and runs in SRCNN_MODE_MFMA through srcnn_forward_y* and srcnn_process_bgr*.
     void set_padding(int padding) { check(srcnn_set_padding(get(), padding)); }
     int padding() const { return srcnn_get_padding(get()); }
+    // A colour 9-f2-5 model (srcnn_set_model_color): kernel1 [64][3][9][9], kernel2 [32][64][f2][f2], kernel3 [3][32][5][5],
+    // bias3 [3].  It runs in SRCNN_MODE_MFMA through forward_color and process_bgr; model_channels() is 3 while it is loaded.
+    void set_model_color(int f2, const float kernel1[64][3][9][9], const float bias1[64], const float *kernel2, const float bias2[32],
+                         const float kernel3[3][32][5][5], const float bias3[3])
+    {
+        check(srcnn_set_model_color(get(), f2, &kernel1[0][0][0][0], bias1, kernel2, bias2, &kernel3[0][0][0][0], bias3));
+    }
+    int model_channels() const { return srcnn_get_model_channels(get()); }
+    // Interleaved 3-byte pixels in and out (rows of 3 * width bytes); preclamp: [h][3w] floats, or null.
+    void forward_color(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int width, int height,
+                       float *preclamp = nullptr, size_t preclamp_stride = 0)
+    {
+        check(srcnn_forward_color(get(), src, src_stride, dst, dst_stride, width, height, preclamp, preclamp_stride));
+    }
 
 private:
     struct Handle {

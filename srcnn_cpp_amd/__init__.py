@@ -27,7 +27,8 @@ import numpy as np
 
 __all__ = [
     "Context", "SrcnnError", "forward_y_striped_frames", "load_library", "library_path", "tuning_library_path", "use_library", "load_weights", "split_weights",
-    "load_model", "split_model", "model_from_state_dict", "model_from_module", "MODEL_SIZES", "PAD_REPLICATE", "PAD_ZERO",
+    "load_model", "split_model", "model_from_state_dict", "model_from_module", "MODEL_SIZES", "COLOR_MODEL_SIZES", "PAD_REPLICATE",
+    "PAD_ZERO",
     "Convolution99", "Convolution11", "Convolution55", "Convolution99x11", "default_context",
     "MODE_MFMA", "MODE_EXACT", "MODE_SPLIT16", "MODE_REFBYTES", "MODE_REFBYTES16", "FLOP_PER_PIXEL",
     "ERR_INVALID", "ERR_HIP", "ERR_NOMEM", "ERR_NODEVICE", "ERR_STATE",
@@ -46,6 +47,8 @@ MODE_REFBYTES16 = 4        # opt-in: the same behind the split-f16 kernel
 N_WEIGHTS = 8129
 # blob sizes of the 9-f2-5 models (srcnn_set_model): b1|W1|b2|W2|b3|W3 with W2 holding 2048 * f2^2 floats
 MODEL_SIZES = {8129: 1, 24513: 3, 57281: 5}
+# colour models (srcnn_set_model_color): blob size -> f2; b1 | W1 [64,3,9,9] | b2 | W2 | b3 [3] | W3 [3,32,5,5]
+COLOR_MODEL_SIZES = {20099: 1, 36483: 3, 69251: 5}
 # padding of every layer's input (srcnn_set_padding): replicate (the default, as the reference) or zero (PyTorch's nn.Conv2d default)
 PAD_REPLICATE = 0
 PAD_ZERO = 1
@@ -125,6 +128,10 @@ def load_library() -> C.CDLL:
         "srcnn_get_model_f2": ([vp], i),
         "srcnn_set_padding": ([vp, i], i),
         "srcnn_get_padding": ([vp], i),
+        "srcnn_set_model_color": ([vp, i, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p], i),
+        "srcnn_get_model_channels": ([vp], i),
+        "srcnn_forward_color": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
+        "srcnn_forward_color_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_y_frames": ([vp, C.POINTER(_u8p), sz, C.POINTER(_u8p), sz, i, i, i], i),
         "srcnn_forward_y_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
@@ -184,6 +191,7 @@ ABI_SYMBOLS = (
     "srcnn_resize_cubic", "srcnn_process_bgr", "srcnn_process_bgr_dev",
     "srcnn_stripe_rows", "srcnn_forward_y_frames_multi", "srcnn_forward_y_lanes_dev", "srcnn_forward_y_striped", "srcnn_forward_y_striped_frames", "srcnn_forward_y_striped_dev",
     "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
+    "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
 )
 
 
@@ -205,11 +213,21 @@ def split_weights(blob: np.ndarray):
 
 def split_model(blob: np.ndarray):
     """A 9-1-5, 9-3-5 or 9-5-5 blob (8,129 / 24,513 / 57,281 floats, b1|W1|b2|W2|b3|W3) ->
-    (w1[64,9,9], b1[64], w2, b2[32], w3[32,5,5], b3) with w2 [32,64] for f2 = 1, else [32,64,f2,f2]."""
+    (w1[64,9,9], b1[64], w2, b2[32], w3[32,5,5], b3) with w2 [32,64] for f2 = 1, else [32,64,f2,f2].
+
+    A colour blob (COLOR_MODEL_SIZES: 20,099 / 36,483 / 69,251 floats, b1|W1|b2|W2|b3[3]|W3) ->
+    (w1[64,3,9,9], b1[64], w2[32,64,f2,f2], b2[32], w3[3,32,5,5], b3[3])."""
     blob = np.ascontiguousarray(blob, dtype=np.float32).ravel()
+    if blob.size in COLOR_MODEL_SIZES:
+        f2 = COLOR_MODEL_SIZES[blob.size]
+        o2 = 64 + 15552                      # b2
+        o3 = o2 + 32 + 2048 * f2 * f2        # b3
+        return (blob[64:o2].reshape(64, 3, 9, 9), blob[0:64], blob[o2 + 32:o3].reshape(32, 64, f2, f2),
+                blob[o2:o2 + 32], blob[o3 + 3:o3 + 2403].reshape(3, 32, 5, 5), blob[o3:o3 + 3].copy())
     f2 = MODEL_SIZES.get(blob.size)
     if f2 is None:
-        raise ValueError(f"model blob has {blob.size} floats, expected one of {sorted(MODEL_SIZES)}")
+        raise ValueError(f"model blob has {blob.size} floats, expected one of {sorted(MODEL_SIZES)} "
+                         f"(colour: {sorted(COLOR_MODEL_SIZES)})")
     if f2 == 1:
         return split_weights(blob)
     n2 = 2048 * f2 * f2
@@ -219,14 +237,15 @@ def split_model(blob: np.ndarray):
 
 
 def load_model(path) -> np.ndarray:
-    """A 9-1-5, 9-3-5 or 9-5-5 model blob from a file (float32 little-endian, b1|W1|b2|W2|b3|W3)."""
+    """A 9-1-5, 9-3-5 or 9-5-5 model blob, 1-channel or colour, from a file (float32 little-endian, b1|W1|b2|W2|b3|W3)."""
     blob = np.fromfile(str(path), dtype="<f4")
-    if blob.size not in MODEL_SIZES:
-        raise ValueError(f"model blob has {blob.size} floats, expected one of {sorted(MODEL_SIZES)}")
+    if blob.size not in MODEL_SIZES and blob.size not in COLOR_MODEL_SIZES:
+        raise ValueError(f"model blob has {blob.size} floats, expected one of {sorted(MODEL_SIZES)} "
+                         f"(colour: {sorted(COLOR_MODEL_SIZES)})")
     return blob
 
 
-def model_from_state_dict(sd, input_scale: float = 255.0):
+def model_from_state_dict(sd, input_scale: float = 255.0, image_order: Optional[str] = None):
     """A PyTorch SRCNN state dict -> (w1, b1, w2, b2, w3, b3) for Context.set_model.
 
     Reads conv1.weight (64,1,9,9), conv1.bias, conv2.weight (32,64,f2,f2) with f2 = 1, 3 or 5, conv2.bias,
@@ -238,6 +257,12 @@ def model_from_state_dict(sd, input_scale: float = 255.0):
     default padding_mode "zeros" -- the usual PyTorch SRCNN -- needs Context.set_padding("zero"); "replicate" (the
     context's default) is for models trained with padding_mode="replicate".  model_from_module reads the padding from an
     nn.Module.
+
+    A colour model (num_channels = 3: conv1.weight (64,3,9,9), conv3.weight (3,32,5,5), conv3.bias (3,)) gives
+    (w1[64,3,9,9], b1, w2[32,64,f2,f2], b2, w3[3,32,5,5], b3[3]) and needs image_order, the channel order of the images it
+    will run on: model channel i reads byte i of a pixel.  "rgb" keeps the trained order; "bgr" (OpenCV images,
+    Context.process_bgr) reverses W1's input axis and W3 / b3's output axis of a model trained on RGB.  ValueError when
+    image_order is missing for a colour model, and when conv1 and conv3 disagree on the channel count.
     """
     def arr(key, shape=None):
         if key not in sd:
@@ -253,15 +278,29 @@ def model_from_state_dict(sd, input_scale: float = 255.0):
         raise ValueError(f"conv2.weight: shape {w2.shape}, expected (32, 64, f2, f2) with f2 in 1, 3, 5")
     s = float(input_scale)
     f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    c_in, c_out = arr("conv1.weight").shape[1:2], arr("conv3.weight").shape[:1]
+    if c_in == (3,) or c_out == (3,):
+        if c_in != c_out:
+            raise ValueError(f"conv1 reads {c_in[0] if c_in else '?'} channels and conv3 writes {c_out[0] if c_out else '?'}: "
+                             "a model has 1 channel in and out, or 3")
+        if image_order not in ("rgb", "bgr"):
+            raise ValueError(f"image_order={image_order!r}: a 3-channel model needs image_order='rgb' or 'bgr' (the channel "
+                             "order of the images it will run on)")
+        w1, w3, b3 = arr("conv1.weight", (64, 3, 9, 9)), arr("conv3.weight", (3, 32, 5, 5)), arr("conv3.bias", (3,))
+        if image_order == "bgr":
+            w1, w3, b3 = w1[:, ::-1], w3[::-1], b3[::-1]
+        return (f32(w1), f32(arr("conv1.bias", (64,)) * s), f32(w2.reshape(32, 64, w2.shape[2], w2.shape[2])),
+                f32(arr("conv2.bias", (32,)) * s), f32(w3), f32(b3 * s))
     return (f32(arr("conv1.weight", (64, 1, 9, 9)).reshape(64, 9, 9)), f32(arr("conv1.bias", (64,)) * s),
             f32(w2 if w2.shape[2] > 1 else w2.reshape(32, 64)), f32(arr("conv2.bias", (32,)) * s),
             f32(arr("conv3.weight", (1, 32, 5, 5)).reshape(32, 5, 5)), float(arr("conv3.bias", (1,))[0] * s))
 
 
-def model_from_module(module, input_scale: float = 255.0):
+def model_from_module(module, input_scale: float = 255.0, image_order: Optional[str] = None):
     """A PyTorch SRCNN nn.Module with conv1, conv2 and conv3 -> (model, padding) for Context.set_model and Context.set_padding.
 
-    model is model_from_state_dict(module.state_dict(), input_scale); padding is "zero" or "replicate", read from each conv's
+    model is model_from_state_dict(module.state_dict(), input_scale, image_order) (a 3-channel module needs image_order);
+    padding is "zero" or "replicate", read from each conv's
     padding and padding_mode.  Every layer must pad by k // 2 in one mode: ValueError for an unpadded layer (0 or "valid"),
     for "reflect" or "circular", and for layers whose modes differ.
     """
@@ -289,7 +328,7 @@ def model_from_module(module, input_scale: float = 255.0):
             raise ValueError(f"{name}: padding_mode={mode!r} (only 'zeros' and 'replicate' are supported)")
     if len(modes) != 1:
         raise ValueError(f"the layers mix padding modes {sorted(modes)}: one mode for all three layers is supported")
-    return model_from_state_dict(module.state_dict(), input_scale), modes.pop()
+    return model_from_state_dict(module.state_dict(), input_scale, image_order), modes.pop()
 
 
 def _plane(a, dtype, name, writable=False):
@@ -395,7 +434,10 @@ class Context:
         self.set_weights(*split_weights(blob))
 
     def set_model(self, w1, b1, w2, b2, w3, b3):
-        """A 9-1-5, 9-3-5 or 9-5-5 model (srcnn_set_model): f2 from w2's shape, (32, 64) or (32, 64, f2, f2)."""
+        """A 9-1-5, 9-3-5 or 9-5-5 model (srcnn_set_model): f2 from w2's shape, (32, 64) or (32, 64, f2, f2).
+        A colour model -- w1 (64, 3, 9, 9), w3 (3, 32, 5, 5), b3 of length 3 -- goes to srcnn_set_model_color."""
+        if tuple(np.shape(w1)) == (64, 3, 9, 9) or tuple(np.shape(w3)) == (3, 32, 5, 5) or np.size(b3) == 3:
+            return self._set_model_color(w1, b1, w2, b2, w3, b3)
         shape = tuple(np.shape(w2))
         if shape == (32, 64):
             f2 = 1
@@ -408,8 +450,55 @@ class Context:
         w3 = _wt(w3, 800, "kernel55")
         self._check(self._lib.srcnn_set_model(self._h, f2, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(w3), float(b3)))
 
+    def _set_model_color(self, w1, b1, w2, b2, w3, b3):
+        for name, a, want in (("kernel1", w1, (64, 3, 9, 9)), ("kernel3", w3, (3, 32, 5, 5)), ("bias3", b3, (3,))):
+            if tuple(np.shape(a)) != want:
+                raise ValueError(f"{name}: shape {tuple(np.shape(a))}, expected {want} (a colour model)")
+        shape = tuple(np.shape(w2))
+        if len(shape) == 4 and shape[:2] == (32, 64) and shape[2] == shape[3] and shape[2] in (1, 3, 5):
+            f2 = shape[2]
+        elif shape == (32, 64):
+            f2 = 1
+        else:
+            raise ValueError(f"kernel2: shape {shape}, expected (32, 64, f2, f2) with f2 in 1, 3, 5")
+        w1, b1 = _wt(w1, 15552, "kernel1"), _wt(b1, 64, "bias1")
+        w2, b2 = _wt(w2, 2048 * f2 * f2, "kernel2"), _wt(b2, 32, "bias2")
+        w3, b3 = _wt(w3, 2400, "kernel3"), _wt(b3, 3, "bias3")
+        self._check(self._lib.srcnn_set_model_color(self._h, f2, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(w3), _fp(b3)))
+
     def set_model_blob(self, blob):
         self.set_model(*split_model(blob))
+
+    def model_channels(self) -> int:
+        """3 while a colour model (srcnn_set_model_color) is loaded, else 1."""
+        return int(self._lib.srcnn_get_model_channels(self._h))
+
+    def forward_color(self, img, dst=None, preclamp=None):
+        """A colour model on an HxWx3 uint8 image of packed pixels (row stride may be padded); model channel i reads and
+        writes byte i of a pixel.  preclamp: an HxWx3 float32 array for the values before truncation, or None."""
+        img, ss = _image(img, "img")
+        h, w, _ = img.shape
+        if dst is None:
+            dst = np.empty((h, w, 3), np.uint8)
+        dst, ds = _image(dst, "dst", True)
+        _same_shape("dst", dst.shape, img.shape)
+        pp, ps = None, 0
+        if preclamp is not None:
+            if not isinstance(preclamp, np.ndarray) or preclamp.dtype != np.float32 or preclamp.ndim != 3:
+                raise TypeError("preclamp: expected an HxWx3 float32 array")
+            _same_shape("preclamp", preclamp.shape, img.shape)
+            if preclamp.strides[2] != 4 or preclamp.strides[1] != 12 or preclamp.strides[0] % 4 or not preclamp.flags.writeable:
+                raise ValueError("preclamp: pixels must be packed and writeable (row stride may be padded)")
+            pp, ps = _fp(preclamp), preclamp.strides[0] // 4
+        self._check(self._lib.srcnn_forward_color(self._h, img.ctypes.data_as(_u8p), ss, dst.ctypes.data_as(_u8p), ds, w, h,
+                                                  pp, ps))
+        return dst
+
+    def forward_color_dev(self, d_src, src_stride, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch,
+                          width, height, n_frames=1, d_preclamp=0):
+        """srcnn_forward_color_dev: strides and frame pitches in bytes; d_preclamp (floats) uses the dst strides."""
+        self._check(self._lib.srcnn_forward_color_dev(self._h, d_src, src_stride, src_frame_pitch, d_dst, dst_stride,
+                                                      dst_frame_pitch, width, height, n_frames, d_preclamp or None))
 
     def model_f2(self) -> int:
         """f2 of the loaded model: 1 (9-1-5, also after set_weights), 3 or 5."""

@@ -184,6 +184,12 @@ struct srcnn_ctx {
     bool whole_model = false;
     int zp_f2 = 0;
     srcnn::host::DevBuf zp_frag;
+    // a colour model (srcnn_set_model_color, srcnn_color.cpp): channels = 3, f2 its layer 2; layers 1-3 run from col_frag
+    // (color_table_floats(f2)) on the band maps above, b3 of each output channel in col_b3.  The 9-1-5 tables then hold a zero
+    // model that no gate lets run (luma_path_ok).
+    int channels = 1;
+    float col_b3[3] = {0.f, 0.f, 0.f};
+    srcnn::host::DevBuf col_frag;
     // staging for the host-buffer entry points
     srcnn::host::DevBuf in_u8, out_u8, pre_f32, planes, plane1, kern, sink;
     // seam scratch (srcnn_kernels.h) is written by one launch and read by the seam kernel behind it: one buffer per
@@ -335,6 +341,10 @@ int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11);
 int use_layer3(srcnn_ctx *c, const float *kernel, float bias);
 inline bool has_model(const srcnn_ctx *c) { return c->has_l12 && c->has_l3; }
+// The luma strip path may run: a 1-channel 9-1-5 model with replicate padding.  Every entry point that runs only that path (row
+// stripes, halo buffers, several GPUs, unfused, per-layer device calls, the row bands of srcnn_forward_y) tests this one
+// predicate; srcnn_forward_y_dev sends the other 1-channel models to the banded path and refuses a colour model.
+inline bool luma_path_ok(const srcnn_ctx *c) { return c->channels == 1 && c->f2 == 1 && c->padding != SRCNN_PAD_ZERO; }
 void drop_spatial_model(srcnn_ctx *c);
 
 // the entry points that run the 9-1-5 path with replicate padding only (row stripes, halo buffers, several GPUs, unfused,
@@ -345,6 +355,17 @@ int refuse_spatial(srcnn_ctx *c, const char *what);
 using ForwardSpatialFn = int (*)(srcnn_ctx *c, const uint8_t *src, size_t src_stride, size_t src_frame_pitch, uint8_t *dst,
                                  size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre);
 extern ForwardSpatialFn forward_spatial;
+// srcnn_process_bgr(_dev) with a colour model loaded (srcnn_color.cpp sets it, as forward_spatial above): the bicubic resize of
+// all three channels, then the colour model on the interleaved result.
+using ProcessColorFn = int (*)(srcnn_ctx *c, const uint8_t *d_bgr, size_t stride, int w, int h, int ow, int oh, uint8_t *d_out,
+                               size_t out_stride);
+extern ProcessColorFn process_bgr_color;
+// ---- srcnn_host.cpp: the cubic resize of n_planes planes on the device ----
+int resize_planes_dev(srcnn_ctx *c, const uint8_t *src, long sstride, long spitch, int sw, int sh, uint8_t *dst, long dstride,
+                      long dpitch, int dw, int dh, int n_planes);
+// ---- srcnn_spatial.cpp: the packers the colour unit shares ----
+void pack_spatial_l2(int f2, const float *w2, const float *b2, float *out);
+void pack_l3z(const float *w3, float *out);
 constexpr size_t kSpatialWorkBytes = (size_t)512 << 20;     // bound of the two band maps (include/srcnn_amd.h, srcnn_set_model)
 extern const char *const kNoModel;
 

@@ -82,6 +82,10 @@ int process_bgr_dev(srcnn_ctx *c, const uint8_t *d_bgr, size_t stride, int w, in
 {
     const int ow = (int)((float)w * scale), oh = (int)((float)h * scale);    // src/srcnn.cpp:573-575
     if (ow <= 0 || oh <= 0) return fail(c, SRCNN_ERR_INVALID, "scale too small");   // :485-495
+    if (c->channels != 1) {       // a colour model: all three channels resized, then the model (srcnn_color.cpp)
+        if (!process_bgr_color) return fail(c, SRCNN_ERR_STATE, "this build has no colour-model path");
+        return process_bgr_color(c, d_bgr, stride, w, h, ow, oh, d_out, out_stride);
+    }
     const size_t lo = (size_t)w * h, hi = (size_t)ow * oh;
     int rc;
     if ((rc = reserve(c, c->ycc_lo, 3 * lo))) return rc;
@@ -302,7 +306,7 @@ int srcnn_forward_y(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uint8_t
     // bands of >= 1024 rows: shorter ones lose more in their launches than the overlap wins (measured: 3840x2160 1.35 ms
     // in one piece, 1.27 in two bands, 1.28 in four, 1.40 in eight; 7680x4320 5.20 -> 4.44 in four)
     int n_bands = env_bands ? std::atoi(env_bands) : ((long)width * height >= (4L << 20) ? std::min(8, height / 1024) : 1);
-    if (c->mode == SRCNN_MODE_EXACT || preclamp || n_bands < 1 || c->f2 > 1 || c->padding == SRCNN_PAD_ZERO)
+    if (c->mode == SRCNN_MODE_EXACT || preclamp || n_bands < 1 || !luma_path_ok(c))
         n_bands = 1;        // (bands: row stripes, the replicate-padded 9-1-5 model only)
     n_bands = std::min(n_bands, std::max(1, height / 64));
     if (n_bands == 1) {

@@ -263,7 +263,7 @@ size_t spatial_l2_lds_bytes(int f2);
 hipError_t launch_spatial_l1(bool zero, const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag,
                              float *map, long mpitch, hipStream_t st);
 // 32 planar maps (row stride W) of rows [o0, o1) from the 64 maps of rows [m0, m1) (which must hold rows o0 - r2 .. o1 + r2 - 1,
-// clamped to the image); zero: the map outside the image is 0 (f2 = 1, 3, 5), else replicated (f2 = 3, 5)
+// clamped to the image); zero: the map outside the image is 0, else replicated (f2 = 1, 3, 5)
 hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
                              const float *frag, const float *bias, float *out, long opitch, hipStream_t st);
 // Layer 3 under zero padding: u8 rows [b0, b1) of dst (row stride dstride, image rows; pre: the value before truncation, same
@@ -273,6 +273,25 @@ hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, i
 constexpr int SPATIAL_NFRAG_L3Z = 16;
 hipError_t launch_spatial_l3z(const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, const float *frag,
                               float b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
+
+// ---- layers 1 and 3 of the colour models (srcnn_color_kernels.hip; srcnn_set_model_color) ----
+// Fragment table of a colour model, floats: layer 1 [3 channels][COLOR_NFRAG_L1 / 3][64] (per input channel c the layer-1 table
+// above: fragment t * 41 + s, lane l: channel 32t + (l & 31), tap 2s + (l >> 5); tap 81: b1 for c = 2, else 0), then layer 2 as
+// above ([8][f2 * f2][4][64] and b2 [32]), then layer 3 [3 output channels][16][64] (per channel the SPATIAL_NFRAG_L3Z set of
+// its W3).
+constexpr int COLOR_NFRAG_L1 = 3 * SPATIAL_NFRAG_L1, COLOR_NFRAG_L3 = 3 * SPATIAL_NFRAG_L3Z;
+__host__ __device__ constexpr size_t color_l2_offset() { return (size_t)COLOR_NFRAG_L1 * 64; }
+__host__ __device__ constexpr size_t color_l3_offset(int f2) { return color_l2_offset() + (size_t)f2 * f2 * 2048 + 32; }
+__host__ __device__ constexpr size_t color_table_floats(int f2) { return color_l3_offset(f2) + (size_t)COLOR_NFRAG_L3 * 64; }
+// 64 planar maps of image rows [m0, m1) from 3 u8 channels at src[y * sstride + x * px_step + c * ch_step]
+hipError_t launch_color_l1(bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
+                           const float *frag, float *map, long mpitch, hipStream_t st);
+// Rows [b0, b1) of an interleaved 3-byte-pixel image dst (pre: the values before truncation at the same element offsets, or
+// null) from the 32 planar maps of rows [o0, o1), as launch_spatial_l3z; frag: the COLOR_NFRAG_L3 fragments, b3: 3 floats
+hipError_t launch_color_l3(bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                           const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
+// interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
+hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 
 // ---- pipeline steps around the conv path (srcnn_pipeline.hip) ---------------
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);

@@ -379,7 +379,7 @@ int srcnn_conv99x11_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, f
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
-    if (c->f2 > 1 || c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv99x11_dev");
+    if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_conv99x11_dev");
     if (!c->has_l12) return fail(c, SRCNN_ERR_STATE, "layers 1-2 not loaded (srcnn_set_weights / srcnn_conv99x11)");
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_planes, plane_stride, width, height) ||
         plane_pitch < plane_stride * (size_t)height || bad_pitch(plane_pitch))
@@ -409,7 +409,7 @@ int srcnn_conv55_dev(srcnn_ctx *c, const float *d_planes, size_t plane_stride, s
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
-    if (c->f2 > 1 || c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv55_dev");
+    if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_conv55_dev");
     if (!c->has_l3) return fail(c, SRCNN_ERR_STATE, "layer 3 not loaded (srcnn_set_weights / srcnn_conv55)");
     if (bad_plane(d_planes, plane_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) ||
         plane_pitch < plane_stride * (size_t)height || bad_pitch(plane_pitch))
@@ -441,7 +441,7 @@ int srcnn_forward_y_unfused_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_s
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
-    if (c->f2 > 1 || c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_forward_y_unfused_dev");
+    if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_forward_y_unfused_dev");
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) || !d_work ||
         n_frames <= 0)
@@ -501,8 +501,10 @@ int srcnn_forward_y_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, s
     if (ranges_overlap(d_src, span_elems(src_stride, src_frame_pitch, width, height, n_frames), d_dst,
                        span_elems(dst_stride, dst_frame_pitch, width, height, n_frames)))
         return fail(c, SRCNN_ERR_INVALID, "forward_y_dev: src and dst overlap (the path cannot run in place)");
-    // a 9-3-5 / 9-5-5 model, or any model under zero padding: banded layer 1 -> spatial layer 2 -> layer 3 (srcnn_spatial.cpp)
-    if (c->f2 > 1 || c->padding == SRCNN_PAD_ZERO) {
+    // a 9-3-5 / 9-5-5 model, or any model under zero padding: banded layer 1 -> spatial layer 2 -> layer 3 (srcnn_spatial.cpp);
+    // a colour model runs through srcnn_forward_color_dev only
+    if (!luma_path_ok(c)) {
+        if (c->channels != 1) return refuse_spatial(c, "srcnn_forward_y_dev");
         if ((rc = flush_seams(c))) return rc;
         if (!forward_spatial) return fail(c, SRCNN_ERR_STATE, "this build has no spatial layer-2 path");
         return forward_spatial(c, d_src, src_stride, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, width, height, n_frames,
@@ -570,7 +572,7 @@ int srcnn_forward_y_rows_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stri
     BIND_KEEP(c);
     int rc = SRCNN_OK;
     (void)rc;
-    if (c->f2 > 1 || c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_forward_y_rows_dev");
+    if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_forward_y_rows_dev");
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) ||
         row_begin < 0 || row_end > height || row_begin >= row_end ||
@@ -597,7 +599,7 @@ int srcnn_forward_y_rows_halo_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src
                                   int row_begin, int row_end)
 {
     BIND_KEEP(c);
-    if (c->f2 > 1 || c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_forward_y_rows_halo_dev");
+    if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_forward_y_rows_halo_dev");
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     const int src_row1 = src_row0 + src_rows;
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) || src_rows <= 0 ||

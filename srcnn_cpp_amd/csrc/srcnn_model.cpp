@@ -243,8 +243,15 @@ const char *const kNoModel = "the model is not loaded: srcnn_set_weights not cal
 // tables equal to the uploaded ones are not packed or uploaded again.
 ForwardSpatialFn forward_spatial = nullptr;
 
+ProcessColorFn process_bgr_color = nullptr;
+
 int refuse_spatial(srcnn_ctx *c, const char *what)
 {
+    if (c->channels != 1)
+        return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model only: the context holds a colour 9-%d-5 model "
+                                        "(srcnn_set_model_color); use srcnn_forward_color / srcnn_forward_color_dev / "
+                                        "srcnn_process_bgr* in SRCNN_MODE_MFMA, or load a 1-channel model",
+                    what, c->f2);
     if (c->padding == SRCNN_PAD_ZERO)
         return fail(c, SRCNN_ERR_STATE, "%s has replicate padding only: the context is set to SRCNN_PAD_ZERO (srcnn_set_padding); "
                                         "use srcnn_forward_y_dev / srcnn_forward_y / srcnn_forward_y_frames / srcnn_process_bgr* "
@@ -255,13 +262,15 @@ int refuse_spatial(srcnn_ctx *c, const char *what)
                 what, c->f2);
 }
 
-// A per-filter call that loads weights under a 9-3-5 / 9-5-5 model ends that model (include/srcnn_amd.h, srcnn_set_model):
-// the context goes back to the 9-1-5 tables holding only the layers loaded from then on, so a whole-path call returns
-// SRCNN_ERR_STATE until srcnn_set_model / srcnn_set_weights (or the per-filter calls have loaded all three layers).
+// A per-filter call that loads weights under a 9-3-5 / 9-5-5 or a colour model ends that model (include/srcnn_amd.h,
+// srcnn_set_model, srcnn_set_model_color): the context goes back to the 9-1-5 tables holding only the layers loaded from then
+// on, so a whole-path call returns SRCNN_ERR_STATE until srcnn_set_model / srcnn_set_weights (or the per-filter calls have
+// loaded all three layers).
 void drop_spatial_model(srcnn_ctx *c)
 {
-    if (c->f2 == 1) return;
+    if (c->f2 == 1 && c->channels == 1) return;
     c->f2 = 1;
+    c->channels = 1;
     c->has_l12 = c->has_l3 = false;
     std::fill(c->host_raw.begin(), c->host_raw.end(), 0.f);
 }
@@ -306,6 +315,10 @@ int srcnn_set_weights(srcnn_ctx *c, const float *k99, const float *b99, const fl
     (void)rc;
     if (!k99 || !b99 || !k11 || !b11 || !k55) return fail(c, SRCNN_ERR_INVALID, "null weight table");
     c->f2 = 1;                  // back on the 9-1-5 path (srcnn_set_model)
+    if (c->channels != 1) {     // the end of a colour model: its zero 9-1-5 tables are replaced whatever the caller passes
+        c->channels = 1;
+        c->has_l12 = c->has_l3 = false;
+    }
     // a caller that passes its const tables on every call (the reference does, src/srcnn.cpp:609,627) packs and uploads once
     const float *hr = c->host_raw.data();
     if (c->has_l12 && c->has_l3 && hr[7328] == b55 && !std::memcmp(hr, b99, 64 * 4) && !std::memcmp(hr + 64, k99, 5184 * 4) &&

@@ -30,7 +30,7 @@ int check_ctx_set(srcnn_ctx *const *ctxs, int n_ctx)
     for (int k = 0; k < n_ctx; ++k) {
         if (!ctxs[k]) return SRCNN_ERR_INVALID;
         if (!has_model(ctxs[k])) return fail(ctxs[k], SRCNN_ERR_STATE, "%s", kNoModel);
-        if (ctxs[k]->f2 > 1 || ctxs[k]->padding == SRCNN_PAD_ZERO) return refuse_spatial(ctxs[k], "the several-GPU entry points (striped, lanes, multi)");
+        if (!luma_path_ok(ctxs[k])) return refuse_spatial(ctxs[k], "the several-GPU entry points (striped, lanes, multi)");
         for (int j = 0; j < k; ++j)
             if (ctxs[j] == ctxs[k]) return fail(ctxs[k], SRCNN_ERR_INVALID, "the same context appears twice");
     }

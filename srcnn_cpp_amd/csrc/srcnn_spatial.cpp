@@ -10,18 +10,10 @@ using namespace srcnn::host;
 namespace srcnn {
 namespace host {
 
-// The fragment table of srcnn_kernels.h (spatial_table_floats()).  w2 is [32][64][f2][f2] (PyTorch's conv2.weight).
-static void pack_spatial(int f2, const float *w1, const float *b1, const float *w2, const float *b2, float *out)
+// Layer 2 of the fragment table (srcnn_kernels.h): [8 chunks][f2 * f2 taps][4 pairs][64], then b2 [32].  w2 is [32][64][f2][f2]
+// (PyTorch's conv2.weight).  Also the layer 2 of a colour model (srcnn_color.cpp).
+void pack_spatial_l2(int f2, const float *w2, const float *b2, float *o2)
 {
-    for (int l = 0; l < 64; ++l) {
-        const int i = l & 31, kk = l >> 5;
-        for (int t = 0; t < 2; ++t)
-            for (int s = 0; s < 41; ++s) {
-                const int tap = 2 * s + kk, c = 32 * t + i;
-                out[(t * 41 + s) * 64 + l] = tap < 81 ? w1[c * 81 + tap] : b1[c];
-            }
-    }
-    float *o2 = out + (size_t)SPATIAL_NFRAG_L1 * 64;
     const int taps = f2 * f2;
     for (int chunk = 0; chunk < 8; ++chunk)
         for (int tap = 0; tap < taps; ++tap)
@@ -33,8 +25,23 @@ static void pack_spatial(int f2, const float *w1, const float *b1, const float *
     std::memcpy(o2 + (size_t)taps * 2048, b2, 32 * sizeof(float));
 }
 
-// The A fragments of spatial_l3z_kernel (srcnn_kernels.h, SPATIAL_NFRAG_L3Z) from W3 [32][5][5].
-static void pack_l3z(const float *w3, float *out)
+// The fragment table of srcnn_kernels.h (spatial_table_floats()).
+static void pack_spatial(int f2, const float *w1, const float *b1, const float *w2, const float *b2, float *out)
+{
+    for (int l = 0; l < 64; ++l) {
+        const int i = l & 31, kk = l >> 5;
+        for (int t = 0; t < 2; ++t)
+            for (int s = 0; s < 41; ++s) {
+                const int tap = 2 * s + kk, c = 32 * t + i;
+                out[(t * 41 + s) * 64 + l] = tap < 81 ? w1[c * 81 + tap] : b1[c];
+            }
+    }
+    pack_spatial_l2(f2, w2, b2, out + (size_t)SPATIAL_NFRAG_L1 * 64);
+}
+
+// The A fragments of spatial_l3z_kernel (srcnn_kernels.h, SPATIAL_NFRAG_L3Z) from W3 [32][5][5]; a colour model packs one
+// such set per output channel.
+void pack_l3z(const float *w3, float *out)
 {
     for (int s = 0; s < SPATIAL_NFRAG_L3Z; ++s)
         for (int l = 0; l < 64; ++l) {
@@ -155,6 +162,7 @@ int srcnn_set_model(srcnn_ctx *c, int f2, const float *k99, const float *b99, co
     // layer 3 (and the has-model state) through the 9-1-5 tables, with a zero 1x1 layer 2 that nothing of this model reads
     static const std::vector<float> zero_w2(2048, 0.f);
     c->f2 = 1;
+    c->channels = 1;
     if ((rc = upload_weights(c, k99, b99, zero_w2.data(), b2, k55, b55))) return rc;
     c->has_l12 = c->has_l3 = true;
     if ((rc = reserve(c, c->sp_frag, table.size() * sizeof(float)))) return rc;

@@ -269,12 +269,14 @@ hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, i
 {
     const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS));
     const size_t lds = spatial_l2_lds_bytes(f2);
-    if (f2 == 3 && !zero) launch_l2<3, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    if (f2 == 1 && !zero) launch_l2<1, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
+    else if (f2 == 3 && !zero) launch_l2<3, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
     else if (f2 == 5 && !zero) launch_l2<5, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
     else if (f2 == 1 && zero) launch_l2<1, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
     else if (f2 == 3 && zero) launch_l2<3, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
     else if (f2 == 5 && zero) launch_l2<5, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else return hipErrorInvalidValue;          // (f2 = 1 under replicate padding is the strip kernels' model)
+    else return hipErrorInvalidValue;
+    // (f2 = 1 under replicate padding: the colour 9-1-5 model; the 1-channel one runs on the strip kernels)
     return hipGetLastError();
 }
 

@@ -1,9 +1,11 @@
 """Time the 9-1-5, 9-3-5 and 9-5-5 models (srcnn_set_model) on one GPU: device-resident planes, HIP events around each call of
 srcnn_forward_y_dev on the context's stream, warm-up calls excluded.  Reports ms per plane, MPix/s and the fraction of the
-f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81 + 32*64*f2^2 + 32*25).
+f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81*C + 32*64*f2^2 + 32*25*C) for C channels.
 
-    python tools/model_bench.py [--f2 1 3 5] [--padding replicate|zero|both] [--sizes 3840x2160 1920x1080] [--steps 20]
-                                [--warmup 3] [--json out.json]
+    python tools/model_bench.py [--channels 1 3] [--f2 1 3 5] [--padding replicate|zero|both] [--sizes 3840x2160 1920x1080]
+                                [--steps 20] [--warmup 3] [--json out.json]
+
+--channels 3 times the colour models (srcnn_set_model_color) through srcnn_forward_color_dev on interleaved 3-byte pixels.
 
 --padding both times each model and size with replicate padding, then with zero padding (srcnn_set_padding), in one process.
 """
@@ -23,8 +25,8 @@ from srcnn_cpp_amd.synth import synth_luma  # noqa: E402
 PEAK_TFLOPS = 157.3
 
 
-def flop_per_pixel(f2):
-    return 2 * (64 * 81 + 32 * 64 * f2 * f2 + 32 * 25)
+def flop_per_pixel(f2, channels=1):
+    return 2 * (64 * 81 * channels + 32 * 64 * f2 * f2 + 32 * 25 * channels)
 
 
 def model(f2, seed=0):
@@ -34,21 +36,34 @@ def model(f2, seed=0):
             rng.normal(0, 0.02, (32, 5, 5)).astype(np.float32), 60.0)
 
 
-def time_plane(ctx, w, h, steps, warmup):
-    d_src = torch.from_numpy(synth_luma(w, h)).cuda()
+def color_model(f2, seed=0):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0, 0.03 / np.sqrt(3), (64, 3, 9, 9)).astype(np.float32), rng.normal(0, 1, 64).astype(np.float32),
+            rng.normal(0, 0.08 / f2, (32, 64, f2, f2)).astype(np.float32), rng.normal(0, 1, 32).astype(np.float32),
+            rng.normal(0, 0.02, (3, 32, 5, 5)).astype(np.float32), np.full(3, 60.0, np.float32))
+
+
+def time_plane(ctx, w, h, steps, warmup, channels=1):
+    if channels == 3:
+        y = synth_luma(w, h)
+        d_src = torch.from_numpy(np.ascontiguousarray(np.stack([y, y[::-1], y[:, ::-1]], axis=2))).cuda()
+        run = lambda: ctx.forward_color_dev(d_src.data_ptr(), 3 * w, 0, d_dst.data_ptr(), 3 * w, 0, w, h, 1)
+    else:
+        d_src = torch.from_numpy(synth_luma(w, h)).cuda()
+        run = lambda: ctx.forward_y_dev(d_src.data_ptr(), w, 0, d_dst.data_ptr(), w, 0, w, h, 1)
     d_dst = torch.empty_like(d_src)
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
     ctx.set_stream(stream.cuda_stream)
     try:
         for _ in range(warmup):
-            ctx.forward_y_dev(d_src.data_ptr(), w, 0, d_dst.data_ptr(), w, 0, w, h, 1)
+            run()
         ctx.synchronize()
         ms = []
         for _ in range(steps):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(stream)
-            ctx.forward_y_dev(d_src.data_ptr(), w, 0, d_dst.data_ptr(), w, 0, w, h, 1)
+            run()
             b.record(stream)
             b.synchronize()
             ms.append(a.elapsed_time(b))
@@ -59,6 +74,7 @@ def time_plane(ctx, w, h, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--channels", type=int, nargs="+", default=[1], choices=[1, 3])
     ap.add_argument("--f2", type=int, nargs="+", default=[3, 5], choices=[1, 3, 5])
     ap.add_argument("--padding", choices=["replicate", "zero", "both"], default="replicate")
     ap.add_argument("--sizes", nargs="+", default=["3840x2160", "1920x1080"])
@@ -69,21 +85,23 @@ def main():
     paddings = ["replicate", "zero"] if args.padding == "both" else [args.padding]
     rows = []
     with S.Context(0) as ctx:
-        for f2 in args.f2:
-            ctx.set_model(*model(f2))
-            for size in args.sizes:
-                w, h = map(int, size.split("x"))
-                for padding in paddings:
-                    ctx.set_padding(padding)
-                    med, best = time_plane(ctx, w, h, args.steps, args.warmup)
-                    px = w * h
-                    tflops = flop_per_pixel(f2) * px / (med * 1e-3) / 1e12
-                    row = dict(model=f"9-{f2}-5", padding=padding, width=w, height=h, ms_per_plane=round(med, 3),
-                               ms_min=round(best, 3), mpix_per_s=round(px / (med * 1e-3) / 1e6, 1),
-                               flop_per_pixel=flop_per_pixel(f2), tflops=round(tflops, 2),
-                               fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps, warmup=args.warmup)
-                    rows.append(row)
-                    print(json.dumps(row), flush=True)
+        for channels in args.channels:
+            for f2 in args.f2:
+                ctx.set_model(*(color_model(f2) if channels == 3 else model(f2)))
+                for size in args.sizes:
+                    w, h = map(int, size.split("x"))
+                    for padding in paddings:
+                        ctx.set_padding(padding)
+                        med, best = time_plane(ctx, w, h, args.steps, args.warmup, channels)
+                        px = w * h
+                        fpp = flop_per_pixel(f2, channels)
+                        tflops = fpp * px / (med * 1e-3) / 1e12
+                        row = dict(model=f"9-{f2}-5", channels=channels, padding=padding, width=w, height=h,
+                                   ms_per_plane=round(med, 3), ms_min=round(best, 3),
+                                   mpix_per_s=round(px / (med * 1e-3) / 1e6, 1), flop_per_pixel=fpp, tflops=round(tflops, 2),
+                                   fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps, warmup=args.warmup)
+                        rows.append(row)
+                        print(json.dumps(row), flush=True)
     if args.json:
         Path(args.json).parent.mkdir(parents=True, exist_ok=True)
         Path(args.json).write_text(json.dumps(rows, indent=1) + "\n")

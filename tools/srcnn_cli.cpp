@@ -101,6 +101,7 @@ void help(const Options &o)
     std::printf("        --scale=( ratio: 0.1 to .. ) : scaling by ratio.\n");
     std::printf("        --noverbose                  : turns off all verbose\n");
     std::printf("        --weights=FILE               : model blob, b1|W1|b2|W2|b3|W3: 8129 (9-1-5), 24513 (9-3-5) or 57281 (9-5-5) floats\n");
+    std::printf("                                       colour (BGR channels): 20099, 36483 or 69251 floats\n");
     std::printf("        --padding=zero|replicate     : padding of every layer's input (default replicate; zero = PyTorch's nn.Conv2d)\n");
     std::printf("        --help                       : this help\n\n");
 }
@@ -122,15 +123,16 @@ bool load_weights(const Options &o, const char *argv0, std::vector<float> &blob)
     cand.push_back(dir + "/../srcnn_cpp_amd/data/srcnn915_weights.f32");
     cand.push_back(dir + "/srcnn915_weights.f32");
     cand.push_back("srcnn_cpp_amd/data/srcnn915_weights.f32");
-    // a 9-1-5, 9-3-5 or 9-5-5 blob (include/srcnn_amd.h, srcnn_set_model): 8,129 / 24,513 / 57,281 floats; a file of any other
-    // size named by --weights= is an error, not a reason to fall back on the shipped model
+    // a 9-1-5, 9-3-5 or 9-5-5 blob (include/srcnn_amd.h, srcnn_set_model): 8,129 / 24,513 / 57,281 floats, or a colour one
+    // (srcnn_set_model_color, channels in BGR order): 20,099 / 36,483 / 69,251 floats; a file of any other size named by
+    // --weights= is an error, not a reason to fall back on the shipped model
     for (const auto &p : cand) {
         FILE *f = std::fopen(p.c_str(), "rb");
         if (!f) continue;
-        std::vector<float> buf(57281 + 1);
+        std::vector<float> buf(69251 + 1);
         const size_t n = std::fread(buf.data(), 4, buf.size(), f);
         std::fclose(f);
-        if (n == 8129 || n == 24513 || n == 57281) {
+        if (n == 8129 || n == 24513 || n == 57281 || n == 20099 || n == 36483 || n == 69251) {
             buf.resize(n);
             blob.swap(buf);
             return true;
@@ -221,9 +223,15 @@ int main(int argc, char **argv)
         std::printf("- GPU failure : no usable gfx950 device (error %d); there is no CPU fallback\n", rc);
         return -1;
     }
-    const int f2 = w.size() == 8129 ? 1 : (w.size() == 24513 ? 3 : 5);
-    const float *b1 = w.data(), *w1 = b1 + 64, *b2 = w1 + 5184, *w2 = b2 + 32, *w3 = w2 + 2048 * f2 * f2 + 1;
-    rc = f2 == 1 ? srcnn_set_weights(ctx, w1, b1, w2, b2, w3, w3[-1]) : srcnn_set_model(ctx, f2, w1, b1, w2, b2, w3, w3[-1]);
+    const bool color = w.size() == 20099 || w.size() == 36483 || w.size() == 69251;
+    const int f2 = (w.size() == 8129 || w.size() == 20099) ? 1 : ((w.size() == 24513 || w.size() == 36483) ? 3 : 5);
+    if (color) {        // b1 | W1 [64][3][9][9] | b2 | W2 | b3[3] | W3 [3][32][5][5]: process_bgr runs it on all three channels
+        const float *b1 = w.data(), *w1 = b1 + 64, *b2 = w1 + 15552, *w2 = b2 + 32, *b3 = w2 + 2048 * f2 * f2, *w3 = b3 + 3;
+        rc = srcnn_set_model_color(ctx, f2, w1, b1, w2, b2, w3, b3);
+    } else {
+        const float *b1 = w.data(), *w1 = b1 + 64, *b2 = w1 + 5184, *w2 = b2 + 32, *w3 = w2 + 2048 * f2 * f2 + 1;
+        rc = f2 == 1 ? srcnn_set_weights(ctx, w1, b1, w2, b2, w3, w3[-1]) : srcnn_set_model(ctx, f2, w1, b1, w2, b2, w3, w3[-1]);
+    }
     if (rc == SRCNN_OK && o.refbytes) rc = srcnn_set_mode(ctx, SRCNN_MODE_REFBYTES);
     if (rc == SRCNN_OK) rc = srcnn_set_padding(ctx, o.padding);
     ph.mark("srcnn_set_weights (pack + upload)");
