@@ -15,15 +15,23 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set and forwards rank
 bench.py --gpus N` (RANK already in the environment) every process is a rank.
 
 Prints ONE JSON line on rank 0, including
-  roofline      dominant kernel vs the f32 MFMA peak (HIP events per launch)
+  roofline      dominant kernel vs the f32 MFMA peak (HIP events of the timed steps)
+
+A plain run does only what that line needs: set-up, warm-up, the K timed steps, --dump-outputs.  `--full` adds the
+secondary legs, none of which is ever `value`:
+  cold_start    W warm-up + K timed steps before the clock-ramp pre-warm
+  sustained     the same step for --sustained-s seconds, N=1 only
+  two_lanes     the planes alternately on two contexts of the one GPU, N=1 only
+  e2e           the same planes from and to host memory, N=1 only
   cpu_baseline  the oracle (port of the reference loops) on the host cores, N=1 only
+  refbytes(16)  the same step in SRCNN_MODE_REFBYTES / _REFBYTES16, checked against cpu_baseline's bytes, N=1 only
+  stripe        the row-striped 7680x4320 plane (configs[3]) over the ranks, N>1 frames only
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
-import socket
 import subprocess
 import sys
 import time
@@ -139,10 +147,12 @@ def cpu_baseline(width, height):
 
 # --------------------------------------------------------------------------- self-launch
 
-def free_port() -> int:
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def rendezvous_store():
+    """The ranks' TCPStore, held by the launcher on a port the OS assigns as it binds: the ranks join it as clients
+    (TORCHELASTIC_USE_AGENT_STORE, as under torch.distributed.run).  A port picked free beforehand and bound later by rank 0
+    can be taken by another process in between (EADDRINUSE).  Makes no GPU call."""
+    from torch.distributed import TCPStore
+    return TCPStore("127.0.0.1", 0, is_master=True, wait_for_workers=False)
 
 
 def launch_ranks(n: int, cmd=None) -> int:
@@ -154,11 +164,15 @@ def launch_ranks(n: int, cmd=None) -> int:
     import signal
     import threading
 
-    port = os.environ.get("MASTER_PORT") or str(free_port())
+    store, extra = None, {}
+    port = os.environ.get("MASTER_PORT")               # given: rank 0 hosts the store there, as before
+    if not port:
+        store = rendezvous_store()
+        port, extra = str(store.port), {"TORCHELASTIC_USE_AGENT_STORE": "True"}
     procs = []
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0")
+                   MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra)
         procs.append(subprocess.Popen(cmd or [sys.executable, str(Path(__file__).resolve())] + sys.argv[1:], env=env,
                                       stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL))
     out0 = []
@@ -180,6 +194,7 @@ def launch_ranks(n: int, cmd=None) -> int:
                 kill_all()
         time.sleep(0.05)
     reader.join(timeout=5)
+    del store                                        # every rank has left: the rendezvous store may go
     for sig, h in old_handlers.items():
         signal.signal(sig, h)
     if failed is None:                               # (every rank may have exited between two polls)
@@ -406,6 +421,10 @@ def parse_args():
                          "MI355X needs ~20 launches (20-30 ms) of load to reach its steady clocks -- the first steps after "
                          "idle run 4-10 %% slower (profiles/r02/clock_ramp.txt) -- and the contract's W = 5 steps are 5 ms.  "
                          "0 disables it.")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (cold_start, sustained, two_lanes, e2e, cpu_baseline, refbytes, refbytes16, "
+                         "stripe) that the --no-* options below switch off one by one.  Without it a run does only set-up, "
+                         "warm-up, the K timed steps and --dump-outputs.")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive secondary figure (`e2e`)")
     ap.add_argument("--sustained-s", type=float, default=6.0,
@@ -648,9 +667,9 @@ def worker(args):
         return t_a, t_b, time.perf_counter(), ev_a.elapsed_time(ev_b) / max(1, k_steps)
 
     # First, the contract exactly as written: W warm-up steps from wherever the device's clocks are, K timed steps.
-    # On an idle MI355X those 25 ms sit inside the clock ramp (profiles/r02/clock_ramp.txt); reported as `cold_start`.
+    # On an idle MI355X those 25 ms sit inside the clock ramp (profiles/r02/clock_ramp.txt); reported as `cold_start` (--full).
     cold = None
-    if args.prewarm_ms > 0:
+    if args.prewarm_ms > 0 and args.full:
         for _ in range(args.warmup):
             step()
         c_a, c_b, _, c_kern = timed(args.steps)
@@ -740,8 +759,8 @@ def worker(args):
             dumped = dump_outputs(args.dump_outputs, {"output": full})
 
     # The OTHER half of the metric ("MPix/s AND ms/image at 1/2/4/8"): ms per image at N > 1 is ONE plane row-striped over the
-    # ranks (BASELINE configs[3]).  The driver's one command per N is the frames workload above; this leg rides on it, after
-    # its timed region, so that the same line carries both curves.  Never `value`.
+    # ranks (BASELINE configs[3]).  With --full this leg rides on the frames workload above, after its timed region, so that
+    # the same line carries both curves.  Never `value`.
     # (It runs LAST, behind the assembly of the line below, under a watchdog: transports that have only ever run with the ranks
     # sharing one GPU must not be able to take the measured frames figure with them if they hang on a real node.)
     stripe_obj = None
@@ -803,7 +822,7 @@ def worker(args):
                                "before the closing barrier (the K steps are bracketed by barrier + synchronize on both sides)",
                        "closing_barrier_ms": round(closing_barrier_ms, 4)},
             # the contract exactly as written -- W warm-up + K timed steps from wherever the clocks were -- measured BEFORE the
-            # pre-warm; `value` / `ms_per_step` are the steady-state figures behind it
+            # pre-warm (--full; null otherwise); `value` / `ms_per_step` are the steady-state figures behind it
             "cold_start": cold,
             "prewarm": {"ms": args.prewarm_ms, "steps": prewarm_steps,
                         "why": "untimed clock ramp before the W warm-up steps; an idle GPU runs its first ~20 launches slower"},
@@ -850,7 +869,8 @@ def worker(args):
                                     "executed_mfma_flop_per_pixel": 43008,
                                     "executed_frac": round(achieved * 43008 / S.FLOP_PER_PIXEL / peak16, 4),
                                     "vs_f32_mfma_peak": round(achieved / PEAK_F32_MFMA_TFLOPS, 4)})
-        if world == 1 and args.path == "fused" and not stripe and args.sustained_s > 0 and not args.no_cpu_baseline:     # (--no-cpu-baseline marks a quick run)
+        # ---- the secondary legs (--full), all behind the timed region ----
+        if args.full and world == 1 and args.path == "fused" and not stripe and args.sustained_s > 0 and not args.no_cpu_baseline:     # (--no-cpu-baseline marks a quick run)
             try:
                 # The timed region is K = 20-50 steps, 20-50 ms of load.  What the device sustains over SECONDS: the same step queued
                 # back to back in chunks of 200, every chunk between two events on the kernels' stream.
@@ -873,7 +893,7 @@ def worker(args):
                                     "what": f"the same step back to back for {args.sustained_s:g} s in chunks of {chunk}, HIP events per chunk; never `value`"}
             except Exception as e:             # noqa: BLE001 -- a secondary leg must not take the measured line with it
                 out["sustained"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if world == 1 and args.path == "fused" and args.mode == "mfma" and not stripe and F == 1 and not args.no_lanes:
+        if args.full and world == 1 and args.path == "fused" and args.mode == "mfma" and not stripe and F == 1 and not args.no_lanes:
             ctx2 = None
             try:
                 # TWO LANES (round 6), never `value`: the planes of a stream alternately on two contexts / HIP streams of this ONE GPU
@@ -916,7 +936,7 @@ def worker(args):
                 if ctx2 is not None:
                     ctx2.close()
                 torch.cuda.set_stream(stream)
-        if world == 1 and args.path == "fused" and not stripe and not args.no_e2e:
+        if args.full and world == 1 and args.path == "fused" and not stripe and not args.no_e2e:
             try:
                 # SURVEY 8d's secondary metric, never `value`: the same planes from and to HOST memory, PCIe-inclusive
                 # (srcnn_forward_y_frames: pinned staging, uploads / kernels / downloads of neighbouring frames overlapped).
@@ -935,12 +955,12 @@ def worker(args):
                               "output_equals_resident": bool(zlib.crc32(ho[n_e2e - 1].tobytes()) == crcs[0])}
             except Exception as e:             # noqa: BLE001 -- a secondary leg must not take the measured line with it
                 out["e2e"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(W, H)
             except Exception as e:             # noqa: BLE001 -- a secondary leg must not take the measured line with it
                 out["cpu_baseline"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if world == 1 and args.path == "fused" and args.mode == "mfma" and not stripe and not args.no_refbytes:
+        if args.full and world == 1 and args.path == "fused" and args.mode == "mfma" and not stripe and not args.no_refbytes:
             try:
                 # The same step in SRCNN_MODE_REFBYTES (the MFMA kernel + exact recomputation of the pixels next to a truncation
                 # boundary): its time, what the fix-up did, and -- against the sha256 the cpu_baseline leg's oracle made of the same
@@ -1015,7 +1035,7 @@ def worker(args):
                 out.setdefault("refbytes", {"error": f"{type(e).__name__}: {str(e)[:300]}"})
                 out.setdefault("refbytes16", {"error": f"{type(e).__name__}: {str(e)[:300]}"})
 
-    if (world > 1 and not stripe and args.path == "fused" and args.mode == "mfma" and F == 1 and not args.no_stripe_leg):
+    if (args.full and world > 1 and not stripe and args.path == "fused" and args.mode == "mfma" and F == 1 and not args.no_stripe_leg):
         import threading
 
         def give_up():
@@ -1126,10 +1146,11 @@ def worker_cxx(args):
 
     cold = None
     if args.prewarm_ms > 0:
-        for _ in range(args.warmup):
-            step()
-        c_el, _, c_kern = timed(args.steps)
-        cold = {"ms_per_step": round(c_el / args.steps * 1e3, 4), "kernel_ms": round(max(c_kern), 4)}
+        if args.full:
+            for _ in range(args.warmup):
+                step()
+            c_el, _, c_kern = timed(args.steps)
+            cold = {"ms_per_step": round(c_el / args.steps * 1e3, 4), "kernel_ms": round(max(c_kern), 4)}
         t_pw = time.perf_counter()
         while (time.perf_counter() - t_pw) * 1e3 < args.prewarm_ms:
             for _ in range(8):

@@ -54,3 +54,34 @@ def test_help_text_formats():
     import subprocess
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "--gpus" in r.stdout, r.stderr[-500:]
+
+
+def test_secondary_legs_are_opt_in(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs only what its line needs; --full asks for the secondary legs."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse_args().full is True
+
+
+GLOO_RANK_SCRIPT = r"""
+import torch, torch.distributed as dist
+dist.init_process_group("gloo")
+t = torch.ones(1) * (dist.get_rank() + 1)
+dist.all_reduce(t)
+dist.barrier()
+if dist.get_rank() == 0:
+    print(int(t.item()), flush=True)
+dist.destroy_process_group()
+"""
+
+
+def test_ranks_rendezvous_on_the_launchers_store(capfd, monkeypatch):
+    """Without MASTER_PORT the launcher holds the ranks' TCPStore itself, bound on a port the OS assigns, and the ranks join
+    it as clients: no port is picked free and bound later, so no other process can take it in between (EADDRINUSE)."""
+    monkeypatch.delenv("MASTER_PORT", raising=False)
+    bench = _bench()
+    rc = bench.launch_ranks(3, cmd=[sys.executable, "-c", GLOO_RANK_SCRIPT])
+    assert rc == 0, capfd.readouterr().err[-2000:]
+    assert capfd.readouterr().out.strip().splitlines()[-1] == "6"        # (gloo prints its own lines before)

@@ -260,13 +260,26 @@ def test_bench_rccl_unavailable_fails_loudly_or_is_marked_degraded():
 
 
 def test_bench_line_reports_both_clock_regimes_and_e2e():
-    """The default line carries the contract-as-written figure (`cold_start`: W warm-up + K steps before the pre-warm), the
+    """The --full line carries the contract-as-written figure (`cold_start`: W warm-up + K steps before the pre-warm), the
     steady-state one, the PCIe-inclusive secondary metric of SURVEY 8d (`e2e`), and what the timed window is."""
-    d = run_bench("--gpus", 1, "--width", 1920, "--height", 1080, "--steps", 10)
+    d = run_bench("--gpus", 1, "--full", "--width", 1920, "--height", 1080, "--steps", 10)
     assert d["cold_start"]["ms_per_step"] > 0 and d["cold_start"]["kernel_ms"] > 0
     assert d["e2e"]["value"] > 0 and d["e2e"]["output_equals_resident"] is True and d["e2e"]["value"] < d["value"]
     assert "closing_barrier_ms" in d["timing"]
     assert d["roofline"]["traffic"] is None or d["pmc_reference"]["traffic"] == d["roofline"]["traffic"]
+
+
+def test_plain_bench_line_runs_no_secondary_leg():
+    """Without --full a run does set-up, warm-up, the K timed steps and nothing else: the line has its headline fields and
+    the roofline of the timed steps, and none of the legs --full adds (the CPU baseline included: no --no-cpu-baseline here)."""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--width", "1920",
+                        "--height", "1080"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "SRCNN Y-channel Mpixels/sec" and d["unit"] == "MPix/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"]["kernel_ms"] > 0
+    assert d["cold_start"] is None and d["prewarm"]["steps"] > 0
+    assert not {"sustained", "two_lanes", "e2e", "cpu_baseline", "refbytes", "refbytes16", "stripe"} & set(d), sorted(d)
 
 
 def test_bench_dump_outputs_are_the_planes_of_the_last_step(tmp_path):
@@ -302,7 +315,7 @@ def test_bench_under_torch_distributed_run():
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--shared-gpu", "--no-cpu-baseline", "--width", "1920", "--height", "1080"],
+                        "--shared-gpu", "--full", "--no-cpu-baseline", "--width", "1920", "--height", "1080"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -335,7 +348,7 @@ def test_bench_four_ranks_under_torch_distributed_run():
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1",
-                        "--shared-gpu", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500)
+                        "--shared-gpu", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -357,10 +370,10 @@ def test_bench_four_ranks_under_torch_distributed_run():
 
 def test_bench_frames_line_carries_the_striped_plane():
     """ONE driver command per N must yield both halves of the metric.  `bench.py --gpus N` (frames, weak
-    scaling: `value`) now also row-stripes the 7680x4320 plane of BASELINE configs[3] over its N ranks after the timed region
+    scaling: `value`) with --full also row-stripes the 7680x4320 plane of BASELINE configs[3] over its N ranks after the timed region
     and reports ms per image per transport in `stripe`: the stitched plane's sha256 is checked in-line against
     tests/golden/config_checksums.json, RCCL's own rank count and the transport are stated, anything else is `degraded`."""
-    d = run_bench("--gpus", 2, "--shared-gpu", "--backend", "gloo", "--steps", 4)
+    d = run_bench("--gpus", 2, "--shared-gpu", "--backend", "gloo", "--full", "--steps", 4)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and d["config"]["width"] == 3840
     one = run_bench("--gpus", 1, "--frames", 2, "--steps", 4)
     assert d["config"]["output_crc32"] == one["config"]["output_crc32"]          # the frames figure's planes are untouched
@@ -373,7 +386,7 @@ def test_bench_frames_line_carries_the_striped_plane():
         assert f["ms_per_image"] > 0 and len(f["per_rank_ms"]) == 2 and f["speedup_vs_one_gpu"] > 0
     assert st["forms"]["halo"]["halo_transport"] == "host-staged (gloo)" and st["forms"]["halo"]["rccl_world"] is None
     assert st["degraded"] is True and any("shared" in w for w in st["degraded_why"])       # two ranks on one GPU is a smoke configuration
-    off = run_bench("--gpus", 2, "--shared-gpu", "--backend", "gloo", "--steps", 3, "--no-stripe-leg")
+    off = run_bench("--gpus", 2, "--shared-gpu", "--backend", "gloo", "--full", "--steps", 3, "--no-stripe-leg")
     assert "stripe" not in off
 
 
@@ -384,7 +397,7 @@ def test_a_hung_stripe_leg_does_not_take_the_frames_figure_with_it():
     waits for it in the leg's first collective."""
     import time
     t = time.time()
-    d = run_bench("--gpus", 2, "--shared-gpu", "--backend", "gloo", "--width", 1280, "--height", 720, "--stripe-timeout-s", 6,
+    d = run_bench("--gpus", 2, "--shared-gpu", "--backend", "gloo", "--full", "--width", 1280, "--height", 720, "--stripe-timeout-s", 6,
                   "--hang-stripe-rank", 1)
     assert time.time() - t < 120
     assert d["n_gpus"] == 2 and d["value"] > 0 and len(d["config"]["output_crc32"]) == 2

@@ -3,7 +3,7 @@
 # usage: tools/measure_all.sh OUTFILE
 OUT=${1:-gpurun_out/measurements.jsonl}
 : > $OUT
-run() { echo "# $*" >> $OUT; python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 >> $OUT; }
+run() { echo "# $*" >> $OUT; python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 >> $OUT; }   # --full: each line keeps its secondary legs
 run --steps 50                                                  # configs[1]: 1 x 3840x2160, fused
 run --steps 20 --path unfused                                   # same, materialising path
 run --steps 5 --frames 64                                       # configs[2]: 64 x 3840x2160, fused

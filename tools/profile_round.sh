@@ -3,7 +3,7 @@
 #   tools/profile_round.sh [OUTDIR]        (default gpurun_out/prof)
 #   PMC_ONLY=1 tools/profile_round.sh [OUTDIR]   only steps 2-3 (kernel trace + PMC passes + summary): what profiles/pmc_traffic.json
 #                                                needs after a change of the launch code that leaves the kernels alone
-# 1. the default bench line (with cpu_baseline), 2. rocprofv3 --kernel-trace --stats of the same command,
+# 1. bench lines with --full (cpu_baseline and the other secondary legs), 2. rocprofv3 --kernel-trace --stats of the same command,
 # 3. PMC passes (one counter group per run, never together with a trace), for the float32 MFMA mode and
 # for the opt-in split-f16 mode, 4. the other configurations (tools/measure_all.sh), 5. in-kernel stamps.
 # tools/pmc_summarize.py turns the PMC csv files into profiles/rNN/*_pmc_summary.json.
@@ -14,14 +14,14 @@ ROOT=$(pwd)
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "$PMC_ONLY" ]; then
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_line.json 2>> $OUT/bench_default.err      # the driver's exact command
-python bench.py --steps 20 --warmup 5 --seam-deferral off > $OUT/bench_driver_line_no_deferral.json 2>> $OUT/bench_default.err
-python bench.py --mode refbytes --no-cpu-baseline > $OUT/bench_refbytes.json 2>> $OUT/bench_default.err
-python bench.py --mode refbytes --frames 64 --steps 5 --no-cpu-baseline > $OUT/bench_refbytes_b64.json 2>> $OUT/bench_default.err
-python bench.py --mode refbytes16 --no-cpu-baseline > $OUT/bench_refbytes16.json 2>> $OUT/bench_default.err
-python bench.py --mode split16 --no-cpu-baseline > $OUT/bench_split16.json 2>> $OUT/bench_default.err
-python bench.py --mode split16 --frames 64 --steps 10 --no-cpu-baseline > $OUT/bench_split16_b64.json 2>> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_line.json 2>> $OUT/bench_default.err      # the driver's command + --full
+python bench.py --full --steps 20 --warmup 5 --seam-deferral off > $OUT/bench_driver_line_no_deferral.json 2>> $OUT/bench_default.err
+python bench.py --full --mode refbytes --no-cpu-baseline > $OUT/bench_refbytes.json 2>> $OUT/bench_default.err
+python bench.py --full --mode refbytes --frames 64 --steps 5 --no-cpu-baseline > $OUT/bench_refbytes_b64.json 2>> $OUT/bench_default.err
+python bench.py --full --mode refbytes16 --no-cpu-baseline > $OUT/bench_refbytes16.json 2>> $OUT/bench_default.err
+python bench.py --full --mode split16 --no-cpu-baseline > $OUT/bench_split16.json 2>> $OUT/bench_default.err
+python bench.py --full --mode split16 --frames 64 --steps 10 --no-cpu-baseline > $OUT/bench_split16_b64.json 2>> $OUT/bench_default.err
 fi
 for mode in mfma split16; do
   ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/trace_$mode -o trace -- \
