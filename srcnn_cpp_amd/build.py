@@ -47,9 +47,8 @@ UNITS = [
     # the resize's vertical pass is OpenCV's float32 multiply-then-add (every product and sum rounded on its own):
     # __fmul_rn / __fadd_rn are plain * and + in HIP's headers, so contraction must be off here too
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
-    # layers 1-2 of the 9-3-5 / 9-5-5 models (srcnn_set_model)
+    # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models
     ("srcnn_spatial_kernels.hip", []),
-    ("srcnn_color_kernels.hip", []),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),
@@ -57,10 +56,9 @@ UNITS = [
     ("srcnn_host.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_table(): OpenCV's float arithmetic, nothing contracted
     ("srcnn_multi.cpp", ["-x", "hip"]),
     ("srcnn_spatial.cpp", ["-x", "hip"]),
-    ("srcnn_color.cpp", ["-x", "hip"]),
 ]
 HOST_UNITS = {"srcnn_api.cpp", "srcnn_model.cpp", "srcnn_plan.cpp", "srcnn_launch.cpp", "srcnn_host.cpp", "srcnn_multi.cpp",
-              "srcnn_spatial.cpp", "srcnn_color.cpp"}
+              "srcnn_spatial.cpp"}
 
 
 def kernel_sources_fingerprint() -> str:

@@ -6,6 +6,7 @@
 //   srcnn_launch.cpp  run_strip() -- the one launch path of the strip kernels and the fix-up -- and the device-pointer entry points
 //   srcnn_host.cpp    host-buffer entry points: staging, band / frame pipelines, the reference call surface, the pipeline steps
 //   srcnn_multi.cpp   several GPUs from one host process: row-striped plane, frame ranges
+//   srcnn_spatial.cpp the banded path (9-3-5 / 9-5-5, zero padding, colour models): weight table, gate, band loop, entry points
 #pragma once
 #include "../../include/srcnn_amd.h"
 #include "srcnn_kernels.h"
@@ -169,27 +170,25 @@ struct srcnn_ctx {
     srcnn::host::DevBuf wfrag16; // split-f16 fragments (SRCNN_MODE_SPLIT16), S16_TABLE_BYTES
     bool split16_ok = false;   // the uploaded weights fit the f16 ranges of that mode (split16_range_ok)
     srcnn::host::DevBuf wraw;    // b1|W1|b2|W2|b3|W3 in convdata.h order (exact kernels)
-    // a 9-3-5 / 9-5-5 model (srcnn_set_model, srcnn_spatial.cpp): f2 > 1 runs layers 1-2 from sp_frag (spatial_table_floats())
-    // and layer 3 from wfrag / b3, which srcnn_set_model loads with W2 = 0; the two maps of one row band, and the event behind
-    // the last launch that used them (so that launches on another stream -- the frame lanes -- wait before reusing them)
+    // The banded path (srcnn_spatial.cpp): every model but a 1-channel 9-1-5 one under replicate padding.  channels, f2: the
+    // loaded model (a colour model: channels = 3, and the 9-1-5 tables hold a zero model that no gate lets run, luma_path_ok).
+    // Layers 1-3 run from sp_table (spatial_table_floats(channels, f2)) with the biases sp_b3, packed for the model with layer 2
+    // sp_f2: srcnn_set_model (f2 > 1) and srcnn_set_model_color pack them when they load, a 9-1-5 model is packed from host_raw
+    // the first time a zero-padded call needs it (sp_f2 = 0: nothing packed since the last upload_weights).  A 1-channel f2 > 1
+    // model under replicate padding runs layer 3 on MODE_L3 from wfrag / b3, which srcnn_set_model loads with W2 = 0.  The two
+    // maps of one row band, and the event behind the last launch that used them (so that launches on another stream -- the frame
+    // lanes -- wait before reusing them).
+    int channels = 1;
     int f2 = 1;
-    srcnn::host::DevBuf sp_frag, sp_map64, sp_map32;
+    srcnn::host::DevBuf sp_table, sp_map64, sp_map32;
+    float sp_b3[3] = {0.f, 0.f, 0.f};
+    int sp_f2 = 0;
     hipEvent_t sp_done = nullptr;
     hipStream_t sp_stream = nullptr;
-    // SRCNN_PAD_ZERO (srcnn_set_padding): every model runs the banded path above with the zero-padding kernels.  whole_model:
-    // the tables came from srcnn_set_weights / srcnn_set_model, not from per-filter calls.  zp_f2: the f2 for which zp_frag
-    // (layer-3 fragments, SPATIAL_NFRAG_L3Z) -- and for f2 = 1 sp_frag -- were packed from host_raw, 0 = not since the last
-    // upload_weights; the replicate path never packs them
+    // SRCNN_PAD_ZERO (srcnn_set_padding): every model runs the banded path with the zero-padding kernels.  whole_model: the
+    // tables came from srcnn_set_weights / srcnn_set_model(_color), not from per-filter calls
     int padding = SRCNN_PAD_REPLICATE;
     bool whole_model = false;
-    int zp_f2 = 0;
-    srcnn::host::DevBuf zp_frag;
-    // a colour model (srcnn_set_model_color, srcnn_color.cpp): channels = 3, f2 its layer 2; layers 1-3 run from col_frag
-    // (color_table_floats(f2)) on the band maps above, b3 of each output channel in col_b3.  The 9-1-5 tables then hold a zero
-    // model that no gate lets run (luma_path_ok).
-    int channels = 1;
-    float col_b3[3] = {0.f, 0.f, 0.f};
-    srcnn::host::DevBuf col_frag;
     // staging for the host-buffer entry points
     srcnn::host::DevBuf in_u8, out_u8, pre_f32, planes, plane1, kern, sink;
     // seam scratch (srcnn_kernels.h) is written by one launch and read by the seam kernel behind it: one buffer per
@@ -350,22 +349,12 @@ void drop_spatial_model(srcnn_ctx *c);
 // the entry points that run the 9-1-5 path with replicate padding only (row stripes, halo buffers, several GPUs, unfused,
 // per-layer device calls; under SRCNN_PAD_ZERO also the per-filter calls): the message names the model or the padding
 int refuse_spatial(srcnn_ctx *c, const char *what);
-// The whole path of an f2 > 1 model on device planes (srcnn_forward_y_dev with srcnn_get_model_f2() > 1), defined in
-// srcnn_spatial.cpp, which sets this pointer when the library loads: the units above reach the spatial path only through it.
-using ForwardSpatialFn = int (*)(srcnn_ctx *c, const uint8_t *src, size_t src_stride, size_t src_frame_pitch, uint8_t *dst,
-                                 size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre);
-extern ForwardSpatialFn forward_spatial;
-// srcnn_process_bgr(_dev) with a colour model loaded (srcnn_color.cpp sets it, as forward_spatial above): the bicubic resize of
-// all three channels, then the colour model on the interleaved result.
-using ProcessColorFn = int (*)(srcnn_ctx *c, const uint8_t *d_bgr, size_t stride, int w, int h, int ow, int oh, uint8_t *d_out,
-                               size_t out_stride);
-extern ProcessColorFn process_bgr_color;
-// ---- srcnn_host.cpp: the cubic resize of n_planes planes on the device ----
-int resize_planes_dev(srcnn_ctx *c, const uint8_t *src, long sstride, long spitch, int sw, int sh, uint8_t *dst, long dstride,
-                      long dpitch, int dw, int dh, int n_planes);
-// ---- srcnn_spatial.cpp: the packers the colour unit shares ----
-void pack_spatial_l2(int f2, const float *w2, const float *b2, float *out);
-void pack_l3z(const float *w3, float *out);
+// ---- srcnn_spatial.cpp: the banded path (layer 1 -> spatial layer 2 -> layer 3 per row band) ----
+// n_frames planes of the loaded model (c->channels, c->f2, c->padding; refused with SRCNN_ERR_STATE where the mode, the padding
+// or the way the model was loaded has no banded arithmetic): input byte c of pixel (y, x) at src[y * src_stride + x * px_step +
+// c * ch_step] (1 channel: px_step 1, ch_step 0), output (and pre, at the same element offsets) pixels of c->channels bytes.
+int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_step, size_t ch_step, size_t src_frame_pitch,
+                   uint8_t *dst, size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre);
 constexpr size_t kSpatialWorkBytes = (size_t)512 << 20;     // bound of the two band maps (include/srcnn_amd.h, srcnn_set_model)
 extern const char *const kNoModel;
 

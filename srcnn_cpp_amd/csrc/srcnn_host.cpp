@@ -65,8 +65,8 @@ int ensure_tables(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResizeTables *t)
 }
 
 // Device-side cubic resize of n_planes planes.
-int resize_planes_dev(srcnn_ctx *c, const uint8_t *src, long sstride, long spitch, int sw, int sh, uint8_t *dst,
-                      long dstride, long dpitch, int dw, int dh, int n_planes)
+static int resize_planes_dev(srcnn_ctx *c, const uint8_t *src, long sstride, long spitch, int sw, int sh, uint8_t *dst,
+                             long dstride, long dpitch, int dw, int dh, int n_planes)
 {
     ResizeTables t;
     int rc;
@@ -82,16 +82,19 @@ int process_bgr_dev(srcnn_ctx *c, const uint8_t *d_bgr, size_t stride, int w, in
 {
     const int ow = (int)((float)w * scale), oh = (int)((float)h * scale);    // src/srcnn.cpp:573-575
     if (ow <= 0 || oh <= 0) return fail(c, SRCNN_ERR_INVALID, "scale too small");   // :485-495
-    if (c->channels != 1) {       // a colour model: all three channels resized, then the model (srcnn_color.cpp)
-        if (!process_bgr_color) return fail(c, SRCNN_ERR_STATE, "this build has no colour-model path");
-        return process_bgr_color(c, d_bgr, stride, w, h, ow, oh, d_out, out_stride);
-    }
     const size_t lo = (size_t)w * h, hi = (size_t)ow * oh;
     int rc;
     if ((rc = reserve(c, c->ycc_lo, 3 * lo))) return rc;
     if ((rc = reserve(c, c->ycc_hi, 3 * hi))) return rc;
-    if ((rc = reserve(c, c->y_sr, hi))) return rc;
     uint8_t *ycc_lo = static_cast<uint8_t *>(c->ycc_lo.p), *ycc_hi = static_cast<uint8_t *>(c->ycc_hi.p);
+    if (c->channels != 1) {
+        // a colour model: the three channels split into planes, each resized with the bicubic arithmetic below, then the model
+        // on the three resized planes (the banded path, srcnn_spatial.cpp), written as interleaved pixels
+        HIP_TRY(c, launch_split3(d_bgr, (long)stride, w, h, ycc_lo, (long)lo, c->stream));
+        if ((rc = resize_planes_dev(c, ycc_lo, w, (long)lo, w, h, ycc_hi, ow, (long)hi, ow, oh, 3))) return rc;
+        return forward_banded(c, ycc_hi, (size_t)ow, 1, hi, 0, d_out, out_stride, 0, ow, oh, 1, nullptr);
+    }
+    if ((rc = reserve(c, c->y_sr, hi))) return rc;
     uint8_t *y_sr = static_cast<uint8_t *>(c->y_sr.p);
     // Two launches around the conv path instead of three (and 54 MB instead of 93 MB at 1080p -> 4K): the colour conversion
     // happens while the resize stages its source tile, the resized Cr / Cb go straight into the final BGR.  Same integer

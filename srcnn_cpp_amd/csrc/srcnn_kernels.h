@@ -251,45 +251,31 @@ hipError_t launch_conv55_exact(const float *planes, long stride, long pitch, lon
                                int w, int h, int n_frames, const float *d_kernel800, float bias,
                                hipStream_t st);
 
-// ---- layers 1-2 of the 9-3-5 / 9-5-5 models (srcnn_spatial_kernels.hip; srcnn_set_model) ----
-// Fragment table of a spatial model, floats: [SPATIAL_NFRAG_L1][64] layer 1 (fragment t * 41 + s, lane l: channel 32t + (l & 31),
-// tap 2s + (l >> 5), 81 = b1), then layer 2 [8 chunks][f2 * f2 taps][4 pairs][64] (lane l: output channel l & 31, input
-// channel 8 chunk + 2 pair + (l >> 5)), then b2 [32].  Unscaled: the maps hold the model's own values.
-constexpr int SPATIAL_NFRAG_L1 = 82;
-__host__ __device__ constexpr size_t spatial_table_floats(int f2) { return (size_t)SPATIAL_NFRAG_L1 * 64 + (size_t)f2 * f2 * 2048 + 32; }
+// ---- the banded path (srcnn_spatial_kernels.hip): 9-3-5 / 9-5-5 models, every model under zero padding, colour models ----
+// Fragment table of a model of C = 1 or 3 channels, floats: layer 1 [C channels][SPATIAL_NFRAG_L1][64] (per input channel c:
+// fragment t * 41 + s, lane l: output channel 32t + (l & 31), tap 2s + (l >> 5); tap 81: b1 on the last channel, else 0), then
+// layer 2 [8 chunks][f2 * f2 taps][4 pairs][64] (lane l: output channel l & 31, input channel 8 chunk + 2 pair + (l >> 5)) and
+// b2 [32], then layer 3 [C output channels][SPATIAL_NFRAG_L3][64] (per output channel o, k-step s, lane l: W3[o][2s + (l >> 5)]
+// at the tap of l3_row_tap(l & 31), 0 for the unused rows).  Unscaled: the maps hold the model's own values.
+constexpr int SPATIAL_NFRAG_L1 = 82, SPATIAL_NFRAG_L3 = 16;
+__host__ __device__ constexpr size_t spatial_l2_offset(int C) { return (size_t)C * SPATIAL_NFRAG_L1 * 64; }
+__host__ __device__ constexpr size_t spatial_l3_offset(int C, int f2) { return spatial_l2_offset(C) + (size_t)f2 * f2 * 2048 + 32; }
+__host__ __device__ constexpr size_t spatial_table_floats(int C, int f2) { return spatial_l3_offset(C, f2) + (size_t)C * SPATIAL_NFRAG_L3 * 64; }
 size_t spatial_l2_lds_bytes(int f2);
-// 64 planar maps (plane pitch mpitch, row stride W) of image rows [m0, m1); zero: luma outside the image is 0 (SRCNN_PAD_ZERO),
-// else replicated
-hipError_t launch_spatial_l1(bool zero, const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag,
-                             float *map, long mpitch, hipStream_t st);
+// 64 planar maps (plane pitch mpitch, row stride W) of image rows [m0, m1) from `channels` u8 channels at src[y * sstride + x *
+// px_step + c * ch_step] (1 channel: a plane, the steps unused); zero: input outside the image is 0 (SRCNN_PAD_ZERO), else replicated
+hipError_t launch_spatial_l1(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
+                             int m0, int m1, const float *frag, float *map, long mpitch, hipStream_t st);
 // 32 planar maps (row stride W) of rows [o0, o1) from the 64 maps of rows [m0, m1) (which must hold rows o0 - r2 .. o1 + r2 - 1,
 // clamped to the image); zero: the map outside the image is 0, else replicated (f2 = 1, 3, 5)
 hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
                              const float *frag, const float *bias, float *out, long opitch, hipStream_t st);
-// Layer 3 under zero padding: u8 rows [b0, b1) of dst (row stride dstride, image rows; pre: the value before truncation, same
-// offsets, or null) from the 32 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch), which must hold every image
-// row of [b0 - 2, b1 + 2).  frag: SPATIAL_NFRAG_L3Z A fragments [16 k-steps][64 lanes] (lane l: W3[2s + (l >> 5)][tap of
-// l3_row_tap(l & 31)], 0 for the unused rows).
-constexpr int SPATIAL_NFRAG_L3Z = 16;
-hipError_t launch_spatial_l3z(const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, const float *frag,
-                              float b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
-
-// ---- layers 1 and 3 of the colour models (srcnn_color_kernels.hip; srcnn_set_model_color) ----
-// Fragment table of a colour model, floats: layer 1 [3 channels][COLOR_NFRAG_L1 / 3][64] (per input channel c the layer-1 table
-// above: fragment t * 41 + s, lane l: channel 32t + (l & 31), tap 2s + (l >> 5); tap 81: b1 for c = 2, else 0), then layer 2 as
-// above ([8][f2 * f2][4][64] and b2 [32]), then layer 3 [3 output channels][16][64] (per channel the SPATIAL_NFRAG_L3Z set of
-// its W3).
-constexpr int COLOR_NFRAG_L1 = 3 * SPATIAL_NFRAG_L1, COLOR_NFRAG_L3 = 3 * SPATIAL_NFRAG_L3Z;
-__host__ __device__ constexpr size_t color_l2_offset() { return (size_t)COLOR_NFRAG_L1 * 64; }
-__host__ __device__ constexpr size_t color_l3_offset(int f2) { return color_l2_offset() + (size_t)f2 * f2 * 2048 + 32; }
-__host__ __device__ constexpr size_t color_table_floats(int f2) { return color_l3_offset(f2) + (size_t)COLOR_NFRAG_L3 * 64; }
-// 64 planar maps of image rows [m0, m1) from 3 u8 channels at src[y * sstride + x * px_step + c * ch_step]
-hipError_t launch_color_l1(bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
-                           const float *frag, float *map, long mpitch, hipStream_t st);
-// Rows [b0, b1) of an interleaved 3-byte-pixel image dst (pre: the values before truncation at the same element offsets, or
-// null) from the 32 planar maps of rows [o0, o1), as launch_spatial_l3z; frag: the COLOR_NFRAG_L3 fragments, b3: 3 floats
-hipError_t launch_color_l3(bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                           const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
+// Layer 3: rows [b0, b1) of dst, pixels of `channels` bytes (row stride dstride; pre: the values before truncation at the same
+// element offsets, or null) from the 32 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch), which must hold every
+// image row of [b0 - 2, b1 + 2).  frag: the layer-3 part of the table above, b3: `channels` floats.  1 channel under replicate
+// padding is not a form of this kernel (the MODE_L3 strip kernel runs it).
+hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                             const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

@@ -506,9 +506,8 @@ int srcnn_forward_y_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, s
     if (!luma_path_ok(c)) {
         if (c->channels != 1) return refuse_spatial(c, "srcnn_forward_y_dev");
         if ((rc = flush_seams(c))) return rc;
-        if (!forward_spatial) return fail(c, SRCNN_ERR_STATE, "this build has no spatial layer-2 path");
-        return forward_spatial(c, d_src, src_stride, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, width, height, n_frames,
-                               d_preclamp);
+        return forward_banded(c, d_src, src_stride, 1, 0, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, width, height,
+                              n_frames, d_preclamp);
     }
     // (a pre-clamp request in REFBYTES mode wants the REFERENCE's float too: the exact kernels deliver both)
     if (c->mode == SRCNN_MODE_EXACT || ((c->mode == SRCNN_MODE_REFBYTES || c->mode == SRCNN_MODE_REFBYTES16) && d_preclamp)) {

@@ -216,7 +216,7 @@ int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float
         for (int t = 0; t < 81; ++t) raw[10177 + t * 64 + ch] = w1[ch * 81 + t];
     std::vector<uint8_t> frag16(S16_TABLE_BYTES);
     pack_fragments16(w1, b1, w2, b2, w3, frag16.data());
-    c->zp_f2 = 0;                // the zero-padding tables are packed from host_raw again when next needed (srcnn_spatial.cpp)
+    c->sp_f2 = 0;                // the banded path's table no longer holds the model (srcnn_spatial.cpp)
     int rc;
     if ((rc = reserve(c, c->wfrag, frag.size() * 4))) return rc;
     if ((rc = reserve(c, c->wfrag16, frag16.size()))) return rc;
@@ -241,10 +241,6 @@ const char *const kNoModel = "the model is not loaded: srcnn_set_weights not cal
 // The per-call tables of the reference surface (src/srcnn.cpp:609, :627: the same const arrays on every call).
 // Layers 1-2 of the model are replaced, layer 3 of any loaded model is kept (and the other way round for layer 3);
 // tables equal to the uploaded ones are not packed or uploaded again.
-ForwardSpatialFn forward_spatial = nullptr;
-
-ProcessColorFn process_bgr_color = nullptr;
-
 int refuse_spatial(srcnn_ctx *c, const char *what)
 {
     if (c->channels != 1)

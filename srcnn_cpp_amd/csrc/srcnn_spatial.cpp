@@ -1,7 +1,7 @@
-// srcnn_spatial.cpp -- the 9-3-5 / 9-5-5 models (srcnn_set_model, f2 = 3 or 5): their weight table and the banded path
-// layer 1 -> spatial layer 2 (srcnn_spatial_kernels.hip) -> MODE_L3 strip kernel (srcnn_mfma.hip) behind srcnn_forward_y_dev;
-// and zero padding (srcnn_set_padding): every model, f2 = 1 included, on the same bands with the kernels' zero-padding forms
-// and the zero-padding layer 3 (spatial_l3z_kernel).
+// srcnn_spatial.cpp -- the banded path, layer 1 -> spatial layer 2 -> layer 3 per row band (srcnn_spatial_kernels.hip): the
+// 9-3-5 / 9-5-5 models (srcnn_set_model, f2 = 3 or 5) behind srcnn_forward_y_dev, every model under zero padding
+// (srcnn_set_padding), f2 = 1 included, and the colour models (srcnn_set_model_color: 3 input and 3 output channels, 9-f2-5)
+// behind srcnn_forward_color(_dev) and srcnn_process_bgr(_dev).  One weight table per model, one gate, one band loop.
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
@@ -10,11 +10,22 @@ using namespace srcnn::host;
 namespace srcnn {
 namespace host {
 
-// Layer 2 of the fragment table (srcnn_kernels.h): [8 chunks][f2 * f2 taps][4 pairs][64], then b2 [32].  w2 is [32][64][f2][f2]
-// (PyTorch's conv2.weight).  Also the layer 2 of a colour model (srcnn_color.cpp).
-void pack_spatial_l2(int f2, const float *w2, const float *b2, float *o2)
+// The fragment table of srcnn_kernels.h (spatial_table_floats()) of a C-channel model.  w1 [64][C][9][9], w2 [32][64][f2][f2],
+// w3 [C][32][5][5] (PyTorch's conv weights).
+static void pack_spatial(int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                         float *out)
 {
+    for (int ch = 0; ch < C; ++ch)
+        for (int l = 0; l < 64; ++l) {
+            const int i = l & 31, kk = l >> 5;
+            for (int t = 0; t < 2; ++t)
+                for (int s = 0; s < 41; ++s) {
+                    const int tap = 2 * s + kk, k = 32 * t + i;
+                    out[((ch * 2 + t) * 41 + s) * 64 + l] = tap < 81 ? w1[(k * C + ch) * 81 + tap] : (ch == C - 1 ? b1[k] : 0.f);
+                }
+        }
     const int taps = f2 * f2;
+    float *o2 = out + spatial_l2_offset(C);
     for (int chunk = 0; chunk < 8; ++chunk)
         for (int tap = 0; tap < taps; ++tap)
             for (int pp = 0; pp < 4; ++pp)
@@ -23,64 +34,38 @@ void pack_spatial_l2(int f2, const float *w2, const float *b2, float *o2)
                     o2[(((size_t)chunk * taps + tap) * 4 + pp) * 64 + l] = w2[((size_t)k * 64 + ci) * taps + tap];
                 }
     std::memcpy(o2 + (size_t)taps * 2048, b2, 32 * sizeof(float));
-}
-
-// The fragment table of srcnn_kernels.h (spatial_table_floats()).
-static void pack_spatial(int f2, const float *w1, const float *b1, const float *w2, const float *b2, float *out)
-{
-    for (int l = 0; l < 64; ++l) {
-        const int i = l & 31, kk = l >> 5;
-        for (int t = 0; t < 2; ++t)
-            for (int s = 0; s < 41; ++s) {
-                const int tap = 2 * s + kk, c = 32 * t + i;
-                out[(t * 41 + s) * 64 + l] = tap < 81 ? w1[c * 81 + tap] : b1[c];
+    float *o3 = out + spatial_l3_offset(C, f2);
+    for (int o = 0; o < C; ++o)
+        for (int s = 0; s < SPATIAL_NFRAG_L3; ++s)
+            for (int l = 0; l < 64; ++l) {
+                const int tap = l3_row_tap(l & 31);
+                o3[((size_t)o * SPATIAL_NFRAG_L3 + s) * 64 + l] = tap < 0 ? 0.f : w3[(size_t)o * 800 + (2 * s + (l >> 5)) * 25 + tap];
             }
-    }
-    pack_spatial_l2(f2, w2, b2, out + (size_t)SPATIAL_NFRAG_L1 * 64);
 }
 
-// The A fragments of spatial_l3z_kernel (srcnn_kernels.h, SPATIAL_NFRAG_L3Z) from W3 [32][5][5]; a colour model packs one
-// such set per output channel.
-void pack_l3z(const float *w3, float *out)
+// The table and b3 of a C-channel 9-f2-5 model into sp_table / sp_b3 (pack_spatial's arguments)
+static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2,
+                        const float *w3, const float *b3)
 {
-    for (int s = 0; s < SPATIAL_NFRAG_L3Z; ++s)
-        for (int l = 0; l < 64; ++l) {
-            const int tap = l3_row_tap(l & 31);
-            out[s * 64 + l] = tap < 0 ? 0.f : w3[(2 * s + (l >> 5)) * 25 + tap];
-        }
-}
-
-// The zero-padding tables of the loaded model, packed from host_raw the first time a zero-padded call needs them after a load:
-// the layer-3 fragments, and for f2 = 1 the layer-1/2 table that srcnn_set_model builds for f2 = 3, 5.
-static int ensure_zero_tables(srcnn_ctx *c)
-{
-    if (c->zp_f2 == c->f2) return SRCNN_OK;
-    const float *hr = c->host_raw.data();
-    std::vector<float> l3((size_t)SPATIAL_NFRAG_L3Z * 64), table;
-    pack_l3z(hr + 7329, l3.data());
-    if (c->f2 == 1) {
-        table.resize(spatial_table_floats(1));
-        pack_spatial(1, hr + 64, hr, hr + 5280, hr + 5248, table.data());
-    }
+    std::vector<float> table(spatial_table_floats(C, f2));
+    pack_spatial(C, f2, w1, b1, w2, b2, w3, table.data());
     int rc;
-    if ((rc = reserve(c, c->zp_frag, l3.size() * sizeof(float)))) return rc;
-    if (!table.empty() && (rc = reserve(c, c->sp_frag, table.size() * sizeof(float)))) return rc;
-    HIP_TRY(c, hipDeviceSynchronize());        // launches on any stream may still read the old tables
-    HIP_TRY(c, hipMemcpy(c->zp_frag.p, l3.data(), l3.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!table.empty()) HIP_TRY(c, hipMemcpy(c->sp_frag.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
-    c->zp_f2 = c->f2;
+    if ((rc = reserve(c, c->sp_table, table.size() * sizeof(float)))) return rc;
+    HIP_TRY(c, hipDeviceSynchronize());        // launches on any stream may still read the old table
+    HIP_TRY(c, hipMemcpy(c->sp_table.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::memcpy(c->sp_b3, b3, C * sizeof(float));
+    c->sp_f2 = f2;
     return SRCNN_OK;
 }
 
-// Rows [b0, b1) of a plane need layer-2 rows [b0 - 2, b1 + 2) and layer-1 rows [b0 - 2 - r2, b1 + 2 + r2), clamped to the
-// image: a band recomputes the 2 + r2 layer-1 rows and 2 layer-2 rows either side it shares with its neighbours.  Bands are
-// as tall as kSpatialWorkBytes allows for the two maps (256 + 128 B per pixel of a row).
-static int forward_spatial_impl(srcnn_ctx *c, const uint8_t *src, size_t src_stride, size_t src_frame_pitch, uint8_t *dst,
-                                size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre)
+// The one gate of the banded path: SRCNN_OK when it may run the loaded model in the current mode and padding, else
+// SRCNN_ERR_STATE with a message that names what blocks the call
+static int banded_refusal(srcnn_ctx *c)
 {
-    int rc;
     const bool zero = c->padding == SRCNN_PAD_ZERO;
-    if (zero && c->mode != SRCNN_MODE_MFMA)
+    if (c->mode != SRCNN_MODE_MFMA && c->channels != 1)
+        return fail(c, SRCNN_ERR_STATE, "a colour model runs in SRCNN_MODE_MFMA only (mode %d has no arithmetic for it)", c->mode);
+    if (c->mode != SRCNN_MODE_MFMA && zero)
         return fail(c, SRCNN_ERR_STATE, "SRCNN_PAD_ZERO (srcnn_set_padding) runs in SRCNN_MODE_MFMA only (mode %d has replicate "
                                         "padding only)", c->mode);
     if (c->mode != SRCNN_MODE_MFMA)
@@ -89,8 +74,32 @@ static int forward_spatial_impl(srcnn_ctx *c, const uint8_t *src, size_t src_str
     if (zero && !c->whole_model)
         return fail(c, SRCNN_ERR_STATE, "SRCNN_PAD_ZERO needs a model loaded by srcnn_set_weights / srcnn_set_model: the loaded "
                                         "layers came from per-filter calls");
-    if (zero && (rc = ensure_zero_tables(c))) return rc;
-    const int r2 = (c->f2 - 1) / 2;
+    return SRCNN_OK;
+}
+
+// the colour entry points run a colour model only
+static int refuse_luma_model(srcnn_ctx *c)
+{
+    if (c->channels == 3) return SRCNN_OK;
+    return fail(c, SRCNN_ERR_STATE, "srcnn_forward_color runs a colour model only: the context holds a 1-channel 9-%d-5 model "
+                                    "(srcnn_set_model_color loads one)", c->f2);
+}
+
+// Rows [b0, b1) of a plane need layer-2 rows [b0 - 2, b1 + 2) and layer-1 rows [b0 - 2 - r2, b1 + 2 + r2), clamped to the
+// image: a band recomputes the 2 + r2 layer-1 rows and 2 layer-2 rows either side it shares with its neighbours.  Bands are
+// as tall as kSpatialWorkBytes allows for the two maps (256 + 128 B per pixel of a row).
+int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_step, size_t ch_step, size_t src_frame_pitch,
+                   uint8_t *dst, size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre)
+{
+    int rc;
+    if ((rc = banded_refusal(c))) return rc;
+    // (only a 9-1-5 model gets here unpacked: the others pack when they load)
+    if (c->sp_f2 != c->f2) {
+        const float *hr = c->host_raw.data();
+        if ((rc = upload_table(c, 1, 1, hr + 64, hr, hr + 5280, hr + 5248, hr + 7329, hr + 7328))) return rc;
+    }
+    const int C = c->channels, r2 = (c->f2 - 1) / 2;
+    const bool zero = c->padding == SRCNN_PAD_ZERO;
     const long row_bytes = 4L * width;
     const long cap = (long)(kSpatialWorkBytes / (size_t)row_bytes) - 64L * (4 + 2 * r2) - 32L * 4;
     const int band_max = (int)std::max(16L, cap / 96);
@@ -99,36 +108,40 @@ static int forward_spatial_impl(srcnn_ctx *c, const uint8_t *src, size_t src_str
     const long mrows = std::min<long>(height, band + 4 + 2 * r2), orows = std::min<long>(height, band + 4);
     const long mpitch = mrows * width, opitch = orows * width;
     if (bad_pitch((size_t)mpitch) || bad_pitch((size_t)opitch))
-        return fail(c, SRCNN_ERR_INVALID, "forward_y_dev: plane too large for a 9-%d-5 model", c->f2);
+        return fail(c, SRCNN_ERR_INVALID, "%s: plane too large for a %s9-%d-5 model", C == 1 ? "forward_y_dev" : "forward_color_dev",
+                    C == 1 ? "" : "colour ", c->f2);
     if ((rc = reserve(c, c->sp_map64, (size_t)64 * mpitch * sizeof(float)))) return rc;
     if ((rc = reserve(c, c->sp_map32, (size_t)32 * opitch * sizeof(float)))) return rc;
     if (!c->sp_done) HIP_TRY(c, hipEventCreateWithFlags(&c->sp_done, hipEventDisableTiming));
     // the maps were last used on another stream (the two lanes of srcnn_forward_y_frames): wait for that work
     if (c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
-    const float *frag = static_cast<const float *>(c->sp_frag.p);
-    const float *frag2 = frag + (size_t)SPATIAL_NFRAG_L1 * 64, *bias2 = frag2 + (size_t)c->f2 * c->f2 * 2048;
+    const float *frag = static_cast<const float *>(c->sp_table.p);
+    const float *frag2 = frag + spatial_l2_offset(C), *bias2 = frag2 + (size_t)c->f2 * c->f2 * 2048;
+    const float *frag3 = frag + spatial_l3_offset(C, c->f2);
     float *map64 = static_cast<float *>(c->sp_map64.p), *map32 = static_cast<float *>(c->sp_map32.p);
     for (int f = 0; f < n_frames; ++f) {
         const uint8_t *sf = src + (size_t)f * src_frame_pitch;
+        uint8_t *df = dst + (size_t)f * dst_frame_pitch;
+        float *pf = pre ? pre + (size_t)f * dst_frame_pitch : nullptr;
         for (int b0 = 0; b0 < height; b0 += band) {
             const int b1 = std::min(height, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
-            HIP_TRY(c, launch_spatial_l1(zero, sf, (long)src_stride, width, height, m0, m1, frag, map64, mpitch, c->stream));
+            HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag, map64,
+                                         mpitch, c->stream));
             HIP_TRY(c, launch_spatial_l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, map32, opitch,
                                          c->stream));
-            if (zero) {
-                HIP_TRY(c, launch_spatial_l3z(map32, opitch, o0, o1, width, height, b0, b1,
-                                              static_cast<const float *>(c->zp_frag.p), c->b3, dst + (size_t)f * dst_frame_pitch,
-                                              (long)dst_stride, pre ? pre + (size_t)f * dst_frame_pitch : nullptr, c->stream));
+            if (C > 1 || zero) {
+                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, df,
+                                             (long)dst_stride, pf, c->stream));
                 continue;
             }
             StripParams q{};
             q.planes_in = map32 - (long)o0 * width;          // MODE_L3 addresses image rows; the band map starts at row o0
             q.pl_stride = width;
             q.pl_pitch = opitch;
-            q.dst = dst + (size_t)f * dst_frame_pitch;
-            q.pre = pre ? pre + (size_t)f * dst_frame_pitch : nullptr;
+            q.dst = df;
+            q.pre = pf;
             q.dst_stride = (long)dst_stride;
             q.width = width;
             q.height = height;
@@ -141,8 +154,6 @@ static int forward_spatial_impl(srcnn_ctx *c, const uint8_t *src, size_t src_str
     c->sp_stream = c->stream;
     return SRCNN_OK;
 }
-
-static const bool forward_spatial_registered = (forward_spatial = &forward_spatial_impl, true);
 
 }  // namespace host
 }  // namespace srcnn
@@ -157,23 +168,41 @@ int srcnn_set_model(srcnn_ctx *c, int f2, const float *k99, const float *b99, co
     int rc;
     if (!k99 || !b99 || !k2 || !b2 || !k55) return fail(c, SRCNN_ERR_INVALID, "null weight table");
     if (f2 != 3 && f2 != 5) return fail(c, SRCNN_ERR_INVALID, "srcnn_set_model: f2 = %d (1, 3 or 5)", f2);
-    std::vector<float> table(spatial_table_floats(f2));
-    pack_spatial(f2, k99, b99, k2, b2, table.data());
     // layer 3 (and the has-model state) through the 9-1-5 tables, with a zero 1x1 layer 2 that nothing of this model reads
     static const std::vector<float> zero_w2(2048, 0.f);
     c->f2 = 1;
     c->channels = 1;
     if ((rc = upload_weights(c, k99, b99, zero_w2.data(), b2, k55, b55))) return rc;
     c->has_l12 = c->has_l3 = true;
-    if ((rc = reserve(c, c->sp_frag, table.size() * sizeof(float)))) return rc;
-    HIP_TRY(c, hipDeviceSynchronize());        // launches on any stream may still read the old table
-    HIP_TRY(c, hipMemcpy(c->sp_frag.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = upload_table(c, 1, f2, k99, b99, k2, b2, k55, &b55))) return rc;
     c->f2 = f2;
     c->whole_model = true;
     return SRCNN_OK;
 }
 
+int srcnn_set_model_color(srcnn_ctx *c, int f2, const float *k1, const float *b1, const float *k2, const float *b2,
+                          const float *k3, const float *b3)
+{
+    BIND(c);
+    int rc;
+    if (!k1 || !b1 || !k2 || !b2 || !k3 || !b3) return fail(c, SRCNN_ERR_INVALID, "null weight table");
+    if (f2 != 1 && f2 != 3 && f2 != 5) return fail(c, SRCNN_ERR_INVALID, "srcnn_set_model_color: f2 = %d (1, 3 or 5)", f2);
+    // the 9-1-5 tables hold a zero model (and the has-model state): no gate lets them run while the colour model is loaded
+    static const std::vector<float> zeros(5184, 0.f);
+    c->f2 = 1;
+    c->channels = 1;
+    if ((rc = upload_weights(c, zeros.data(), zeros.data(), zeros.data(), zeros.data(), zeros.data(), 0.f))) return rc;
+    c->has_l12 = c->has_l3 = true;
+    if ((rc = upload_table(c, 3, f2, k1, b1, k2, b2, k3, b3))) return rc;
+    c->f2 = f2;
+    c->channels = 3;
+    c->whole_model = true;
+    return SRCNN_OK;
+}
+
 int srcnn_get_model_f2(const srcnn_ctx *c) { return c ? c->f2 : SRCNN_ERR_INVALID; }
+
+int srcnn_get_model_channels(const srcnn_ctx *c) { return c ? c->channels : SRCNN_ERR_INVALID; }
 
 int srcnn_set_padding(srcnn_ctx *c, int padding)
 {
@@ -185,5 +214,47 @@ int srcnn_set_padding(srcnn_ctx *c, int padding)
 }
 
 int srcnn_get_padding(const srcnn_ctx *c) { return c ? c->padding : SRCNN_ERR_INVALID; }
+
+int srcnn_forward_color_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, size_t src_frame_pitch, uint8_t *d_dst,
+                            size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *d_preclamp)
+{
+    BIND(c);
+    int rc;
+    if (width <= 0 || height <= 0 || width > (1 << 28) || bad_plane(d_src, src_stride, 3 * width, height) ||
+        bad_plane(d_dst, dst_stride, 3 * width, height) || n_frames <= 0)
+        return fail(c, SRCNN_ERR_INVALID, "forward_color_dev: bad arguments");
+    // every output pixel reads a window of input pixels that other workgroups may already have overwritten
+    if (ranges_overlap(d_src, span_elems(src_stride, src_frame_pitch, 3 * width, height, n_frames), d_dst,
+                       span_elems(dst_stride, dst_frame_pitch, 3 * width, height, n_frames)))
+        return fail(c, SRCNN_ERR_INVALID, "forward_color_dev: src and dst overlap (the path cannot run in place)");
+    if ((rc = refuse_luma_model(c))) return rc;
+    return forward_banded(c, d_src, src_stride, 3, 1, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, width, height, n_frames,
+                          d_preclamp);
+}
+
+int srcnn_forward_color(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int width, int height,
+                        float *preclamp, size_t preclamp_stride)
+{
+    BIND(c);
+    int rc;
+    if (width <= 0 || height <= 0 || width > (1 << 28) || bad_plane(src, src_stride, 3 * width, height) ||
+        bad_plane(dst, dst_stride, 3 * width, height) || (preclamp && preclamp_stride < 3 * (size_t)width))
+        return fail(c, SRCNN_ERR_INVALID, "forward_color: bad arguments");
+    if ((rc = refuse_luma_model(c)) || (rc = banded_refusal(c))) return rc;     // before anything is staged
+    const size_t row = 3 * (size_t)width, n = row * height;
+    if ((rc = reserve(c, c->in_u8, n))) return rc;
+    if ((rc = reserve(c, c->out_u8, n))) return rc;
+    if (preclamp && (rc = reserve(c, c->pre_f32, n * sizeof(float)))) return rc;
+    uint8_t *d_in = static_cast<uint8_t *>(c->in_u8.p), *d_out = static_cast<uint8_t *>(c->out_u8.p);
+    float *d_pre = preclamp ? static_cast<float *>(c->pre_f32.p) : nullptr;
+    HIP_TRY(c, hipMemcpy2DAsync(d_in, row, src, src_stride, row, height, hipMemcpyHostToDevice, c->stream));
+    if ((rc = forward_banded(c, d_in, row, 3, 1, n, d_out, row, n, width, height, 1, d_pre))) return rc;
+    HIP_TRY(c, hipMemcpy2DAsync(dst, dst_stride, d_out, row, row, height, hipMemcpyDeviceToHost, c->stream));
+    if (preclamp)
+        HIP_TRY(c, hipMemcpy2DAsync(preclamp, preclamp_stride * sizeof(float), d_pre, row * sizeof(float), row * sizeof(float), height,
+                                    hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SRCNN_OK;
+}
 
 }  // extern "C"

@@ -1,26 +1,39 @@
-// srcnn_spatial_kernels.hip -- layers 1 and 2 of the 9-3-5 / 9-5-5 SRCNN models (srcnn_set_model, f2 = 3 or 5), and the banded
-// path of every model under zero padding (srcnn_set_padding), for gfx950.
+// srcnn_spatial_kernels.hip -- the banded path, for gfx950: the 9-3-5 / 9-5-5 models (srcnn_set_model, f2 = 3 or 5), every
+// model under zero padding (srcnn_set_padding), and the colour models (srcnn_set_model_color: 3 input and 3 output channels,
+// 9-f2-5, f2 = 1, 3, 5).
 //
 // A spatial layer 2 (32 x 64 x f2 x f2) is 10 or 28 times the work of the 9-1-5 model's 1x1 layer and needs an f2 x f2 window
 // of the 64-channel layer-1 map, which at 256 B per pixel does not fit beside the strip kernels' rings in LDS.  The path is
-// therefore three launches per row band (srcnn_spatial.cpp):
+// therefore three launches per row band (srcnn_spatial.cpp), for a model of C = 1 or 3 channels:
 //
-//   spatial_l1_kernel   u8 luma -> 64 planar f32 maps (layer 1, + bias, ReLU)
-//   spatial_l2_kernel   64 maps -> 32 planar f32 maps (layer 2, + bias, ReLU), in exactly the layout MODE_L3 reads
-//   MODE_L3 strip kernel (srcnn_mfma.hip), unchanged: layer 3, truncate, clamp
+//   spatial_l1_kernel<C>   C u8 channels -> 64 planar f32 maps (layer 1, + bias, ReLU)
+//   spatial_l2_kernel      64 maps -> 32 planar f32 maps (layer 2, + bias, ReLU), in exactly the layout MODE_L3 reads
+//   spatial_l3_kernel<C>   32 maps -> C channels (layer 3, + b3[c], truncate, clamp): u8 pixels of C bytes, pre-clamp floats;
+//                          the 1-channel model under replicate padding runs the MODE_L3 strip kernel (srcnn_mfma.hip) instead
 //
-// Both kernels use v_mfma_f32_32x32x2_f32 with the weights as the A operand (output channel on the accumulator ROW) and one
+// The input is read at src[y * sstride + x * px_step + c * ch_step]: px_step = 3, ch_step = 1 for interleaved 3-byte pixels
+// (srcnn_forward_color*), px_step = 1, ch_step = plane pitch for the three resized planes of srcnn_process_bgr, and a plain
+// plane for C = 1.  Model channel c reads byte c of a pixel and writes byte c of an output pixel.
+//
+// The kernels use v_mfma_f32_32x32x2_f32 with the weights as the A operand (output channel on the accumulator ROW) and one
 // pixel per lane as the B operand; accumulator register r of lane-half h holds output channel acc_row(r, h), lane & 31 the pixel.
-// Each layer pads ITS OWN input.  Replicate padding (the default, ZERO = false): layer 1 clamps luma coordinates, layer 2 clamps
-// layer-1 map coordinates, and layer 3 is MODE_L3.  Zero padding (srcnn_set_padding(SRCNN_PAD_ZERO), ZERO = true; also for
-// f2 = 1): layers 1 and 2 stage 0 for every luma / map value outside the image, and layer 3 is spatial_l3z_kernel below,
-// because MODE_L3 builds the replicate border into its column offsets and vertical chains.
+// Each layer pads ITS OWN input.  Replicate padding (the default, ZERO = false): layer 1 clamps the image coordinates, layer 2
+// clamps layer-1 map coordinates, layer 3 reads clamped map rows and columns (1 channel: MODE_L3, which builds the replicate
+// border into its column offsets and vertical chains).  Zero padding (srcnn_set_padding(SRCNN_PAD_ZERO), ZERO = true; also for
+// f2 = 1): layers 1 and 2 stage 0 for every input value outside the image, and layer 3 zeroes the tap partials of map pixels
+// outside the image.
 //
 // Summation order (each MFMA is a 2-term fmaf chain, srcnn_mfma.hip):
-//   layer 1, channel c:  0 + w1[c][0] y0 + w1[c][1] y1 + ... + w1[c][80] y80 + b1[c]   (taps row-major, the bias tap last)
+//   layer 1, channel k:  0 + sum over c = 0 .. C - 1 of (w1[k][c][0] x0 + ... + w1[k][c][80] x80 + t_c), taps row-major,
+//                        where t_c = 0 * 1 (a zero tap) for c < C - 1 and t_{C-1} = b1[k] * 1 (the bias tap); for C = 1:
+//                        0 + w1[k][0] y0 + w1[k][1] y1 + ... + w1[k][80] y80 + b1[k]
 //   layer 2, channel k:  b2[k], then the input channels in chunks of 8 (ascending); inside a chunk the taps (kh, kw)
 //                        row-major, inside a tap the channel pairs ascending, channel 2p before 2p + 1.
+//   layer 3, channel o:  per map pixel the tap partials T[tap] = sum_c w3[o][c][tap] F_c (channel pairs ascending), summed
+//                        down the 5 tap rows (m ascending), then ((((V_0 + V_1) + V_2) + V_3) + V_4) + b3[o]
 #include "srcnn_kernels.h"
+
+#include <type_traits>
 
 namespace srcnn {
 
@@ -31,28 +44,57 @@ __device__ __forceinline__ int sclamp(int v, int lo, int hi) { return v < lo ? l
 
 // ---- layer 1 ----------------------------------------------------------------------------------------------------------
 // Workgroup: 4 waves, a tile of SL1_COLS columns x SL1_ROWS rows.  Wave w owns columns 32w .. 32w + 31 of the tile and walks
-// its rows; per row 82 MFMAs (2 channel tiles x 41 k-steps of 2 taps).  LDS: the luma window (f32) and the 82 A fragments.
+// its rows; per row C x 82 MFMAs (channels x 2 channel tiles x 41 k-steps of 2 taps).  LDS: the C channels' A fragments and
+// the window.  C = 1: an f32 window, all LDS static (29 KiB).  C = 3: the three tables (61.5 KiB) and a u8 window of the three
+// channels (6.4 KiB), dynamic (68 KiB, two workgroups per CU); no static LDS may sit ahead of it and shift its float4 stores.
 constexpr int SL1_COLS = 128, SL1_ROWS = 8;
-constexpr int SL1_YP = SL1_COLS + 8, SL1_YR = SL1_ROWS + 8;
+constexpr int SL1_YP = SL1_COLS + 8, SL1_YR = SL1_ROWS + 8, SL1_YC = SL1_YR * SL1_YP;
+constexpr size_t SL1_LDS3 = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC;
 
-template <bool ZERO>
-__global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restrict__ src, long sstride, int W, int H,
-                                                         int m0, int m1, const float *__restrict__ frag,
-                                                         float *__restrict__ map, long mpitch)
+// Kernel arguments are passed as they always were, so that each form compiles to the instructions it had: layer 1 takes the
+// steps of the input (int px_step, long ch_step) for 3 channels and none for 1, layer 3 takes its C biases as C floats.
+// Byte c of input pixel (y, x), without and with steps:
+__device__ __forceinline__ uint8_t l1_at(const uint8_t *p, long stride, int y, int x, int) { return p[(long)y * stride + x]; }
+__device__ __forceinline__ uint8_t l1_at(const uint8_t *p, long stride, int y, int x, int c, int px_step, long ch_step)
 {
-    __shared__ float ys[SL1_YR * SL1_YP];
-    __shared__ float as[SPATIAL_NFRAG_L1 * 64];
+    return p[(long)y * stride + (long)x * px_step + c * ch_step];
+}
+
+template <int C, bool ZERO, typename... Steps>
+__global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restrict__ src, long sstride, Steps... steps, int W, int H,
+                                                         int m0, int m1, const float *__restrict__ frag, float *__restrict__ map,
+                                                         long mpitch)
+{
+    static_assert(sizeof...(Steps) == (C == 1 ? 0 : 2), "px_step and ch_step for 3 channels only");
+    using T = std::conditional_t<C == 1, float, uint8_t>;      // the window's element type
+    float *as;
+    T *ys;
+    if constexpr (C == 1) {
+        __shared__ float win[SL1_YC], afr[SPATIAL_NFRAG_L1 * 64];
+        ys = win;
+        as = afr;
+    } else {
+        extern __shared__ float lds[];
+        as = lds;
+        ys = reinterpret_cast<uint8_t *>(lds + C * SPATIAL_NFRAG_L1 * 64);
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * SL1_COLS, y0 = m0 + blockIdx.y * SL1_ROWS;
-    for (int e = tid; e < SL1_YR * SL1_YP; e += 256) {
-        const int rr = e / SL1_YP, cc = e - rr * SL1_YP;
+    // the window, channel fastest (consecutive bytes of interleaved pixels go to consecutive threads)
+    for (int e = tid; e < C * SL1_YC; e += 256) {
+        const int rr = e / (C * SL1_YP), rem = e - rr * (C * SL1_YP), cc = rem / C, ch = rem - C * cc;
         const int yy = sclamp(y0 - 4 + rr, 0, H - 1), xx = sclamp(x0 - 4 + cc, 0, W - 1);
-        const float v = (float)src[(long)yy * sstride + xx];
+        const T v = l1_at(src, sstride, yy, xx, ch, steps...);
         // ZERO: 0 where the load was clamped, by a multiply: a select lets the compiler branch around the load (measured slower)
-        if constexpr (ZERO) ys[e] = v * ((yy == y0 - 4 + rr && xx == x0 - 4 + cc) ? 1.f : 0.f);
-        else ys[e] = v;
+        if constexpr (ZERO) ys[ch * SL1_YC + rr * SL1_YP + cc] = (T)(v * ((yy == y0 - 4 + rr && xx == x0 - 4 + cc) ? (T)1 : (T)0));
+        else ys[ch * SL1_YC + rr * SL1_YP + cc] = v;
     }
-    for (int e = tid; e < SPATIAL_NFRAG_L1 * 64; e += 256) as[e] = frag[e];
+    if constexpr (C == 1) {
+        for (int e = tid; e < SPATIAL_NFRAG_L1 * 64; e += 256) as[e] = frag[e];
+    } else {
+        const float4 *fa = reinterpret_cast<const float4 *>(frag);
+        for (int e = tid; e < C * SPATIAL_NFRAG_L1 * 16; e += 256) reinterpret_cast<float4 *>(as)[e] = fa[e];
+    }
     __syncthreads();
     const int j = lane & 31, kk = lane >> 5;
     const int x = x0 + 32 * wave + j;
@@ -61,12 +103,18 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restri
         if (y >= m1) break;                        // uniform over the workgroup
         f32x16 acc0 = {0}, acc1 = {0};
 #pragma unroll
-        for (int s = 0; s < 41; ++s) {
-            const int tap = 2 * s + kk;            // 81: the bias tap, B = 1
-            const int ty = tap / 9, tx = tap - 9 * (tap / 9);
-            const float b = tap < 81 ? ys[(r + ty) * SL1_YP + 32 * wave + j + tx] : 1.f;
-            acc0 = SMFMA(as[s * 64 + lane], b, acc0);
-            acc1 = SMFMA(as[(41 + s) * 64 + lane], b, acc1);
+        for (int ch = 0; ch < C; ++ch) {
+            const T *yc = ys + ch * SL1_YC + r * SL1_YP + 32 * wave + j;
+            const float *ac = as + ch * (SPATIAL_NFRAG_L1 * 64) + lane;
+#pragma unroll
+            for (int s = 0; s < 41; ++s) {
+                const int tap = 2 * s + kk;        // 81: the zero / bias tap, B = 1
+                const int ty = tap / 9, tx = tap - 9 * (tap / 9);
+                // (one address, written per form as each kernel had it: the two writings compile differently)
+                const float b = tap < 81 ? (float)(C == 1 ? ys[(r + ty) * SL1_YP + 32 * wave + j + tx] : yc[ty * SL1_YP + tx]) : 1.f;
+                acc0 = SMFMA(ac[s * 64], b, acc0);
+                acc1 = SMFMA(ac[(41 + s) * 64], b, acc1);
+            }
         }
         if (x < W) {
             float *o = map + (long)(y - m0) * W + x;
@@ -154,28 +202,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     }
 }
 
-// ---- layer 3 under zero padding ---------------------------------------------------------------------------------------
+// ---- layer 3 ----------------------------------------------------------------------------------------------------------
 // Workgroup: 4 waves, a strip of SL3_COLS = 128 map columns (image columns 124 bx - 2 ..), of which the middle SL3_OUT = 124
 // are output, and a segment of SL3_SEG output rows; wave w owns map columns 32w .. 32w + 31 and walks the map rows
-// y0 - 2 .. y1 + 1.  Per map row 16 MFMAs give the 25 tap partials T[tap] = sum_c W3[c][tap] F_c (A: W3 with the rows of
-// l3_row_tap(); B: the 32 channels of the lane's pixel; the partials of a pixel outside the image are set to 0), so register
-// 5s + m of lane-half h holds tap (m, n = s (h = 0) or 3 + s (h = 1)).  Each wave keeps SL3_AHEAD map rows of loads in
-// flight (the kernel is bound by the 128 B per pixel it reads).  The 5 tap rows are summed down register chains, m ascending; the finished
-// per-tap-column sums V_n cross lanes through a double-buffered LDS row, and
-//   out(y, x) = (V_0(x - 2) + V_1(x - 1) + V_2(x) + V_3(x + 1) + V_4(x + 2)) + b3,  truncated, clamped to 0..255
-// (the epilogue of MODE_L3).  Zero padding needs no clamp in the sums: a feature outside the image contributes T = 0.
-// The map rows outside the band that the image holds are inside [o0, o1) (srcnn_spatial.cpp); the tiles are handed out
-// XCD by XCD (block b runs on XCD b % 8), so horizontally neighbouring strips share their halo columns in one L2.
+// y0 - 2 .. y1 + 1.  Per map row C x 16 MFMAs give the C x 25 tap partials T[tap] = sum_c W3[o][c][tap] F_c (A set o: W3[o]
+// with the rows of l3_row_tap(); B: the 32 channels of the lane's pixel), so register 5s + m of lane-half h holds tap (m, n = s
+// (h = 0) or 3 + s (h = 1)).  The loads are clamped to the band's rows and the image's columns, which is replicate padding;
+// ZERO sets the partials of a map pixel outside the image to 0 (a feature outside the image contributes nothing, so the sums
+// need no clamp).  Each wave keeps sl3_ahead(C) map rows of loads in flight: the 1-channel kernel is bound by the 128 B per
+// pixel it reads, and 48 MFMAs per row cover the loads of the 3-channel one.  The 5 tap rows are summed down register chains,
+// m ascending; the finished per-tap-column sums V_n of the C channels cross lanes through a double-buffered LDS row, and a lane
+// of half 0 finishes its pixel's channels:
+//   out(y, x)[o] = (V_0(x - 2) + V_1(x - 1) + V_2(x) + V_3(x + 1) + V_4(x + 2)) + b3[o],  truncated, clamped to 0..255
+// (the epilogue of MODE_L3).  The map rows outside the band that the image holds are inside [o0, o1) (srcnn_spatial.cpp); the
+// tiles are handed out XCD by XCD (block b runs on XCD b % 8), so horizontally neighbouring strips share their halo columns in
+// one L2.
 constexpr int SL3_COLS = 128, SL3_OUT = SL3_COLS - 4, SL3_SEG = 16, SL3_XCDS = 8;
-constexpr int SL3_AHEAD = 4;        // map rows in flight per wave: a ring of SL3_AHEAD x 16 registers
+__host__ __device__ constexpr int sl3_ahead(int C) { return C == 1 ? 4 : 2; }   // a ring of sl3_ahead x 16 registers
 
-template <bool PRE>
-__global__ __launch_bounds__(256) void spatial_l3z_kernel(const float *__restrict__ map, long mpitch, int o0, int o1, int W,
-                                                          int H, int b0, int b1, int nx, int n_tiles,
-                                                          const float *__restrict__ frag, float b3, uint8_t *__restrict__ dst,
-                                                          long dstride, float *__restrict__ pre)
+template <int C, bool PRE, bool ZERO, typename... B3>
+__global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict__ map, long mpitch, int o0, int o1, int W, int H,
+                                                         int b0, int b1, int nx, int n_tiles, const float *__restrict__ frag,
+                                                         B3... b3, uint8_t *__restrict__ dst, long dstride, float *__restrict__ pre)
 {
-    __shared__ float vt[2][5][SL3_COLS];
+    static_assert(sizeof...(B3) == C, "one bias per output channel");
+    constexpr int AHEAD = sl3_ahead(C);
+    __shared__ float vt[2][C][5][SL3_COLS];
     const int per = (n_tiles + SL3_XCDS - 1) / SL3_XCDS;
     const int tile = (int)(blockIdx.x % SL3_XCDS) * per + (int)(blockIdx.x / SL3_XCDS);
     if (tile >= n_tiles) return;                   // uniform over the workgroup
@@ -184,72 +236,106 @@ __global__ __launch_bounds__(256) void spatial_l3z_kernel(const float *__restric
     const int c = 32 * wave + j, x = tx * SL3_OUT - 2 + c;
     const int y0 = b0 + ty * SL3_SEG, y1 = min(b1, y0 + SL3_SEG), r_end = y1 + 2;
     const bool col_ok = x >= 0 && x < W;
-    float a[16];
+    const float bias[C] = {b3...};
+    float a[C][16];
 #pragma unroll
-    for (int s = 0; s < 16; ++s) a[s] = frag[s * 64 + lane];
-    // channels 2s + kk of map row r at the lane's column, from a clamped (always valid) address: no branch between the loads;
-    // the rows and columns outside the image are zeroed in the tap partials instead
+    for (int o = 0; o < C; ++o)
+#pragma unroll
+        for (int s = 0; s < 16; ++s) a[o][s] = frag[(o * 16 + s) * 64 + lane];
+    // channels 2s + kk of map row r at the lane's column, from a clamped (always valid) address: no branch between the loads
     const float *colp = map + (long)kk * mpitch + sclamp(x, 0, W - 1);
     auto load = [&](int r, float *v) {
         const float *p = colp + (long)(sclamp(r, o0, o1 - 1) - o0) * W;
 #pragma unroll
         for (int s = 0; s < 16; ++s) v[s] = p[(long)(2 * s) * mpitch];
     };
-    float xr[SL3_AHEAD][16], ch[3][4];
+    float xr[AHEAD][16], chn[C][3][4];
 #pragma unroll
-    for (int s = 0; s < 3; ++s)
+    for (int o = 0; o < C; ++o)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ch[s][k] = 0.f;
+        for (int s = 0; s < 3; ++s)
 #pragma unroll
-    for (int d = 0; d < SL3_AHEAD; ++d)
+            for (int k = 0; k < 4; ++k) chn[o][s][k] = 0.f;
+#pragma unroll
+    for (int d = 0; d < AHEAD; ++d)
         if (y0 - 2 + d < r_end) load(y0 - 2 + d, xr[d]);
-    for (int rb = y0 - 2; rb < r_end; rb += SL3_AHEAD) {
+    for (int rb = y0 - 2; rb < r_end; rb += AHEAD) {
 #pragma unroll
-        for (int d = 0; d < SL3_AHEAD; ++d) {
+        for (int d = 0; d < AHEAD; ++d) {
             const int r = rb + d;
             if (r >= r_end) break;                 // uniform over the workgroup
-            f32x16 t = {0};
+            f32x16 t[C];
 #pragma unroll
-            for (int s = 0; s < 16; ++s) t = SMFMA(a[s], xr[d][s], t);
-            if (r + SL3_AHEAD < r_end) load(r + SL3_AHEAD, xr[d]);
-            const bool ok = col_ok && r >= 0 && r < H;   // zero padding: a feature outside the image contributes nothing
-            float v[3];
+            for (int o = 0; o < C; ++o) t[o] = (f32x16){0};
 #pragma unroll
-            for (int s = 0; s < 3; ++s) {              // ch[s][k]: tap rows 0 .. k of output row r + 1 - k
-                v[s] = ch[s][3] + (ok ? t[5 * s + 4] : 0.f);
-                ch[s][3] = ch[s][2] + (ok ? t[5 * s + 3] : 0.f);
-                ch[s][2] = ch[s][1] + (ok ? t[5 * s + 2] : 0.f);
-                ch[s][1] = ch[s][0] + (ok ? t[5 * s + 1] : 0.f);
-                ch[s][0] = ok ? t[5 * s] : 0.f;
-            }
+            for (int s = 0; s < 16; ++s)
+#pragma unroll
+                for (int o = 0; o < C; ++o) t[o] = SMFMA(a[o][s], xr[d][s], t[o]);
+            if (r + AHEAD < r_end) load(r + AHEAD, xr[d]);
+            const bool ok = !ZERO || (col_ok && r >= 0 && r < H);
+            float v[C][3];
+#pragma unroll
+            for (int o = 0; o < C; ++o)
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {          // chn[o][s][k]: tap rows 0 .. k of output row r + 1 - k
+                    v[o][s] = chn[o][s][3] + (ok ? t[o][5 * s + 4] : 0.f);
+                    chn[o][s][3] = chn[o][s][2] + (ok ? t[o][5 * s + 3] : 0.f);
+                    chn[o][s][2] = chn[o][s][1] + (ok ? t[o][5 * s + 2] : 0.f);
+                    chn[o][s][1] = chn[o][s][0] + (ok ? t[o][5 * s + 1] : 0.f);
+                    chn[o][s][0] = ok ? t[o][5 * s] : 0.f;
+                }
             const int y = r - 2;
             if (y >= y0) {                             // uniform over the workgroup
-                float *vr = &vt[r & 1][0][0];
+                float *vr = &vt[r & 1][0][0][0];
 #pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    const int n = kk ? 3 + s : s;
-                    if (n < 5) vr[n * SL3_COLS + c] = v[s];
-                }
+                for (int o = 0; o < C; ++o)
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) {
+                        const int n = kk ? 3 + s : s;
+                        if (n < 5) vr[(o * 5 + n) * SL3_COLS + c] = v[o][s];
+                    }
                 __syncthreads();
                 if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
-                    const float sum = (((vr[c - 2] + vr[SL3_COLS + c - 1]) + vr[2 * SL3_COLS + c]) + vr[3 * SL3_COLS + c + 1]) +
-                                      vr[4 * SL3_COLS + c + 2];
-                    const float val = sum + b3;
-                    const long o = (long)y * dstride + x;
-                    dst[o] = (uint8_t)sclamp((int)val, 0, 255);
-                    if constexpr (PRE) pre[o] = val;
+                    const long ob = (long)y * dstride + (long)C * x;
+#pragma unroll
+                    for (int o = 0; o < C; ++o) {
+                        const float *vo = vr + o * 5 * SL3_COLS;
+                        const float sum = (((vo[c - 2] + vo[SL3_COLS + c - 1]) + vo[2 * SL3_COLS + c]) + vo[3 * SL3_COLS + c + 1]) +
+                                          vo[4 * SL3_COLS + c + 2];
+                        const float val = sum + bias[o];
+                        dst[ob + o] = (uint8_t)sclamp((int)val, 0, 255);
+                        if constexpr (PRE) pre[ob + o] = val;
+                    }
                 }
             }
         }
     }
 }
 
-hipError_t launch_spatial_l1(bool zero, const uint8_t *src, long sstride, int W, int H, int m0, int m1, const float *frag,
-                             float *map, long mpitch, hipStream_t st)
+template <int C, bool ZERO>
+static void launch_l1(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
+                      const float *frag, float *map, long mpitch, hipStream_t st)
+{
+    if constexpr (C == 1) {
+        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
+    } else {
+        // (68 KiB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, int, long>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
+        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step, ch_step, W,
+                           H, m0, m1, frag, map, mpitch);
+    }
+}
+
+hipError_t launch_spatial_l1(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
+                             int m0, int m1, const float *frag, float *map, long mpitch, hipStream_t st)
 {
     const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
-    if (zero) hipLaunchKernelGGL(spatial_l1_kernel<true>, grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
-    else hipLaunchKernelGGL(spatial_l1_kernel<false>, grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
+    if (channels == 1 && !zero) launch_l1<1, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
+    else if (channels == 1) launch_l1<1, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
+    else if (channels == 3 && !zero) launch_l1<3, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
+    else if (channels == 3) launch_l1<3, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -280,17 +366,52 @@ hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, i
     return hipGetLastError();
 }
 
-hipError_t launch_spatial_l3z(const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, const float *frag,
-                              float b3, uint8_t *dst, long dstride, float *pre, hipStream_t st)
+template <int C, bool ZERO, typename... B3>
+static void launch_l3(dim3 grid, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, int nx, int n_tiles,
+                      const float *frag, uint8_t *dst, long dstride, float *pre, hipStream_t st, B3... b3)
+{
+    if (pre)
+        hipLaunchKernelGGL((spatial_l3_kernel<C, true, ZERO, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
+                           n_tiles, frag, b3..., dst, dstride, pre);
+    else
+        hipLaunchKernelGGL((spatial_l3_kernel<C, false, ZERO, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
+                           n_tiles, frag, b3..., dst, dstride, pre);
+}
+
+hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                             const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st)
 {
     const int nx = (W + SL3_OUT - 1) / SL3_OUT, ny = (b1 - b0 + SL3_SEG - 1) / SL3_SEG, n_tiles = nx * ny;
     const dim3 grid((unsigned)(SL3_XCDS * ((n_tiles + SL3_XCDS - 1) / SL3_XCDS)));
-    if (pre)
-        hipLaunchKernelGGL(spatial_l3z_kernel<true>, grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag,
-                           b3, dst, dstride, pre);
+    // (1 channel under replicate padding: MODE_L3)
+    if (channels == 1 && zero)
+        launch_l3<1, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, pre, st, b3[0]);
+    else if (channels == 3 && zero)
+        launch_l3<3, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, pre, st, b3[0], b3[1], b3[2]);
+    else if (channels == 3)
+        launch_l3<3, false>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, pre, st, b3[0], b3[1], b3[2]);
     else
-        hipLaunchKernelGGL(spatial_l3z_kernel<false>, grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag,
-                           b3, dst, dstride, pre);
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---- srcnn_process_bgr: interleaved BGR -> three planes (before the planar bicubic resize) ------------------------------
+__global__ __launch_bounds__(256) void split3_kernel(const uint8_t *__restrict__ src, long sstride, int W, uint8_t *__restrict__ planes,
+                                                     long ppitch)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const uint8_t *p = src + (long)y * sstride + 3L * x;
+    uint8_t *q = planes + (long)y * W + x;
+    q[0] = p[0];
+    q[ppitch] = p[1];
+    q[2 * ppitch] = p[2];
+}
+
+hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st)
+{
+    hipLaunchKernelGGL(split3_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, st, src, sstride, W, planes,
+                       ppitch);
     return hipGetLastError();
 }
 

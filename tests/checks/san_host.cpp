@@ -1,4 +1,4 @@
-// san_host.cpp -- sanitizer harness for the host-only logic of srcnn_cpp_amd/csrc/srcnn_{api,model,plan,launch,host,multi}.cpp: the work-item
+// san_host.cpp -- sanitizer harness for the host-only logic of srcnn_cpp_amd/csrc/srcnn_{api,model,plan,launch,host,multi,spatial}.cpp: the work-item
 // planner (plan_items), the MFMA / split-f16 fragment packers and the cubic coefficient tables, reached through the
 // tuning build's debug hooks.  tests/test_sanitizers.py compiles those files themselves (-DSRCNN_TUNING_BUILD) with
 // -fsanitize=address,undefined (host compiler, no device code), links it with the kernel-launch stubs below and
@@ -36,6 +36,10 @@ hipError_t launch_resize_cubic(const uint8_t *, long, long, int, int, uint8_t *,
 bool fused_pipeline_ok(int, int, int, int, const void *, long, const void *, long) { return false; }
 hipError_t launch_bgr_to_y_resized(const uint8_t *, long, int, int, uint8_t *, long, int, int, const int *, const short *, const int *, const short *, hipStream_t) { return never(); }
 hipError_t launch_resize_merge(const uint8_t *, long, int, int, const uint8_t *, long, uint8_t *, long, int, int, const int *, const short *, const int *, const short *, hipStream_t) { return never(); }
+hipError_t launch_spatial_l1(int, bool, const uint8_t *, long, int, long, int, int, int, int, const float *, float *, long, hipStream_t) { return never(); }
+hipError_t launch_spatial_l2(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, float *, long, hipStream_t) { return never(); }
+hipError_t launch_spatial_l3(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, uint8_t *, long, float *, hipStream_t) { return never(); }
+hipError_t launch_split3(const uint8_t *, long, int, int, uint8_t *, long, hipStream_t) { return never(); }
 }  // namespace srcnn
 
 extern "C" {

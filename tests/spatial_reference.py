@@ -81,6 +81,17 @@ def model_blob(model):
     return np.concatenate([np.ravel(b1), np.ravel(w1), np.ravel(b2), np.ravel(w2), [b3], np.ravel(w3)]).astype(np.float32)
 
 
+def band_seams(width, height, f2):
+    """The rows where the context's row bands meet (srcnn_spatial.cpp: two maps of 384 B per pixel within 512 MiB), for a model
+    of any channel count."""
+    r2 = (f2 - 1) // 2
+    cap = (512 << 20) // (4 * width) - 64 * (4 + 2 * r2) - 32 * 4
+    band_max = max(16, cap // 96)
+    n = (height + band_max - 1) // band_max
+    band = (height + n - 1) // n
+    return list(range(band, height, band))
+
+
 def pre_tolerance(ref):
     return 5e-3 * max(1.0, float(np.abs(ref).max()) / 255.0)
 

@@ -8,7 +8,7 @@ import torch
 import oracle
 import srcnn_cpp_amd as S
 from srcnn_cpp_amd.synth import synth_luma
-from spatial_reference import assert_u8_consistent, pre_tolerance, random_model, torch_forward
+from spatial_reference import assert_u8_consistent, band_seams, pre_tolerance, random_model, torch_forward
 from color_reference import random_color_model, synth_color, torch_forward_color, torch_forward_color_rows
 
 pytestmark = pytest.mark.gpu
@@ -44,16 +44,6 @@ def check(out, pre, ref):
     tol = pre_tolerance(ref)
     assert np.abs(pre.astype(np.float64) - ref).max() <= tol
     assert_u8_consistent(out, ref, tol)
-
-
-def band_seams(width, height, f2):
-    """The rows where the context's row bands meet (srcnn_color.cpp: the bands of the 1-channel spatial path)."""
-    r2 = (f2 - 1) // 2
-    cap = (512 << 20) // (4 * width) - 64 * (4 + 2 * r2) - 32 * 4
-    band_max = max(16, cap // 96)
-    n = (height + band_max - 1) // band_max
-    band = (height + n - 1) // n
-    return list(range(band, height, band))
 
 
 @pytest.mark.parametrize("padding", PADDINGS)

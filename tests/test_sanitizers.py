@@ -18,7 +18,8 @@ SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-f
 ENV = {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1", "PATH": "/usr/bin:/bin"}
 
 pytestmark = pytest.mark.skipif(not CLANG.exists(), reason="ROCm clang++ not found")
-HOST_UNITS = [str(ROOT / "srcnn_cpp_amd" / "csrc" / f"srcnn_{u}.cpp") for u in ("api", "model", "plan", "launch", "host", "multi")]
+HOST_UNITS = [str(ROOT / "srcnn_cpp_amd" / "csrc" / f"srcnn_{u}.cpp") for u in
+              ("api", "model", "plan", "launch", "host", "multi", "spatial")]
 
 
 def test_host_logic_under_asan_ubsan(tmp_path):
