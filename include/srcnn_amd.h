@@ -86,8 +86,26 @@ enum {
  *   SRCNN_MODE_REFBYTES16 opt-in, like SPLIT16 outside the float32 north star: the same flag-and-recompute
  *                    scheme behind the split-f16 kernel (threshold 8/6 of REFBYTES': that kernel's noise is a
  *                    little wider).  The reference's bytes at 0.52-0.56 of the float32 MFMA mode's TIME
- *                    (0.49-0.55 ms per 3840x2160 plane on one MI355X). */
-enum { SRCNN_MODE_MFMA = 0, SRCNN_MODE_EXACT = 1, SRCNN_MODE_SPLIT16 = 2, SRCNN_MODE_REFBYTES = 3, SRCNN_MODE_REFBYTES16 = 4 };
+ *                    (0.49-0.55 ms per 3840x2160 plane on one MI355X).
+ *   SRCNN_MODE_BANDED16 opt-in, like SPLIT16 outside the float32 north star: the fast mode of the models that run on the
+ *                    banded path (srcnn_set_model with f2 = 3 or 5, srcnn_set_padding(SRCNN_PAD_ZERO), srcnn_set_model_color).
+ *                    EVERY whole model -- 1 or 3 channels, f2 = 1, 3, 5, replicate or zero padding -- runs banded in this mode
+ *                    (layer 1, layer 2, layer 3 per row band) with layer 2 on v_mfma_f32_32x32x16_f16: both of its float32
+ *                    operands are split into f16 (hi, lo) pairs under exact power-of-two scales derived from the model, the
+ *                    products hi*hi + lo*hi + hi*lo are accumulated in float32.  Layers 1 and 3 keep their float32 MFMA
+ *                    arithmetic and summation order.  Output: the tolerance of SRCNN_MODE_MFMA for these models (no bitwise
+ *                    CPU model: the f16 MFMA's internal summation order is not documented).  Entry points:
+ *                    srcnn_forward_y, srcnn_forward_y_dev, srcnn_forward_y_frames, srcnn_forward_color(_dev),
+ *                    srcnn_process_bgr(_dev).  A replicate-padded 1-channel 9-1-5 model runs banded here too and is
+ *                    slower than in SRCNN_MODE_MFMA: SRCNN_MODE_SPLIT16 is the fast mode for that one.  Layers loaded by
+ *                    per-filter calls are refused (load the model with srcnn_set_weights / srcnn_set_model(_color)), and so
+ *                    is a model whose layer-1/2 weights are not finite or cannot be scaled within float32.  Every entry
+ *                    point that runs the strip path only (row stripes, halo buffers, several GPUs, lanes, unfused,
+ *                    srcnn_conv99x11_dev, srcnn_conv55_dev and the _to_dev / _from_dev forms) returns SRCNN_ERR_STATE in
+ *                    this mode for any model; the per-filter calls on host planes (srcnn_conv99, srcnn_conv11,
+ *                    srcnn_conv55, srcnn_conv99x11) ignore the mode as they ignore every mode. */
+enum { SRCNN_MODE_MFMA = 0, SRCNN_MODE_EXACT = 1, SRCNN_MODE_SPLIT16 = 2, SRCNN_MODE_REFBYTES = 3, SRCNN_MODE_REFBYTES16 = 4,
+       SRCNN_MODE_BANDED16 = 5 };
 
 typedef struct srcnn_ctx srcnn_ctx;
 
@@ -213,7 +231,8 @@ int srcnn_set_weights(srcnn_ctx *ctx,
  * own input (layer 2 pads the 64-channel layer-1 map by (f2 - 1) / 2; srcnn_set_padding selects zero padding instead), so an
  * output pixel sees a radius of 6 + (f2 - 1) / 2.
  * f2 = 1 is srcnn_set_weights, bit for bit in every mode.  For f2 > 1:
- *   - only SRCNN_MODE_MFMA has arithmetic (float32 v_mfma_f32_32x32x2_f32; summation order in srcnn_spatial_kernels.hip): in any other
+ *   - SRCNN_MODE_MFMA has the arithmetic (float32 v_mfma_f32_32x32x2_f32; summation order in srcnn_spatial_kernels.hip), and opt-in
+ *     SRCNN_MODE_BANDED16 runs layer 2 in split f16 (see the modes above): in any other
  *     mode the whole-path calls return SRCNN_ERR_STATE and srcnn_last_error() says why;
  *   - srcnn_forward_y, srcnn_forward_y_dev (any n_frames, frame pitches, d_preclamp), srcnn_forward_y_frames,
  *     srcnn_process_bgr and srcnn_process_bgr_dev run the model;
@@ -239,7 +258,7 @@ int srcnn_get_model_f2(const srcnn_ctx *ctx);
  *   SRCNN_PAD_ZERO: every layer zero-pads its own input -- torch.nn.functional.conv2d(x, w, b, padding=k // 2), i.e. a PyTorch
  *     nn.Conv2d(..., padding=k // 2) with its default padding_mode "zeros": luma outside the image is 0, and so are the layer-1
  *     and layer-2 maps outside it.  Rows inside the image are never padded, also where two row bands meet.  For f2 = 1, 3
- *     and 5, in SRCNN_MODE_MFMA only, srcnn_forward_y, srcnn_forward_y_dev, srcnn_forward_y_frames and srcnn_process_bgr(_dev)
+ *     and 5, in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only, srcnn_forward_y, srcnn_forward_y_dev, srcnn_forward_y_frames and srcnn_process_bgr(_dev)
  *     run the model on the banded path of srcnn_set_model (three launches per band, layer 3 by its own zero-padding kernel).
  *     Every other mode, every other entry point (row stripes, halo buffers, the several-GPU calls, unfused,
  *     srcnn_conv99x11_dev, srcnn_conv55_dev) and the per-filter calls (srcnn_conv99, _conv11, _conv55, _conv99x11 and their
@@ -259,7 +278,8 @@ int srcnn_get_padding(const srcnn_ctx *ctx);
  * (replicate by default, or zero); output channel c is (int)(layer 3 + bias3[c]) clamped to 0..255.  Model channel i reads
  * byte i of each input pixel and writes byte i of each output pixel: for a BGR image channel 0 is B, so the weights carry
  * the channel order.
- *   - only SRCNN_MODE_MFMA has arithmetic (summation order in srcnn_color_kernels.hip); other modes return SRCNN_ERR_STATE;
+ *   - SRCNN_MODE_MFMA and, opt-in, SRCNN_MODE_BANDED16 have arithmetic (summation order in srcnn_spatial_kernels.hip); other modes
+ *     return SRCNN_ERR_STATE;
  *   - srcnn_forward_color and srcnn_forward_color_dev run the model.  A row holds 3 * width bytes; strides and frame
  *     pitches are in bytes and a stride is at least 3 * width.  The pre-clamp values (may be NULL) have the layout of the
  *     output, in floats: preclamp_stride floats per row, and for srcnn_forward_color_dev the dst stride and frame pitch;

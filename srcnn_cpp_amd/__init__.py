@@ -30,7 +30,7 @@ __all__ = [
     "load_model", "split_model", "model_from_state_dict", "model_from_module", "MODEL_SIZES", "COLOR_MODEL_SIZES", "PAD_REPLICATE",
     "PAD_ZERO",
     "Convolution99", "Convolution11", "Convolution55", "Convolution99x11", "default_context",
-    "MODE_MFMA", "MODE_EXACT", "MODE_SPLIT16", "MODE_REFBYTES", "MODE_REFBYTES16", "FLOP_PER_PIXEL",
+    "MODE_MFMA", "MODE_EXACT", "MODE_SPLIT16", "MODE_REFBYTES", "MODE_REFBYTES16", "MODE_BANDED16", "FLOP_PER_PIXEL",
     "ERR_INVALID", "ERR_HIP", "ERR_NOMEM", "ERR_NODEVICE", "ERR_STATE",
     "stripe_rows", "forward_y_frames_multi", "forward_y_lanes_dev", "forward_y_striped", "forward_y_striped_dev",
 ]
@@ -44,6 +44,7 @@ MODE_EXACT = 1
 MODE_SPLIT16 = 2
 MODE_REFBYTES = 3          # float32 MFMA + exact fix-up of the pixels next to a truncation boundary: the reference's bytes
 MODE_REFBYTES16 = 4        # opt-in: the same behind the split-f16 kernel
+MODE_BANDED16 = 5          # opt-in: every whole model on the banded path with layer 2 in split f16 (9-3-5, 9-5-5, zero padding, colour)
 N_WEIGHTS = 8129
 # blob sizes of the 9-f2-5 models (srcnn_set_model): b1|W1|b2|W2|b3|W3 with W2 holding 2048 * f2^2 floats
 MODEL_SIZES = {8129: 1, 24513: 3, 57281: 5}
@@ -263,6 +264,9 @@ def model_from_state_dict(sd, input_scale: float = 255.0, image_order: Optional[
     will run on: model channel i reads byte i of a pixel.  "rgb" keeps the trained order; "bgr" (OpenCV images,
     Context.process_bgr) reverses W1's input axis and W3 / b3's output axis of a model trained on RGB.  ValueError when
     image_order is missing for a colour model, and when conv1 and conv3 disagree on the channel count.
+
+    Every such model runs in MODE_MFMA (the default) and, opt-in, in MODE_BANDED16 (layer 2 in split f16: the same
+    tolerance, a 9-5-5 model several times faster).
     """
     def arr(key, shape=None):
         if key not in sd:
@@ -302,7 +306,7 @@ def model_from_module(module, input_scale: float = 255.0, image_order: Optional[
     model is model_from_state_dict(module.state_dict(), input_scale, image_order) (a 3-channel module needs image_order);
     padding is "zero" or "replicate", read from each conv's
     padding and padding_mode.  Every layer must pad by k // 2 in one mode: ValueError for an unpadded layer (0 or "valid"),
-    for "reflect" or "circular", and for layers whose modes differ.
+    for "reflect" or "circular", and for layers whose modes differ.  Both paddings run in MODE_MFMA and MODE_BANDED16.
     """
     modes = set()
     for name in ("conv1", "conv2", "conv3"):
@@ -407,6 +411,9 @@ class Context:
 
     # -- configuration ------------------------------------------------------
     def set_mode(self, mode: int):
+        """MODE_MFMA (the default), MODE_EXACT, MODE_SPLIT16, MODE_REFBYTES, MODE_REFBYTES16, or MODE_BANDED16: every whole
+        model (1 or 3 channels, f2 = 1, 3, 5, either padding) on the banded path with layer 2 in split f16, the tolerance of
+        MODE_MFMA; row stripes, several GPUs and the per-layer device calls are refused in it (srcnn_set_mode)."""
         self._check(self._lib.srcnn_set_mode(self._h, int(mode)))
 
     def set_stream(self, hip_stream: int):
@@ -435,7 +442,9 @@ class Context:
 
     def set_model(self, w1, b1, w2, b2, w3, b3):
         """A 9-1-5, 9-3-5 or 9-5-5 model (srcnn_set_model): f2 from w2's shape, (32, 64) or (32, 64, f2, f2).
-        A colour model -- w1 (64, 3, 9, 9), w3 (3, 32, 5, 5), b3 of length 3 -- goes to srcnn_set_model_color."""
+        A colour model -- w1 (64, 3, 9, 9), w3 (3, 32, 5, 5), b3 of length 3 -- goes to srcnn_set_model_color.
+        f2 = 3, 5 and colour models run in MODE_MFMA and, with layer 2 in split f16, in MODE_BANDED16; every other mode
+        refuses them."""
         if tuple(np.shape(w1)) == (64, 3, 9, 9) or tuple(np.shape(w3)) == (3, 32, 5, 5) or np.size(b3) == 3:
             return self._set_model_color(w1, b1, w2, b2, w3, b3)
         shape = tuple(np.shape(w2))
@@ -506,7 +515,8 @@ class Context:
 
     def set_padding(self, padding):
         """"zero" (PyTorch's nn.Conv2d(..., padding=k // 2)) or "replicate" (the default), or PAD_ZERO / PAD_REPLICATE
-        (srcnn_set_padding).  A setting of the context: it applies to the model loaded before or after it."""
+        (srcnn_set_padding).  A setting of the context: it applies to the model loaded before or after it.  Zero padding
+        runs in MODE_MFMA and MODE_BANDED16."""
         if isinstance(padding, str):
             if padding not in _PADDINGS:
                 raise ValueError(f"padding {padding!r}: expected 'zero' or 'replicate'")

@@ -131,7 +131,7 @@ void srcnn_destroy(srcnn_ctx *c)
     (void)hipDeviceSynchronize();          // work on any stream the context was given may still use its buffers
     for (DevBuf *b : {&c->wfrag, &c->wraw, &c->in_u8, &c->out_u8, &c->pre_f32, &c->planes, &c->plane1, &c->kern, &c->sink,
                       &c->bgr_in, &c->bgr_out, &c->ycc_lo, &c->ycc_hi, &c->y_sr, &c->tables, &c->wfrag16,
-                      &c->band_top, &c->band_bot, &c->stripe_ext, &c->sp_table, &c->sp_map64, &c->sp_map32})
+                      &c->band_top, &c->band_bot, &c->stripe_ext, &c->sp_table, &c->sp16_table, &c->sp_map64, &c->sp_map32})
         release(*b);
     if (c->sp_done) (void)hipEventDestroy(c->sp_done);
     for (int k = 0; k < srcnn_ctx::kHaloSets; ++k) {
@@ -177,7 +177,7 @@ const char *srcnn_last_error(const srcnn_ctx *c) { return c ? c->err : "null con
 int srcnn_set_mode(srcnn_ctx *c, int mode)
 {
     if (!c || (mode != SRCNN_MODE_MFMA && mode != SRCNN_MODE_EXACT && mode != SRCNN_MODE_SPLIT16 && mode != SRCNN_MODE_REFBYTES &&
-               mode != SRCNN_MODE_REFBYTES16))
+               mode != SRCNN_MODE_REFBYTES16 && mode != SRCNN_MODE_BANDED16))
         return SRCNN_ERR_INVALID;
     BIND(c);
     c->mode = mode;

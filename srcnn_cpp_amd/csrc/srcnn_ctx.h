@@ -183,12 +183,22 @@ struct srcnn_ctx {
     srcnn::host::DevBuf sp_table, sp_map64, sp_map32;
     float sp_b3[3] = {0.f, 0.f, 0.f};
     int sp_f2 = 0;
+    // SRCNN_MODE_BANDED16 (layer 2 in split f16): a host copy of W2 [32][64][sp_f2][sp_f2] and the bound of the layer-1 map for
+    // 8-bit input, max_k (255 sum |w1[k]| + |b1[k]|), both kept by upload_table; the split W2 table (srcnn_kernels.h) and the
+    // two power-of-two scales are made from them the first time a call in that mode runs the model (sp16_f2 = 0: not made since
+    // the model was loaded; -1: the model cannot be scaled, the mode refuses it)
+    std::vector<float> sp_w2;
+    double sp_l1_bound = 0.0;
+    srcnn::host::DevBuf sp16_table;
+    int sp16_f2 = 0;
+    float sp16_scale1 = 1.f, sp16_unscale = 1.f;
     hipEvent_t sp_done = nullptr;
     hipStream_t sp_stream = nullptr;
     // SRCNN_PAD_ZERO (srcnn_set_padding): every model runs the banded path with the zero-padding kernels.  whole_model: the
     // tables came from srcnn_set_weights / srcnn_set_model(_color), not from per-filter calls
     int padding = SRCNN_PAD_REPLICATE;
     bool whole_model = false;
+    bool per_filter = false;     // inside srcnn_conv99x11 / srcnn_conv55 on host planes (luma_path_ok)
     // staging for the host-buffer entry points
     srcnn::host::DevBuf in_u8, out_u8, pre_f32, planes, plane1, kern, sink;
     // seam scratch (srcnn_kernels.h) is written by one launch and read by the seam kernel behind it: one buffer per
@@ -335,6 +345,12 @@ constexpr int kHaloRows = 6;   // 4 input rows of the 9x9 layer + 2 feature rows
 float fixup_delta(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, double margin = kFixMargin);
 void pack_fragments(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, float *out);
 void pack_fragments16(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, uint8_t *out);
+void split16(float w, float scale, uint16_t *hi, uint16_t *lo);     // f16 bits of hi = f16(w scale), lo = f16(w scale - hi)
+// SRCNN_MODE_BANDED16 (srcnn_spatial.cpp): the layer-1 bound for 8-bit input, the exponent that puts a bound in [2^14, 2^15),
+// and W2 times its power-of-two scale as the split A-operand table of spatial_l2h_kernel (false: the model cannot be scaled)
+double banded16_l1_bound(int C, const float *w1, const float *b1);
+bool banded16_exponent(double bound, int *e);
+bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2);
 bool split16_range_ok(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3);
 int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float *k11, const float *b11, const float *k55, float b55);
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11);
@@ -343,12 +359,18 @@ inline bool has_model(const srcnn_ctx *c) { return c->has_l12 && c->has_l3; }
 // The luma strip path may run: a 1-channel 9-1-5 model with replicate padding.  Every entry point that runs only that path (row
 // stripes, halo buffers, several GPUs, unfused, per-layer device calls, the row bands of srcnn_forward_y) tests this one
 // predicate; srcnn_forward_y_dev sends the other 1-channel models to the banded path and refuses a colour model.
-inline bool luma_path_ok(const srcnn_ctx *c) { return c->channels == 1 && c->f2 == 1 && c->padding != SRCNN_PAD_ZERO; }
+// SRCNN_MODE_BANDED16 runs every model on the banded path, so none of these entry points runs in it -- but for the per-filter
+// calls on host planes (srcnn_conv99x11, srcnn_conv55: per_filter is set while they run), which ignore every mode.
+inline bool luma_path_ok(const srcnn_ctx *c)
+{
+    return c->channels == 1 && c->f2 == 1 && c->padding != SRCNN_PAD_ZERO && (c->mode != SRCNN_MODE_BANDED16 || c->per_filter);
+}
 void drop_spatial_model(srcnn_ctx *c);
 
 // the entry points that run the 9-1-5 path with replicate padding only (row stripes, halo buffers, several GPUs, unfused,
-// per-layer device calls; under SRCNN_PAD_ZERO also the per-filter calls): the message names the model or the padding
-int refuse_spatial(srcnn_ctx *c, const char *what);
+// per-layer device calls; under SRCNN_PAD_ZERO also the per-filter calls): the message names the model, the padding or, in
+// SRCNN_MODE_BANDED16, the mode (banded_entry: `what` does run the banded path, so the mode is not what blocks it)
+int refuse_spatial(srcnn_ctx *c, const char *what, bool banded_entry = false);
 // ---- srcnn_spatial.cpp: the banded path (layer 1 -> spatial layer 2 -> layer 3 per row band) ----
 // n_frames planes of the loaded model (c->channels, c->f2, c->padding; refused with SRCNN_ERR_STATE where the mode, the padding
 // or the way the model was loaded has no banded arithmetic): input byte c of pixel (y, x) at src[y * src_stride + x * px_step +

@@ -386,8 +386,10 @@ int srcnn_conv99x11(srcnn_ctx *c, const uint8_t *src, size_t src_stride, float *
     if ((rc = reserve(c, c->planes, n * 32 * 4))) return rc;
     HIP_TRY(c, hipMemcpy2DAsync(c->in_u8.p, width, src, src_stride, width, height, hipMemcpyHostToDevice,
                                 c->stream));
+    c->per_filter = true;      // a per-filter call runs in every mode (luma_path_ok)
     rc = srcnn_conv99x11_dev(c, static_cast<uint8_t *>(c->in_u8.p), width, static_cast<float *>(c->planes.p),
                              width, n, width, height);
+    c->per_filter = false;
     if (rc) return rc;
     return planes_to_host(c, static_cast<const float *>(c->planes.p), n, dst, dst_stride, width, height, 32);
 }
@@ -406,8 +408,10 @@ int srcnn_conv55(srcnn_ctx *c, const float *const *src, size_t src_stride, uint8
     if ((rc = reserve(c, c->planes, n * 32 * 4))) return rc;
     if ((rc = reserve(c, c->out_u8, n))) return rc;
     if ((rc = planes_from_host(c, src, src_stride, static_cast<float *>(c->planes.p), n, width, height, 32))) return rc;
+    c->per_filter = true;      // a per-filter call runs in every mode (luma_path_ok)
     rc = srcnn_conv55_dev(c, static_cast<float *>(c->planes.p), width, n, static_cast<uint8_t *>(c->out_u8.p),
                           width, width, height, nullptr);
+    c->per_filter = false;
     if (rc) return rc;
     HIP_TRY(c, hipMemcpy2DAsync(dst, dst_stride, c->out_u8.p, width, width, height, hipMemcpyDeviceToHost,
                                 c->stream));
@@ -457,7 +461,7 @@ int srcnn_conv99(srcnn_ctx *c, const uint8_t *src, size_t src_stride, float *dst
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
-    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv99");
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv99", true);
     if (bad_plane(src, src_stride, width, height) || bad_plane(dst, dst_stride, width, height) || !kernel)
         return fail(c, SRCNN_ERR_INVALID, "conv99: bad arguments");
     const size_t n = (size_t)width * height;
@@ -481,7 +485,7 @@ int srcnn_conv11(srcnn_ctx *c, const float *const *src, size_t src_stride, float
     BIND(c);
     int rc = SRCNN_OK;
     (void)rc;
-    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv11");
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "srcnn_conv11", true);
     if (!src || src_stride < (size_t)width || bad_plane(dst, dst_stride, width, height) || !kernel)
         return fail(c, SRCNN_ERR_INVALID, "conv11: bad arguments");
     for (int k = 0; k < 64; ++k)

@@ -276,6 +276,21 @@ hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, i
 // padding is not a form of this kernel (the MODE_L3 strip kernel runs it).
 hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
                              const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
+// SRCNN_MODE_BANDED16: layer 2 in split f16 (spatial_l2h_kernel).  launch_spatial_l1h is launch_spatial_l1 with the split-output
+// epilogue: `map` (the same bytes) holds 8 planes of 32-byte pixels, every activation times `scale` (a power of two) as an f16
+// (hi, lo) pair; launch_spatial_l2h is launch_spatial_l2 on that map with frag = the split W2 table
+// (spatial_l2h_table_bytes(f2): [4 K steps][f2 * f2 taps][hi, lo][64 lanes][8 f16], lane l: output channel l & 31, element e:
+// layer-1 channel spatial_l2h_channel(step, l >> 5, e)) and unscale = 1 / (scale x the W2 scale).
+// WEAK declarations: a host-only build of srcnn_spatial.cpp that defines just the three launchers above still links, and
+// forward_banded() refuses the mode where these two are null.
+__host__ __device__ constexpr int spatial_l2h_channel(int step, int h, int e) { return 32 * (step >> 1) + acc_row(8 * (step & 1) + e, h); }
+__host__ __device__ constexpr size_t spatial_l2h_table_bytes(int f2) { return (size_t)4 * f2 * f2 * 2 * 64 * 16; }
+hipError_t launch_spatial_l1h(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
+                              int m0, int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
+    __attribute__((weak));
+hipError_t launch_spatial_l2h(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                              const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
+    __attribute__((weak));
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

@@ -504,7 +504,7 @@ int srcnn_forward_y_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, s
     // a 9-3-5 / 9-5-5 model, or any model under zero padding: banded layer 1 -> spatial layer 2 -> layer 3 (srcnn_spatial.cpp);
     // a colour model runs through srcnn_forward_color_dev only
     if (!luma_path_ok(c)) {
-        if (c->channels != 1) return refuse_spatial(c, "srcnn_forward_y_dev");
+        if (c->channels != 1) return refuse_spatial(c, "srcnn_forward_y_dev", true);
         if ((rc = flush_seams(c))) return rc;
         return forward_banded(c, d_src, src_stride, 1, 0, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, width, height,
                               n_frames, d_preclamp);

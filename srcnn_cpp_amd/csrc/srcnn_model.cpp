@@ -216,7 +216,7 @@ int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float
         for (int t = 0; t < 81; ++t) raw[10177 + t * 64 + ch] = w1[ch * 81 + t];
     std::vector<uint8_t> frag16(S16_TABLE_BYTES);
     pack_fragments16(w1, b1, w2, b2, w3, frag16.data());
-    c->sp_f2 = 0;                // the banded path's table no longer holds the model (srcnn_spatial.cpp)
+    c->sp_f2 = c->sp16_f2 = 0;   // the banded path's tables no longer hold the model (srcnn_spatial.cpp)
     int rc;
     if ((rc = reserve(c, c->wfrag, frag.size() * 4))) return rc;
     if ((rc = reserve(c, c->wfrag16, frag16.size()))) return rc;
@@ -241,12 +241,17 @@ const char *const kNoModel = "the model is not loaded: srcnn_set_weights not cal
 // The per-call tables of the reference surface (src/srcnn.cpp:609, :627: the same const arrays on every call).
 // Layers 1-2 of the model are replaced, layer 3 of any loaded model is kept (and the other way round for layer 3);
 // tables equal to the uploaded ones are not packed or uploaded again.
-int refuse_spatial(srcnn_ctx *c, const char *what)
+int refuse_spatial(srcnn_ctx *c, const char *what, bool banded_entry)
 {
+    if (c->mode == SRCNN_MODE_BANDED16 && !banded_entry)
+        return fail(c, SRCNN_ERR_STATE, "%s does not run in SRCNN_MODE_BANDED16 (that mode runs whole models on the banded path: "
+                                        "srcnn_forward_y / srcnn_forward_y_dev / srcnn_forward_y_frames / srcnn_forward_color* / "
+                                        "srcnn_process_bgr*); use SRCNN_MODE_MFMA",
+                    what);
     if (c->channels != 1)
         return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model only: the context holds a colour 9-%d-5 model "
                                         "(srcnn_set_model_color); use srcnn_forward_color / srcnn_forward_color_dev / "
-                                        "srcnn_process_bgr* in SRCNN_MODE_MFMA, or load a 1-channel model",
+                                        "srcnn_process_bgr* in SRCNN_MODE_MFMA or SRCNN_MODE_BANDED16, or load a 1-channel model",
                     what, c->f2);
     if (c->padding == SRCNN_PAD_ZERO)
         return fail(c, SRCNN_ERR_STATE, "%s has replicate padding only: the context is set to SRCNN_PAD_ZERO (srcnn_set_padding); "
@@ -273,7 +278,7 @@ void drop_spatial_model(srcnn_ctx *c)
 
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11)
 {
-    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "a per-filter call");
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "a per-filter call", true);
     drop_spatial_model(c);
     const float *hr = c->host_raw.data();
     const bool same = c->has_l12 && !std::memcmp(hr, bias99, 64 * 4) && !std::memcmp(hr + 64, kernel99, 5184 * 4) &&
@@ -287,7 +292,7 @@ int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const
 }
 int use_layer3(srcnn_ctx *c, const float *kernel, float bias)
 {
-    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "a per-filter call");
+    if (c->padding == SRCNN_PAD_ZERO) return refuse_spatial(c, "a per-filter call", true);
     drop_spatial_model(c);
     const float *hr = c->host_raw.data();
     if (c->has_l3 && hr[7328] == bias && !std::memcmp(hr + 7329, kernel, 800 * 4)) return SRCNN_OK;

@@ -43,6 +43,56 @@ static void pack_spatial(int C, int f2, const float *w1, const float *b1, const 
             }
 }
 
+// ---- SRCNN_MODE_BANDED16: exact power-of-two scales and the split W2 table (srcnn_spatial_kernels.hip, spatial_l2h_kernel) ----
+// The largest value layer 1 can give for 8-bit input: max over the 64 channels of 255 sum |w1[k]| + |b1[k]|
+double banded16_l1_bound(int C, const float *w1, const float *b1)
+{
+    double bound = 0.0;
+    for (int k = 0; k < 64; ++k) {
+        double sum = 0.0;
+        for (int i = 0; i < C * 81; ++i) sum += std::fabs((double)w1[(size_t)k * C * 81 + i]);
+        bound = std::max(bound, 255.0 * sum + std::fabs((double)b1[k]));
+        if (!std::isfinite(sum) || !std::isfinite((double)b1[k])) return HUGE_VAL;
+    }
+    return bound;
+}
+
+// e with bound * 2^e in [2^14, 2^15) (0 for a bound of 0); false when the bound is not finite
+bool banded16_exponent(double bound, int *e)
+{
+    *e = 0;
+    if (!std::isfinite(bound)) return false;
+    if (bound > 0.0) {
+        int x;
+        (void)std::frexp(bound, &x);           // bound = m 2^x, m in [0.5, 1)
+        *e = 15 - x;
+    }
+    return true;
+}
+
+// W2 [32][64][f2][f2] times 2^e2 (max |W2| 2^e2 in [2^14, 2^15)) as f16 (hi, lo) pairs, round to nearest, in the A-operand order
+// of spatial_l2h_kernel (srcnn_kernels.h); false when a weight is not finite or the scaled weights leave float32's range
+bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2)
+{
+    const int taps = f2 * f2;
+    double wmax = 0.0;
+    for (size_t i = 0; i < (size_t)2048 * taps; ++i) {
+        if (!std::isfinite(w2[i])) return false;
+        wmax = std::max(wmax, std::fabs((double)w2[i]));
+    }
+    if (!banded16_exponent(wmax, e2) || std::abs(*e2) > 120) return false;
+    const float scale = std::ldexp(1.f, *e2);
+    for (int s = 0; s < 4; ++s)
+        for (int tap = 0; tap < taps; ++tap)
+            for (int l = 0; l < 64; ++l)
+                for (int e = 0; e < 8; ++e) {
+                    const int k = l & 31, ci = spatial_l2h_channel(s, l >> 5, e);
+                    uint16_t *hi = table + ((((size_t)s * taps + tap) * 2) * 64 + l) * 8 + e;
+                    split16(w2[((size_t)k * 64 + ci) * taps + tap], scale, hi, hi + 64 * 8);
+                }
+    return true;
+}
+
 // The table and b3 of a C-channel 9-f2-5 model into sp_table / sp_b3 (pack_spatial's arguments)
 static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2,
                         const float *w3, const float *b3)
@@ -55,6 +105,35 @@ static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const floa
     HIP_TRY(c, hipMemcpy(c->sp_table.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
     std::memcpy(c->sp_b3, b3, C * sizeof(float));
     c->sp_f2 = f2;
+    // what SRCNN_MODE_BANDED16 makes its table and scales from, when a call first runs the model in that mode
+    c->sp_w2.assign(w2, w2 + (size_t)2048 * f2 * f2);
+    c->sp_l1_bound = banded16_l1_bound(C, w1, b1);
+    c->sp16_f2 = 0;
+    return SRCNN_OK;
+}
+
+// The split W2 table and the scales of SRCNN_MODE_BANDED16 for the model in sp_table, made once per loaded model
+static int upload_table16(srcnn_ctx *c)
+{
+    if (c->sp16_f2 == c->sp_f2) return SRCNN_OK;
+    const char *const refuse = "SRCNN_MODE_BANDED16 cannot scale this model into f16 (a weight or bias of layers 1-2 is not finite, "
+                               "or their magnitudes are beyond float32's exponent range); use SRCNN_MODE_MFMA";
+    if (c->sp16_f2 < 0) return fail(c, SRCNN_ERR_STATE, "%s", refuse);
+    const int f2 = c->sp_f2;
+    int e1 = 0, e2 = 0;
+    std::vector<uint16_t> table(spatial_l2h_table_bytes(f2) / sizeof(uint16_t));
+    if (!banded16_exponent(c->sp_l1_bound, &e1) || !banded16_pack_w2(f2, c->sp_w2.data(), table.data(), &e2) ||
+        std::abs(e1 + e2) > 120) {
+        c->sp16_f2 = -1;
+        return fail(c, SRCNN_ERR_STATE, "%s", refuse);
+    }
+    int rc;
+    if ((rc = reserve(c, c->sp16_table, table.size() * sizeof(uint16_t)))) return rc;
+    HIP_TRY(c, hipDeviceSynchronize());        // launches on any stream may still read the old table
+    HIP_TRY(c, hipMemcpy(c->sp16_table.p, table.data(), table.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    c->sp16_scale1 = std::ldexp(1.f, e1);
+    c->sp16_unscale = std::ldexp(1.f, -(e1 + e2));
+    c->sp16_f2 = f2;
     return SRCNN_OK;
 }
 
@@ -63,6 +142,14 @@ static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const floa
 static int banded_refusal(srcnn_ctx *c)
 {
     const bool zero = c->padding == SRCNN_PAD_ZERO;
+    if (c->mode == SRCNN_MODE_BANDED16) {      // every whole model, in either padding
+        if (!launch_spatial_l1h || !launch_spatial_l2h)
+            return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16: built without the split-f16 banded kernels");
+        if (!c->whole_model)
+            return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16 needs a model loaded by srcnn_set_weights / srcnn_set_model(_color): "
+                                            "the loaded layers came from per-filter calls");
+        return SRCNN_OK;
+    }
     if (c->mode != SRCNN_MODE_MFMA && c->channels != 1)
         return fail(c, SRCNN_ERR_STATE, "a colour model runs in SRCNN_MODE_MFMA only (mode %d has no arithmetic for it)", c->mode);
     if (c->mode != SRCNN_MODE_MFMA && zero)
@@ -98,6 +185,8 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
         const float *hr = c->host_raw.data();
         if ((rc = upload_table(c, 1, 1, hr + 64, hr, hr + 5280, hr + 5248, hr + 7329, hr + 7328))) return rc;
     }
+    const bool split = c->mode == SRCNN_MODE_BANDED16;
+    if (split && (rc = upload_table16(c))) return rc;
     const int C = c->channels, r2 = (c->f2 - 1) / 2;
     const bool zero = c->padding == SRCNN_PAD_ZERO;
     const long row_bytes = 4L * width;
@@ -127,10 +216,17 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
             const int b1 = std::min(height, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
-            HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag, map64,
-                                         mpitch, c->stream));
-            HIP_TRY(c, launch_spatial_l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, map32, opitch,
-                                         c->stream));
+            if (split) {       // the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
+                HIP_TRY(c, launch_spatial_l1h(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
+                                              map64, mpitch, c->sp16_scale1, c->stream));
+                HIP_TRY(c, launch_spatial_l2h(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, c->sp16_table.p, bias2,
+                                              c->sp16_unscale, map32, opitch, c->stream));
+            } else {
+                HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
+                                             map64, mpitch, c->stream));
+                HIP_TRY(c, launch_spatial_l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, map32, opitch,
+                                             c->stream));
+            }
             if (C > 1 || zero) {
                 HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, df,
                                              (long)dst_stride, pf, c->stream));
@@ -199,6 +295,25 @@ int srcnn_set_model_color(srcnn_ctx *c, int f2, const float *k1, const float *b1
     c->whole_model = true;
     return SRCNN_OK;
 }
+
+#ifdef SRCNN_TUNING_BUILD
+/* Undocumented test hook (not part of the ABI, needs no device): the host side of SRCNN_MODE_BANDED16 for a model of `channels`
+ * channels.  table: spatial_l2h_table_bytes(f2) bytes or null; exps: {e1, e2}, the exponents of the layer-1 map's and W2's
+ * scales.  Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the mode refuses. */
+int srcnn_debug_banded16_tables(int channels, int f2, const float *w1, const float *b1, const float *w2, uint16_t *table, int *exps)
+{
+    if ((channels != 1 && channels != 3) || (f2 != 1 && f2 != 3 && f2 != 5) || !w1 || !b1 || !w2 || !exps) return SRCNN_ERR_INVALID;
+    std::vector<uint16_t> own;
+    if (!table) {
+        own.resize(spatial_l2h_table_bytes(f2) / sizeof(uint16_t));
+        table = own.data();
+    }
+    if (!banded16_exponent(banded16_l1_bound(channels, w1, b1), &exps[0]) || !banded16_pack_w2(f2, w2, table, &exps[1]) ||
+        std::abs(exps[0] + exps[1]) > 120)
+        return SRCNN_ERR_STATE;
+    return (int)spatial_l2h_table_bytes(f2);
+}
+#endif
 
 int srcnn_get_model_f2(const srcnn_ctx *c) { return c ? c->f2 : SRCNN_ERR_INVALID; }
 

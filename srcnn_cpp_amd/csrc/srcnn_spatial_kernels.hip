@@ -11,6 +11,10 @@
 //   spatial_l3_kernel<C>   32 maps -> C channels (layer 3, + b3[c], truncate, clamp): u8 pixels of C bytes, pre-clamp floats;
 //                          the 1-channel model under replicate padding runs the MODE_L3 strip kernel (srcnn_mfma.hip) instead
 //
+// SRCNN_MODE_BANDED16 runs the same three launches with layer 2 in split f16: spatial_l1_kernel<C, ZERO, float> writes the
+// layer-1 map as f16 (hi, lo) pairs (the same bytes), spatial_l2h_kernel reads it on v_mfma_f32_32x32x16_f16 and writes the same
+// 32 planar f32 maps, layer 3 is unchanged.
+//
 // The input is read at src[y * sstride + x * px_step + c * ch_step]: px_step = 3, ch_step = 1 for interleaved 3-byte pixels
 // (srcnn_forward_color*), px_step = 1, ch_step = plane pitch for the three resized planes of srcnn_process_bgr, and a plain
 // plane for C = 1.  Model channel c reads byte c of a pixel and writes byte c of an output pixel.
@@ -60,11 +64,40 @@ __device__ __forceinline__ uint8_t l1_at(const uint8_t *p, long stride, int y, i
     return p[(long)y * stride + (long)x * px_step + c * ch_step];
 }
 
-template <int C, bool ZERO, typename... Steps>
+// SPLIT (Scale = float, SRCNN_MODE_BANDED16): the epilogue writes the map for spatial_l2h_kernel instead.  Every ReLU'd activation a, times the
+// power-of-two `scale` of the model (exact), becomes the f16 pair a_hi = rtz_f16(a), a_lo = f16(a - a_hi) (a - a_hi is exact in
+// f32; the split of srcnn_split16.hip): the same 4 bytes per value.  The map is 8 planes of 32-byte pixels (plane pitch mpitch
+// pixels, row stride W pixels): plane g = 4a + 2t + h holds the 8 channels that lane-half h keeps in registers 8t .. 8t + 7 of
+// accumulator a -- channel 32a + acc_row(8t + e, h), e = 0 .. 7 -- as [8 x a_hi][8 x a_lo], so a lane stores 32 consecutive bytes
+// per plane, and a lane of the layer-2 MFMA (K = 16: planes 2s and 2s + 1 on its two lane-halves) reads its 8 K values of one
+// pixel as one 16-byte word.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void l1_store_split(uint4 *o, const f32x16 &acc, int t, float scale)
+{
+    f16x8 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const float a0 = __builtin_fmaxf(acc[8 * t + e], 0.f) * scale, a1 = __builtin_fmaxf(acc[8 * t + e + 1], 0.f) * scale;
+        const f16x2 h = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(a0, a1));
+        hi[e] = h[0];
+        hi[e + 1] = h[1];
+        lo[e] = (_Float16)(a0 - (float)h[0]);
+        lo[e + 1] = (_Float16)(a1 - (float)h[1]);
+    }
+    o[0] = __builtin_bit_cast(uint4, hi);
+    o[1] = __builtin_bit_cast(uint4, lo);
+}
+
+struct NoScale {};         // the last argument of the forms that write plain f32 maps: nothing
+
+template <int C, bool ZERO, typename Scale, typename... Steps>
 __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restrict__ src, long sstride, Steps... steps, int W, int H,
                                                          int m0, int m1, const float *__restrict__ frag, float *__restrict__ map,
-                                                         long mpitch)
+                                                         long mpitch, Scale scale)
 {
+    constexpr bool SPLIT = std::is_same_v<Scale, float>;
     static_assert(sizeof...(Steps) == (C == 1 ? 0 : 2), "px_step and ch_step for 3 channels only");
     using T = std::conditional_t<C == 1, float, uint8_t>;      // the window's element type
     float *as;
@@ -117,12 +150,21 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restri
             }
         }
         if (x < W) {
-            float *o = map + (long)(y - m0) * W + x;
+            if constexpr (SPLIT) {
+                uint4 *o = reinterpret_cast<uint4 *>(map) + 2 * ((long)kk * mpitch + (long)(y - m0) * W + x);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int ch = acc_row(q, kk);
-                o[(long)ch * mpitch] = __builtin_fmaxf(acc0[q], 0.f);
-                o[(long)(32 + ch) * mpitch] = __builtin_fmaxf(acc1[q], 0.f);
+                for (int t = 0; t < 2; ++t) {
+                    l1_store_split(o + 2 * (2 * t) * mpitch, acc0, t, scale);
+                    l1_store_split(o + 2 * (4 + 2 * t) * mpitch, acc1, t, scale);
+                }
+            } else {
+                float *o = map + (long)(y - m0) * W + x;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int ch = acc_row(q, kk);
+                    o[(long)ch * mpitch] = __builtin_fmaxf(acc0[q], 0.f);
+                    o[(long)(32 + ch) * mpitch] = __builtin_fmaxf(acc1[q], 0.f);
+                }
             }
         }
     }
@@ -198,6 +240,136 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
             float *o = out + (long)(y - o0) * W + x;
 #pragma unroll
             for (int q = 0; q < 16; ++q) o[(long)acc_row(q, kk) * opitch] = __builtin_fmaxf(acc[u][q], 0.f);
+        }
+    }
+}
+
+// ---- layer 2 in split f16 (SRCNN_MODE_BANDED16) ------------------------------------------------------------------------------
+// The same implicit GEMM on v_mfma_f32_32x32x16_f16 (16 K values per instruction at half the cycles of the f32 one), with both
+// float32 operands split into f16 (hi, lo) pairs as in srcnn_split16.hip:
+//   w * 2^e2 = w_hi + w_lo   (host, round to nearest: srcnn_spatial.cpp)      a * 2^e1 = a_hi + a_lo   (spatial_l1_kernel<C, ZERO, float>)
+//   w a 2^(e1 + e2) ~= w_hi a_hi + w_lo a_hi + w_hi a_lo                      (the dropped w_lo a_lo is <= 2^-22 |w a|)
+// f16 x f16 products are exact in the f32 accumulation.  The accumulators start at 0; the epilogue is
+// max(fma(acc, 2^-(e1 + e2), b2[k]), 0), and the output is the 32 planar f32 maps of spatial_l2_kernel.  The power-of-two
+// scales (per model, exact) put the largest layer-1 activation any 8-bit input can give and max |W2| in [2^14, 2^15), so the hi
+// parts of all but vanishing values are normal f16 numbers.
+// Summation order: the input channels in 4 steps of 16 (ascending); inside a step the taps (kh, kw) row-major; per tap three
+// MFMAs, hi hi, then lo hi, then hi lo.  The order of the 16 products inside one MFMA is the hardware's (not documented), so
+// there is no bitwise CPU model of this kernel: it is held to the tolerance of the f32 path.
+// Workgroup and tile as spatial_l2_kernel: 4 waves, 64 columns x 16 rows, wave w rows 4w .. 4w + 3 and both 32-column units, so
+// each A fragment pair (w_hi, w_lo: 2 x 16 B per lane) feeds 24 MFMAs, with 16 B-operand reads: 18 ds_read_b128 per 24 MFMAs.
+// K step s reads map planes 2s (lane-half 0) and 2s + 1 (lane-half 1), i.e. K slot 8h + e is layer-1 channel
+// 32 (s >> 1) + acc_row(8 (s & 1) + e, h); the A table is packed in that order: [4 steps][f2 x f2 taps][hi, lo][64 lanes][8 f16],
+// lane l: output channel l & 31, K slots 8 (l >> 5) ...  Per step the two planes' (16 + 2 r2) x (64 + 2 r2) window is staged as
+// four LDS planes [plane][hi, lo] of 16-byte words, so the 16 lanes the LDS serves together read 256 consecutive bytes (no bank
+// conflict), and the step's A fragments beside it: 66 / 93 / 135 KiB for f2 = 1 / 3 / 5, one workgroup per CU for f2 = 3, 5.
+// With one wave per SIMD nothing else hides the global loads, so step s + 1 is fetched into registers while step s computes.
+constexpr int SL2H_STEPS = 4;
+__host__ __device__ constexpr int sl2h_ps(int r2) { return (((SL2_ROWS + 2 * r2) * (SL2_COLS + 2 * r2) + 7) / 8) * 8 + 4; }
+static size_t spatial_l2h_lds_bytes(int f2) { return ((size_t)4 * sl2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * sizeof(uint4); }
+#define HMFMA(a, b, c) \
+    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, (a)), __builtin_bit_cast(f16x8, (b)), (c), 0, 0, 0)
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+template <int F2, bool ZERO>
+__global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restrict__ map_, long mpitch, int m0, int m1, int W, int H,
+                                                          int o0, int o1, const uint4 *__restrict__ frag_,
+                                                          const float *__restrict__ bias, float unscale, float *__restrict__ out,
+                                                          long opitch)
+{
+    constexpr int R = (F2 - 1) / 2, PS = sl2h_ps(R), WR = SL2_ROWS + 2 * R, WC = SL2_COLS + 2 * R;
+    constexpr int NA = F2 * F2 * 2 * 64, NAK = (NA + 255) / 256;     // A words (16 B) per step, and per thread
+    // a window LINE is one row of one plane, 2 WC words [column][hi, lo] as the map has them; wave w stages lines w, w + 4, ..
+    constexpr int LW = 2 * WC, NK = (LW + 63) / 64, NL = 2 * WR / 4;
+    static_assert(2 * WR % 4 == 0, "the lines divide among the 4 waves");
+    extern __shared__ uint4 lds16[];
+    const u32x4 *map = reinterpret_cast<const u32x4 *>(map_), *frag = reinterpret_cast<const u32x4 *>(frag_);
+    u32x4 *xs = reinterpret_cast<u32x4 *>(lds16), *as = xs + 4 * PS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, kk = lane >> 5;
+    const int x0 = blockIdx.x * SL2_COLS, y0 = o0 + blockIdx.y * SL2_ROWS;
+    // the lane's words of a line (the same in every line): word min(lane + 64 k, LW - 1) -- past the end the last word again,
+    // which stores the same value to the same place; its offset in a map row (column replicate-clamped) and in an LDS plane pair
+    int goff[NK], loff[NK];
+    unsigned keep[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int idx = min(lane + 64 * k, LW - 1), part = idx & 1, cc = idx >> 1, ix = x0 - R + cc;
+        goff[k] = 2 * sclamp(ix, 0, W - 1) + part;
+        loff[k] = part * PS + cc;
+        keep[k] = (ix >= 0 && ix < W) ? ~0u : 0u;
+    }
+    // Step s + 1 is fetched into registers while step s computes, and goes to LDS between two barriers: the global loads
+    // have a whole step of MFMAs to land.
+    u32x4 wreg[NL][NK], areg[NAK];
+    auto fetch = [&](int s) {
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int line = wave + 4 * n, g = line / WR, rr = line - g * WR;
+            // image row, replicate-clamped, then kept inside the rows the map holds (only rows that are not stored differ)
+            const int yy = sclamp(sclamp(y0 - R + rr, 0, H - 1), m0, m1 - 1);
+            const u32x4 *row = map + 2 * ((long)(2 * s + g) * mpitch + (long)(yy - m0) * W);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                wreg[n][k] = row[goff[k]];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NAK; ++i) areg[i] = frag[(size_t)s * NA + min(tid + 256 * i, NA - 1)];
+    };
+    f32x16 acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = (f32x16){0};
+    fetch(0);
+    for (int s = 0; s < SL2H_STEPS; ++s) {
+        __syncthreads();
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int line = wave + 4 * n, g = line / WR, rr = line - g * WR;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                // ZERO: 0 outside the image, the replicate load under a mask (as in layer 1: no branch around the load)
+                if constexpr (ZERO) wreg[n][k] &= (y0 - R + rr >= 0 && y0 - R + rr < H) ? keep[k] : 0u;
+                xs[2 * g * PS + rr * WC + loff[k]] = wreg[n][k];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NAK; ++i) as[min(tid + 256 * i, NA - 1)] = areg[i];
+        __syncthreads();
+        if (s + 1 < SL2H_STEPS) fetch(s + 1);
+        const u32x4 *xb = xs + 2 * kk * PS + (4 * wave) * WC + j;
+        for (int kh = 0; kh < F2; ++kh) {
+#pragma unroll 1
+            for (int kw = 0; kw < F2; ++kw) {     // (not unrolled: the next step's words live in registers across this loop)
+                const u32x4 a_hi = as[((kh * F2 + kw) * 2) * 64 + lane], a_lo = as[((kh * F2 + kw) * 2 + 1) * 64 + lane];
+                const u32x4 *xq = xb + kh * WC + kw;
+                u32x4 b_hi[8], b_lo[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    b_hi[u] = xq[(u >> 1) * WC + 32 * (u & 1)];
+                    b_lo[u] = xq[PS + (u >> 1) * WC + 32 * (u & 1)];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc[u] = HMFMA(a_hi, b_hi[u], acc[u]);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc[u] = HMFMA(a_lo, b_hi[u], acc[u]);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc[u] = HMFMA(a_hi, b_lo[u], acc[u]);
+            }
+        }
+    }
+    float b[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) b[q] = bias[acc_row(q, kk)];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int y = y0 + 4 * wave + (u >> 1), x = x0 + 32 * (u & 1) + j;
+        if (y < o1 && x < W) {
+            float *o = out + (long)(y - o0) * W + x;
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                o[(long)acc_row(q, kk) * opitch] = __builtin_fmaxf(__builtin_fmaf(acc[u][q], unscale, b[q]), 0.f);
         }
     }
 }
@@ -317,13 +489,14 @@ static void launch_l1(dim3 grid, const uint8_t *src, long sstride, int px_step, 
                       const float *frag, float *map, long mpitch, hipStream_t st)
 {
     if constexpr (C == 1) {
-        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch);
+        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, NoScale>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch,
+                           NoScale{});
     } else {
         // (68 KiB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, int, long>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, NoScale, int, long>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
-        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step, ch_step, W,
-                           H, m0, m1, frag, map, mpitch);
+        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, NoScale, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step,
+                           ch_step, W, H, m0, m1, frag, map, mpitch, NoScale{});
     }
 }
 
@@ -363,6 +536,60 @@ hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, i
     else if (f2 == 5 && zero) launch_l2<5, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
     else return hipErrorInvalidValue;
     // (f2 = 1 under replicate padding: the colour 9-1-5 model; the 1-channel one runs on the strip kernels)
+    return hipGetLastError();
+}
+
+// ---- SRCNN_MODE_BANDED16: the split-output layer 1 and the split-f16 layer 2 -------------------------------------------------
+template <int C, bool ZERO>
+static void launch_l1h(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
+                       const float *frag, float *map, long mpitch, float scale, hipStream_t st)
+{
+    if constexpr (C == 1) {
+        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, float>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch, scale);
+    } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, float, int, long>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
+        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, float, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step, ch_step, W,
+                           H, m0, m1, frag, map, mpitch, scale);
+    }
+}
+
+hipError_t launch_spatial_l1h(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
+                              int m0, int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
+{
+    const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
+    float *m = static_cast<float *>(map);
+    if (channels == 1 && !zero) launch_l1h<1, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
+    else if (channels == 1) launch_l1h<1, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
+    else if (channels == 3 && !zero) launch_l1h<3, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
+    else if (channels == 3) launch_l1h<3, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+template <int F2, bool ZERO>
+static void launch_l2h(dim3 grid, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1, const void *frag,
+                       const float *bias, float unscale, float *out, long opitch, hipStream_t st)
+{
+    const size_t lds = spatial_l2h_lds_bytes(F2);
+    // (more than the default dynamic-LDS limit; set per call: the attribute is per device)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l2h_kernel<F2, ZERO>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    hipLaunchKernelGGL((spatial_l2h_kernel<F2, ZERO>), grid, dim3(256), lds, st, static_cast<const uint4 *>(map), mpitch, m0, m1, W, H,
+                       o0, o1, static_cast<const uint4 *>(frag), bias, unscale, out, opitch);
+}
+
+hipError_t launch_spatial_l2h(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                              const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
+{
+    const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS));
+    if (f2 == 1 && !zero) launch_l2h<1, false>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
+    else if (f2 == 3 && !zero) launch_l2h<3, false>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
+    else if (f2 == 5 && !zero) launch_l2h<5, false>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
+    else if (f2 == 1 && zero) launch_l2h<1, true>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
+    else if (f2 == 3 && zero) launch_l2h<3, true>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
+    else if (f2 == 5 && zero) launch_l2h<5, true>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

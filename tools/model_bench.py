@@ -3,11 +3,15 @@ srcnn_forward_y_dev on the context's stream, warm-up calls excluded.  Reports ms
 f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81*C + 32*64*f2^2 + 32*25*C) for C channels.
 
     python tools/model_bench.py [--channels 1 3] [--f2 1 3 5] [--padding replicate|zero|both] [--sizes 3840x2160 1920x1080]
-                                [--steps 20] [--warmup 3] [--json out.json]
+                                [--mode mfma|banded16|both] [--steps 20] [--warmup 3] [--json out.json]
 
 --channels 3 times the colour models (srcnn_set_model_color) through srcnn_forward_color_dev on interleaved 3-byte pixels.
 
 --padding both times each model and size with replicate padding, then with zero padding (srcnn_set_padding), in one process.
+
+--mode banded16 times SRCNN_MODE_BANDED16 (layer 2 in split f16); --mode both times each configuration in SRCNN_MODE_MFMA and
+then in SRCNN_MODE_BANDED16 in one process, and reports both times and their ratio (banded16 / mfma).  The fraction of peak is
+of the f32 peak by the algorithmic FLOP in either mode: the figure to compare is the time.
 """
 import argparse
 import json
@@ -77,6 +81,7 @@ def main():
     ap.add_argument("--channels", type=int, nargs="+", default=[1], choices=[1, 3])
     ap.add_argument("--f2", type=int, nargs="+", default=[3, 5], choices=[1, 3, 5])
     ap.add_argument("--padding", choices=["replicate", "zero", "both"], default="replicate")
+    ap.add_argument("--mode", choices=["mfma", "banded16", "both"], default="mfma")
     ap.add_argument("--sizes", nargs="+", default=["3840x2160", "1920x1080"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -92,6 +97,7 @@ def main():
                     w, h = map(int, size.split("x"))
                     for padding in paddings:
                         ctx.set_padding(padding)
+                        ctx.set_mode(S.MODE_BANDED16 if args.mode == "banded16" else S.MODE_MFMA)
                         med, best = time_plane(ctx, w, h, args.steps, args.warmup, channels)
                         px = w * h
                         fpp = flop_per_pixel(f2, channels)
@@ -100,6 +106,14 @@ def main():
                                    ms_per_plane=round(med, 3), ms_min=round(best, 3),
                                    mpix_per_s=round(px / (med * 1e-3) / 1e6, 1), flop_per_pixel=fpp, tflops=round(tflops, 2),
                                    fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps, warmup=args.warmup)
+                        if args.mode != "mfma":
+                            row["mode"] = "mfma" if args.mode == "both" else "banded16"
+                        if args.mode == "both":
+                            ctx.set_mode(S.MODE_BANDED16)
+                            med16, best16 = time_plane(ctx, w, h, args.steps, args.warmup, channels)
+                            ctx.set_mode(S.MODE_MFMA)
+                            row.update(mode="both", ms_per_plane_banded16=round(med16, 3), ms_min_banded16=round(best16, 3),
+                                       banded16_over_mfma=round(med16 / med, 3))
                         rows.append(row)
                         print(json.dumps(row), flush=True)
     if args.json:
