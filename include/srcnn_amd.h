@@ -306,6 +306,45 @@ int srcnn_forward_color_dev(srcnn_ctx *ctx,
                             uint8_t *d_dst, size_t dst_stride, size_t dst_frame_pitch,
                             int width, int height, int n_frames, float *d_preclamp /*may be NULL; dst strides*/);
 
+/* The float image path: the loaded whole model on float32 planes, float in, float out -- what a PyTorch SRCNN module computes as
+ * module(x).  The input is in the model's OWN units (a model trained on [0, 1] runs on [0, 1] with its weights and biases as
+ * trained: nothing is scaled by 255), and the output is the value layer 3 gives, + bias3: no (int) truncation, no clamp, no
+ * byte.  Every whole model runs: 1 or 3 channels (the count comes from the loaded model), f2 = 1, 3, 5, replicate or zero
+ * padding (srcnn_set_padding).
+ *   - Layout: planar.  Element (frame f, channel c, row y, column x) lies at p[f * frame_pitch + c * ch_pitch + y * stride + x];
+ *     strides and pitches are in ELEMENTS (floats), a stride is at least `width`, and the channel pitches are ignored for a
+ *     1-channel model.  That is a contiguous NCHW tensor and any row-, channel- or frame-strided view of one.  The output planes
+ *     must not overlap each other or the input (SRCNN_ERR_INVALID, like null pointers, sizes <= 0 and a stride below the width).
+ *     Interleaved float pixels are not supported.
+ *   - SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only: every other mode returns SRCNN_ERR_STATE and srcnn_last_error() names the
+ *     mode, as it names a model whose layers came from per-filter calls.  The context stays usable.
+ *   - Always the banded path of srcnn_set_model: three launches per row band, the summation order of the byte path (on
+ *     integer-valued input 0..255 the output equals the byte path's pre-clamp floats bit for bit where that path runs the banded
+ *     layer 3).  The 1-channel replicate-padded 9-1-5 model runs banded here too: there is no float-input form of the fused strip
+ *     kernel, so that model is slower here than through srcnn_forward_y_dev: measured on one MI355X, 2.73 ms per 3840x2160
+ *     plane (1.88 ms in SRCNN_MODE_BANDED16) against 1.01 ms fused.
+ *   - Inputs must be FINITE: the zero-padding kernels blank a border value by a multiply with 0, so an infinity or NaN next to
+ *     the image border spreads NaN into the output.
+ *   - SRCNN_MODE_BANDED16 scales the layer-1 map by a bound that holds for inputs of magnitude <= the context's input range
+ *     (srcnn_set_input_range, default 255): inside it the results are finite and within the tolerance of the mode; outside it
+ *     they are unspecified (the f16 halves may overflow to infinity), but nothing faults.
+ * srcnn_forward_f32_dev: device memory, n_frames images, asynchronous on the context's stream.  srcnn_forward_f32: one image in
+ * host memory, staged on the device; returns when dst is complete. */
+int srcnn_forward_f32_dev(srcnn_ctx *ctx,
+                          const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
+                          float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch,
+                          int width, int height, int n_frames);
+int srcnn_forward_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_t src_ch_pitch,
+                      float *dst, size_t dst_stride, size_t dst_ch_pitch, int width, int height);
+/* The largest |input| of a float call, a setting of the CONTEXT like the padding: default 255, it survives model loads.  Only
+ * SRCNN_MODE_BANDED16 reads it, and only in srcnn_forward_f32(_dev): it replaces 255 in the bound the power-of-two scale of the
+ * layer-1 map is made from (255 for [0, 255] data, 1 for [0, 1], 1023 for 10-bit video ...).  The split W2 table does not
+ * depend on it, so changing it repacks nothing; SRCNN_MODE_MFMA ignores it, and the byte entry points keep 255 whatever it is.
+ * r must be finite and > 0, else SRCNN_ERR_INVALID.  srcnn_get_input_range returns the setting (SRCNN_ERR_INVALID as a float
+ * for a null context). */
+int srcnn_set_input_range(srcnn_ctx *ctx, float r);
+float srcnn_get_input_range(const srcnn_ctx *ctx);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

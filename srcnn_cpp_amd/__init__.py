@@ -133,6 +133,10 @@ def load_library() -> C.CDLL:
         "srcnn_get_model_channels": ([vp], i),
         "srcnn_forward_color": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_color_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
+        "srcnn_forward_f32": ([vp, _f32p, sz, sz, _f32p, sz, sz, i, i], i),
+        "srcnn_forward_f32_dev": ([vp, vp, sz, sz, sz, vp, sz, sz, sz, i, i, i], i),
+        "srcnn_set_input_range": ([vp, C.c_float], i),
+        "srcnn_get_input_range": ([vp], C.c_float),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_y_frames": ([vp, C.POINTER(_u8p), sz, C.POINTER(_u8p), sz, i, i, i], i),
         "srcnn_forward_y_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
@@ -193,6 +197,7 @@ ABI_SYMBOLS = (
     "srcnn_stripe_rows", "srcnn_forward_y_frames_multi", "srcnn_forward_y_lanes_dev", "srcnn_forward_y_striped", "srcnn_forward_y_striped_frames", "srcnn_forward_y_striped_dev",
     "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
+    "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
 )
 
 
@@ -343,6 +348,24 @@ def _plane(a, dtype, name, writable=False):
     if writable and not a.flags.writeable:
         raise ValueError(f"{name}: output plane is read-only")
     return a, a.strides[0] // a.itemsize
+
+
+def _f32_planes(a, name, writable=False):
+    """A float32 (H, W), (C, H, W) or (N, C, H, W) array as its (N, C, H, W) view: rows contiguous, the other strides whole
+    floats, positive and no smaller than a row (TypeError / ValueError otherwise, before any call into the library)."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim not in (2, 3, 4):
+        raise TypeError(f"{name}: expected a float32 numpy array of shape (H, W), (C, H, W) or (N, C, H, W)")
+    if 0 in a.shape:
+        raise ValueError(f"{name}: empty array of shape {tuple(a.shape)}")
+    a4 = a[(None,) * (4 - a.ndim)]
+    w = a4.shape[3]
+    if a4.strides[3] != 4 or (a4.shape[2] > 1 and (a4.strides[2] % 4 or a4.strides[2] < 4 * w)):
+        raise ValueError(f"{name}: rows must be contiguous (row, channel and frame strides may be padded)")
+    if any(a4.shape[d] > 1 and (a4.strides[d] % 4 or a4.strides[d] <= 0) for d in (0, 1)):
+        raise ValueError(f"{name}: channel and frame strides must be positive multiples of 4 bytes")
+    if writable and not a.flags.writeable:
+        raise ValueError(f"{name}: output array is read-only")
+    return a4
 
 
 def _same_shape(name, got, want):
@@ -508,6 +531,45 @@ class Context:
         """srcnn_forward_color_dev: strides and frame pitches in bytes; d_preclamp (floats) uses the dst strides."""
         self._check(self._lib.srcnn_forward_color_dev(self._h, d_src, src_stride, src_frame_pitch, d_dst, dst_stride,
                                                       dst_frame_pitch, width, height, n_frames, d_preclamp or None))
+
+    def forward_f32(self, x, out=None):
+        """The loaded whole model on float32 planes in the model's own units, the value before truncation out (srcnn_forward_f32):
+        x is (H, W), (C, H, W) or (N, C, H, W) with C the model's channel count ((H, W): a 1-channel model), rows contiguous,
+        row / channel / frame strides free; returns an array of the same shape (out, or a new one).  MODE_MFMA and
+        MODE_BANDED16 only; inputs must be finite (and within set_input_range() in MODE_BANDED16)."""
+        x4 = _f32_planes(x, "x")
+        if out is None:
+            out = np.empty(x.shape, np.float32)
+        o4 = _f32_planes(out, "out", True)
+        _same_shape("out", out.shape, x.shape)
+        n, c, h, w = x4.shape
+        if c not in (1, 3):
+            raise ValueError(f"x: shape {tuple(x.shape)}: a model has 1 channel or 3")
+        channels = self.model_channels()
+        if c != channels:
+            raise ValueError(f"x: shape {tuple(x.shape)} for a model of {channels} channel(s): expected (N, {channels}, H, W), "
+                             f"({channels}, H, W)" + (" or (H, W)" if channels == 1 else ""))
+        stride = lambda a4: a4.strides[2] // 4 if h > 1 else w
+        for k in range(n):
+            self._check(self._lib.srcnn_forward_f32(self._h, _fp(x4[k]), stride(x4), x4.strides[1] // 4 if c > 1 else 0, _fp(o4[k]),
+                                                    stride(o4), o4.strides[1] // 4 if c > 1 else 0, w, h))
+        return out
+
+    def forward_f32_dev(self, d_src, src_stride, src_ch_pitch, src_frame_pitch, d_dst, dst_stride, dst_ch_pitch,
+                        dst_frame_pitch, width, height, n_frames=1):
+        """srcnn_forward_f32_dev: device addresses of float32 planes, strides and pitches in floats, asynchronous on the
+        context's stream; the channel pitches are ignored for a 1-channel model."""
+        self._check(self._lib.srcnn_forward_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, d_dst, dst_stride,
+                                                    dst_ch_pitch, dst_frame_pitch, width, height, n_frames))
+
+    def set_input_range(self, r: float):
+        """The largest |input| of a float call (srcnn_set_input_range): 255 by default, 1.0 for [0, 1] data.  A setting of the
+        context; only MODE_BANDED16 reads it, and only in forward_f32 / forward_f32_dev."""
+        self._check(self._lib.srcnn_set_input_range(self._h, float(r)))
+
+    def input_range(self) -> float:
+        """srcnn_get_input_range."""
+        return float(self._lib.srcnn_get_input_range(self._h))
 
     def model_f2(self) -> int:
         """f2 of the loaded model: 1 (9-1-5, also after set_weights), 3 or 5."""

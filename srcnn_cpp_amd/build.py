@@ -49,6 +49,8 @@ UNITS = [
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models
     ("srcnn_spatial_kernels.hip", []),
+    # the float image path (srcnn_forward_f32*): the float forms of that file's layer-1 and layer-3 templates, a unit of their own
+    ("srcnn_spatial_f32.hip", []),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),
@@ -112,7 +114,8 @@ TUNING_LIB = PKG / "libsrcnn_amd_tuning.so"
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [CSRC / "srcnn_kernels.h", CSRC / "srcnn_ctx.h", PKG.parent / "include" / "srcnn_amd.h", Path(__file__)]
+    headers = [CSRC / "srcnn_kernels.h", CSRC / "srcnn_ctx.h", CSRC / "srcnn_spatial_kernels.hip",
+               PKG.parent / "include" / "srcnn_amd.h", Path(__file__)]
     objs, tuning_objs = [], []
     for unit in UNITS:
         src, extra = unit[0], unit[1]

@@ -192,6 +192,13 @@ struct srcnn_ctx {
     srcnn::host::DevBuf sp16_table;
     int sp16_f2 = 0;
     float sp16_scale1 = 1.f, sp16_unscale = 1.f;
+    // The float image path (srcnn_forward_f32*) in SRCNN_MODE_BANDED16 bounds the layer-1 map by input_range (srcnn_set_input_range,
+    // a setting of the context like the padding: default 255, kept across model loads) instead of 255: upload_table keeps
+    // sum |w1[k]| and |b1[k]| per layer-1 channel, upload_table16 the exponent of W2's scale, and a float call makes its two
+    // scales from them.  The W2 table does not depend on the range; the byte entry points keep sp16_scale1 / sp16_unscale.
+    float input_range = 255.f;
+    double sp_l1_sum[64] = {}, sp_l1_absb[64] = {};
+    int sp16_e2 = 0;
     hipEvent_t sp_done = nullptr;
     hipStream_t sp_stream = nullptr;
     // SRCNN_PAD_ZERO (srcnn_set_padding): every model runs the banded path with the zero-padding kernels.  whole_model: the
@@ -348,7 +355,7 @@ void pack_fragments16(const float *w1, const float *b1, const float *w2, const f
 void split16(float w, float scale, uint16_t *hi, uint16_t *lo);     // f16 bits of hi = f16(w scale), lo = f16(w scale - hi)
 // SRCNN_MODE_BANDED16 (srcnn_spatial.cpp): the layer-1 bound for 8-bit input, the exponent that puts a bound in [2^14, 2^15),
 // and W2 times its power-of-two scale as the split A-operand table of spatial_l2h_kernel (false: the model cannot be scaled)
-double banded16_l1_bound(int C, const float *w1, const float *b1);
+double banded16_l1_bound(int C, const float *w1, const float *b1, double range = 255.0);
 bool banded16_exponent(double bound, int *e);
 bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2);
 bool split16_range_ok(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3);
@@ -375,6 +382,18 @@ int refuse_spatial(srcnn_ctx *c, const char *what, bool banded_entry = false);
 // n_frames planes of the loaded model (c->channels, c->f2, c->padding; refused with SRCNN_ERR_STATE where the mode, the padding
 // or the way the model was loaded has no banded arithmetic): input byte c of pixel (y, x) at src[y * src_stride + x * px_step +
 // c * ch_step] (1 channel: px_step 1, ch_step 0), output (and pre, at the same element offsets) pixels of c->channels bytes.
+// The planes of one call: u8 (f32 false: src / dst point at bytes, strides in bytes, pre optional) or float32 (the float image
+// path: strides in floats, channel o of the output at dst + o * dst_ch_pitch, px_step 1, no pre).
+struct BandedPlanes {
+    bool f32 = false;
+    const void *src = nullptr;
+    size_t src_stride = 0, ch_step = 0, src_frame_pitch = 0;
+    int px_step = 1;
+    void *dst = nullptr;
+    size_t dst_stride = 0, dst_ch_pitch = 0, dst_frame_pitch = 0;
+    float *pre = nullptr;
+};
+int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, int n_frames);
 int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_step, size_t ch_step, size_t src_frame_pitch,
                    uint8_t *dst, size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre);
 constexpr size_t kSpatialWorkBytes = (size_t)512 << 20;     // bound of the two band maps (include/srcnn_amd.h, srcnn_set_model)

@@ -291,6 +291,17 @@ hipError_t launch_spatial_l1h(int channels, bool zero, const uint8_t *src, long 
 hipError_t launch_spatial_l2h(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
                               const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
     __attribute__((weak));
+// The float image path (srcnn_forward_f32*).  launch_spatial_l1f is launch_spatial_l1 / launch_spatial_l1h (split: the f16 pair
+// map, every activation times `scale`) on `channels` float planes, channel c of pixel (y, x) at src[y * sstride + x + c * ch_step],
+// in the model's own units (finite values); launch_spatial_l3f is launch_spatial_l3 writing the value before truncation to
+// `channels` float planes, dst[y * dstride + x + o * ch_pitch], and no byte -- 1 channel under replicate padding included.
+// WEAK declarations, as the two above: forward_banded() refuses a float call where they are null.
+hipError_t launch_spatial_l1f(int channels, bool zero, bool split, const float *src, long sstride, long ch_step, int W, int H, int m0,
+                              int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
+    __attribute__((weak));
+hipError_t launch_spatial_l3f(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                              const float *frag, const float *b3, float *dst, long dstride, long ch_pitch, hipStream_t st)
+    __attribute__((weak));
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

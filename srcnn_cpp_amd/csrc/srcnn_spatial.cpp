@@ -1,7 +1,8 @@
 // srcnn_spatial.cpp -- the banded path, layer 1 -> spatial layer 2 -> layer 3 per row band (srcnn_spatial_kernels.hip): the
 // 9-3-5 / 9-5-5 models (srcnn_set_model, f2 = 3 or 5) behind srcnn_forward_y_dev, every model under zero padding
 // (srcnn_set_padding), f2 = 1 included, and the colour models (srcnn_set_model_color: 3 input and 3 output channels, 9-f2-5)
-// behind srcnn_forward_color(_dev) and srcnn_process_bgr(_dev).  One weight table per model, one gate, one band loop.
+// behind srcnn_forward_color(_dev) and srcnn_process_bgr(_dev); and the float image path, srcnn_forward_f32(_dev): every whole
+// model on float32 planes, the value before truncation out.  One weight table per model, one gate, one band loop.
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
@@ -44,17 +45,33 @@ static void pack_spatial(int C, int f2, const float *w1, const float *b1, const 
 }
 
 // ---- SRCNN_MODE_BANDED16: exact power-of-two scales and the split W2 table (srcnn_spatial_kernels.hip, spatial_l2h_kernel) ----
-// The largest value layer 1 can give for 8-bit input: max over the 64 channels of 255 sum |w1[k]| + |b1[k]|
-double banded16_l1_bound(int C, const float *w1, const float *b1)
+// sum |w1[k]| and |b1[k]| of the 64 layer-1 channels (doubles), what the bound below is made from; false when one is not finite
+static bool l1_magnitudes(int C, const float *w1, const float *b1, double *sum, double *absb)
+{
+    bool finite = true;
+    for (int k = 0; k < 64; ++k) {
+        sum[k] = 0.0;
+        for (int i = 0; i < C * 81; ++i) sum[k] += std::fabs((double)w1[(size_t)k * C * 81 + i]);
+        absb[k] = std::fabs((double)b1[k]);
+        finite = finite && std::isfinite(sum[k]) && std::isfinite(absb[k]);
+    }
+    return finite;
+}
+
+// The largest value layer 1 can give for inputs of magnitude <= range: max over the 64 channels of range sum |w1[k]| + |b1[k]|
+static double l1_bound(const double *sum, const double *absb, double range)
 {
     double bound = 0.0;
-    for (int k = 0; k < 64; ++k) {
-        double sum = 0.0;
-        for (int i = 0; i < C * 81; ++i) sum += std::fabs((double)w1[(size_t)k * C * 81 + i]);
-        bound = std::max(bound, 255.0 * sum + std::fabs((double)b1[k]));
-        if (!std::isfinite(sum) || !std::isfinite((double)b1[k])) return HUGE_VAL;
-    }
+    for (int k = 0; k < 64; ++k) bound = std::max(bound, range * sum[k] + absb[k]);
     return bound;
+}
+
+// ... for 8-bit input (range 255, what the byte entry points use), or the range of a float call (srcnn_set_input_range)
+double banded16_l1_bound(int C, const float *w1, const float *b1, double range)
+{
+    double sum[64], absb[64];
+    if (!l1_magnitudes(C, w1, b1, sum, absb)) return HUGE_VAL;
+    return l1_bound(sum, absb, range);
 }
 
 // e with bound * 2^e in [2^14, 2^15) (0 for a bound of 0); false when the bound is not finite
@@ -107,7 +124,7 @@ static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const floa
     c->sp_f2 = f2;
     // what SRCNN_MODE_BANDED16 makes its table and scales from, when a call first runs the model in that mode
     c->sp_w2.assign(w2, w2 + (size_t)2048 * f2 * f2);
-    c->sp_l1_bound = banded16_l1_bound(C, w1, b1);
+    c->sp_l1_bound = l1_magnitudes(C, w1, b1, c->sp_l1_sum, c->sp_l1_absb) ? l1_bound(c->sp_l1_sum, c->sp_l1_absb, 255.0) : HUGE_VAL;
     c->sp16_f2 = 0;
     return SRCNN_OK;
 }
@@ -133,15 +150,27 @@ static int upload_table16(srcnn_ctx *c)
     HIP_TRY(c, hipMemcpy(c->sp16_table.p, table.data(), table.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     c->sp16_scale1 = std::ldexp(1.f, e1);
     c->sp16_unscale = std::ldexp(1.f, -(e1 + e2));
+    c->sp16_e2 = e2;
     c->sp16_f2 = f2;
     return SRCNN_OK;
 }
 
 // The one gate of the banded path: SRCNN_OK when it may run the loaded model in the current mode and padding, else
-// SRCNN_ERR_STATE with a message that names what blocks the call
-static int banded_refusal(srcnn_ctx *c)
+// SRCNN_ERR_STATE with a message that names what blocks the call.  f32: a call of the float image path (srcnn_forward_f32*),
+// which runs every whole model in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 and nothing else
+static int banded_refusal(srcnn_ctx *c, bool f32 = false)
 {
     const bool zero = c->padding == SRCNN_PAD_ZERO;
+    if (f32) {
+        if (c->mode != SRCNN_MODE_MFMA && c->mode != SRCNN_MODE_BANDED16)
+            return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 runs in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only (mode %d has no "
+                                            "float image path)", c->mode);
+        if (!launch_spatial_l1f || !launch_spatial_l3f)
+            return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32: built without the float-plane banded kernels");
+        if (!c->whole_model)
+            return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 needs a model loaded by srcnn_set_weights / srcnn_set_model(_color): "
+                                            "the loaded layers came from per-filter calls");
+    }
     if (c->mode == SRCNN_MODE_BANDED16) {      // every whole model, in either padding
         if (!launch_spatial_l1h || !launch_spatial_l2h)
             return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16: built without the split-f16 banded kernels");
@@ -178,8 +207,23 @@ static int refuse_luma_model(srcnn_ctx *c)
 int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_step, size_t ch_step, size_t src_frame_pitch,
                    uint8_t *dst, size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre)
 {
+    BandedPlanes io;
+    io.src = src;
+    io.src_stride = src_stride;
+    io.px_step = px_step;
+    io.ch_step = ch_step;
+    io.src_frame_pitch = src_frame_pitch;
+    io.dst = dst;
+    io.dst_stride = dst_stride;
+    io.dst_frame_pitch = dst_frame_pitch;
+    io.pre = pre;
+    return forward_banded(c, io, width, height, n_frames);
+}
+
+int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, int n_frames)
+{
     int rc;
-    if ((rc = banded_refusal(c))) return rc;
+    if ((rc = banded_refusal(c, io.f32))) return rc;
     // (only a 9-1-5 model gets here unpacked: the others pack when they load)
     if (c->sp_f2 != c->f2) {
         const float *hr = c->host_raw.data();
@@ -187,6 +231,16 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
     }
     const bool split = c->mode == SRCNN_MODE_BANDED16;
     if (split && (rc = upload_table16(c))) return rc;
+    // a float call scales the layer-1 map by the bound for inputs up to input_range, not 255: the same W2 table, other scales
+    float scale1 = c->sp16_scale1, unscale = c->sp16_unscale;
+    if (split && io.f32) {
+        int e1 = 0;
+        if (!banded16_exponent(l1_bound(c->sp_l1_sum, c->sp_l1_absb, (double)c->input_range), &e1) || std::abs(e1 + c->sp16_e2) > 120)
+            return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16 cannot scale this model into f16 for inputs up to %g "
+                                            "(srcnn_set_input_range); use SRCNN_MODE_MFMA", (double)c->input_range);
+        scale1 = std::ldexp(1.f, e1);
+        unscale = std::ldexp(1.f, -(e1 + c->sp16_e2));
+    }
     const int C = c->channels, r2 = (c->f2 - 1) / 2;
     const bool zero = c->padding == SRCNN_PAD_ZERO;
     const long row_bytes = 4L * width;
@@ -197,8 +251,8 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
     const long mrows = std::min<long>(height, band + 4 + 2 * r2), orows = std::min<long>(height, band + 4);
     const long mpitch = mrows * width, opitch = orows * width;
     if (bad_pitch((size_t)mpitch) || bad_pitch((size_t)opitch))
-        return fail(c, SRCNN_ERR_INVALID, "%s: plane too large for a %s9-%d-5 model", C == 1 ? "forward_y_dev" : "forward_color_dev",
-                    C == 1 ? "" : "colour ", c->f2);
+        return fail(c, SRCNN_ERR_INVALID, "%s: plane too large for a %s9-%d-5 model",
+                    io.f32 ? "forward_f32_dev" : C == 1 ? "forward_y_dev" : "forward_color_dev", C == 1 ? "" : "colour ", c->f2);
     if ((rc = reserve(c, c->sp_map64, (size_t)64 * mpitch * sizeof(float)))) return rc;
     if ((rc = reserve(c, c->sp_map32, (size_t)32 * opitch * sizeof(float)))) return rc;
     if (!c->sp_done) HIP_TRY(c, hipEventCreateWithFlags(&c->sp_done, hipEventDisableTiming));
@@ -208,24 +262,47 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
     const float *frag2 = frag + spatial_l2_offset(C), *bias2 = frag2 + (size_t)c->f2 * c->f2 * 2048;
     const float *frag3 = frag + spatial_l3_offset(C, c->f2);
     float *map64 = static_cast<float *>(c->sp_map64.p), *map32 = static_cast<float *>(c->sp_map32.p);
+    const size_t src_stride = io.src_stride, ch_step = io.ch_step, dst_stride = io.dst_stride;
+    const int px_step = io.px_step;
     for (int f = 0; f < n_frames; ++f) {
-        const uint8_t *sf = src + (size_t)f * src_frame_pitch;
-        uint8_t *df = dst + (size_t)f * dst_frame_pitch;
-        float *pf = pre ? pre + (size_t)f * dst_frame_pitch : nullptr;
+        // frame f of the call's planes: bytes, or floats (the float image path); the other pair stays null
+        const uint8_t *sf = nullptr;
+        uint8_t *df = nullptr;
+        float *pf = nullptr;
+        const float *sff = nullptr;
+        float *dff = nullptr;
+        if (io.f32) {
+            sff = static_cast<const float *>(io.src) + (size_t)f * io.src_frame_pitch;
+            dff = static_cast<float *>(io.dst) + (size_t)f * io.dst_frame_pitch;
+        } else {
+            sf = static_cast<const uint8_t *>(io.src) + (size_t)f * io.src_frame_pitch;
+            df = static_cast<uint8_t *>(io.dst) + (size_t)f * io.dst_frame_pitch;
+            pf = io.pre ? io.pre + (size_t)f * io.dst_frame_pitch : nullptr;
+        }
         for (int b0 = 0; b0 < height; b0 += band) {
             const int b1 = std::min(height, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
+            if (io.f32)        // float planes in: one launcher for both forms of the map
+                HIP_TRY(c, launch_spatial_l1f(C, zero, split, sff, (long)src_stride, (long)ch_step, width, height, m0, m1, frag, map64,
+                                              mpitch, scale1, c->stream));
             if (split) {       // the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
-                HIP_TRY(c, launch_spatial_l1h(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
-                                              map64, mpitch, c->sp16_scale1, c->stream));
+                if (!io.f32)
+                    HIP_TRY(c, launch_spatial_l1h(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
+                                                  map64, mpitch, scale1, c->stream));
                 HIP_TRY(c, launch_spatial_l2h(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, c->sp16_table.p, bias2,
-                                              c->sp16_unscale, map32, opitch, c->stream));
+                                              unscale, map32, opitch, c->stream));
             } else {
-                HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
-                                             map64, mpitch, c->stream));
+                if (!io.f32)
+                    HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
+                                                 map64, mpitch, c->stream));
                 HIP_TRY(c, launch_spatial_l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, map32, opitch,
                                              c->stream));
+            }
+            if (io.f32) {      // float planes out, the 1-channel replicate model included (no float form of MODE_L3)
+                HIP_TRY(c, launch_spatial_l3f(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, dff,
+                                              (long)dst_stride, (long)io.dst_ch_pitch, c->stream));
+                continue;
             }
             if (C > 1 || zero) {
                 HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, df,
@@ -300,18 +377,39 @@ int srcnn_set_model_color(srcnn_ctx *c, int f2, const float *k1, const float *b1
 /* Undocumented test hook (not part of the ABI, needs no device): the host side of SRCNN_MODE_BANDED16 for a model of `channels`
  * channels.  table: spatial_l2h_table_bytes(f2) bytes or null; exps: {e1, e2}, the exponents of the layer-1 map's and W2's
  * scales.  Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the mode refuses. */
+int srcnn_debug_banded16_tables_range(int channels, int f2, const float *w1, const float *b1, const float *w2, float range,
+                                      uint16_t *table, int *exps);
 int srcnn_debug_banded16_tables(int channels, int f2, const float *w1, const float *b1, const float *w2, uint16_t *table, int *exps)
 {
-    if ((channels != 1 && channels != 3) || (f2 != 1 && f2 != 3 && f2 != 5) || !w1 || !b1 || !w2 || !exps) return SRCNN_ERR_INVALID;
+    return srcnn_debug_banded16_tables_range(channels, f2, w1, b1, w2, 255.f, table, exps);
+}
+
+/* ... for a float call with srcnn_set_input_range(range): e1 follows the range, the table and e2 do not. */
+int srcnn_debug_banded16_tables_range(int channels, int f2, const float *w1, const float *b1, const float *w2, float range,
+                                      uint16_t *table, int *exps)
+{
+    if ((channels != 1 && channels != 3) || (f2 != 1 && f2 != 3 && f2 != 5) || !w1 || !b1 || !w2 || !exps || !std::isfinite(range) ||
+        !(range > 0.f))
+        return SRCNN_ERR_INVALID;
     std::vector<uint16_t> own;
     if (!table) {
         own.resize(spatial_l2h_table_bytes(f2) / sizeof(uint16_t));
         table = own.data();
     }
-    if (!banded16_exponent(banded16_l1_bound(channels, w1, b1), &exps[0]) || !banded16_pack_w2(f2, w2, table, &exps[1]) ||
+    if (!banded16_exponent(banded16_l1_bound(channels, w1, b1, (double)range), &exps[0]) || !banded16_pack_w2(f2, w2, table, &exps[1]) ||
         std::abs(exps[0] + exps[1]) > 120)
         return SRCNN_ERR_STATE;
     return (int)spatial_l2h_table_bytes(f2);
+}
+
+/* srcnn_set_input_range on a context that is bound to no device (the call touches none): its return code, and in *after the
+ * setting the context then holds. */
+int srcnn_debug_set_input_range(float r, float *after)
+{
+    srcnn_ctx ctx;
+    const int rc = srcnn_set_input_range(&ctx, r);
+    if (after) *after = srcnn_get_input_range(&ctx);
+    return rc;
 }
 #endif
 
@@ -367,6 +465,99 @@ int srcnn_forward_color(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uin
     HIP_TRY(c, hipMemcpy2DAsync(dst, dst_stride, d_out, row, row, height, hipMemcpyDeviceToHost, c->stream));
     if (preclamp)
         HIP_TRY(c, hipMemcpy2DAsync(preclamp, preclamp_stride * sizeof(float), d_pre, row * sizeof(float), row * sizeof(float), height,
+                                    hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SRCNN_OK;
+}
+
+int srcnn_set_input_range(srcnn_ctx *c, float r)
+{
+    if (!c) return SRCNN_ERR_INVALID;
+    if (!std::isfinite(r) || !(r > 0.f))
+        return fail(c, SRCNN_ERR_INVALID, "srcnn_set_input_range: %g (a finite range > 0: the largest |input| of a float call)", (double)r);
+    c->input_range = r;        // read when a float call launches, like the padding
+    return SRCNN_OK;
+}
+
+float srcnn_get_input_range(const srcnn_ctx *c) { return c ? c->input_range : (float)SRCNN_ERR_INVALID; }
+
+// the float planes of a call: elements spanned from the first, and whether the planes the call WRITES are disjoint (frames of
+// channels, or channels of frames)
+static size_t f32_span(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames)
+{
+    return (size_t)(n_frames - 1) * frame_pitch + (size_t)(C - 1) * ch_pitch + (size_t)(height - 1) * stride + (size_t)width;
+}
+static bool f32_planes_disjoint(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames)
+{
+    const size_t plane = (size_t)(height - 1) * stride + (size_t)width;
+    if (C == 1) return n_frames == 1 || frame_pitch >= plane;
+    if (n_frames == 1) return ch_pitch >= plane;
+    return (ch_pitch >= plane && frame_pitch >= (size_t)(C - 1) * ch_pitch + plane) ||
+           (frame_pitch >= plane && ch_pitch >= (size_t)(n_frames - 1) * frame_pitch + plane);
+}
+
+int srcnn_forward_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
+                          float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int width, int height,
+                          int n_frames)
+{
+    BIND(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const int C = c->channels;
+    constexpr size_t kMaxPitch = (size_t)1 << 40;      // (elements: every offset the kernels form stays far inside 63 bits)
+    if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) || n_frames <= 0 ||
+        src_ch_pitch >= kMaxPitch || dst_ch_pitch >= kMaxPitch || src_frame_pitch >= kMaxPitch || dst_frame_pitch >= kMaxPitch)
+        return fail(c, SRCNN_ERR_INVALID, "forward_f32_dev: bad arguments");
+    if (!f32_planes_disjoint(C, dst_stride, dst_ch_pitch, dst_frame_pitch, width, height, n_frames))
+        return fail(c, SRCNN_ERR_INVALID, "forward_f32_dev: the output planes overlap each other (channel pitch %zu, frame pitch %zu "
+                                          "floats for %d channel(s) and %d frame(s))", dst_ch_pitch, dst_frame_pitch, C, n_frames);
+    // every output pixel reads a window of input pixels that other workgroups may already have overwritten
+    if (ranges_overlap(d_src, sizeof(float) * f32_span(C, src_stride, src_ch_pitch, src_frame_pitch, width, height, n_frames), d_dst,
+                       sizeof(float) * f32_span(C, dst_stride, dst_ch_pitch, dst_frame_pitch, width, height, n_frames)))
+        return fail(c, SRCNN_ERR_INVALID, "forward_f32_dev: src and dst overlap (the path cannot run in place)");
+    BandedPlanes io;
+    io.f32 = true;
+    io.src = d_src;
+    io.src_stride = src_stride;
+    io.ch_step = C == 1 ? 0 : src_ch_pitch;
+    io.src_frame_pitch = src_frame_pitch;
+    io.dst = d_dst;
+    io.dst_stride = dst_stride;
+    io.dst_ch_pitch = C == 1 ? 0 : dst_ch_pitch;
+    io.dst_frame_pitch = dst_frame_pitch;
+    if ((rc = forward_banded(c, io, width, height, n_frames))) return rc;
+    return SRCNN_OK;
+}
+
+int srcnn_forward_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, float *dst, size_t dst_stride,
+                      size_t dst_ch_pitch, int width, int height)
+{
+    BIND(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const int C = c->channels;
+    if (bad_plane(src, src_stride, width, height) || bad_plane(dst, dst_stride, width, height) ||
+        !f32_planes_disjoint(C, dst_stride, dst_ch_pitch, 0, width, height, 1))
+        return fail(c, SRCNN_ERR_INVALID, "forward_f32: bad arguments");
+    if ((rc = banded_refusal(c, true))) return rc;      // before anything is staged
+    const size_t row = (size_t)width * sizeof(float), plane = (size_t)width * height;
+    if ((rc = reserve(c, c->in_u8, C * plane * sizeof(float)))) return rc;
+    if ((rc = reserve(c, c->pre_f32, C * plane * sizeof(float)))) return rc;
+    float *d_in = static_cast<float *>(c->in_u8.p), *d_out = static_cast<float *>(c->pre_f32.p);
+    for (int ch = 0; ch < C; ++ch)
+        HIP_TRY(c, hipMemcpy2DAsync(d_in + ch * plane, row, src + ch * src_ch_pitch, src_stride * sizeof(float), row, height,
+                                    hipMemcpyHostToDevice, c->stream));
+    BandedPlanes io;
+    io.f32 = true;
+    io.src = d_in;
+    io.src_stride = width;
+    io.ch_step = plane;
+    io.dst = d_out;
+    io.dst_stride = width;
+    io.dst_ch_pitch = plane;
+    if ((rc = forward_banded(c, io, width, height, 1))) return rc;
+    for (int ch = 0; ch < C; ++ch)
+        HIP_TRY(c, hipMemcpy2DAsync(dst + ch * dst_ch_pitch, dst_stride * sizeof(float), d_out + ch * plane, row, row, height,
                                     hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SRCNN_OK;

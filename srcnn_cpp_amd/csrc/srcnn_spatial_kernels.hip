@@ -11,6 +11,14 @@
 //   spatial_l3_kernel<C>   32 maps -> C channels (layer 3, + b3[c], truncate, clamp): u8 pixels of C bytes, pre-clamp floats;
 //                          the 1-channel model under replicate padding runs the MODE_L3 strip kernel (srcnn_mfma.hip) instead
 //
+// The float image path (srcnn_forward_f32*: float32 planes in the model's own units in, the value before truncation out) runs
+// the same launches with two more compile-time forms: spatial_l1_kernel<C, ZERO, Scale, float> reads C float planes at
+// src[y * sstride + x + c * ch_step] (the window is f32 for C = 3 too: 87 KiB of LDS, one workgroup per CU), and
+// spatial_l3_kernel<C, false, ZERO, float> stores val = sum + b3[o] to C float planes, dst[y * dstride + x + o * ch_pitch], and
+// no byte; C = 1 under replicate padding included (the u8 path of that model stays on MODE_L3).  Same arithmetic, same order:
+// on integer-valued input the planes equal the pre-clamp floats of the byte path bit for bit.  Inputs must be finite: the
+// zero-padding form multiplies a clamped load by 0, and inf * 0 is NaN.
+//
 // SRCNN_MODE_BANDED16 runs the same three launches with layer 2 in split f16: spatial_l1_kernel<C, ZERO, float> writes the
 // layer-1 map as f16 (hi, lo) pairs (the same bytes), spatial_l2h_kernel reads it on v_mfma_f32_32x32x16_f16 and writes the same
 // 32 planar f32 maps, layer 3 is unchanged.
@@ -57,9 +65,11 @@ constexpr size_t SL1_LDS3 = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 
 
 // Kernel arguments are passed as they always were, so that each form compiles to the instructions it had: layer 1 takes the
 // steps of the input (int px_step, long ch_step) for 3 channels and none for 1, layer 3 takes its C biases as C floats.
-// Byte c of input pixel (y, x), without and with steps:
-__device__ __forceinline__ uint8_t l1_at(const uint8_t *p, long stride, int y, int x, int) { return p[(long)y * stride + x]; }
-__device__ __forceinline__ uint8_t l1_at(const uint8_t *p, long stride, int y, int x, int c, int px_step, long ch_step)
+// Channel c of input pixel (y, x) (a byte, or a float of the float image path), without and with steps:
+template <typename In>
+__device__ __forceinline__ In l1_at(const In *p, long stride, int y, int x, int) { return p[(long)y * stride + x]; }
+template <typename In>
+__device__ __forceinline__ In l1_at(const In *p, long stride, int y, int x, int c, int px_step, long ch_step)
 {
     return p[(long)y * stride + (long)x * px_step + c * ch_step];
 }
@@ -92,14 +102,15 @@ __device__ __forceinline__ void l1_store_split(uint4 *o, const f32x16 &acc, int 
 
 struct NoScale {};         // the last argument of the forms that write plain f32 maps: nothing
 
-template <int C, bool ZERO, typename Scale, typename... Steps>
-__global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restrict__ src, long sstride, Steps... steps, int W, int H,
+template <int C, bool ZERO, typename Scale, typename In, typename... Steps>
+__global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ src, long sstride, Steps... steps, int W, int H,
                                                          int m0, int m1, const float *__restrict__ frag, float *__restrict__ map,
                                                          long mpitch, Scale scale)
 {
     constexpr bool SPLIT = std::is_same_v<Scale, float>;
+    constexpr bool F32 = std::is_same_v<In, float>;            // float planes in (px_step = 1, ch_step = the plane pitch)
     static_assert(sizeof...(Steps) == (C == 1 ? 0 : 2), "px_step and ch_step for 3 channels only");
-    using T = std::conditional_t<C == 1, float, uint8_t>;      // the window's element type
+    using T = std::conditional_t<C == 1 || F32, float, uint8_t>;      // the window's element type
     float *as;
     T *ys;
     if constexpr (C == 1) {
@@ -109,13 +120,24 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restri
     } else {
         extern __shared__ float lds[];
         as = lds;
-        ys = reinterpret_cast<uint8_t *>(lds + C * SPATIAL_NFRAG_L1 * 64);
+        ys = reinterpret_cast<T *>(lds + C * SPATIAL_NFRAG_L1 * 64);
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * SL1_COLS, y0 = m0 + blockIdx.y * SL1_ROWS;
-    // the window, channel fastest (consecutive bytes of interleaved pixels go to consecutive threads)
+    // the window, channel fastest (consecutive bytes of interleaved pixels go to consecutive threads); float planes: channel
+    // slowest (consecutive floats of a plane's row)
     for (int e = tid; e < C * SL1_YC; e += 256) {
-        const int rr = e / (C * SL1_YP), rem = e - rr * (C * SL1_YP), cc = rem / C, ch = rem - C * cc;
+        int rr, cc, ch;
+        if constexpr (F32 && C > 1) {
+            ch = e / SL1_YC;
+            rr = (e - ch * SL1_YC) / SL1_YP;
+            cc = e - ch * SL1_YC - rr * SL1_YP;
+        } else {
+            rr = e / (C * SL1_YP);
+            const int rem = e - rr * (C * SL1_YP);
+            cc = rem / C;
+            ch = rem - C * cc;
+        }
         const int yy = sclamp(y0 - 4 + rr, 0, H - 1), xx = sclamp(x0 - 4 + cc, 0, W - 1);
         const T v = l1_at(src, sstride, yy, xx, ch, steps...);
         // ZERO: 0 where the load was clamped, by a multiply: a select lets the compiler branch around the load (measured slower)
@@ -178,10 +200,12 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const uint8_t *__restri
 // A channel plane of the window is SL2_PS floats, = 32 mod 64: the two lane-halves (channels 2p, 2p + 1) read disjoint banks.
 constexpr int SL2_COLS = 64, SL2_ROWS = 16, SL2_CC = 8, SL2_XP = 72;
 __host__ __device__ constexpr int sl2_ps(int r2) { return ((((SL2_ROWS + 2 * r2) * SL2_XP) + 31) / 64) * 64 + 32; }
+#ifndef SRCNN_SPATIAL_F32_UNIT
 size_t spatial_l2_lds_bytes(int f2)
 {
     return ((size_t)SL2_CC * sl2_ps((f2 - 1) / 2) + (size_t)f2 * f2 * (SL2_CC / 2) * 64) * sizeof(float);
 }
+#endif
 
 template <int F2, bool ZERO>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void spatial_l2_kernel(const float *__restrict__ map, long mpitch, int m0, int m1,
@@ -392,12 +416,18 @@ __global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restric
 constexpr int SL3_COLS = 128, SL3_OUT = SL3_COLS - 4, SL3_SEG = 16, SL3_XCDS = 8;
 __host__ __device__ constexpr int sl3_ahead(int C) { return C == 1 ? 4 : 2; }   // a ring of sl3_ahead x 16 registers
 
-template <int C, bool PRE, bool ZERO, typename... B3>
+// Out = float (the float image path): the last argument is the channel pitch of C float planes, and a finished value goes to
+// dst[y * dstride + x + o * ch_pitch] as it is -- no truncation, no clamp, no byte.
+typedef float *__restrict__ l3_pre_ptr;
+template <typename Out> using l3_last_arg = std::conditional_t<std::is_same_v<Out, float>, long, l3_pre_ptr>;
+
+template <int C, bool PRE, bool ZERO, typename Out, typename... B3>
 __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict__ map, long mpitch, int o0, int o1, int W, int H,
                                                          int b0, int b1, int nx, int n_tiles, const float *__restrict__ frag,
-                                                         B3... b3, uint8_t *__restrict__ dst, long dstride, float *__restrict__ pre)
+                                                         B3... b3, Out *__restrict__ dst, long dstride, l3_last_arg<Out> pre)
 {
     static_assert(sizeof...(B3) == C, "one bias per output channel");
+    static_assert(!(std::is_same_v<Out, float> && PRE), "the float form has no second output");
     constexpr int AHEAD = sl3_ahead(C);
     __shared__ float vt[2][C][5][SL3_COLS];
     const int per = (n_tiles + SL3_XCDS - 1) / SL3_XCDS;
@@ -467,7 +497,18 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
                         if (n < 5) vr[(o * 5 + n) * SL3_COLS + c] = v[o][s];
                     }
                 __syncthreads();
-                if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
+                if constexpr (std::is_same_v<Out, float>) {
+                    if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
+                        const long ob = (long)y * dstride + x;
+#pragma unroll
+                        for (int o = 0; o < C; ++o) {
+                            const float *vo = vr + o * 5 * SL3_COLS;
+                            const float sum = (((vo[c - 2] + vo[SL3_COLS + c - 1]) + vo[2 * SL3_COLS + c]) + vo[3 * SL3_COLS + c + 1]) +
+                                              vo[4 * SL3_COLS + c + 2];
+                            dst[ob + o * pre] = sum + bias[o];
+                        }
+                    }
+                } else if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
                     const long ob = (long)y * dstride + (long)C * x;
 #pragma unroll
                     for (int o = 0; o < C; ++o) {
@@ -484,18 +525,22 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
     }
 }
 
+// The launchers.  This file is compiled twice (srcnn_cpp_amd/build.py): as itself it instantiates the kernels of the byte entry
+// points, and through srcnn_spatial_f32.hip (which defines SRCNN_SPATIAL_F32_UNIT and includes it) the float forms of layers 1
+// and 3 and nothing else -- the kernels of this unit stay the ones they were, one for one.
+#ifndef SRCNN_SPATIAL_F32_UNIT
 template <int C, bool ZERO>
 static void launch_l1(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
                       const float *frag, float *map, long mpitch, hipStream_t st)
 {
     if constexpr (C == 1) {
-        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, NoScale>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch,
+        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, NoScale, uint8_t>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch,
                            NoScale{});
     } else {
         // (68 KiB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, NoScale, int, long>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, NoScale, uint8_t, int, long>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
-        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, NoScale, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step,
+        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, NoScale, uint8_t, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step,
                            ch_step, W, H, m0, m1, frag, map, mpitch, NoScale{});
     }
 }
@@ -545,11 +590,11 @@ static void launch_l1h(dim3 grid, const uint8_t *src, long sstride, int px_step,
                        const float *frag, float *map, long mpitch, float scale, hipStream_t st)
 {
     if constexpr (C == 1) {
-        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, float>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch, scale);
+        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, float, uint8_t>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch, scale);
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, float, int, long>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, float, uint8_t, int, long>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
-        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, float, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step, ch_step, W,
+        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, float, uint8_t, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step, ch_step, W,
                            H, m0, m1, frag, map, mpitch, scale);
     }
 }
@@ -598,10 +643,10 @@ static void launch_l3(dim3 grid, const float *map, long mpitch, int o0, int o1, 
                       const float *frag, uint8_t *dst, long dstride, float *pre, hipStream_t st, B3... b3)
 {
     if (pre)
-        hipLaunchKernelGGL((spatial_l3_kernel<C, true, ZERO, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
+        hipLaunchKernelGGL((spatial_l3_kernel<C, true, ZERO, uint8_t, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
                            n_tiles, frag, b3..., dst, dstride, pre);
     else
-        hipLaunchKernelGGL((spatial_l3_kernel<C, false, ZERO, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
+        hipLaunchKernelGGL((spatial_l3_kernel<C, false, ZERO, uint8_t, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
                            n_tiles, frag, b3..., dst, dstride, pre);
 }
 
@@ -641,5 +686,74 @@ hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t
                        ppitch);
     return hipGetLastError();
 }
+
+#else   // SRCNN_SPATIAL_F32_UNIT
+// ---- the float image path (srcnn_forward_f32*): layer 1 on float planes, layer 3 writing float planes ---------------------
+// the three tables and an f32 window of the three channels: 61.5 + 25.5 KiB, one workgroup per CU
+constexpr size_t SL1_LDS3F = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC * sizeof(float);
+
+template <int C, bool ZERO, typename Scale>
+static void launch_l1f(dim3 grid, const float *src, long sstride, long ch_step, int W, int H, int m0, int m1, const float *frag,
+                       float *map, long mpitch, Scale scale, hipStream_t st)
+{
+    if constexpr (C == 1) {
+        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, Scale, float>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch,
+                           scale);
+    } else {
+        // (87 KiB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, Scale, float, int, long>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3F);
+        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, Scale, float, int, long>), grid, dim3(256), SL1_LDS3F, st, src, sstride, 1, ch_step,
+                           W, H, m0, m1, frag, map, mpitch, scale);
+    }
+}
+
+template <typename Scale>
+static hipError_t launch_l1f_any(int channels, bool zero, dim3 grid, const float *src, long sstride, long ch_step, int W, int H, int m0,
+                                 int m1, const float *frag, float *map, long mpitch, Scale scale, hipStream_t st)
+{
+    if (channels == 1 && !zero) launch_l1f<1, false>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
+    else if (channels == 1) launch_l1f<1, true>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
+    else if (channels == 3 && !zero) launch_l1f<3, false>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
+    else if (channels == 3) launch_l1f<3, true>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_spatial_l1f(int channels, bool zero, bool split, const float *src, long sstride, long ch_step, int W, int H, int m0,
+                              int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
+{
+    const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
+    float *m = static_cast<float *>(map);
+    if (split) return launch_l1f_any(channels, zero, grid, src, sstride, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
+    return launch_l1f_any(channels, zero, grid, src, sstride, ch_step, W, H, m0, m1, frag, m, mpitch, NoScale{}, st);
+}
+
+template <int C, bool ZERO, typename... B3>
+static void launch_l3f(dim3 grid, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, int nx, int n_tiles,
+                       const float *frag, float *dst, long dstride, long ch_pitch, hipStream_t st, B3... b3)
+{
+    hipLaunchKernelGGL((spatial_l3_kernel<C, false, ZERO, float, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
+                       n_tiles, frag, b3..., dst, dstride, ch_pitch);
+}
+
+hipError_t launch_spatial_l3f(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                              const float *frag, const float *b3, float *dst, long dstride, long ch_pitch, hipStream_t st)
+{
+    const int nx = (W + SL3_OUT - 1) / SL3_OUT, ny = (b1 - b0 + SL3_SEG - 1) / SL3_SEG, n_tiles = nx * ny;
+    const dim3 grid((unsigned)(SL3_XCDS * ((n_tiles + SL3_XCDS - 1) / SL3_XCDS)));
+    if (channels == 1 && zero)
+        launch_l3f<1, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0]);
+    else if (channels == 1)
+        launch_l3f<1, false>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0]);
+    else if (channels == 3 && zero)
+        launch_l3f<3, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0], b3[1], b3[2]);
+    else if (channels == 3)
+        launch_l3f<3, false>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0], b3[1], b3[2]);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+#endif  // SRCNN_SPATIAL_F32_UNIT
 
 }  // namespace srcnn

@@ -1,0 +1,105 @@
+"""A PyTorch SRCNN module on this library's kernels: float32 tensors on the GPU in, float32 tensors out.
+
+    from srcnn_cpp_amd.torch_api import compile_module
+    fast = compile_module(module)              # an nn.Module with conv1, conv2, conv3 (9-f2-5, 1 or 3 channels)
+    y = fast(x)                                # x: float32 (N, C, H, W) or (C, H, W) on that GPU; y ~ module(x)
+
+The weights go in as they are (the data is already in the model's units), the module's padding mode is the context's padding,
+the call runs on torch.cuda.current_stream() and reads the tensor where it lies: data_ptr() and strides, no copy.  torch is
+imported when compile_module is called, not when this module is.
+"""
+from __future__ import annotations
+
+from . import MODE_BANDED16, MODE_MFMA, Context, model_from_module
+
+__all__ = ["compile_module", "CompiledModule"]
+
+
+def check_input(x, channels: int, device_index: int):
+    """ValueError unless x is a float32 CUDA tensor (N, C, H, W) or (C, H, W) on GPU `device_index` with C = channels, rows
+    contiguous and the other strides positive.  Returns (n, h, w, row stride, channel pitch, frame pitch) in elements.  Runs
+    before any call into the library."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"expected a torch.Tensor, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"expected a float32 tensor, got {x.dtype}")
+    if x.dim() not in (3, 4):
+        raise ValueError(f"expected shape (N, {channels}, H, W) or ({channels}, H, W), got {tuple(x.shape)}")
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    n, c, h, w = x.shape
+    if c != channels:
+        raise ValueError(f"the module has {channels} channel(s), the tensor {c}: shape {tuple(x.shape)}")
+    if 0 in (n, h, w):
+        raise ValueError(f"empty tensor of shape {tuple(x.shape)}")
+    sn, sc, sh, sw = x.stride()
+    if w > 1 and sw != 1:
+        raise ValueError("the innermost dimension must be contiguous (stride 1): interleaved pixels are not supported; "
+                         "call .contiguous()")
+    if (h > 1 and sh < w) or (c > 1 and sc <= 0) or (n > 1 and sn <= 0):
+        raise ValueError(f"strides {tuple(x.stride())}: rows must not overlap and channel / frame strides must be positive")
+    if x.device.type != "cuda":
+        raise ValueError(f"expected a tensor on cuda:{device_index}, got one on {x.device} (there is no CPU path)")
+    if x.device.index != device_index:
+        raise ValueError(f"expected a tensor on cuda:{device_index}, got one on {x.device}")
+    return n, h, w, (sh if h > 1 else w), (sc if c > 1 else 0), (sn if n > 1 else 0)
+
+
+class CompiledModule:
+    """What compile_module returns: a callable that owns its Context (one GPU, the module's weights and padding)."""
+
+    def __init__(self, ctx: Context, channels: int, device: int):
+        self.ctx, self.channels, self.device = ctx, channels, device
+        self._side = None
+
+    def __call__(self, x):
+        import torch
+        n, h, w, stride, ch_pitch, frame_pitch = check_input(x, self.channels, self.device)
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        cur = torch.cuda.current_stream(x.device)
+        # The library takes a stream handle and reads 0 as "the context's own stream", so torch's default stream (handle 0)
+        # cannot be handed over: the call then runs on a side stream of this callable, ordered after and before the default
+        # stream by events, which for the caller is the same as running on it.
+        run_on = cur
+        if cur.cuda_stream == 0:
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=x.device)
+            run_on = self._side
+            run_on.wait_stream(cur)
+        self.ctx.set_stream(run_on.cuda_stream)
+        self.ctx.forward_f32_dev(x.data_ptr(), stride, ch_pitch, frame_pitch, out.data_ptr(), w, h * w, self.channels * h * w,
+                                 w, h, n)
+        if run_on is not cur:
+            cur.wait_stream(run_on)
+        return out
+
+    def close(self):
+        self.ctx.close()
+
+
+def compile_module(module, device: int = 0, mode: int = MODE_MFMA, input_range: float = 1.0) -> CompiledModule:
+    """An SRCNN nn.Module (conv1 9x9, conv2 f2 x f2 with f2 = 1, 3, 5, conv3 5x5; 1 or 3 channels; every layer padded by k // 2
+    with padding_mode "zeros" or "replicate") -> a callable on float32 CUDA tensors that computes module(x) with this library's
+    HIP kernels.  mode: MODE_MFMA (float32 throughout) or MODE_BANDED16 (layer 2 in split f16, faster; input_range is then the
+    largest |x| the tensors will hold, 1.0 for [0, 1] data).  The weights are read once, here: a module trained further needs a
+    new compile_module."""
+    if mode not in (MODE_MFMA, MODE_BANDED16):
+        raise ValueError(f"mode {mode}: the float image path runs in MODE_MFMA and MODE_BANDED16 only")
+    conv1 = getattr(module, "conv1", None)
+    if conv1 is None:
+        raise ValueError("module has no conv1")
+    channels = int(conv1.in_channels)
+    if channels not in (1, 3):
+        raise ValueError(f"conv1 reads {channels} channels: a model has 1 channel or 3")
+    model, padding = model_from_module(module, input_scale=1.0, image_order="rgb" if channels == 3 else None)
+    ctx = Context(int(device))
+    try:
+        ctx.set_model(*model)
+        ctx.set_padding(padding)
+        ctx.set_mode(mode)
+        ctx.set_input_range(input_range)
+    except Exception:
+        ctx.close()
+        raise
+    return CompiledModule(ctx, channels, int(device))

@@ -3,7 +3,7 @@ srcnn_forward_y_dev on the context's stream, warm-up calls excluded.  Reports ms
 f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81*C + 32*64*f2^2 + 32*25*C) for C channels.
 
     python tools/model_bench.py [--channels 1 3] [--f2 1 3 5] [--padding replicate|zero|both] [--sizes 3840x2160 1920x1080]
-                                [--mode mfma|banded16|both] [--steps 20] [--warmup 3] [--json out.json]
+                                [--mode mfma|banded16|both] [--dtype u8 f32] [--steps 20] [--warmup 3] [--json out.json]
 
 --channels 3 times the colour models (srcnn_set_model_color) through srcnn_forward_color_dev on interleaved 3-byte pixels.
 
@@ -12,6 +12,10 @@ f32-MFMA peak (157.3 TFLOP/s) by the algorithmic FLOP per pixel, 2 x (64*81*C + 
 --mode banded16 times SRCNN_MODE_BANDED16 (layer 2 in split f16); --mode both times each configuration in SRCNN_MODE_MFMA and
 then in SRCNN_MODE_BANDED16 in one process, and reports both times and their ratio (banded16 / mfma).  The fraction of peak is
 of the f32 peak by the algorithmic FLOP in either mode: the figure to compare is the time.
+
+--dtype f32 times the float image path (srcnn_forward_f32_dev: float32 planes in and out, the same pixel values as floats,
+planar for 3 channels) instead of the byte entry points; --dtype u8 f32 times both in one process, the byte call first, and
+reports the float times beside the byte times with their ratio (f32 / u8) per mode.
 """
 import argparse
 import json
@@ -47,8 +51,13 @@ def color_model(f2, seed=0):
             rng.normal(0, 0.02, (3, 32, 5, 5)).astype(np.float32), np.full(3, 60.0, np.float32))
 
 
-def time_plane(ctx, w, h, steps, warmup, channels=1):
-    if channels == 3:
+def time_plane(ctx, w, h, steps, warmup, channels=1, dtype="u8"):
+    if dtype == "f32":
+        y = synth_luma(w, h)
+        planes = np.stack([y, y[::-1], y[:, ::-1]]) if channels == 3 else y[None]
+        d_src = torch.from_numpy(np.ascontiguousarray(planes).astype(np.float32)).cuda()
+        run = lambda: ctx.forward_f32_dev(d_src.data_ptr(), w, w * h, 0, d_dst.data_ptr(), w, w * h, 0, w, h, 1)
+    elif channels == 3:
         y = synth_luma(w, h)
         d_src = torch.from_numpy(np.ascontiguousarray(np.stack([y, y[::-1], y[:, ::-1]], axis=2))).cuda()
         run = lambda: ctx.forward_color_dev(d_src.data_ptr(), 3 * w, 0, d_dst.data_ptr(), 3 * w, 0, w, h, 1)
@@ -82,6 +91,7 @@ def main():
     ap.add_argument("--f2", type=int, nargs="+", default=[3, 5], choices=[1, 3, 5])
     ap.add_argument("--padding", choices=["replicate", "zero", "both"], default="replicate")
     ap.add_argument("--mode", choices=["mfma", "banded16", "both"], default="mfma")
+    ap.add_argument("--dtype", nargs="+", default=["u8"], choices=["u8", "f32"])
     ap.add_argument("--sizes", nargs="+", default=["3840x2160", "1920x1080"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -98,7 +108,8 @@ def main():
                     for padding in paddings:
                         ctx.set_padding(padding)
                         ctx.set_mode(S.MODE_BANDED16 if args.mode == "banded16" else S.MODE_MFMA)
-                        med, best = time_plane(ctx, w, h, args.steps, args.warmup, channels)
+                        first = "u8" if "u8" in args.dtype else "f32"
+                        med, best = time_plane(ctx, w, h, args.steps, args.warmup, channels, first)
                         px = w * h
                         fpp = flop_per_pixel(f2, channels)
                         tflops = fpp * px / (med * 1e-3) / 1e12
@@ -106,14 +117,24 @@ def main():
                                    ms_per_plane=round(med, 3), ms_min=round(best, 3),
                                    mpix_per_s=round(px / (med * 1e-3) / 1e6, 1), flop_per_pixel=fpp, tflops=round(tflops, 2),
                                    fraction_of_peak=round(tflops / PEAK_TFLOPS, 3), steps=args.steps, warmup=args.warmup)
+                        if args.dtype != ["u8"]:
+                            row["dtype"] = first if len(args.dtype) == 1 else "both"
+                        both_dtypes = set(args.dtype) == {"u8", "f32"}
+                        if both_dtypes:
+                            medf, bestf = time_plane(ctx, w, h, args.steps, args.warmup, channels, "f32")
+                            row.update(ms_per_plane_f32=round(medf, 3), ms_min_f32=round(bestf, 3), f32_over_u8=round(medf / med, 3))
                         if args.mode != "mfma":
                             row["mode"] = "mfma" if args.mode == "both" else "banded16"
                         if args.mode == "both":
                             ctx.set_mode(S.MODE_BANDED16)
-                            med16, best16 = time_plane(ctx, w, h, args.steps, args.warmup, channels)
-                            ctx.set_mode(S.MODE_MFMA)
+                            med16, best16 = time_plane(ctx, w, h, args.steps, args.warmup, channels, first)
                             row.update(mode="both", ms_per_plane_banded16=round(med16, 3), ms_min_banded16=round(best16, 3),
                                        banded16_over_mfma=round(med16 / med, 3))
+                            if both_dtypes:
+                                med16f, best16f = time_plane(ctx, w, h, args.steps, args.warmup, channels, "f32")
+                                row.update(ms_per_plane_banded16_f32=round(med16f, 3), ms_min_banded16_f32=round(best16f, 3),
+                                           banded16_f32_over_u8=round(med16f / med16, 3))
+                            ctx.set_mode(S.MODE_MFMA)
                         rows.append(row)
                         print(json.dumps(row), flush=True)
     if args.json:
