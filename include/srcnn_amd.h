@@ -102,7 +102,8 @@ enum {
  *                    is a model whose layer-1/2 weights are not finite or cannot be scaled within float32.  Every entry
  *                    point that runs the strip path only (row stripes, halo buffers, several GPUs, lanes, unfused,
  *                    srcnn_conv99x11_dev, srcnn_conv55_dev and the _to_dev / _from_dev forms) returns SRCNN_ERR_STATE in
- *                    this mode for any model; the per-filter calls on host planes (srcnn_conv99, srcnn_conv11,
+ *                    this mode for any model -- row stripes and stripes over several contexts of the 1-channel models run
+ *                    through srcnn_model_rows_dev, srcnn_model_rows_halo_dev and srcnn_model_striped(_dev); the per-filter calls on host planes (srcnn_conv99, srcnn_conv11,
  *                    srcnn_conv55, srcnn_conv99x11) ignore the mode as they ignore every mode. */
 enum { SRCNN_MODE_MFMA = 0, SRCNN_MODE_EXACT = 1, SRCNN_MODE_SPLIT16 = 2, SRCNN_MODE_REFBYTES = 3, SRCNN_MODE_REFBYTES16 = 4,
        SRCNN_MODE_BANDED16 = 5 };
@@ -237,7 +238,9 @@ int srcnn_set_weights(srcnn_ctx *ctx,
  *   - srcnn_forward_y, srcnn_forward_y_dev (any n_frames, frame pitches, d_preclamp), srcnn_forward_y_frames,
  *     srcnn_process_bgr and srcnn_process_bgr_dev run the model;
  *   - row stripes (srcnn_forward_y_rows_dev), halo buffers (_rows_halo_dev), the several-GPU calls (striped, lanes, multi),
- *     srcnn_forward_y_unfused_dev, srcnn_conv99x11_dev and srcnn_conv55_dev return SRCNN_ERR_STATE: they run the 9-1-5 path;
+ *     srcnn_forward_y_unfused_dev, srcnn_conv99x11_dev and srcnn_conv55_dev return SRCNN_ERR_STATE: they run the 9-1-5 path.
+ *     Row stripes of this model, with or without halo buffers, and one plane striped over several contexts are
+ *     srcnn_model_rows_dev, srcnn_model_rows_halo_dev and srcnn_model_striped(_dev), with a halo of srcnn_model_halo_rows() rows;
  *   - a per-filter call that loads weights (srcnn_conv99x11, srcnn_conv55 and their _to_dev / _from_dev forms) ENDS the model:
  *     the context is back on the 9-1-5 tables holding only the layers loaded from then on, srcnn_get_model_f2() returns 1,
  *     and the next whole-path call returns SRCNN_ERR_STATE until a full model is loaded again.  srcnn_conv99 / srcnn_conv11
@@ -263,7 +266,8 @@ int srcnn_get_model_f2(const srcnn_ctx *ctx);
  *     Every other mode, every other entry point (row stripes, halo buffers, the several-GPU calls, unfused,
  *     srcnn_conv99x11_dev, srcnn_conv55_dev) and the per-filter calls (srcnn_conv99, _conv11, _conv55, _conv99x11 and their
  *     _to_dev / _from_dev forms) return SRCNN_ERR_STATE, as do the whole-path calls when the loaded layers came from per-filter
- *     calls; the context stays usable.
+ *     calls; the context stays usable.  Row stripes under zero padding are srcnn_model_rows_dev, srcnn_model_rows_halo_dev and
+ *     srcnn_model_striped(_dev): zero padding refers to the image there too, never to a stripe.
  * srcnn_set_padding returns SRCNN_ERR_INVALID for any other value; srcnn_get_padding returns the setting. */
 enum { SRCNN_PAD_REPLICATE = 0, SRCNN_PAD_ZERO = 1 };
 int srcnn_set_padding(srcnn_ctx *ctx, int padding);
@@ -466,6 +470,63 @@ int srcnn_forward_y_rows_halo_dev(srcnn_ctx *ctx,
                                   const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride,
                                   uint8_t *d_dst, size_t dst_stride, int dst_row0,
                                   int width, int height, int row_begin, int row_end);
+
+/* ---- row stripes of every 1-channel model --------------------------------------------------------------------------------
+ * The srcnn_forward_y_rows* and srcnn_forward_y_striped* calls above run the replicate-padded 9-1-5 model on the strip path and
+ * return SRCNN_ERR_STATE for everything else.  The calls below run WHATEVER srcnn_forward_y_dev would run for the loaded
+ * 1-channel model in the context's mode and padding, on a row range of the image:
+ *   - a model on the banded path (f2 = 3 or 5, any model under SRCNN_PAD_ZERO, any whole model in SRCNN_MODE_BANDED16) runs that
+ *     path's three launches per row band inside the range.  Padding refers to the IMAGE (rows 0 and height - 1, columns 0 and
+ *     width - 1), never to the stripe, and a pixel's value does not depend on which stripe computed it: the assembled rows are
+ *     bit-identical to srcnn_forward_y_dev on the whole plane, output bytes and pre-clamp floats, in both modes;
+ *   - a model on the strip path (replicate-padded 9-1-5 in SRCNN_MODE_MFMA, SPLIT16, REFBYTES, REFBYTES16) is handed to the
+ *     srcnn_forward_y_rows* / srcnn_forward_y_striped* call of the same shape: the same bytes, the same refusals (SRCNN_MODE_EXACT;
+ *     halo buffers outside the float32 MFMA modes), and a d_preclamp request returns SRCNN_ERR_STATE, because those calls have
+ *     no pre-clamp output.
+ * The halo is R = srcnn_model_halo_rows(ctx) = 6 + (f2 - 1) / 2 rows: 4 input rows of the 9x9 layer, (f2 - 1) / 2 rows of layer 2's
+ * window, 2 rows of the 5x5 layer.  A colour model and a model whose layers came from per-filter calls return SRCNN_ERR_STATE, and
+ * srcnn_last_error() names the reason; so does a mode or padding in which srcnn_forward_y_dev refuses the model.  Asynchronous on the
+ * context's stream.  Out of scope: a pipelined form like srcnn_forward_y_striped_frames, lanes, float planes (srcnn_forward_f32*),
+ * stripes of a colour model; seam deferral does not apply to the banded path. */
+
+/* R of the loaded model: 6, 7 or 8 for f2 = 1, 3, 5. */
+int srcnn_model_halo_rows(const srcnn_ctx *ctx);
+
+/* Output rows [row_begin, row_end) of ONE width x height image.  d_src points at image row src_row0 and must hold rows
+ * [max(0, row_begin - R), min(height, row_end + R)); no row outside that range is read.  d_dst, and d_preclamp when given (floats
+ * at the element offsets of the output bytes), point at image row dst_row0. */
+int srcnn_model_rows_dev(srcnn_ctx *ctx,
+                         const uint8_t *d_src, size_t src_stride, int src_row0,
+                         uint8_t *d_dst, size_t dst_stride, int dst_row0,
+                         int width, int height, int row_begin, int row_end,
+                         float *d_preclamp /*may be NULL; dst strides*/);
+
+/* The same stripe with its halo rows in SEPARATE device buffers: d_src holds image rows [src_row0, src_row0 + src_rows),
+ * d_halo_top rows [src_row0 - R, src_row0), d_halo_bot rows [src_row0 + src_rows, + R), both with row stride halo_stride.  A halo
+ * pointer may be NULL when rows [row_begin - R, row_end + R) need nothing on that side.  Bit-identical to srcnn_model_rows_dev on
+ * the assembled rows.  The halo pointers may point into a neighbour's stripe where it lies (same device, or peer-mapped). */
+int srcnn_model_rows_halo_dev(srcnn_ctx *ctx,
+                              const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
+                              const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride,
+                              uint8_t *d_dst, size_t dst_stride, int dst_row0,
+                              int width, int height, int row_begin, int row_end,
+                              float *d_preclamp /*may be NULL; dst strides*/);
+
+/* ONE plane row-striped over n_ctx contexts that hold the same model, mode and padding, as srcnn_forward_y_striped_dev:
+ * d_stripes[k] / d_out[k] are DEVICE pointers on ctxs[k]'s GPU to that context's rows srcnn_stripe_rows(height, n_ctx, k).  With
+ * neighbours on the same device, or peer access, context k reads the R edge rows of stripes k - 1 and k + 1 where they lie (no
+ * copy); a link that refuses peer access gets copies of them into the context's halo buffers (srcnn_halo_transport() says
+ * which).  Needs height / n_ctx >= R.  Asynchronous on each context's stream, and ORDERING IS THE CALLER'S exactly as for
+ * srcnn_forward_y_striped_dev: all stripes complete when the call is made, unchanged until every context has finished. */
+int srcnn_model_striped_dev(srcnn_ctx *const *ctxs, int n_ctx,
+                            const uint8_t *const *d_stripes, size_t stripe_stride,
+                            uint8_t *const *d_out, size_t out_stride, int width, int height);
+
+/* The same for a host plane, one host thread per context: context k uploads its own rows only, runs its stripe and returns its
+ * rows; the call returns when dst is complete.  Bit-identical to srcnn_forward_y. */
+int srcnn_model_striped(srcnn_ctx *const *ctxs, int n_ctx,
+                        const uint8_t *src, size_t src_stride,
+                        uint8_t *dst, size_t dst_stride, int width, int height);
 
 /* Materialising variant of the whole path (layer-1/2 kernel writes the 32
  * planar f32 maps to HBM, layer-3 kernel reads them back), n_frames planes.

@@ -33,6 +33,7 @@ __all__ = [
     "MODE_MFMA", "MODE_EXACT", "MODE_SPLIT16", "MODE_REFBYTES", "MODE_REFBYTES16", "MODE_BANDED16", "FLOP_PER_PIXEL",
     "ERR_INVALID", "ERR_HIP", "ERR_NOMEM", "ERR_NODEVICE", "ERR_STATE",
     "stripe_rows", "forward_y_frames_multi", "forward_y_lanes_dev", "forward_y_striped", "forward_y_striped_dev",
+    "model_striped", "model_striped_dev",
 ]
 
 _PKG = Path(__file__).resolve().parent
@@ -176,6 +177,11 @@ def load_library() -> C.CDLL:
         "srcnn_forward_y_striped": ([C.POINTER(vp), i, _u8p, sz, _u8p, sz, i, i], i),
         "srcnn_forward_y_striped_frames": ([C.POINTER(vp), i, C.POINTER(_u8p), sz, C.POINTER(_u8p), sz, i, i, i], i),
         "srcnn_forward_y_striped_dev": ([C.POINTER(vp), i, C.POINTER(vp), sz, C.POINTER(vp), sz, i, i], i),
+        "srcnn_model_halo_rows": ([vp], i),
+        "srcnn_model_rows_dev": ([vp, vp, sz, i, vp, sz, i, i, i, i, i, vp], i),
+        "srcnn_model_rows_halo_dev": ([vp, vp, sz, i, i, vp, vp, sz, vp, sz, i, i, i, i, i, vp], i),
+        "srcnn_model_striped": ([C.POINTER(vp), i, _u8p, sz, _u8p, sz, i, i], i),
+        "srcnn_model_striped_dev": ([C.POINTER(vp), i, C.POINTER(vp), sz, C.POINTER(vp), sz, i, i], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
@@ -198,6 +204,7 @@ ABI_SYMBOLS = (
     "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
+    "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
 )
 
 
@@ -780,6 +787,32 @@ class Context:
         """0 none yet, 1 same device, 2 peer access (xGMI), 3 staged through the host (srcnn_halo_transport)."""
         return int(self._lib.srcnn_halo_transport(self._h))
 
+    # -- row stripes of every 1-channel model (9-3-5, 9-5-5, zero padding, MODE_BANDED16; 9-1-5 on the strip path) -----------
+    def model_halo_rows(self) -> int:
+        """Halo rows of the loaded model's stripes: 6 + (f2 - 1) / 2 (srcnn_model_halo_rows)."""
+        return int(self._lib.srcnn_model_halo_rows(self._h))
+
+    def model_rows_dev(self, d_src, src_stride, src_row0, d_dst, dst_stride, dst_row0, width, height, row_begin, row_end,
+                       d_preclamp=0):
+        """Output rows [row_begin, row_end) of a width x height image with whatever forward_y_dev would run for the loaded
+        model; d_src starts at image row src_row0 and holds the rows within model_halo_rows() of the range."""
+        _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0)
+        self._check(self._lib.srcnn_model_rows_dev(self._h, d_src, src_stride, src_row0, d_dst, dst_stride, dst_row0, width,
+                                                   height, row_begin, row_end, d_preclamp or None))
+
+    def model_rows_halo_dev(self, d_src, src_stride, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride,
+                            d_dst, dst_stride, dst_row0, width, height, row_begin, row_end, d_preclamp=0):
+        """The same stripe with its model_halo_rows() halo rows either side in buffers of their own (0 / None = no rows on
+        that side); the pointers may point into a neighbour's stripe."""
+        _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0)
+        if src_rows <= 0 or src_row0 + src_rows > height:
+            raise ValueError(f"src rows [{src_row0}, {src_row0 + src_rows}) are not rows of a {height}-row image")
+        if (d_halo_top or d_halo_bot) and halo_stride < width:
+            raise ValueError(f"halo_stride {halo_stride} is less than the width {width}")
+        self._check(self._lib.srcnn_model_rows_halo_dev(self._h, d_src, src_stride, src_row0, src_rows, d_halo_top or None,
+                                                        d_halo_bot or None, halo_stride, d_dst, dst_stride, dst_row0, width,
+                                                        height, row_begin, row_end, d_preclamp or None))
+
     def forward_y_unfused_dev(self, d_src, src_stride, src_frame_pitch, d_dst, dst_stride,
                               dst_frame_pitch, width, height, n_frames, d_work):
         self._check(self._lib.srcnn_forward_y_unfused_dev(self._h, d_src, src_stride, src_frame_pitch,
@@ -954,6 +987,47 @@ def forward_y_striped_dev(ctxs: Sequence[Context], d_stripes, stripe_stride, d_o
     outs = (C.c_void_p * n)(*[int(p) for p in d_out])
     ctxs[0]._check_multi(ctxs, load_library().srcnn_forward_y_striped_dev(_ctx_array(ctxs), n, ins, stripe_stride, outs,
                                                                          out_stride, width, height))
+
+
+def _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0):
+    """The geometry of a stripe call, checked before the library is entered."""
+    if width <= 0 or height <= 0:
+        raise ValueError(f"empty image {width} x {height}")
+    if not 0 <= row_begin < row_end <= height:
+        raise ValueError(f"rows [{row_begin}, {row_end}) are not a row range of a {height}-row image")
+    if src_stride < width or dst_stride < width:
+        raise ValueError(f"row strides {src_stride} / {dst_stride} are less than the width {width}")
+    if not 0 <= src_row0 <= row_begin or not 0 <= dst_row0 <= row_begin:
+        raise ValueError(f"src_row0 {src_row0} / dst_row0 {dst_row0} must lie in [0, row_begin = {row_begin}]")
+
+
+def model_striped(ctxs: Sequence[Context], src, dst=None):
+    """ONE host plane row-striped over several contexts / GPUs with whatever forward_y would run for the model they hold
+    (srcnn_model_striped): 9-3-5, 9-5-5, zero padding, MODE_BANDED16; a 9-1-5 model on the strip path runs forward_y_striped."""
+    handles = _ctx_array(ctxs)
+    src, ss = _plane(src, np.uint8, "src")
+    h, w = src.shape
+    if dst is None:
+        dst = np.empty((h, w), np.uint8)
+    dst, ds = _plane(dst, np.uint8, "dst", True)
+    _same_shape("dst", dst.shape, src.shape)
+    ctxs[0]._check_multi(ctxs, load_library().srcnn_model_striped(handles, len(ctxs), src.ctypes.data_as(_u8p), ss,
+                                                                 dst.ctypes.data_as(_u8p), ds, w, h))
+    return dst
+
+
+def model_striped_dev(ctxs: Sequence[Context], d_stripes, stripe_stride, d_out, out_stride, width, height):
+    """Device-resident striped step of the same: d_stripes[k] / d_out[k] are integer device addresses on ctxs[k]'s GPU of that
+    context's rows stripe_rows(height, len(ctxs), k).  Asynchronous; the caller orders it behind whatever wrote the stripes."""
+    handles, n = _ctx_array(ctxs), len(ctxs)
+    if len(d_stripes) != n or len(d_out) != n:
+        raise ValueError(f"need one input and one output stripe per context: {len(d_stripes)} / {len(d_out)} for {n} contexts")
+    if width <= 0 or height <= 0 or stripe_stride < width or out_stride < width:
+        raise ValueError(f"bad geometry: {width} x {height}, strides {stripe_stride} / {out_stride}")
+    ins = (C.c_void_p * n)(*[int(p) for p in d_stripes])
+    outs = (C.c_void_p * n)(*[int(p) for p in d_out])
+    ctxs[0]._check_multi(ctxs, load_library().srcnn_model_striped_dev(handles, n, ins, stripe_stride, outs, out_stride,
+                                                                     width, height))
 
 
 def _check_multi(self, ctxs, rc):

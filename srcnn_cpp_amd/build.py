@@ -51,6 +51,9 @@ UNITS = [
     ("srcnn_spatial_kernels.hip", []),
     # the float image path (srcnn_forward_f32*): the float forms of that file's layer-1 and layer-3 templates, a unit of their own
     ("srcnn_spatial_f32.hip", []),
+    # row stripes of the banded models (srcnn_model_rows*_dev, srcnn_model_striped*): the stripe forms of that file's layer-1
+    # template, again a unit of their own
+    ("srcnn_spatial_rows.hip", []),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),

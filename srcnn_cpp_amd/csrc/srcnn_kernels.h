@@ -302,6 +302,21 @@ hipError_t launch_spatial_l1f(int channels, bool zero, bool split, const float *
 hipError_t launch_spatial_l3f(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
                               const float *frag, const float *b3, float *dst, long dstride, long ch_pitch, hipStream_t st)
     __attribute__((weak));
+// Row stripes of a 1-channel model (srcnn_model_rows_dev, srcnn_model_rows_halo_dev, srcnn_model_striped*; srcnn_spatial_rows.hip).
+// L1Rows: where the image's rows are.  src (the launcher's argument, row stride sstride) starts at image row src_row0; with
+// `top` the halo_rows rows above src_row0 come from it, with `bot` the halo_rows rows from src_row1 on, both with row stride
+// halo_stride (a null pointer: no buffer on that side, src holds those rows too).  launch_spatial_l1_rows is launch_spatial_l1
+// (split: launch_spatial_l1h) for one byte channel with rows from there, and it reads no input row outside
+// [max(0, m0 - 4), min(H, m1 + 4)); padding refers to the image (0, H - 1, 0, W - 1), never to the stripe.  Same arithmetic as the
+// whole-image forms, same order.  A WEAK declaration, as the four above: the stripe entry points refuse where it is null.
+struct L1Rows {
+    const uint8_t *top, *bot;
+    long halo_stride;
+    int src_row0, src_row1, halo_rows;
+};
+hipError_t launch_spatial_l1_rows(bool zero, bool split, const uint8_t *src, long sstride, const L1Rows &rows, int W, int H, int m0,
+                                  int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
+    __attribute__((weak));
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

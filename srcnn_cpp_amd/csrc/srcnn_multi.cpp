@@ -1,5 +1,6 @@
 // srcnn_multi.cpp -- several GPUs driven from ONE host process: a row-striped plane whose stripes read their
-// neighbours' 6 edge rows over xGMI (or copies of them), frame ranges over contexts; one persistent host thread per context.
+// neighbours' 6 edge rows (6 + (f2 - 1) / 2 for a model on the banded path: srcnn_model_striped*) over xGMI (or copies of them),
+// frame ranges over contexts; one persistent host thread per context.
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
@@ -96,6 +97,33 @@ int stripe_setup(srcnn_ctx *const *ctxs, int n_ctx, int k)
     return SRCNN_OK;
 }
 
+// A link without peer access: copies of the neighbours' `rows` edge rows into the context's next halo set (kHaloSets sets in
+// turn), on the halo stream; the context's stream waits for them.  The launch that reads the set is followed by halo_set_read().
+int stage_halo_rows(srcnn_ctx *c, const srcnn_ctx *above, const uint8_t *nb_top, const srcnn_ctx *below, const uint8_t *nb_bot,
+                    size_t stripe_stride, int width, int rows, int *set_out, uint8_t **top, uint8_t **bot)
+{
+    int rc;
+    const int set = (int)(c->stripe_steps++ % srcnn_ctx::kHaloSets);
+    const size_t halo_bytes = (size_t)rows * width;
+    if ((rc = reserve(c, c->halo_top[set], halo_bytes))) return rc;
+    if ((rc = reserve(c, c->halo_bot[set], halo_bytes))) return rc;
+    *top = static_cast<uint8_t *>(c->halo_top[set].p);
+    *bot = static_cast<uint8_t *>(c->halo_bot[set].p);
+    if (c->halo_free_set[set]) HIP_TRY(c, hipStreamWaitEvent(c->halo_stream, c->halo_free[set], 0));
+    if (nb_top) HIP_TRY(c, copy_rows_between(c, *top, width, above, nb_top, stripe_stride, width, rows, c->halo_stream));
+    if (nb_bot) HIP_TRY(c, copy_rows_between(c, *bot, width, below, nb_bot, stripe_stride, width, rows, c->halo_stream));
+    HIP_TRY(c, hipEventRecord(c->halo_ready, c->halo_stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->halo_ready, 0));
+    *set_out = set;
+    return SRCNN_OK;
+}
+int halo_set_read(srcnn_ctx *c, int set)
+{
+    HIP_TRY(c, hipEventRecord(c->halo_free[set], c->stream));
+    c->halo_free_set[set] = true;
+    return SRCNN_OK;
+}
+
 // One context's part of the striped step.  Runs on its own host thread (one thread per device).
 //
 // float32 MFMA kernel (SRCNN_MODE_MFMA / REFBYTES): ONE launch per stripe through srcnn_forward_y_rows_halo_dev -- the kernel
@@ -126,22 +154,15 @@ int striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const uint8_t *const 
         if (c->halo_transport != 3)       // the neighbours' rows where they lie (same device, or peer-mapped over xGMI)
             return srcnn_forward_y_rows_halo_dev(c, d_stripes[k], stripe_stride, r0, r1 - r0, nb_top, nb_bot, stripe_stride,
                                                  d_out[k], out_stride, r0, width, height, r0, r1);
-        const int set = (int)(c->stripe_steps++ % srcnn_ctx::kHaloSets);
-        const size_t halo_bytes = (size_t)kHalo * width;
-        if ((rc = reserve(c, c->halo_top[set], halo_bytes))) return rc;
-        if ((rc = reserve(c, c->halo_bot[set], halo_bytes))) return rc;
-        uint8_t *top = static_cast<uint8_t *>(c->halo_top[set].p), *bot = static_cast<uint8_t *>(c->halo_bot[set].p);
-        if (c->halo_free_set[set]) HIP_TRY(c, hipStreamWaitEvent(c->halo_stream, c->halo_free[set], 0));
-        if (has_top) HIP_TRY(c, copy_rows_between(c, top, width, ctxs[k - 1], nb_top, stripe_stride, width, kHalo, c->halo_stream));
-        if (has_bot) HIP_TRY(c, copy_rows_between(c, bot, width, ctxs[k + 1], nb_bot, stripe_stride, width, kHalo, c->halo_stream));
-        HIP_TRY(c, hipEventRecord(c->halo_ready, c->halo_stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->halo_ready, 0));
+        int set = 0;
+        uint8_t *top = nullptr, *bot = nullptr;
+        if ((rc = stage_halo_rows(c, has_top ? ctxs[k - 1] : nullptr, nb_top, has_bot ? ctxs[k + 1] : nullptr, nb_bot, stripe_stride,
+                                  width, kHalo, &set, &top, &bot)))
+            return rc;
         if ((rc = srcnn_forward_y_rows_halo_dev(c, d_stripes[k], stripe_stride, r0, r1 - r0, has_top ? top : nullptr,
                                                 has_bot ? bot : nullptr, (size_t)width, d_out[k], out_stride, r0, width, height, r0, r1)))
             return rc;
-        HIP_TRY(c, hipEventRecord(c->halo_free[set], c->stream));
-        c->halo_free_set[set] = true;
-        return SRCNN_OK;
+        return halo_set_read(c, set);
     }
     const size_t band_bytes = (size_t)3 * kHalo * width;
     if ((rc = reserve(c, c->band_top, band_bytes))) return rc;
@@ -197,6 +218,57 @@ int striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const uint8_t *const 
     return SRCNN_OK;
 }
 
+// The same set for srcnn_model_striped*: every context holds a whole 1-channel model that its mode and padding can run, and all
+// of them the same kind -- one halo height, and either all on the banded path or all on the strip path
+int check_model_ctx_set(srcnn_ctx *const *ctxs, int n_ctx)
+{
+    if (!ctxs || n_ctx <= 0) return SRCNN_ERR_INVALID;
+    for (int k = 0; k < n_ctx; ++k) {
+        if (!ctxs[k]) return SRCNN_ERR_INVALID;
+        if (!has_model(ctxs[k])) return fail(ctxs[k], SRCNN_ERR_STATE, "%s", kNoModel);
+        if (int rc = model_rows_refusal(ctxs[k])) return rc;
+        for (int j = 0; j < k; ++j)
+            if (ctxs[j] == ctxs[k]) return fail(ctxs[k], SRCNN_ERR_INVALID, "the same context appears twice");
+        if (ctxs[k]->f2 != ctxs[0]->f2 || luma_path_ok(ctxs[k]) != luma_path_ok(ctxs[0]))
+            return fail(ctxs[k], SRCNN_ERR_INVALID, "srcnn_model_striped: the contexts hold different models, modes or paddings "
+                                                    "(context %d: 9-%d-5, context 0: 9-%d-5)", k, ctxs[k]->f2, ctxs[0]->f2);
+    }
+    return SRCNN_OK;
+}
+
+// One context's part of srcnn_model_striped* for a model on the banded path: ONE call of srcnn_model_rows_halo_dev, i.e. one
+// layer-1 launch per row band whose row select picks the buffer an input row lives in.  With neighbours on the same device or
+// peer access the halo "buffers" are the neighbours' stripes, read where they lie; a link that refuses peer access gets copies
+// of the R rows either side into this context's halo sets (stage_halo_rows()), as striped_step() above.
+int model_striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const uint8_t *const *d_stripes, size_t stripe_stride,
+                       uint8_t *const *d_out, size_t out_stride, int width, int height)
+{
+    srcnn_ctx *c = ctxs[k];
+    BIND(c);
+    int rc, r0, r1, a0 = 0, a1 = 0;
+    srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
+    const bool has_top = k > 0, has_bot = k < n_ctx - 1;
+    if (!has_top && !has_bot)
+        return srcnn_model_rows_dev(c, d_stripes[k], stripe_stride, 0, d_out[k], out_stride, 0, width, height, 0, height, nullptr);
+    if (has_top) srcnn_stripe_rows(height, n_ctx, k - 1, &a0, &a1);
+    if ((rc = stripe_setup(ctxs, n_ctx, k))) return rc;
+    const int R = srcnn_model_halo_rows(c);
+    const uint8_t *nb_top = has_top ? d_stripes[k - 1] + (size_t)(a1 - a0 - R) * stripe_stride : nullptr;
+    const uint8_t *nb_bot = has_bot ? d_stripes[k + 1] : nullptr;
+    if (c->halo_transport != 3)
+        return srcnn_model_rows_halo_dev(c, d_stripes[k], stripe_stride, r0, r1 - r0, nb_top, nb_bot, stripe_stride, d_out[k],
+                                         out_stride, r0, width, height, r0, r1, nullptr);
+    int set = 0;
+    uint8_t *top = nullptr, *bot = nullptr;
+    if ((rc = stage_halo_rows(c, has_top ? ctxs[k - 1] : nullptr, nb_top, has_bot ? ctxs[k + 1] : nullptr, nb_bot, stripe_stride, width,
+                              R, &set, &top, &bot)))
+        return rc;
+    if ((rc = srcnn_model_rows_halo_dev(c, d_stripes[k], stripe_stride, r0, r1 - r0, has_top ? top : nullptr, has_bot ? bot : nullptr,
+                                        (size_t)width, d_out[k], out_stride, r0, width, height, r0, r1, nullptr)))
+        return rc;
+    return halo_set_read(c, set);
+}
+
 // fn(k) for every context of the set, context k > 0 on the k-th persistent worker thread of ctxs[0]'s pool
 template <typename Fn>
 int run_per_context(srcnn_ctx *const *ctxs, int n_ctx, Fn fn)
@@ -214,6 +286,46 @@ int run_per_context(srcnn_ctx *const *ctxs, int n_ctx, Fn fn, Abort on_incomplet
     if (!ctxs[0]->pool) ctxs[0]->pool.reset(new (std::nothrow) WorkerPool());
     if (!ctxs[0]->pool) return fail(ctxs[0], SRCNN_ERR_NOMEM, "worker pool");
     return ctxs[0]->pool->run(n_ctx, fn, SRCNN_ERR_NOMEM, on_incomplete);
+}
+
+using StripeStep = int (*)(srcnn_ctx *const *, int, int, const uint8_t *const *, size_t, uint8_t *const *, size_t, int, int);
+
+// A host plane striped over the contexts, `step` being one context's part of the device-resident step (striped_step,
+// model_striped_step)
+int striped_host(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int width,
+                 int height, StripeStep step)
+{
+    std::vector<const uint8_t *> d_in((size_t)n_ctx);
+    std::vector<uint8_t *> d_res((size_t)n_ctx);
+    // phase 1: every device receives ITS rows only (the halo rows then travel device to device)
+    int rc = run_per_context(ctxs, n_ctx, [&](int k) -> int {
+        srcnn_ctx *c = ctxs[k];
+        BIND(c);
+        int r, r0, r1;
+        srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
+        const size_t n = (size_t)(r1 - r0) * width;
+        if ((r = reserve(c, c->in_u8, n))) return r;
+        if ((r = reserve(c, c->out_u8, n))) return r;
+        HIP_TRY(c, hipMemcpy2DAsync(c->in_u8.p, width, src + (size_t)r0 * src_stride, src_stride, width, r1 - r0,
+                                    hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        d_in[(size_t)k] = static_cast<const uint8_t *>(c->in_u8.p);
+        d_res[(size_t)k] = static_cast<uint8_t *>(c->out_u8.p);
+        return SRCNN_OK;
+    });
+    if (rc) return rc;
+    // phase 2: halo copies + interior rows + edge bands, then each device returns its rows
+    return run_per_context(ctxs, n_ctx, [&](int k) -> int {
+        srcnn_ctx *c = ctxs[k];
+        BIND(c);
+        int r, r0, r1;
+        srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
+        if ((r = step(ctxs, n_ctx, k, d_in.data(), width, d_res.data(), width, width, height))) return r;
+        HIP_TRY(c, hipMemcpy2DAsync(dst + (size_t)r0 * dst_stride, dst_stride, c->out_u8.p, width, width, r1 - r0,
+                                    hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return SRCNN_OK;
+    });
 }
 
 }  // namespace
@@ -248,37 +360,42 @@ int srcnn_forward_y_striped(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *sr
         return fail(ctxs[0], SRCNN_ERR_INVALID, "forward_y_striped: bad plane geometry");
     if (n_ctx > 1 && height / n_ctx < kHalo)
         return fail(ctxs[0], SRCNN_ERR_INVALID, "forward_y_striped: stripes thinner than the %d-row halo", kHalo);
-    std::vector<const uint8_t *> d_in((size_t)n_ctx);
-    std::vector<uint8_t *> d_res((size_t)n_ctx);
-    // phase 1: every device receives ITS rows only (the halo rows then travel device to device)
-    rc = run_per_context(ctxs, n_ctx, [&](int k) -> int {
-        srcnn_ctx *c = ctxs[k];
-        BIND(c);
-        int r, r0, r1;
-        srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
-        const size_t n = (size_t)(r1 - r0) * width;
-        if ((r = reserve(c, c->in_u8, n))) return r;
-        if ((r = reserve(c, c->out_u8, n))) return r;
-        HIP_TRY(c, hipMemcpy2DAsync(c->in_u8.p, width, src + (size_t)r0 * src_stride, src_stride, width, r1 - r0,
-                                    hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        d_in[(size_t)k] = static_cast<const uint8_t *>(c->in_u8.p);
-        d_res[(size_t)k] = static_cast<uint8_t *>(c->out_u8.p);
-        return SRCNN_OK;
-    });
+    return striped_host(ctxs, n_ctx, src, src_stride, dst, dst_stride, width, height, striped_step);
+}
+
+int srcnn_model_striped_dev(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *const *d_stripes, size_t stripe_stride,
+                            uint8_t *const *d_out, size_t out_stride, int width, int height)
+{
+    int rc = check_model_ctx_set(ctxs, n_ctx);
     if (rc) return rc;
-    // phase 2: halo copies + interior rows + edge bands, then each device returns its rows
-    return run_per_context(ctxs, n_ctx, [&](int k) -> int {
-        srcnn_ctx *c = ctxs[k];
-        BIND(c);
-        int r, r0, r1;
-        srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
-        if ((r = striped_step(ctxs, n_ctx, k, d_in.data(), width, d_res.data(), width, width, height))) return r;
-        HIP_TRY(c, hipMemcpy2DAsync(dst + (size_t)r0 * dst_stride, dst_stride, c->out_u8.p, width, width, r1 - r0,
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return SRCNN_OK;
+    // the strip path runs this model: its striped step, 6 halo rows, the same bytes
+    if (luma_path_ok(ctxs[0])) return srcnn_forward_y_striped_dev(ctxs, n_ctx, d_stripes, stripe_stride, d_out, out_stride, width, height);
+    const int R = srcnn_model_halo_rows(ctxs[0]);
+    if (!d_stripes || !d_out || width <= 0 || height <= 0 || stripe_stride < (size_t)width || out_stride < (size_t)width)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_dev: bad arguments");
+    if (n_ctx > 1 && height / n_ctx < R)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_dev: %d rows over %d contexts leaves stripes thinner than the %d-row "
+                                                "halo of a 9-%d-5 model", height, n_ctx, R, ctxs[0]->f2);
+    for (int k = 0; k < n_ctx; ++k)
+        if (!d_stripes[k] || !d_out[k]) return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_dev: null stripe %d", k);
+    return run_per_context(ctxs, n_ctx, [&](int k) {
+        return model_striped_step(ctxs, n_ctx, k, d_stripes, stripe_stride, d_out, out_stride, width, height);
     });
+}
+
+int srcnn_model_striped(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride,
+                        int width, int height)
+{
+    int rc = check_model_ctx_set(ctxs, n_ctx);
+    if (rc) return rc;
+    if (luma_path_ok(ctxs[0])) return srcnn_forward_y_striped(ctxs, n_ctx, src, src_stride, dst, dst_stride, width, height);
+    const int R = srcnn_model_halo_rows(ctxs[0]);
+    if (bad_plane(src, src_stride, width, height) || bad_plane(dst, dst_stride, width, height))
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped: bad plane geometry");
+    if (n_ctx > 1 && height / n_ctx < R)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped: %d rows over %d contexts leaves stripes thinner than the %d-row halo "
+                                                "of a 9-%d-5 model", height, n_ctx, R, ctxs[0]->f2);
+    return striped_host(ctxs, n_ctx, src, src_stride, dst, dst_stride, width, height, model_striped_step);
 }
 
 /* A STREAM of planes, each row-striped over the contexts: a pipeline, not n_planes one-shot calls.  Context k keeps two stripe

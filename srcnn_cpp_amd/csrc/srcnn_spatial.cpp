@@ -157,10 +157,12 @@ static int upload_table16(srcnn_ctx *c)
 
 // The one gate of the banded path: SRCNN_OK when it may run the loaded model in the current mode and padding, else
 // SRCNN_ERR_STATE with a message that names what blocks the call.  f32: a call of the float image path (srcnn_forward_f32*),
-// which runs every whole model in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 and nothing else
-static int banded_refusal(srcnn_ctx *c, bool f32 = false)
+// which runs every whole model in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 and nothing else.  rows: a call of the stripe entry
+// points (srcnn_model_rows*_dev, srcnn_model_striped*), which run the whole 1-channel models
+static int banded_refusal(srcnn_ctx *c, bool f32 = false, bool rows = false)
 {
     const bool zero = c->padding == SRCNN_PAD_ZERO;
+    if (rows && !launch_spatial_l1_rows) return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows: built without the stripe kernels");
     if (f32) {
         if (c->mode != SRCNN_MODE_MFMA && c->mode != SRCNN_MODE_BANDED16)
             return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 runs in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only (mode %d has no "
@@ -193,6 +195,19 @@ static int banded_refusal(srcnn_ctx *c, bool f32 = false)
     return SRCNN_OK;
 }
 
+// The stripe entry points (srcnn_model_rows*_dev, srcnn_model_striped*) run the whole 1-channel models: on the banded path behind
+// banded_refusal(), or, where the strip path runs the model, through that path's stripe calls, which gate themselves
+int model_rows_refusal(srcnn_ctx *c)
+{
+    if (c->channels != 1)
+        return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows / srcnn_model_striped: the context holds a colour model (3 channels, "
+                                        "9-%d-5); row stripes run the 1-channel models only", c->f2);
+    if (!c->whole_model)
+        return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows / srcnn_model_striped need a model loaded by srcnn_set_weights / "
+                                        "srcnn_set_model: the loaded layers came from per-filter calls");
+    return luma_path_ok(c) ? SRCNN_OK : banded_refusal(c, false, true);
+}
+
 // the colour entry points run a colour model only
 static int refuse_luma_model(srcnn_ctx *c)
 {
@@ -204,6 +219,9 @@ static int refuse_luma_model(srcnn_ctx *c)
 // Rows [b0, b1) of a plane need layer-2 rows [b0 - 2, b1 + 2) and layer-1 rows [b0 - 2 - r2, b1 + 2 + r2), clamped to the
 // image: a band recomputes the 2 + r2 layer-1 rows and 2 layer-2 rows either side it shares with its neighbours.  Bands are
 // as tall as kSpatialWorkBytes allows for the two maps (256 + 128 B per pixel of a row).
+// A stripe call (io.rows) runs the same loop inside [row_begin, row_end): o0 / o1 / m0 / m1 are clamped to the IMAGE, so the
+// first and last band of a stripe compute the map rows beyond it that a whole-image call's neighbouring band would, from input
+// rows the caller provides (layer 1 reads [m0 - 4, m1 + 4), i.e. no further than R = 6 + r2 rows from the stripe).
 int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_step, size_t ch_step, size_t src_frame_pitch,
                    uint8_t *dst, size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre)
 {
@@ -223,7 +241,7 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
 int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, int n_frames)
 {
     int rc;
-    if ((rc = banded_refusal(c, io.f32))) return rc;
+    if ((rc = banded_refusal(c, io.f32, io.rows))) return rc;
     // (only a 9-1-5 model gets here unpacked: the others pack when they load)
     if (c->sp_f2 != c->f2) {
         const float *hr = c->host_raw.data();
@@ -246,13 +264,15 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     const long row_bytes = 4L * width;
     const long cap = (long)(kSpatialWorkBytes / (size_t)row_bytes) - 64L * (4 + 2 * r2) - 32L * 4;
     const int band_max = (int)std::max(16L, cap / 96);
-    const int n_bands = (height + band_max - 1) / band_max;
-    const int band = (height + n_bands - 1) / n_bands;
+    const int row_begin = io.rows ? io.row_begin : 0, row_end = io.rows ? io.row_end : height;
+    const int n_bands = (row_end - row_begin + band_max - 1) / band_max;
+    const int band = (row_end - row_begin + n_bands - 1) / n_bands;
     const long mrows = std::min<long>(height, band + 4 + 2 * r2), orows = std::min<long>(height, band + 4);
     const long mpitch = mrows * width, opitch = orows * width;
     if (bad_pitch((size_t)mpitch) || bad_pitch((size_t)opitch))
         return fail(c, SRCNN_ERR_INVALID, "%s: plane too large for a %s9-%d-5 model",
-                    io.f32 ? "forward_f32_dev" : C == 1 ? "forward_y_dev" : "forward_color_dev", C == 1 ? "" : "colour ", c->f2);
+                    io.rows ? "model_rows_dev" : io.f32 ? "forward_f32_dev" : C == 1 ? "forward_y_dev" : "forward_color_dev",
+                    C == 1 ? "" : "colour ", c->f2);
     if ((rc = reserve(c, c->sp_map64, (size_t)64 * mpitch * sizeof(float)))) return rc;
     if ((rc = reserve(c, c->sp_map32, (size_t)32 * opitch * sizeof(float)))) return rc;
     if (!c->sp_done) HIP_TRY(c, hipEventCreateWithFlags(&c->sp_done, hipEventDisableTiming));
@@ -264,6 +284,9 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     float *map64 = static_cast<float *>(c->sp_map64.p), *map32 = static_cast<float *>(c->sp_map32.p);
     const size_t src_stride = io.src_stride, ch_step = io.ch_step, dst_stride = io.dst_stride;
     const int px_step = io.px_step;
+    // a stripe: where the image's rows are for layer 1, and dst / pre addressed by image row from dst_row0
+    const L1Rows l1rows{io.halo_top, io.halo_bot, (long)io.halo_stride, io.src_row0, io.src_row0 + io.src_rows, kHaloRows + r2};
+    const long dst_off = io.rows ? (long)io.dst_row0 * (long)dst_stride : 0;
     for (int f = 0; f < n_frames; ++f) {
         // frame f of the call's planes: bytes, or floats (the float image path); the other pair stays null
         const uint8_t *sf = nullptr;
@@ -279,21 +302,24 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
             df = static_cast<uint8_t *>(io.dst) + (size_t)f * io.dst_frame_pitch;
             pf = io.pre ? io.pre + (size_t)f * io.dst_frame_pitch : nullptr;
         }
-        for (int b0 = 0; b0 < height; b0 += band) {
-            const int b1 = std::min(height, b0 + band);
+        for (int b0 = row_begin; b0 < row_end; b0 += band) {
+            const int b1 = std::min(row_end, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
             if (io.f32)        // float planes in: one launcher for both forms of the map
                 HIP_TRY(c, launch_spatial_l1f(C, zero, split, sff, (long)src_stride, (long)ch_step, width, height, m0, m1, frag, map64,
                                               mpitch, scale1, c->stream));
+            if (io.rows)       // a stripe: one launcher for both forms of the map, rows from src and the halo buffers
+                HIP_TRY(c, launch_spatial_l1_rows(zero, split, sf, (long)src_stride, l1rows, width, height, m0, m1, frag, map64,
+                                                  mpitch, scale1, c->stream));
             if (split) {       // the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
-                if (!io.f32)
+                if (!io.f32 && !io.rows)
                     HIP_TRY(c, launch_spatial_l1h(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
                                                   map64, mpitch, scale1, c->stream));
                 HIP_TRY(c, launch_spatial_l2h(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, c->sp16_table.p, bias2,
                                               unscale, map32, opitch, c->stream));
             } else {
-                if (!io.f32)
+                if (!io.f32 && !io.rows)
                     HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
                                                  map64, mpitch, c->stream));
                 HIP_TRY(c, launch_spatial_l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, map32, opitch,
@@ -305,8 +331,8 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
                 continue;
             }
             if (C > 1 || zero) {
-                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, df,
-                                             (long)dst_stride, pf, c->stream));
+                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, df - dst_off,
+                                             (long)dst_stride, pf ? pf - dst_off : nullptr, c->stream));
                 continue;
             }
             StripParams q{};
@@ -316,6 +342,7 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
             q.dst = df;
             q.pre = pf;
             q.dst_stride = (long)dst_stride;
+            q.dst_row0 = io.rows ? io.dst_row0 : 0;
             q.width = width;
             q.height = height;
             q.row_begin = b0;
@@ -468,6 +495,94 @@ int srcnn_forward_color(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uin
                                     hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SRCNN_OK;
+}
+
+/* ---- row stripes of every 1-channel model (include/srcnn_amd.h) ---- */
+
+int srcnn_model_halo_rows(const srcnn_ctx *c) { return c ? kHaloRows + (c->f2 - 1) / 2 : SRCNN_ERR_INVALID; }
+
+// Both stripe calls.  src_rows < 0: srcnn_model_rows_dev, d_src holds every row the range needs
+static int model_rows(srcnn_ctx *c, const char *what, const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
+                      const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride, uint8_t *d_dst, size_t dst_stride,
+                      int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
+{
+    BIND_KEEP(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const bool halo = src_rows >= 0;
+    if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) || width > (1 << 28) ||
+        row_begin < 0 || row_end > height || row_begin >= row_end || src_row0 < 0 || dst_row0 < 0 || dst_row0 > row_begin ||
+        (halo && (src_rows == 0 || src_rows > height - src_row0 || ((d_halo_top || d_halo_bot) && halo_stride < (size_t)width) ||
+                  halo_stride >= ((size_t)1 << 30))))
+        return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    if ((rc = model_rows_refusal(c))) return rc;         // a colour model, layers from per-filter calls, the banded path's gate
+    // the receptive field of rows [row_begin, row_end) must lie in src (halo form: in top | src | bot)
+    const int R = srcnn_model_halo_rows(c);
+    const int need0 = std::max(0, row_begin - R), need1 = std::min(height, row_end + R);
+    const int src_row1 = halo ? src_row0 + src_rows : height;
+    if (!halo && src_row0 > need0)
+        return fail(c, SRCNN_ERR_INVALID, "%s: rows [%d,%d) need input rows [%d,%d) (a halo of %d rows); src starts at row %d", what,
+                    row_begin, row_end, need0, need1, R, src_row0);
+    if (halo && ((need0 < src_row0 && (!d_halo_top || src_row0 < R || need0 < src_row0 - R)) ||
+                 (need1 > src_row1 && (!d_halo_bot || need1 > src_row1 + R))))
+        return fail(c, SRCNN_ERR_INVALID, "%s: rows [%d,%d) need input rows [%d,%d); src holds [%d,%d) and the halo buffers %d rows "
+                                          "either side", what, row_begin, row_end, need0, need1, src_row0, src_row1, R);
+    // a side the call reads nothing from keeps a null pointer: with both null this is srcnn_model_rows_dev
+    const uint8_t *top = halo && need0 < src_row0 ? d_halo_top : nullptr, *bot = halo && need1 > src_row1 ? d_halo_bot : nullptr;
+    if (luma_path_ok(c)) {      // the strip path runs this model: the stripe calls of that path, R = 6, the same bytes
+        if (d_preclamp)
+            return fail(c, SRCNN_ERR_STATE, "%s: the replicate-padded 9-1-5 model runs its stripes on the strip path, which has no "
+                                            "pre-clamp output (srcnn_forward_y_dev has one)", what);
+        if (!halo)
+            return srcnn_forward_y_rows_dev(c, d_src, src_stride, src_row0, d_dst, dst_stride, dst_row0, width, height, row_begin,
+                                            row_end);
+        return srcnn_forward_y_rows_halo_dev(c, d_src, src_stride, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, d_dst,
+                                             dst_stride, dst_row0, width, height, row_begin, row_end);
+    }
+    {   // like srcnn_forward_y_dev: the path cannot run in place -- the rows written must overlap none of the rows read
+        const size_t row_bytes = (size_t)width;
+        const uint8_t *out0 = d_dst + (size_t)(row_begin - dst_row0) * dst_stride;
+        const size_t out_bytes = (size_t)(row_end - row_begin - 1) * dst_stride + row_bytes;
+        const int s0 = top ? src_row0 : need0, s1 = bot ? src_row1 : need1;         // the rows read from src
+        const size_t halo_bytes = (size_t)(R - 1) * halo_stride + row_bytes;
+        if ((s1 > s0 && ranges_overlap(out0, out_bytes, d_src + (size_t)(s0 - src_row0) * src_stride,
+                                       (size_t)(s1 - s0 - 1) * src_stride + row_bytes)) ||
+            (top && ranges_overlap(out0, out_bytes, top, halo_bytes)) || (bot && ranges_overlap(out0, out_bytes, bot, halo_bytes)))
+            return fail(c, SRCNN_ERR_INVALID, "%s: the output rows overlap the input (src or a halo buffer)", what);
+    }
+    if ((rc = flush_seams(c))) return rc;
+    BandedPlanes io;
+    io.src = d_src;
+    io.src_stride = src_stride;
+    io.dst = d_dst;
+    io.dst_stride = dst_stride;
+    io.pre = d_preclamp;
+    io.rows = true;
+    io.row_begin = row_begin;
+    io.row_end = row_end;
+    io.src_row0 = src_row0;
+    io.src_rows = src_row1 - src_row0;
+    io.dst_row0 = dst_row0;
+    io.halo_top = top;
+    io.halo_bot = bot;
+    io.halo_stride = halo_stride;
+    return forward_banded(c, io, width, height, 1);
+}
+
+int srcnn_model_rows_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, int src_row0, uint8_t *d_dst, size_t dst_stride,
+                         int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
+{
+    return model_rows(c, "model_rows_dev", d_src, src_stride, src_row0, -1, nullptr, nullptr, 0, d_dst, dst_stride, dst_row0, width,
+                      height, row_begin, row_end, d_preclamp);
+}
+
+int srcnn_model_rows_halo_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
+                              const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride, uint8_t *d_dst,
+                              size_t dst_stride, int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
+{
+    if (c && src_rows < 0) return fail(c, SRCNN_ERR_INVALID, "model_rows_halo_dev: bad arguments");
+    return model_rows(c, "model_rows_halo_dev", d_src, src_stride, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, d_dst,
+                      dst_stride, dst_row0, width, height, row_begin, row_end, d_preclamp);
 }
 
 int srcnn_set_input_range(srcnn_ctx *c, float r)

@@ -23,6 +23,11 @@
 // layer-1 map as f16 (hi, lo) pairs (the same bytes), spatial_l2h_kernel reads it on v_mfma_f32_32x32x16_f16 and writes the same
 // 32 planar f32 maps, layer 3 is unchanged.
 //
+// Row stripes (srcnn_model_rows_dev, srcnn_model_rows_halo_dev, srcnn_model_striped*) run the same launches on a row range of
+// the image with one more compile-time form of layer 1, spatial_l1_kernel<1, ZERO, Scale, uint8_t, L1Rows> (srcnn_spatial_rows.hip):
+// the image's rows come from up to three buffers, and no row outside the ones the launch's map rows need is read.  Layers 2
+// and 3 read the context's own band maps only and have no such form.
+//
 // The input is read at src[y * sstride + x * px_step + c * ch_step]: px_step = 3, ch_step = 1 for interleaved 3-byte pixels
 // (srcnn_forward_color*), px_step = 1, ch_step = plane pitch for the three resized planes of srcnn_process_bgr, and a plain
 // plane for C = 1.  Model channel c reads byte c of a pixel and writes byte c of an output pixel.
@@ -102,6 +107,17 @@ __device__ __forceinline__ void l1_store_split(uint4 *o, const f32x16 &acc, int 
 
 struct NoScale {};         // the last argument of the forms that write plain f32 maps: nothing
 
+// The stripe form (Steps = L1Rows, srcnn_kernels.h): where image row y lives -- the R rows above src_row0 in `top`, the R rows
+// from src_row1 on in `bot` (a null pointer: no such buffer, the row is in src), every other row in src, whose first row is
+// image row src_row0.  y is uniform over the workgroup, so the select and the row's base address are scalar.
+__device__ __forceinline__ const uint8_t *l1_row(const uint8_t *src, long sstride, int y, const L1Rows &rs)
+{
+    if (rs.top && y < rs.src_row0) return rs.top + (long)(y - (rs.src_row0 - rs.halo_rows)) * rs.halo_stride;
+    if (rs.bot && y >= rs.src_row1) return rs.bot + (long)(y - rs.src_row1) * rs.halo_stride;
+    return src + (long)(y - rs.src_row0) * sstride;
+}
+__device__ __forceinline__ const L1Rows &l1_rows_of(const L1Rows &rs) { return rs; }
+
 template <int C, bool ZERO, typename Scale, typename In, typename... Steps>
 __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ src, long sstride, Steps... steps, int W, int H,
                                                          int m0, int m1, const float *__restrict__ frag, float *__restrict__ map,
@@ -109,7 +125,9 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
 {
     constexpr bool SPLIT = std::is_same_v<Scale, float>;
     constexpr bool F32 = std::is_same_v<In, float>;            // float planes in (px_step = 1, ch_step = the plane pitch)
-    static_assert(sizeof...(Steps) == (C == 1 ? 0 : 2), "px_step and ch_step for 3 channels only");
+    constexpr bool ROWS = (std::is_same_v<Steps, L1Rows> || ...);    // the stripe form: rows from src and two halo buffers
+    static_assert(ROWS ? (sizeof...(Steps) == 1 && C == 1 && !F32) : sizeof...(Steps) == (C == 1 ? 0 : 2),
+                  "px_step and ch_step for 3 channels only; the stripe form for one byte channel only");
     using T = std::conditional_t<C == 1 || F32, float, uint8_t>;      // the window's element type
     float *as;
     T *ys;
@@ -124,25 +142,46 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * SL1_COLS, y0 = m0 + blockIdx.y * SL1_ROWS;
-    // the window, channel fastest (consecutive bytes of interleaved pixels go to consecutive threads); float planes: channel
-    // slowest (consecutive floats of a plane's row)
-    for (int e = tid; e < C * SL1_YC; e += 256) {
-        int rr, cc, ch;
-        if constexpr (F32 && C > 1) {
-            ch = e / SL1_YC;
-            rr = (e - ch * SL1_YC) / SL1_YP;
-            cc = e - ch * SL1_YC - rr * SL1_YP;
-        } else {
-            rr = e / (C * SL1_YP);
-            const int rem = e - rr * (C * SL1_YP);
-            cc = rem / C;
-            ch = rem - C * cc;
+    if constexpr (ROWS) {
+        // The stripe form stages the window row by row: window row rr is image row y0 - 4 + rr, clamped to the IMAGE (yi: what
+        // replicate and zero padding refer to, exactly as below), and then to y_last, the last input row this launch may read.
+        // Computed row y reads window rows y - y0 .. y - y0 + 8, i.e. image rows y - 4 .. y + 4, and the row loop below stops at
+        // y = m1 - 1: image rows beyond y_last = m1 + 3 feed no computed row (they are there when m1 - m0 is no multiple of
+        // SL1_ROWS).  Their window rows hold copies of row y_last, and nothing reads them.  At the other end y0 >= m0, so no
+        // window row lies above m0 - 4: the rows read are [max(0, m0 - 4), min(H, m1 + 4)), what the caller of a stripe provides.
+        const L1Rows &rs = l1_rows_of(steps...);
+        const int y_last = min(H - 1, m1 + 3);
+        const int cc = tid, xx = sclamp(x0 - 4 + cc, 0, W - 1);
+        for (int rr = 0; rr < SL1_YR; ++rr) {
+            const int yi = sclamp(y0 - 4 + rr, 0, H - 1);
+            const uint8_t *row = l1_row(src, sstride, min(yi, y_last), rs);     // uniform over the workgroup
+            if (cc < SL1_YP) {
+                const T v = row[xx];
+                if constexpr (ZERO) ys[rr * SL1_YP + cc] = (T)(v * ((yi == y0 - 4 + rr && xx == x0 - 4 + cc) ? (T)1 : (T)0));
+                else ys[rr * SL1_YP + cc] = v;
+            }
         }
-        const int yy = sclamp(y0 - 4 + rr, 0, H - 1), xx = sclamp(x0 - 4 + cc, 0, W - 1);
-        const T v = l1_at(src, sstride, yy, xx, ch, steps...);
-        // ZERO: 0 where the load was clamped, by a multiply: a select lets the compiler branch around the load (measured slower)
-        if constexpr (ZERO) ys[ch * SL1_YC + rr * SL1_YP + cc] = (T)(v * ((yy == y0 - 4 + rr && xx == x0 - 4 + cc) ? (T)1 : (T)0));
-        else ys[ch * SL1_YC + rr * SL1_YP + cc] = v;
+    } else {
+        // the window, channel fastest (consecutive bytes of interleaved pixels go to consecutive threads); float planes: channel
+        // slowest (consecutive floats of a plane's row)
+        for (int e = tid; e < C * SL1_YC; e += 256) {
+            int rr, cc, ch;
+            if constexpr (F32 && C > 1) {
+                ch = e / SL1_YC;
+                rr = (e - ch * SL1_YC) / SL1_YP;
+                cc = e - ch * SL1_YC - rr * SL1_YP;
+            } else {
+                rr = e / (C * SL1_YP);
+                const int rem = e - rr * (C * SL1_YP);
+                cc = rem / C;
+                ch = rem - C * cc;
+            }
+            const int yy = sclamp(y0 - 4 + rr, 0, H - 1), xx = sclamp(x0 - 4 + cc, 0, W - 1);
+            const T v = l1_at(src, sstride, yy, xx, ch, steps...);
+            // ZERO: 0 where the load was clamped, by a multiply: a select lets the compiler branch around the load (measured slower)
+            if constexpr (ZERO) ys[ch * SL1_YC + rr * SL1_YP + cc] = (T)(v * ((yy == y0 - 4 + rr && xx == x0 - 4 + cc) ? (T)1 : (T)0));
+            else ys[ch * SL1_YC + rr * SL1_YP + cc] = v;
+        }
     }
     if constexpr (C == 1) {
         for (int e = tid; e < SPATIAL_NFRAG_L1 * 64; e += 256) as[e] = frag[e];
@@ -200,7 +239,7 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
 // A channel plane of the window is SL2_PS floats, = 32 mod 64: the two lane-halves (channels 2p, 2p + 1) read disjoint banks.
 constexpr int SL2_COLS = 64, SL2_ROWS = 16, SL2_CC = 8, SL2_XP = 72;
 __host__ __device__ constexpr int sl2_ps(int r2) { return ((((SL2_ROWS + 2 * r2) * SL2_XP) + 31) / 64) * 64 + 32; }
-#ifndef SRCNN_SPATIAL_F32_UNIT
+#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT)
 size_t spatial_l2_lds_bytes(int f2)
 {
     return ((size_t)SL2_CC * sl2_ps((f2 - 1) / 2) + (size_t)f2 * f2 * (SL2_CC / 2) * 64) * sizeof(float);
@@ -527,8 +566,9 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
 
 // The launchers.  This file is compiled twice (srcnn_cpp_amd/build.py): as itself it instantiates the kernels of the byte entry
 // points, and through srcnn_spatial_f32.hip (which defines SRCNN_SPATIAL_F32_UNIT and includes it) the float forms of layers 1
-// and 3 and nothing else -- the kernels of this unit stay the ones they were, one for one.
-#ifndef SRCNN_SPATIAL_F32_UNIT
+// and 3 and nothing else -- the kernels of this unit stay the ones they were, one for one.  srcnn_spatial_rows.hip (which
+// defines SRCNN_SPATIAL_ROWS_UNIT) includes it for the templates alone and instantiates the stripe forms of layer 1 itself.
+#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT)
 template <int C, bool ZERO>
 static void launch_l1(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
                       const float *frag, float *map, long mpitch, hipStream_t st)
@@ -687,7 +727,7 @@ hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t
     return hipGetLastError();
 }
 
-#else   // SRCNN_SPATIAL_F32_UNIT
+#elif defined(SRCNN_SPATIAL_F32_UNIT)
 // ---- the float image path (srcnn_forward_f32*): layer 1 on float planes, layer 3 writing float planes ---------------------
 // the three tables and an f32 window of the three channels: 61.5 + 25.5 KiB, one workgroup per CU
 constexpr size_t SL1_LDS3F = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC * sizeof(float);

@@ -3,7 +3,8 @@
     python tools/isa_identity.py srcnn_spatial_kernels.hip [--rev HEAD]
 
 Compiles srcnn_cpp_amd/csrc/<unit> twice with `hipcc -S --cuda-device-only --offload-arch=gfx950` and the build's flags for the
-unit: once as `git show <rev>:` has it (with that revision's srcnn_kernels.h), once from the working tree.  Every kernel's
+unit: once as `git show <rev>:` has it (with that revision's srcnn_kernels.h and srcnn_spatial_kernels.hip, which the units
+of the float and stripe forms include), once from the working tree.  Every kernel's
 instruction stream and kernel descriptor (registers, LDS, private segment) is normalised -- comments and directives dropped,
 kernel symbols and basic-block labels renamed -- and hashed; the check passes when every kernel of the old listing has a kernel
 of the new listing with the same hash.  Kernels are matched by content, not by name: a template parameter added to a kernel
@@ -70,7 +71,8 @@ def main():
         if args.old and args.new:
             old, new = Path(args.old).read_text(), Path(args.new).read_text()
         else:
-            for f in (args.unit, "srcnn_kernels.h"):
+            # the unit as the revision has it, with that revision's header and the kernel file a unit may include
+            for f in dict.fromkeys((args.unit, "srcnn_kernels.h", "srcnn_spatial_kernels.hip")):
                 text = subprocess.run(["git", "-C", str(ROOT), "show", f"{args.rev}:srcnn_cpp_amd/csrc/{f}"], check=True,
                                       capture_output=True, text=True).stdout
                 (d / f).write_text(text)
