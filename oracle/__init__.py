@@ -75,6 +75,7 @@ def lib() -> C.CDLL:
         _lib.opencv_resize_cubic.argtypes = [_u8p, sz, i, i, _u8p, sz, i, i]
         _lib.opencv_resize_cubic_variant.argtypes = [_u8p, sz, i, i, _u8p, sz, i, i, i]
         _lib.opencv_scaled_dim.argtypes = [i, C.c_float]
+        _lib.opencv_cubic_table.argtypes = [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int16)]
         _lib.srcnn_adv_point.argtypes = [_u8p, _f32p, _f32p, _f32p]
         _lib.srcnn_adv_search.argtypes = [_f32p, _u8p, i, i, i, C.c_uint64, _u8p, _f32p, _f32p]
         _lib.srcnn_adv_search.restype = C.c_long
@@ -299,6 +300,16 @@ def resize_cubic(src, dst_w, dst_h, vertical=VERTICAL_SIMD_FLOAT):
     rc = lib().opencv_resize_cubic_variant(ps, w, w, h, out.ctypes.data_as(_u8p), dst_w, dst_w, dst_h, int(vertical))
     assert rc == 0
     return out
+
+
+def cubic_table(n_src, n_dst):
+    """The coefficient table of one axis of the cubic resize -> (ofs int32 [n_dst], coef int16 [n_dst, 4])."""
+    ofs = np.empty(n_dst, np.int32)
+    coef = np.empty((n_dst, 4), np.int16)
+    rc = lib().opencv_cubic_table(int(n_src), int(n_dst), ofs.ctypes.data_as(C.POINTER(C.c_int)),
+                                  coef.ctypes.data_as(C.POINTER(C.c_int16)))
+    assert rc == 0
+    return ofs, coef
 
 
 def scaled_size(w, h, scale):

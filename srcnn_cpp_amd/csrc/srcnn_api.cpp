@@ -413,6 +413,23 @@ int srcnn_debug_cubic_table(int n_src, int n_dst, int *ofs, short *coef)
     cubic_table(n_src, n_dst, ofs, coef);
     return SRCNN_OK;
 }
+
+/* Undocumented test hooks (need no device): which resize kernel a geometry reaches (2 tiled4, 1 tiled, 0 direct; resize_variant()
+ * in srcnn_kernels.h, what launch_resize_cubic and fused_pipeline_ok ask), and the tile sizes and LDS capacities the kernels were
+ * compiled with: RT, RMAX, RT4, RMAX4, SMAX, columns per tile. */
+int srcnn_debug_resize_variant(int sw, int sh, int dw, int dh, int dword_ok)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return SRCNN_ERR_INVALID;
+    return resize_variant(sw, sh, dw, dh, dword_ok != 0);
+}
+
+int srcnn_debug_resize_limits(int *out6)
+{
+    if (!out6) return SRCNN_ERR_INVALID;
+    const int v[6] = {RT, RMAX, RT4, RMAX4, SMAX, 256};
+    for (int k = 0; k < 6; ++k) out6[k] = v[k];
+    return SRCNN_OK;
+}
 #endif  /* SRCNN_TUNING_BUILD */
 
 }  // extern "C"

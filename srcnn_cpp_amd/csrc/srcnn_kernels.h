@@ -321,6 +321,32 @@ hipError_t launch_spatial_l1_rows(bool zero, bool split, const uint8_t *src, lon
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 
 // ---- pipeline steps around the conv path (srcnn_pipeline.hip) ---------------
+// Tile geometry of the cubic resize's three kernels.  tiled: a workgroup produces RT output rows x 256 columns from at most
+// RMAX source rows x SMAX source columns held in LDS; tiled4 (and the two fused launches, which share its layout): RT4 rows
+// (four row groups of RPT rows per thread) x 256 columns from at most RMAX4 x SMAX.
+constexpr int RT = 8;        // output rows per workgroup
+constexpr int RMAX = 16;     // source rows a tile may span
+constexpr int SMAX = 288;    // source columns a 256-wide tile may span
+#ifndef SRCNN_RT4
+#define SRCNN_RT4 32
+#endif
+constexpr int RT4 = SRCNN_RT4;          // output rows per workgroup (four row groups of RPT rows)
+constexpr int RPT = RT4 / 4;            // rows per thread
+constexpr int RMAX4 = RT4 == 32 ? 28 : 20;     // source rows such a tile may span
+enum { RESIZE_DIRECT = 0, RESIZE_TILED = 1, RESIZE_TILED4 = 2 };
+// Which kernel resizes (sw x sh) -> (dw x dh): the ONE place that keeps a tile inside its LDS arrays.  A tile of T output
+// rows spans at most ceil(T * sh / dh) + 4 source rows (4-tap support), 256 output columns at most ceil(256 * sw / dw) + 5
+// source columns.  dword_ok: destination base, row stride and plane pitch are multiples of four (tiled4 stores dwords).
+inline int resize_variant(int sw, int sh, int dw, int dh, bool dword_ok)
+{
+    const long span = ((long)RT * sh + dh - 1) / dh + 4;
+    const long cspan = (256L * sw + dw - 1) / dw + 5;
+    const long span4 = ((long)RT4 * sh + dh - 1) / dh + 4;
+    if (span4 <= RMAX4 && cspan <= SMAX && dword_ok) return RESIZE_TILED4;
+    if (span <= RMAX && cspan <= SMAX) return RESIZE_TILED;
+    return RESIZE_DIRECT;
+}
+
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);
 hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8_t *planes, long pstride,
                             long ppitch, hipStream_t st);

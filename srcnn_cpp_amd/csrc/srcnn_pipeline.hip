@@ -106,9 +106,8 @@ __global__ __launch_bounds__(256) void resize_cubic_kernel(const uint8_t *__rest
 // columns.  The horizontal pass of every source row the tile touches is done ONCE into LDS (as the
 // int sums OpenCV's HResize produces), the vertical pass then reads LDS: ~4 byte loads per output
 // pixel instead of 16.  Same integer arithmetic, bit-identical results.
-constexpr int RT = 8;        // output rows per workgroup
-constexpr int RMAX = 16;     // source rows a tile may span (host checks before choosing this kernel)
-constexpr int SMAX = 288;    // source columns a 256-wide tile may span
+// (RT = 8 output rows per workgroup from at most RMAX = 16 source rows x SMAX = 288 source columns: srcnn_kernels.h, where
+// resize_variant() checks a geometry against them before this kernel is chosen)
 
 __global__ __launch_bounds__(256) void resize_cubic_tiled_kernel(const uint8_t *__restrict__ src, long sstride,
                                                                  long spitch, int sw, int sh,
@@ -186,12 +185,7 @@ __device__ __forceinline__ unsigned vpass4(const float (*hbuf)[256], int tx, int
 // the vertical pass reads its taps as one 16-byte LDS word per row and stores one dword per row: a quarter of the
 // store and LDS instructions of the kernel above (which remains the fallback for small scales / odd strides).
 // Same arithmetic, bit-identical results.
-#ifndef SRCNN_RT4
-#define SRCNN_RT4 32
-#endif
-constexpr int RT4 = SRCNN_RT4;          // output rows per workgroup (four row groups of RPT rows)
-constexpr int RPT = RT4 / 4;            // rows per thread
-constexpr int RMAX4 = RT4 == 32 ? 28 : 20;     // source rows such a tile may span (host checks)
+// (RT4 = 32 rows, RPT = 8 per thread, at most RMAX4 = 28 source rows: srcnn_kernels.h, resize_variant())
 
 __global__ __launch_bounds__(256) void resize_cubic_tiled4_kernel(const uint8_t *__restrict__ src, long sstride,
                                                                   long spitch, int sw, int sh,
@@ -381,9 +375,8 @@ __global__ __launch_bounds__(256) void resize_merge_kernel(const uint8_t *__rest
 // true when the two fused launches apply (the tiled4 geometry limits, dword-aligned rows)
 bool fused_pipeline_ok(int sw, int sh, int dw, int dh, const void *y_hi, long ystride, const void *out, long ostride)
 {
-    const long cspan = (256L * sw + dw - 1) / dw + 5, span4 = ((long)RT4 * sh + dh - 1) / dh + 4;
     const bool aligned = ((reinterpret_cast<uintptr_t>(y_hi) | (uintptr_t)ystride | reinterpret_cast<uintptr_t>(out) | (uintptr_t)ostride) & 3) == 0;
-    return span4 <= RMAX4 && cspan <= SMAX && aligned;
+    return resize_variant(sw, sh, dw, dh, aligned) == RESIZE_TILED4;
 }
 
 hipError_t launch_bgr_to_y_resized(const uint8_t *bgr, long stride, int sw, int sh, uint8_t *dst, long dstride, int dw, int dh,
@@ -448,15 +441,12 @@ hipError_t launch_resize_cubic(const uint8_t *src, long sstride, long spitch, in
                                long dstride, long dpitch, int dw, int dh, int n_planes, const int *xofs,
                                const short *alpha, const int *yofs, const short *beta, hipStream_t st)
 {
-    // a tile of RT output rows spans at most ceil(RT * sh / dh) + 4 source rows (4-tap support)
-    const long span = ((long)RT * sh + dh - 1) / dh + 4;
-    const long cspan = (256L * sw + dw - 1) / dw + 5;      // likewise for 256 output columns
-    const long span4 = ((long)RT4 * sh + dh - 1) / dh + 4;
     const bool dword_ok = ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dstride | (uintptr_t)dpitch) & 3) == 0;
-    if (span4 <= RMAX4 && cspan <= SMAX && dword_ok)
+    const int variant = resize_variant(sw, sh, dw, dh, dword_ok);      // the tiles' LDS limits: srcnn_kernels.h
+    if (variant == RESIZE_TILED4)
         hipLaunchKernelGGL(resize_cubic_tiled4_kernel, dim3((dw + 255) / 256, (dh + RT4 - 1) / RT4, n_planes), dim3(256),
                            0, st, src, sstride, spitch, sw, sh, dst, dstride, dpitch, dw, dh, xofs, alpha, yofs, beta);
-    else if (span <= RMAX && cspan <= SMAX)
+    else if (variant == RESIZE_TILED)
         hipLaunchKernelGGL(resize_cubic_tiled_kernel, dim3((dw + 255) / 256, (dh + RT - 1) / RT, n_planes), dim3(256),
                            0, st, src, sstride, spitch, sw, sh, dst, dstride, dpitch, dw, dh, xofs, alpha, yofs, beta);
     else
