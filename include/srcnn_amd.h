@@ -291,7 +291,8 @@ int srcnn_get_padding(const srcnn_ctx *ctx);
  *     pipeline and run the model on the result (no YCrCb conversion);
  *   - every entry point that runs a 1-channel model (srcnn_forward_y*, row stripes, halo buffers, the several-GPU calls,
  *     srcnn_forward_y_unfused_dev, srcnn_conv99x11_dev, srcnn_conv55_dev) returns SRCNN_ERR_STATE, and srcnn_last_error()
- *     names the colour model;
+ *     names the colour model; its row stripes and its stripes over several contexts are srcnn_model_color_rows_dev,
+ *     srcnn_model_color_rows_halo_dev and srcnn_model_color_striped(_dev), below;
  *   - srcnn_set_weights, srcnn_set_model or a per-filter call that loads weights ENDS the model, as for srcnn_set_model;
  *     srcnn_get_model_channels() then returns 1.  With a 1-channel model loaded srcnn_forward_color* return SRCNN_ERR_STATE;
  *   - workspace: the band maps of srcnn_set_model (within 512 MiB), and the host-buffer form stages the image on the device. */
@@ -486,8 +487,9 @@ int srcnn_forward_y_rows_halo_dev(srcnn_ctx *ctx,
  * The halo is R = srcnn_model_halo_rows(ctx) = 6 + (f2 - 1) / 2 rows: 4 input rows of the 9x9 layer, (f2 - 1) / 2 rows of layer 2's
  * window, 2 rows of the 5x5 layer.  A colour model and a model whose layers came from per-filter calls return SRCNN_ERR_STATE, and
  * srcnn_last_error() names the reason; so does a mode or padding in which srcnn_forward_y_dev refuses the model.  Asynchronous on the
- * context's stream.  Out of scope: a pipelined form like srcnn_forward_y_striped_frames, lanes, float planes (srcnn_forward_f32*),
- * stripes of a colour model; seam deferral does not apply to the banded path. */
+ * context's stream.  A colour model, and float planes, have calls of their own below (srcnn_model_color_rows*_dev,
+ * srcnn_model_rows*_f32_dev and their striped forms).  Out of scope: a pipelined form like srcnn_forward_y_striped_frames, lanes;
+ * seam deferral does not apply to the banded path. */
 
 /* R of the loaded model: 6, 7 or 8 for f2 = 1, 3, 5. */
 int srcnn_model_halo_rows(const srcnn_ctx *ctx);
@@ -527,6 +529,70 @@ int srcnn_model_striped_dev(srcnn_ctx *const *ctxs, int n_ctx,
 int srcnn_model_striped(srcnn_ctx *const *ctxs, int n_ctx,
                         const uint8_t *src, size_t src_stride,
                         uint8_t *dst, size_t dst_stride, int width, int height);
+
+/* ---- row stripes of a colour model, and of float planes -----------------------------------------------------------------
+ * The same four calls for the two other kinds of image the library runs a whole model on.  Each runs, on a row range of the
+ * image, what the whole-image call of the same data type runs for the loaded model in the context's mode and padding:
+ *   srcnn_model_color_*       srcnn_forward_color_dev: a colour model (srcnn_set_model_color), packed 3-byte pixels, strides in
+ *                             BYTES (>= 3 * width); pre-clamp floats at the element offsets of the output bytes
+ *   srcnn_model_*_f32*        srcnn_forward_f32_dev: every whole model, 1 or 3 planar float32 channels by the loaded model, strides
+ *                             and channel pitches in ELEMENTS (the pitches are ignored for one channel); the output is the
+ *                             unclamped value; in SRCNN_MODE_BANDED16 the inputs lie within srcnn_set_input_range()
+ * in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16, under either padding, for f2 = 1, 3, 5.  They mirror the 1-channel calls above in
+ * argument order, asynchrony and ordering contract, and these hold for all of them:
+ *   - the halo is R = srcnn_model_halo_rows(ctx) rows (it depends on f2 only);
+ *   - a plain stripe's d_src must hold rows [max(0, row_begin - R), min(height, row_end + R)), and no other row is read, nor any
+ *     element beyond a row's width; a halo pointer may be NULL where the range needs nothing on that side;
+ *   - halo pointers may point into a neighbour's stripe -- a float halo buffer has a channel pitch of its own for that -- and in
+ *     the _striped*_dev calls they do, with no copy, when the neighbour is on the same device or under peer access; a link that
+ *     refuses peer access copies R rows per side and channel into the context's halo buffers (srcnn_halo_transport(): 1 / 2 / 3);
+ *   - padding refers to the IMAGE, never to the stripe, and the assembled rows equal the whole-image call BIT FOR BIT (output
+ *     bytes, pre-clamp floats, float planes) in both modes;
+ *   - the _striped* calls need height / n_ctx >= R and contexts that hold the same model, mode, padding and, for float planes,
+ *     input range (else SRCNN_ERR_INVALID); the ordering of the _striped*_dev calls is the caller's, as for
+ *     srcnn_model_striped_dev;
+ *   - SRCNN_ERR_STATE, with the context still usable and srcnn_last_error() naming the reason: a colour call while a 1-channel
+ *     model is loaded, any mode other than SRCNN_MODE_MFMA / SRCNN_MODE_BANDED16, layers loaded by per-filter calls, a library
+ *     built without the colour / float stripe kernels;
+ *   - SRCNN_ERR_INVALID: null pointers, sizes <= 0, a stride below the row, a range outside the image, src or the halo buffers
+ *     not covering the rows the range needs, float output planes that overlap each other, output rows that overlap the input.
+ * Out of scope: interleaved float pixels, a pipelined form, a several-GPU form of the torch module. */
+int srcnn_model_color_rows_dev(srcnn_ctx *ctx,
+                               const uint8_t *d_src, size_t src_stride, int src_row0,
+                               uint8_t *d_dst, size_t dst_stride, int dst_row0,
+                               int width, int height, int row_begin, int row_end,
+                               float *d_preclamp /*may be NULL; dst strides*/);
+int srcnn_model_color_rows_halo_dev(srcnn_ctx *ctx,
+                                    const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
+                                    const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride,
+                                    uint8_t *d_dst, size_t dst_stride, int dst_row0,
+                                    int width, int height, int row_begin, int row_end,
+                                    float *d_preclamp /*may be NULL; dst strides*/);
+int srcnn_model_color_striped_dev(srcnn_ctx *const *ctxs, int n_ctx,
+                                  const uint8_t *const *d_stripes, size_t stripe_stride,
+                                  uint8_t *const *d_out, size_t out_stride, int width, int height);
+int srcnn_model_color_striped(srcnn_ctx *const *ctxs, int n_ctx,
+                              const uint8_t *src, size_t src_stride,
+                              uint8_t *dst, size_t dst_stride, int width, int height);
+
+/* Float planes: channel c of the stripe at d_src + c * src_ch_pitch, of a halo buffer at + c * halo_ch_pitch (rows halo_stride
+ * apart), of the output at d_dst + c * dst_ch_pitch; d_src points at image row src_row0 and d_dst at image row dst_row0 of every
+ * channel.  In the striped calls every stripe has the same row stride and channel pitch. */
+int srcnn_model_rows_f32_dev(srcnn_ctx *ctx,
+                             const float *d_src, size_t src_stride, size_t src_ch_pitch, int src_row0,
+                             float *d_dst, size_t dst_stride, size_t dst_ch_pitch, int dst_row0,
+                             int width, int height, int row_begin, int row_end);
+int srcnn_model_rows_halo_f32_dev(srcnn_ctx *ctx,
+                                  const float *d_src, size_t src_stride, size_t src_ch_pitch, int src_row0, int src_rows,
+                                  const float *d_halo_top, const float *d_halo_bot, size_t halo_stride, size_t halo_ch_pitch,
+                                  float *d_dst, size_t dst_stride, size_t dst_ch_pitch, int dst_row0,
+                                  int width, int height, int row_begin, int row_end);
+int srcnn_model_striped_f32_dev(srcnn_ctx *const *ctxs, int n_ctx,
+                                const float *const *d_stripes, size_t stripe_stride, size_t stripe_ch_pitch,
+                                float *const *d_out, size_t out_stride, size_t out_ch_pitch, int width, int height);
+int srcnn_model_striped_f32(srcnn_ctx *const *ctxs, int n_ctx,
+                            const float *src, size_t src_stride, size_t src_ch_pitch,
+                            float *dst, size_t dst_stride, size_t dst_ch_pitch, int width, int height);
 
 /* Materialising variant of the whole path (layer-1/2 kernel writes the 32
  * planar f32 maps to HBM, layer-3 kernel reads them back), n_frames planes.

@@ -34,6 +34,7 @@ __all__ = [
     "ERR_INVALID", "ERR_HIP", "ERR_NOMEM", "ERR_NODEVICE", "ERR_STATE",
     "stripe_rows", "forward_y_frames_multi", "forward_y_lanes_dev", "forward_y_striped", "forward_y_striped_dev",
     "model_striped", "model_striped_dev",
+    "model_color_striped", "model_color_striped_dev", "model_striped_f32", "model_striped_f32_dev",
 ]
 
 _PKG = Path(__file__).resolve().parent
@@ -182,6 +183,14 @@ def load_library() -> C.CDLL:
         "srcnn_model_rows_halo_dev": ([vp, vp, sz, i, i, vp, vp, sz, vp, sz, i, i, i, i, i, vp], i),
         "srcnn_model_striped": ([C.POINTER(vp), i, _u8p, sz, _u8p, sz, i, i], i),
         "srcnn_model_striped_dev": ([C.POINTER(vp), i, C.POINTER(vp), sz, C.POINTER(vp), sz, i, i], i),
+        "srcnn_model_color_rows_dev": ([vp, vp, sz, i, vp, sz, i, i, i, i, i, vp], i),
+        "srcnn_model_color_rows_halo_dev": ([vp, vp, sz, i, i, vp, vp, sz, vp, sz, i, i, i, i, i, vp], i),
+        "srcnn_model_color_striped": ([C.POINTER(vp), i, _u8p, sz, _u8p, sz, i, i], i),
+        "srcnn_model_color_striped_dev": ([C.POINTER(vp), i, C.POINTER(vp), sz, C.POINTER(vp), sz, i, i], i),
+        "srcnn_model_rows_f32_dev": ([vp, vp, sz, sz, i, vp, sz, sz, i, i, i, i, i], i),
+        "srcnn_model_rows_halo_f32_dev": ([vp, vp, sz, sz, i, i, vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i], i),
+        "srcnn_model_striped_f32": ([C.POINTER(vp), i, _f32p, sz, sz, _f32p, sz, sz, i, i], i),
+        "srcnn_model_striped_f32_dev": ([C.POINTER(vp), i, C.POINTER(vp), sz, sz, C.POINTER(vp), sz, sz, i, i], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
@@ -205,6 +214,8 @@ ABI_SYMBOLS = (
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
+    "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
+    "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
 )
 
 
@@ -813,6 +824,47 @@ class Context:
                                                         d_halo_bot or None, halo_stride, d_dst, dst_stride, dst_row0, width,
                                                         height, row_begin, row_end, d_preclamp or None))
 
+    # -- row stripes of a colour model (packed 3-byte pixels, strides in bytes) and of float planes (strides in floats) --------
+    def model_color_rows_dev(self, d_src, src_stride, src_row0, d_dst, dst_stride, dst_row0, width, height, row_begin, row_end,
+                             d_preclamp=0):
+        """Output rows [row_begin, row_end) of a width x height image of packed 3-byte pixels with what forward_color_dev runs
+        for the loaded colour model; d_src starts at image row src_row0 and holds the rows within model_halo_rows() of the
+        range.  Strides in bytes (>= 3 * width)."""
+        _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0, row=3 * width)
+        self._check(self._lib.srcnn_model_color_rows_dev(self._h, d_src, src_stride, src_row0, d_dst, dst_stride, dst_row0, width,
+                                                         height, row_begin, row_end, d_preclamp or None))
+
+    def model_color_rows_halo_dev(self, d_src, src_stride, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride,
+                                  d_dst, dst_stride, dst_row0, width, height, row_begin, row_end, d_preclamp=0):
+        """The same stripe with its model_halo_rows() halo rows either side in buffers of their own (0 / None = no rows on
+        that side); the pointers may point into a neighbour's stripe."""
+        _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0, row=3 * width)
+        _halo_args(height, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, 3 * width)
+        self._check(self._lib.srcnn_model_color_rows_halo_dev(self._h, d_src, src_stride, src_row0, src_rows, d_halo_top or None,
+                                                              d_halo_bot or None, halo_stride, d_dst, dst_stride, dst_row0, width,
+                                                              height, row_begin, row_end, d_preclamp or None))
+
+    def model_rows_f32_dev(self, d_src, src_stride, src_ch_pitch, src_row0, d_dst, dst_stride, dst_ch_pitch, dst_row0,
+                           width, height, row_begin, row_end):
+        """Output rows [row_begin, row_end) of a width x height image of float32 planes (1 or 3 by the loaded model) with what
+        forward_f32_dev runs; strides and channel pitches in floats, the pitches ignored for one channel."""
+        _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0)
+        _pitch_args(src_ch_pitch, dst_ch_pitch)
+        self._check(self._lib.srcnn_model_rows_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_row0, d_dst, dst_stride,
+                                                       dst_ch_pitch, dst_row0, width, height, row_begin, row_end))
+
+    def model_rows_halo_f32_dev(self, d_src, src_stride, src_ch_pitch, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride,
+                                halo_ch_pitch, d_dst, dst_stride, dst_ch_pitch, dst_row0, width, height, row_begin, row_end):
+        """The same stripe with its halo rows in buffers of their own, which have a row stride and a channel pitch of their own
+        (0 / None = no rows on that side); the pointers may point into a neighbour's stripe."""
+        _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0)
+        _halo_args(height, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, width)
+        _pitch_args(src_ch_pitch, dst_ch_pitch, halo_ch_pitch)
+        self._check(self._lib.srcnn_model_rows_halo_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_row0, src_rows,
+                                                            d_halo_top or None, d_halo_bot or None, halo_stride, halo_ch_pitch,
+                                                            d_dst, dst_stride, dst_ch_pitch, dst_row0, width, height, row_begin,
+                                                            row_end))
+
     def forward_y_unfused_dev(self, d_src, src_stride, src_frame_pitch, d_dst, dst_stride,
                               dst_frame_pitch, width, height, n_frames, d_work):
         self._check(self._lib.srcnn_forward_y_unfused_dev(self._h, d_src, src_stride, src_frame_pitch,
@@ -989,16 +1041,93 @@ def forward_y_striped_dev(ctxs: Sequence[Context], d_stripes, stripe_stride, d_o
                                                                          out_stride, width, height))
 
 
-def _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0):
-    """The geometry of a stripe call, checked before the library is entered."""
+def _stripe_args(width, height, row_begin, row_end, src_stride, dst_stride, src_row0, dst_row0, row=None):
+    """The geometry of a stripe call, checked before the library is entered.  row: elements of a row (3 * width for packed
+    3-byte pixels), the width by default."""
     if width <= 0 or height <= 0:
         raise ValueError(f"empty image {width} x {height}")
     if not 0 <= row_begin < row_end <= height:
         raise ValueError(f"rows [{row_begin}, {row_end}) are not a row range of a {height}-row image")
-    if src_stride < width or dst_stride < width:
-        raise ValueError(f"row strides {src_stride} / {dst_stride} are less than the width {width}")
+    row = width if row is None else row
+    if src_stride < row or dst_stride < row:
+        raise ValueError(f"row strides {src_stride} / {dst_stride} are less than the row of {row} elements")
     if not 0 <= src_row0 <= row_begin or not 0 <= dst_row0 <= row_begin:
         raise ValueError(f"src_row0 {src_row0} / dst_row0 {dst_row0} must lie in [0, row_begin = {row_begin}]")
+
+
+def _halo_args(height, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, row):
+    if src_rows <= 0 or src_row0 + src_rows > height:
+        raise ValueError(f"src rows [{src_row0}, {src_row0 + src_rows}) are not rows of a {height}-row image")
+    if (d_halo_top or d_halo_bot) and halo_stride < row:
+        raise ValueError(f"halo_stride {halo_stride} is less than the row of {row} elements")
+
+
+def _pitch_args(*pitches):
+    if any(p < 0 for p in pitches):
+        raise ValueError(f"channel pitches {pitches} must not be negative")
+
+
+def _striped_dev_args(ctxs, d_stripes, stripe_stride, d_out, out_stride, width, height, row):
+    handles, n = _ctx_array(ctxs), len(ctxs)
+    if len(d_stripes) != n or len(d_out) != n:
+        raise ValueError(f"need one input and one output stripe per context: {len(d_stripes)} / {len(d_out)} for {n} contexts")
+    if width <= 0 or height <= 0 or stripe_stride < row or out_stride < row:
+        raise ValueError(f"bad geometry: {width} x {height}, strides {stripe_stride} / {out_stride} for rows of {row} elements")
+    return handles, n, (C.c_void_p * n)(*[int(p) for p in d_stripes]), (C.c_void_p * n)(*[int(p) for p in d_out])
+
+
+def model_color_striped(ctxs: Sequence[Context], img, dst=None):
+    """ONE host image (H, W, 3) of packed 3-byte pixels row-striped over several contexts / GPUs that hold the same colour model
+    (srcnn_model_color_striped); bit-identical to forward_color."""
+    handles = _ctx_array(ctxs)
+    img, ss = _image(img, "img")
+    h, w, _ = img.shape
+    if dst is None:
+        dst = np.empty((h, w, 3), np.uint8)
+    dst, ds = _image(dst, "dst", True)
+    _same_shape("dst", dst.shape, img.shape)
+    ctxs[0]._check_multi(ctxs, load_library().srcnn_model_color_striped(handles, len(ctxs), img.ctypes.data_as(_u8p), ss,
+                                                                       dst.ctypes.data_as(_u8p), ds, w, h))
+    return dst
+
+
+def model_color_striped_dev(ctxs: Sequence[Context], d_stripes, stripe_stride, d_out, out_stride, width, height):
+    """Device-resident striped step of the same: d_stripes[k] / d_out[k] are integer device addresses on ctxs[k]'s GPU of that
+    context's rows stripe_rows(height, len(ctxs), k), strides in bytes (>= 3 * width).  Asynchronous; the caller orders it."""
+    handles, n, ins, outs = _striped_dev_args(ctxs, d_stripes, stripe_stride, d_out, out_stride, width, height, 3 * width)
+    ctxs[0]._check_multi(ctxs, load_library().srcnn_model_color_striped_dev(handles, n, ins, stripe_stride, outs, out_stride,
+                                                                           width, height))
+
+
+def model_striped_f32(ctxs: Sequence[Context], x, out=None):
+    """ONE host image of float32 planes, (H, W) or (C, H, W) with any row / channel stride, row-striped over several contexts /
+    GPUs that hold the same model (srcnn_model_striped_f32); bit-identical to forward_f32."""
+    handles = _ctx_array(ctxs)
+    if isinstance(x, np.ndarray) and x.ndim == 4:
+        raise TypeError("x: expected one image, (H, W) or (C, H, W)")
+    x4 = _f32_planes(x, "x")
+    if out is None:
+        out = np.empty(x.shape, np.float32)
+    o4 = _f32_planes(out, "out", True)
+    _same_shape("out", out.shape, x.shape)
+    _, c, h, w = x4.shape
+    if c not in (1, 3):
+        raise ValueError(f"x: shape {tuple(x.shape)}: a model has 1 channel or 3")
+    stride = lambda a4: a4.strides[2] // 4 if h > 1 else w
+    ctxs[0]._check_multi(ctxs, load_library().srcnn_model_striped_f32(handles, len(ctxs), _fp(x4[0]), stride(x4),
+                                                                     x4.strides[1] // 4 if c > 1 else 0, _fp(o4[0]), stride(o4),
+                                                                     o4.strides[1] // 4 if c > 1 else 0, w, h))
+    return out
+
+
+def model_striped_f32_dev(ctxs: Sequence[Context], d_stripes, stripe_stride, stripe_ch_pitch, d_out, out_stride, out_ch_pitch,
+                          width, height):
+    """Device-resident striped step of the same: strides and channel pitches in floats, one stride and one pitch for all the
+    stripes (and all the outputs).  Asynchronous; the caller orders it."""
+    handles, n, ins, outs = _striped_dev_args(ctxs, d_stripes, stripe_stride, d_out, out_stride, width, height, width)
+    _pitch_args(stripe_ch_pitch, out_ch_pitch)
+    ctxs[0]._check_multi(ctxs, load_library().srcnn_model_striped_f32_dev(handles, n, ins, stripe_stride, stripe_ch_pitch, outs,
+                                                                         out_stride, out_ch_pitch, width, height))
 
 
 def model_striped(ctxs: Sequence[Context], src, dst=None):

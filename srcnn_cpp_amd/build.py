@@ -54,6 +54,9 @@ UNITS = [
     # row stripes of the banded models (srcnn_model_rows*_dev, srcnn_model_striped*): the stripe forms of that file's layer-1
     # template, again a unit of their own
     ("srcnn_spatial_rows.hip", []),
+    # ... and of the colour models and the float planes (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev and their
+    # striped calls): the stripe forms of the other three inputs of layer 1, once more a unit of their own
+    ("srcnn_spatial_rows_cf.hip", []),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),

@@ -392,19 +392,21 @@ struct BandedPlanes {
     void *dst = nullptr;
     size_t dst_stride = 0, dst_ch_pitch = 0, dst_frame_pitch = 0;
     float *pre = nullptr;
-    // A row stripe (srcnn_model_rows*_dev; 1-channel u8 models, one frame): output rows [row_begin, row_end) of the width x height
-    // image.  src starts at image row src_row0, dst and pre at image row dst_row0.  With halo_top / halo_bot the R = 6 + (f2 - 1) / 2
-    // rows above src_row0 / from src_row0 + src_rows on come from those buffers (row stride halo_stride); null: src holds them.
+    // A row stripe (srcnn_model_rows*_dev, srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev; one frame): output rows
+    // [row_begin, row_end) of the width x height image.  src starts at image row src_row0, dst and pre at image row dst_row0.  With
+    // halo_top / halo_bot the R = 6 + (f2 - 1) / 2 rows above src_row0 / from src_row0 + src_rows on come from those buffers (row
+    // stride halo_stride, and for float planes channel pitch halo_ch_pitch, in elements as src_stride); null: src holds them.
     bool rows = false;
     int row_begin = 0, row_end = 0, src_row0 = 0, src_rows = 0, dst_row0 = 0;
-    const uint8_t *halo_top = nullptr, *halo_bot = nullptr;
-    size_t halo_stride = 0;
+    const void *halo_top = nullptr, *halo_bot = nullptr;
+    size_t halo_stride = 0, halo_ch_pitch = 0;
 };
 int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, int n_frames);
 int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_step, size_t ch_step, size_t src_frame_pitch,
                    uint8_t *dst, size_t dst_stride, size_t dst_frame_pitch, int width, int height, int n_frames, float *pre);
-// the gate of the stripe entry points (srcnn_model_rows*_dev, srcnn_model_striped*): SRCNN_OK, or SRCNN_ERR_STATE and the reason
-int model_rows_refusal(srcnn_ctx *c);
+// the gate of the stripe entry points: SRCNN_OK, or SRCNN_ERR_STATE and the reason.  kind: what the entry point takes
+enum StripeKind { STRIPE_Y = 0, STRIPE_COLOR = 1, STRIPE_F32 = 2 };    // one byte channel, 3-byte pixels, 1 or 3 float planes
+int model_rows_refusal(srcnn_ctx *c, StripeKind kind = STRIPE_Y);
 constexpr size_t kSpatialWorkBytes = (size_t)512 << 20;     // bound of the two band maps (include/srcnn_amd.h, srcnn_set_model)
 extern const char *const kNoModel;
 

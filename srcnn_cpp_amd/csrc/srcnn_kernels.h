@@ -317,6 +317,24 @@ struct L1Rows {
 hipError_t launch_spatial_l1_rows(bool zero, bool split, const uint8_t *src, long sstride, const L1Rows &rows, int W, int H, int m0,
                                   int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
     __attribute__((weak));
+// Row stripes of a colour model and of float planes (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev,
+// srcnn_model_color_striped*, srcnn_model_striped_f32*; srcnn_spatial_rows_cf.hip).  L1RowsCF is L1Rows for the three other
+// inputs of layer 1, every stride and pitch in ELEMENTS of the input (bytes, or floats):
+//   3 byte channels   a row holds interleaved pixels (byte c of pixel x at row[3 x + c]); the channel pitches are unused
+//   1 float plane     a plain plane; the channel pitches are unused
+//   3 float planes    channel c of a row of src at + c * src_ch_pitch, of a row of a halo buffer at + c * halo_ch_pitch: a
+//                     halo buffer has a pitch of its own, so that a neighbour's stripe can be read where it lies
+// launch_spatial_l1_rows_cf is launch_spatial_l1 / launch_spatial_l1h / launch_spatial_l1f (f32: float planes; split: the f16
+// pair map) with rows from there; it reads no input row outside [max(0, m0 - 4), min(H, m1 + 4)) and no column beyond W - 1.
+// Same arithmetic as the whole-image forms, same order.  A WEAK declaration, as the five above.
+struct L1RowsCF {
+    const void *top, *bot;
+    long halo_stride, halo_ch_pitch, src_ch_pitch;
+    int src_row0, src_row1, halo_rows;
+};
+hipError_t launch_spatial_l1_rows_cf(int channels, bool zero, bool split, bool f32, const void *src, long sstride, const L1RowsCF &rows,
+                                     int W, int H, int m0, int m1, const float *frag, void *map, long mpitch, float scale,
+                                     hipStream_t st) __attribute__((weak));
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

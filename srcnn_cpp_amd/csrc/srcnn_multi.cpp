@@ -1,5 +1,6 @@
 // srcnn_multi.cpp -- several GPUs driven from ONE host process: a row-striped plane whose stripes read their
-// neighbours' 6 edge rows (6 + (f2 - 1) / 2 for a model on the banded path: srcnn_model_striped*) over xGMI (or copies of them),
+// neighbours' 6 edge rows (6 + (f2 - 1) / 2 for a model on the banded path: srcnn_model_striped* and its colour and float
+// forms) over xGMI (or copies of them),
 // frame ranges over contexts; one persistent host thread per context.
 #include "srcnn_ctx.h"
 
@@ -99,19 +100,28 @@ int stripe_setup(srcnn_ctx *const *ctxs, int n_ctx, int k)
 
 // A link without peer access: copies of the neighbours' `rows` edge rows into the context's next halo set (kHaloSets sets in
 // turn), on the halo stream; the context's stream waits for them.  The launch that reads the set is followed by halo_set_read().
+// Rows of `width` bytes; `planes` channel planes (float planes of a colour model), ch_pitch bytes apart in the neighbours' stripes
+// and rows * width bytes apart in the set.
 int stage_halo_rows(srcnn_ctx *c, const srcnn_ctx *above, const uint8_t *nb_top, const srcnn_ctx *below, const uint8_t *nb_bot,
-                    size_t stripe_stride, int width, int rows, int *set_out, uint8_t **top, uint8_t **bot)
+                    size_t stripe_stride, int width, int rows, int *set_out, uint8_t **top, uint8_t **bot, int planes = 1,
+                    size_t ch_pitch = 0)
 {
     int rc;
     const int set = (int)(c->stripe_steps++ % srcnn_ctx::kHaloSets);
-    const size_t halo_bytes = (size_t)rows * width;
+    const size_t plane_bytes = (size_t)rows * width, halo_bytes = planes * plane_bytes;
     if ((rc = reserve(c, c->halo_top[set], halo_bytes))) return rc;
     if ((rc = reserve(c, c->halo_bot[set], halo_bytes))) return rc;
     *top = static_cast<uint8_t *>(c->halo_top[set].p);
     *bot = static_cast<uint8_t *>(c->halo_bot[set].p);
     if (c->halo_free_set[set]) HIP_TRY(c, hipStreamWaitEvent(c->halo_stream, c->halo_free[set], 0));
-    if (nb_top) HIP_TRY(c, copy_rows_between(c, *top, width, above, nb_top, stripe_stride, width, rows, c->halo_stream));
-    if (nb_bot) HIP_TRY(c, copy_rows_between(c, *bot, width, below, nb_bot, stripe_stride, width, rows, c->halo_stream));
+    for (int ch = 0; ch < planes; ++ch) {
+        if (nb_top)
+            HIP_TRY(c, copy_rows_between(c, *top + ch * plane_bytes, width, above, nb_top + ch * ch_pitch, stripe_stride, width, rows,
+                                         c->halo_stream));
+        if (nb_bot)
+            HIP_TRY(c, copy_rows_between(c, *bot + ch * plane_bytes, width, below, nb_bot + ch * ch_pitch, stripe_stride, width, rows,
+                                         c->halo_stream));
+    }
     HIP_TRY(c, hipEventRecord(c->halo_ready, c->halo_stream));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->halo_ready, 0));
     *set_out = set;
@@ -218,30 +228,71 @@ int striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const uint8_t *const 
     return SRCNN_OK;
 }
 
-// The same set for srcnn_model_striped*: every context holds a whole 1-channel model that its mode and padding can run, and all
-// of them the same kind -- one halo height, and either all on the banded path or all on the strip path
-int check_model_ctx_set(srcnn_ctx *const *ctxs, int n_ctx)
+// What the stripes of a srcnn_model_striped* call hold: one byte channel, interleaved 3-byte pixels, or `planes` float planes
+struct StripeFmt {
+    StripeKind kind;
+    int planes;          // channel planes (the bytes of a colour pixel share a row: 1)
+    size_t es;           // bytes per element
+    int row_elems(int width) const { return kind == STRIPE_COLOR ? 3 * width : width; }
+};
+const char *striped_name(StripeKind kind)
+{
+    return kind == STRIPE_F32 ? "srcnn_model_striped_f32" : kind == STRIPE_COLOR ? "srcnn_model_color_striped" : "srcnn_model_striped";
+}
+
+// The same set for srcnn_model_striped* and its colour and float forms: every context holds a whole model of the call's kind that
+// its mode and padding can run, and all of them the same -- one halo height, one path (banded or strip), and for the colour and
+// float forms the same weights, mode, padding and (floats) input range
+int check_model_ctx_set(srcnn_ctx *const *ctxs, int n_ctx, StripeKind kind = STRIPE_Y)
 {
     if (!ctxs || n_ctx <= 0) return SRCNN_ERR_INVALID;
     for (int k = 0; k < n_ctx; ++k) {
         if (!ctxs[k]) return SRCNN_ERR_INVALID;
         if (!has_model(ctxs[k])) return fail(ctxs[k], SRCNN_ERR_STATE, "%s", kNoModel);
-        if (int rc = model_rows_refusal(ctxs[k])) return rc;
+        if (int rc = model_rows_refusal(ctxs[k], kind)) return rc;
         for (int j = 0; j < k; ++j)
             if (ctxs[j] == ctxs[k]) return fail(ctxs[k], SRCNN_ERR_INVALID, "the same context appears twice");
-        if (ctxs[k]->f2 != ctxs[0]->f2 || luma_path_ok(ctxs[k]) != luma_path_ok(ctxs[0]))
-            return fail(ctxs[k], SRCNN_ERR_INVALID, "srcnn_model_striped: the contexts hold different models, modes or paddings "
-                                                    "(context %d: 9-%d-5, context 0: 9-%d-5)", k, ctxs[k]->f2, ctxs[0]->f2);
+        const srcnn_ctx *a = ctxs[k], *b = ctxs[0];
+        bool same = a->f2 == b->f2 && luma_path_ok(a) == luma_path_ok(b);
+        if (kind != STRIPE_Y)
+            same = same && a->channels == b->channels && a->mode == b->mode && a->padding == b->padding &&
+                   (kind != STRIPE_F32 || a->input_range == b->input_range) && a->host_raw == b->host_raw &&
+                   // (a 9-1-5 model is packed when a call first runs it on the banded path: host_raw holds all of it)
+                   (a->sp_f2 != a->f2 || b->sp_f2 != b->f2 || (a->sp_w2 == b->sp_w2 && std::equal(a->sp_b3, a->sp_b3 + a->channels, b->sp_b3) &&
+                                          std::equal(a->sp_l1_sum, a->sp_l1_sum + 64, b->sp_l1_sum) &&
+                                          std::equal(a->sp_l1_absb, a->sp_l1_absb + 64, b->sp_l1_absb)));
+        if (!same)
+            return fail(ctxs[k], SRCNN_ERR_INVALID, "%s: the contexts hold different models, modes or paddings "
+                                                    "(context %d: 9-%d-5, context 0: 9-%d-5)", striped_name(kind), k, ctxs[k]->f2, ctxs[0]->f2);
     }
     return SRCNN_OK;
 }
 
-// One context's part of srcnn_model_striped* for a model on the banded path: ONE call of srcnn_model_rows_halo_dev, i.e. one
-// layer-1 launch per row band whose row select picks the buffer an input row lives in.  With neighbours on the same device or
-// peer access the halo "buffers" are the neighbours' stripes, read where they lie; a link that refuses peer access gets copies
-// of the R rows either side into this context's halo sets (stage_halo_rows()), as striped_step() above.
-int model_striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const uint8_t *const *d_stripes, size_t stripe_stride,
-                       uint8_t *const *d_out, size_t out_stride, int width, int height)
+// the stripe call of a kind (srcnn_model_rows_halo_dev and its colour and float forms; no halo pointer: the plain form)
+int stripe_rows_call(srcnn_ctx *c, const StripeFmt &fmt, const uint8_t *src, size_t src_stride, size_t src_ch_pitch, int src_row0,
+                     int src_rows, const uint8_t *top, const uint8_t *bot, size_t halo_stride, size_t halo_ch_pitch, uint8_t *dst,
+                     size_t dst_stride, size_t dst_ch_pitch, int dst_row0, int width, int height, int r0, int r1)
+{
+    if (fmt.kind == STRIPE_F32)
+        return srcnn_model_rows_halo_f32_dev(c, reinterpret_cast<const float *>(src), src_stride, src_ch_pitch, src_row0, src_rows,
+                                             reinterpret_cast<const float *>(top), reinterpret_cast<const float *>(bot), halo_stride,
+                                             halo_ch_pitch, reinterpret_cast<float *>(dst), dst_stride, dst_ch_pitch, dst_row0, width,
+                                             height, r0, r1);
+    if (fmt.kind == STRIPE_COLOR)
+        return srcnn_model_color_rows_halo_dev(c, src, src_stride, src_row0, src_rows, top, bot, halo_stride, dst, dst_stride, dst_row0,
+                                               width, height, r0, r1, nullptr);
+    return srcnn_model_rows_halo_dev(c, src, src_stride, src_row0, src_rows, top, bot, halo_stride, dst, dst_stride, dst_row0, width,
+                                     height, r0, r1, nullptr);
+}
+
+// One context's part of srcnn_model_striped* (and of its colour and float forms) for a model on the banded path: ONE call of the
+// kind's _rows_halo_dev, i.e. one layer-1 launch per row band whose row select picks the buffer an input row lives in.  With
+// neighbours on the same device or peer access the halo "buffers" are the neighbours' stripes, read where they lie (float
+// planes: with the stripes' channel pitch); a link that refuses peer access gets copies of the R rows either side, per channel,
+// into this context's halo sets (stage_halo_rows()), as striped_step() above.  Strides and pitches in elements.
+int model_striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const StripeFmt &fmt, const uint8_t *const *d_stripes,
+                       size_t stripe_stride, size_t stripe_ch_pitch, uint8_t *const *d_out, size_t out_stride, size_t out_ch_pitch,
+                       int width, int height)
 {
     srcnn_ctx *c = ctxs[k];
     BIND(c);
@@ -249,22 +300,26 @@ int model_striped_step(srcnn_ctx *const *ctxs, int n_ctx, int k, const uint8_t *
     srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
     const bool has_top = k > 0, has_bot = k < n_ctx - 1;
     if (!has_top && !has_bot)
-        return srcnn_model_rows_dev(c, d_stripes[k], stripe_stride, 0, d_out[k], out_stride, 0, width, height, 0, height, nullptr);
+        return stripe_rows_call(c, fmt, d_stripes[k], stripe_stride, stripe_ch_pitch, 0, height, nullptr, nullptr, stripe_stride, 0,
+                                d_out[k], out_stride, out_ch_pitch, 0, width, height, 0, height);
     if (has_top) srcnn_stripe_rows(height, n_ctx, k - 1, &a0, &a1);
     if ((rc = stripe_setup(ctxs, n_ctx, k))) return rc;
     const int R = srcnn_model_halo_rows(c);
-    const uint8_t *nb_top = has_top ? d_stripes[k - 1] + (size_t)(a1 - a0 - R) * stripe_stride : nullptr;
+    const uint8_t *nb_top = has_top ? d_stripes[k - 1] + fmt.es * (size_t)(a1 - a0 - R) * stripe_stride : nullptr;
     const uint8_t *nb_bot = has_bot ? d_stripes[k + 1] : nullptr;
     if (c->halo_transport != 3)
-        return srcnn_model_rows_halo_dev(c, d_stripes[k], stripe_stride, r0, r1 - r0, nb_top, nb_bot, stripe_stride, d_out[k],
-                                         out_stride, r0, width, height, r0, r1, nullptr);
+        return stripe_rows_call(c, fmt, d_stripes[k], stripe_stride, stripe_ch_pitch, r0, r1 - r0, nb_top, nb_bot, stripe_stride,
+                                stripe_ch_pitch, d_out[k], out_stride, out_ch_pitch, r0, width, height, r0, r1);
     int set = 0;
     uint8_t *top = nullptr, *bot = nullptr;
-    if ((rc = stage_halo_rows(c, has_top ? ctxs[k - 1] : nullptr, nb_top, has_bot ? ctxs[k + 1] : nullptr, nb_bot, stripe_stride, width,
-                              R, &set, &top, &bot)))
+    const int row_elems = fmt.row_elems(width);
+    if ((rc = stage_halo_rows(c, has_top ? ctxs[k - 1] : nullptr, nb_top, has_bot ? ctxs[k + 1] : nullptr, nb_bot,
+                              fmt.es * stripe_stride, (int)(fmt.es * row_elems), R, &set, &top, &bot, fmt.planes,
+                              fmt.es * stripe_ch_pitch)))
         return rc;
-    if ((rc = srcnn_model_rows_halo_dev(c, d_stripes[k], stripe_stride, r0, r1 - r0, has_top ? top : nullptr, has_bot ? bot : nullptr,
-                                        (size_t)width, d_out[k], out_stride, r0, width, height, r0, r1, nullptr)))
+    if ((rc = stripe_rows_call(c, fmt, d_stripes[k], stripe_stride, stripe_ch_pitch, r0, r1 - r0, has_top ? top : nullptr,
+                               has_bot ? bot : nullptr, (size_t)row_elems, (size_t)R * row_elems, d_out[k], out_stride, out_ch_pitch,
+                               r0, width, height, r0, r1)))
         return rc;
     return halo_set_read(c, set);
 }
@@ -288,13 +343,18 @@ int run_per_context(srcnn_ctx *const *ctxs, int n_ctx, Fn fn, Abort on_incomplet
     return ctxs[0]->pool->run(n_ctx, fn, SRCNN_ERR_NOMEM, on_incomplete);
 }
 
-using StripeStep = int (*)(srcnn_ctx *const *, int, int, const uint8_t *const *, size_t, uint8_t *const *, size_t, int, int);
-
-// A host plane striped over the contexts, `step` being one context's part of the device-resident step (striped_step,
-// model_striped_step)
-int striped_host(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int width,
-                 int height, StripeStep step)
+// A host image striped over the contexts: every device receives ITS rows only, channel plane by channel plane, runs
+// step(k, stripes, stripe stride, stripe channel pitch, outputs) -- one context's part of the device-resident step (striped_step,
+// model_striped_step) -- and returns its rows.  Strides and pitches in elements of fmt.es bytes.  The device stripes are packed
+// rows; their channel pitch is that of the tallest stripe, one pitch for all contexts as the device-resident calls take it.
+template <typename Step>
+int striped_host(srcnn_ctx *const *ctxs, int n_ctx, const StripeFmt &fmt, const void *src_, size_t src_stride, size_t src_ch_pitch,
+                 void *dst_, size_t dst_stride, size_t dst_ch_pitch, int width, int height, Step step)
 {
+    const uint8_t *src = static_cast<const uint8_t *>(src_);
+    uint8_t *dst = static_cast<uint8_t *>(dst_);
+    const size_t es = fmt.es, row = (size_t)fmt.row_elems(width), row_bytes = es * row;
+    const size_t ch_pitch = (size_t)((height + n_ctx - 1) / n_ctx) * row;
     std::vector<const uint8_t *> d_in((size_t)n_ctx);
     std::vector<uint8_t *> d_res((size_t)n_ctx);
     // phase 1: every device receives ITS rows only (the halo rows then travel device to device)
@@ -303,11 +363,13 @@ int striped_host(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t s
         BIND(c);
         int r, r0, r1;
         srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
-        const size_t n = (size_t)(r1 - r0) * width;
+        const size_t n = es * ((size_t)(fmt.planes - 1) * ch_pitch + (size_t)(r1 - r0) * row);
         if ((r = reserve(c, c->in_u8, n))) return r;
         if ((r = reserve(c, c->out_u8, n))) return r;
-        HIP_TRY(c, hipMemcpy2DAsync(c->in_u8.p, width, src + (size_t)r0 * src_stride, src_stride, width, r1 - r0,
-                                    hipMemcpyHostToDevice, c->stream));
+        for (int ch = 0; ch < fmt.planes; ++ch)
+            HIP_TRY(c, hipMemcpy2DAsync(static_cast<uint8_t *>(c->in_u8.p) + es * ch * ch_pitch, row_bytes,
+                                        src + es * (ch * src_ch_pitch + (size_t)r0 * src_stride), es * src_stride, row_bytes, r1 - r0,
+                                        hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         d_in[(size_t)k] = static_cast<const uint8_t *>(c->in_u8.p);
         d_res[(size_t)k] = static_cast<uint8_t *>(c->out_u8.p);
@@ -320,12 +382,55 @@ int striped_host(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t s
         BIND(c);
         int r, r0, r1;
         srcnn_stripe_rows(height, n_ctx, k, &r0, &r1);
-        if ((r = step(ctxs, n_ctx, k, d_in.data(), width, d_res.data(), width, width, height))) return r;
-        HIP_TRY(c, hipMemcpy2DAsync(dst + (size_t)r0 * dst_stride, dst_stride, c->out_u8.p, width, width, r1 - r0,
-                                    hipMemcpyDeviceToHost, c->stream));
+        if ((r = step(k, d_in.data(), row, ch_pitch, d_res.data()))) return r;
+        for (int ch = 0; ch < fmt.planes; ++ch)
+            HIP_TRY(c, hipMemcpy2DAsync(dst + es * (ch * dst_ch_pitch + (size_t)r0 * dst_stride), es * dst_stride,
+                                        static_cast<uint8_t *>(c->out_u8.p) + es * ch * ch_pitch, row_bytes, row_bytes, r1 - r0,
+                                        hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return SRCNN_OK;
     });
+}
+
+constexpr StripeFmt kFmtY{STRIPE_Y, 1, 1}, kFmtColor{STRIPE_COLOR, 1, 1};
+
+// the checks the device-resident striped calls of every kind share (strides in elements), then one step per context
+int model_striped_dev(srcnn_ctx *const *ctxs, int n_ctx, const StripeFmt &fmt, const char *what, const void *const *d_stripes,
+                      size_t stripe_stride, size_t stripe_ch_pitch, void *const *d_out, size_t out_stride, size_t out_ch_pitch,
+                      int width, int height)
+{
+    const int R = srcnn_model_halo_rows(ctxs[0]);
+    constexpr size_t kMaxPitch = (size_t)1 << 40;
+    if (!d_stripes || !d_out || width <= 0 || height <= 0 || width > (1 << 28) || stripe_stride < (size_t)fmt.row_elems(width) ||
+        out_stride < (size_t)fmt.row_elems(width) || stripe_ch_pitch >= kMaxPitch || out_ch_pitch >= kMaxPitch)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    if (n_ctx > 1 && height / n_ctx < R)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "%s: %d rows over %d contexts leaves stripes thinner than the %d-row "
+                                                "halo of a 9-%d-5 model", what, height, n_ctx, R, ctxs[0]->f2);
+    for (int k = 0; k < n_ctx; ++k)
+        if (!d_stripes[k] || !d_out[k]) return fail(ctxs[0], SRCNN_ERR_INVALID, "%s: null stripe %d", what, k);
+    return run_per_context(ctxs, n_ctx, [&](int k) {
+        return model_striped_step(ctxs, n_ctx, k, fmt, reinterpret_cast<const uint8_t *const *>(d_stripes), stripe_stride,
+                                  stripe_ch_pitch, reinterpret_cast<uint8_t *const *>(d_out), out_stride, out_ch_pitch, width, height);
+    });
+}
+
+// ... and the host forms
+int model_striped_host(srcnn_ctx *const *ctxs, int n_ctx, const StripeFmt &fmt, const char *what, const void *src, size_t src_stride,
+                       size_t src_ch_pitch, void *dst, size_t dst_stride, size_t dst_ch_pitch, int width, int height)
+{
+    const int R = srcnn_model_halo_rows(ctxs[0]);
+    if (width > (1 << 28) || bad_plane(src, src_stride, fmt.row_elems(width), height) ||
+        bad_plane(dst, dst_stride, fmt.row_elems(width), height))
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "%s: bad plane geometry", what);
+    if (n_ctx > 1 && height / n_ctx < R)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "%s: %d rows over %d contexts leaves stripes thinner than the %d-row halo "
+                                                "of a 9-%d-5 model", what, height, n_ctx, R, ctxs[0]->f2);
+    return striped_host(ctxs, n_ctx, fmt, src, src_stride, src_ch_pitch, dst, dst_stride, dst_ch_pitch, width, height,
+                        [&](int k, const uint8_t *const *d_in, size_t in_stride, size_t ch_pitch, uint8_t *const *d_res) {
+                            return model_striped_step(ctxs, n_ctx, k, fmt, d_in, in_stride, ch_pitch, d_res, in_stride, ch_pitch, width,
+                                                      height);
+                        });
 }
 
 }  // namespace
@@ -360,7 +465,10 @@ int srcnn_forward_y_striped(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *sr
         return fail(ctxs[0], SRCNN_ERR_INVALID, "forward_y_striped: bad plane geometry");
     if (n_ctx > 1 && height / n_ctx < kHalo)
         return fail(ctxs[0], SRCNN_ERR_INVALID, "forward_y_striped: stripes thinner than the %d-row halo", kHalo);
-    return striped_host(ctxs, n_ctx, src, src_stride, dst, dst_stride, width, height, striped_step);
+    return striped_host(ctxs, n_ctx, kFmtY, src, src_stride, 0, dst, dst_stride, 0, width, height,
+                        [&](int k, const uint8_t *const *d_in, size_t in_stride, size_t, uint8_t *const *d_res) {
+                            return striped_step(ctxs, n_ctx, k, d_in, in_stride, d_res, in_stride, width, height);
+                        });
 }
 
 int srcnn_model_striped_dev(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *const *d_stripes, size_t stripe_stride,
@@ -370,17 +478,8 @@ int srcnn_model_striped_dev(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *co
     if (rc) return rc;
     // the strip path runs this model: its striped step, 6 halo rows, the same bytes
     if (luma_path_ok(ctxs[0])) return srcnn_forward_y_striped_dev(ctxs, n_ctx, d_stripes, stripe_stride, d_out, out_stride, width, height);
-    const int R = srcnn_model_halo_rows(ctxs[0]);
-    if (!d_stripes || !d_out || width <= 0 || height <= 0 || stripe_stride < (size_t)width || out_stride < (size_t)width)
-        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_dev: bad arguments");
-    if (n_ctx > 1 && height / n_ctx < R)
-        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_dev: %d rows over %d contexts leaves stripes thinner than the %d-row "
-                                                "halo of a 9-%d-5 model", height, n_ctx, R, ctxs[0]->f2);
-    for (int k = 0; k < n_ctx; ++k)
-        if (!d_stripes[k] || !d_out[k]) return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_dev: null stripe %d", k);
-    return run_per_context(ctxs, n_ctx, [&](int k) {
-        return model_striped_step(ctxs, n_ctx, k, d_stripes, stripe_stride, d_out, out_stride, width, height);
-    });
+    return model_striped_dev(ctxs, n_ctx, kFmtY, "model_striped_dev", reinterpret_cast<const void *const *>(d_stripes), stripe_stride, 0,
+                             reinterpret_cast<void *const *>(d_out), out_stride, 0, width, height);
 }
 
 int srcnn_model_striped(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride,
@@ -389,13 +488,51 @@ int srcnn_model_striped(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, s
     int rc = check_model_ctx_set(ctxs, n_ctx);
     if (rc) return rc;
     if (luma_path_ok(ctxs[0])) return srcnn_forward_y_striped(ctxs, n_ctx, src, src_stride, dst, dst_stride, width, height);
-    const int R = srcnn_model_halo_rows(ctxs[0]);
-    if (bad_plane(src, src_stride, width, height) || bad_plane(dst, dst_stride, width, height))
-        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped: bad plane geometry");
-    if (n_ctx > 1 && height / n_ctx < R)
-        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped: %d rows over %d contexts leaves stripes thinner than the %d-row halo "
-                                                "of a 9-%d-5 model", height, n_ctx, R, ctxs[0]->f2);
-    return striped_host(ctxs, n_ctx, src, src_stride, dst, dst_stride, width, height, model_striped_step);
+    return model_striped_host(ctxs, n_ctx, kFmtY, "model_striped", src, src_stride, 0, dst, dst_stride, 0, width, height);
+}
+
+/* ---- a colour model, and float planes, striped over the contexts (include/srcnn_amd.h) ---- */
+
+int srcnn_model_color_striped_dev(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *const *d_stripes, size_t stripe_stride,
+                                  uint8_t *const *d_out, size_t out_stride, int width, int height)
+{
+    int rc = check_model_ctx_set(ctxs, n_ctx, STRIPE_COLOR);
+    if (rc) return rc;
+    return model_striped_dev(ctxs, n_ctx, kFmtColor, "model_color_striped_dev", reinterpret_cast<const void *const *>(d_stripes),
+                             stripe_stride, 0, reinterpret_cast<void *const *>(d_out), out_stride, 0, width, height);
+}
+
+int srcnn_model_color_striped(srcnn_ctx *const *ctxs, int n_ctx, const uint8_t *src, size_t src_stride, uint8_t *dst,
+                              size_t dst_stride, int width, int height)
+{
+    int rc = check_model_ctx_set(ctxs, n_ctx, STRIPE_COLOR);
+    if (rc) return rc;
+    return model_striped_host(ctxs, n_ctx, kFmtColor, "model_color_striped", src, src_stride, 0, dst, dst_stride, 0, width, height);
+}
+
+int srcnn_model_striped_f32_dev(srcnn_ctx *const *ctxs, int n_ctx, const float *const *d_stripes, size_t stripe_stride,
+                                size_t stripe_ch_pitch, float *const *d_out, size_t out_stride, size_t out_ch_pitch, int width,
+                                int height)
+{
+    int rc = check_model_ctx_set(ctxs, n_ctx, STRIPE_F32);
+    if (rc) return rc;
+    const StripeFmt fmt{STRIPE_F32, ctxs[0]->channels, sizeof(float)};
+    return model_striped_dev(ctxs, n_ctx, fmt, "model_striped_f32_dev", reinterpret_cast<const void *const *>(d_stripes), stripe_stride,
+                             stripe_ch_pitch, reinterpret_cast<void *const *>(d_out), out_stride, out_ch_pitch, width, height);
+}
+
+int srcnn_model_striped_f32(srcnn_ctx *const *ctxs, int n_ctx, const float *src, size_t src_stride, size_t src_ch_pitch, float *dst,
+                            size_t dst_stride, size_t dst_ch_pitch, int width, int height)
+{
+    int rc = check_model_ctx_set(ctxs, n_ctx, STRIPE_F32);
+    if (rc) return rc;
+    const StripeFmt fmt{STRIPE_F32, ctxs[0]->channels, sizeof(float)};
+    // the output planes of the host call must not overlap each other (the device stripes are the contexts' own buffers)
+    if (fmt.planes > 1 && height > 0 && width > 0 && dst_ch_pitch < (size_t)(height - 1) * dst_stride + (size_t)width)
+        return fail(ctxs[0], SRCNN_ERR_INVALID, "model_striped_f32: the output planes overlap each other (channel pitch %zu floats)",
+                    dst_ch_pitch);
+    return model_striped_host(ctxs, n_ctx, fmt, "model_striped_f32", src, src_stride, src_ch_pitch, dst, dst_stride, dst_ch_pitch,
+                              width, height);
 }
 
 /* A STREAM of planes, each row-striped over the contexts: a pipeline, not n_planes one-shot calls.  Context k keeps two stripe

@@ -158,11 +158,16 @@ static int upload_table16(srcnn_ctx *c)
 // The one gate of the banded path: SRCNN_OK when it may run the loaded model in the current mode and padding, else
 // SRCNN_ERR_STATE with a message that names what blocks the call.  f32: a call of the float image path (srcnn_forward_f32*),
 // which runs every whole model in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 and nothing else.  rows: a call of the stripe entry
-// points (srcnn_model_rows*_dev, srcnn_model_striped*), which run the whole 1-channel models
+// points (srcnn_model_rows*_dev, srcnn_model_striped* and their colour and float forms), which run the whole models
 static int banded_refusal(srcnn_ctx *c, bool f32 = false, bool rows = false)
 {
     const bool zero = c->padding == SRCNN_PAD_ZERO;
-    if (rows && !launch_spatial_l1_rows) return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows: built without the stripe kernels");
+    if (rows && (f32 || c->channels != 1)) {
+        if (!launch_spatial_l1_rows_cf)
+            return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows: built without the colour / float stripe kernels");
+    } else if (rows && !launch_spatial_l1_rows) {
+        return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows: built without the stripe kernels");
+    }
     if (f32) {
         if (c->mode != SRCNN_MODE_MFMA && c->mode != SRCNN_MODE_BANDED16)
             return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 runs in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only (mode %d has no "
@@ -197,8 +202,16 @@ static int banded_refusal(srcnn_ctx *c, bool f32 = false, bool rows = false)
 
 // The stripe entry points (srcnn_model_rows*_dev, srcnn_model_striped*) run the whole 1-channel models: on the banded path behind
 // banded_refusal(), or, where the strip path runs the model, through that path's stripe calls, which gate themselves
-int model_rows_refusal(srcnn_ctx *c)
+int model_rows_refusal(srcnn_ctx *c, StripeKind kind)
 {
+    // float planes: every whole model, as srcnn_forward_f32 (whose gate names the mode or the per-filter layers)
+    if (kind == STRIPE_F32) return banded_refusal(c, true, true);
+    if (kind == STRIPE_COLOR) {
+        if (c->channels != 3)
+            return fail(c, SRCNN_ERR_STATE, "srcnn_model_color_rows / srcnn_model_color_striped run a colour model only: the context "
+                                            "holds a 1-channel 9-%d-5 model (srcnn_set_model_color loads one)", c->f2);
+        return banded_refusal(c, false, true);
+    }
     if (c->channels != 1)
         return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows / srcnn_model_striped: the context holds a colour model (3 channels, "
                                         "9-%d-5); row stripes run the 1-channel models only", c->f2);
@@ -271,7 +284,8 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     const long mpitch = mrows * width, opitch = orows * width;
     if (bad_pitch((size_t)mpitch) || bad_pitch((size_t)opitch))
         return fail(c, SRCNN_ERR_INVALID, "%s: plane too large for a %s9-%d-5 model",
-                    io.rows ? "model_rows_dev" : io.f32 ? "forward_f32_dev" : C == 1 ? "forward_y_dev" : "forward_color_dev",
+                    io.rows ? (io.f32 ? "model_rows_f32_dev" : C == 1 ? "model_rows_dev" : "model_color_rows_dev")
+                            : io.f32 ? "forward_f32_dev" : C == 1 ? "forward_y_dev" : "forward_color_dev",
                     C == 1 ? "" : "colour ", c->f2);
     if ((rc = reserve(c, c->sp_map64, (size_t)64 * mpitch * sizeof(float)))) return rc;
     if ((rc = reserve(c, c->sp_map32, (size_t)32 * opitch * sizeof(float)))) return rc;
@@ -285,7 +299,12 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     const size_t src_stride = io.src_stride, ch_step = io.ch_step, dst_stride = io.dst_stride;
     const int px_step = io.px_step;
     // a stripe: where the image's rows are for layer 1, and dst / pre addressed by image row from dst_row0
-    const L1Rows l1rows{io.halo_top, io.halo_bot, (long)io.halo_stride, io.src_row0, io.src_row0 + io.src_rows, kHaloRows + r2};
+    const L1Rows l1rows{static_cast<const uint8_t *>(io.halo_top), static_cast<const uint8_t *>(io.halo_bot), (long)io.halo_stride,
+                        io.src_row0, io.src_row0 + io.src_rows, kHaloRows + r2};
+    // ... of a colour model or of float planes: the halo buffers have a channel pitch of their own
+    const bool rows_cf = io.rows && (io.f32 || C != 1);
+    const L1RowsCF l1rows_cf{io.halo_top, io.halo_bot, (long)io.halo_stride, (long)io.halo_ch_pitch, (long)ch_step, io.src_row0,
+                             io.src_row0 + io.src_rows, kHaloRows + r2};
     const long dst_off = io.rows ? (long)io.dst_row0 * (long)dst_stride : 0;
     for (int f = 0; f < n_frames; ++f) {
         // frame f of the call's planes: bytes, or floats (the float image path); the other pair stays null
@@ -306,10 +325,14 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
             const int b1 = std::min(row_end, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
-            if (io.f32)        // float planes in: one launcher for both forms of the map
+            if (rows_cf)       // a stripe of a colour model or of float planes: one launcher for every form
+                HIP_TRY(c, launch_spatial_l1_rows_cf(C, zero, split, io.f32, io.f32 ? (const void *)sff : (const void *)sf,
+                                                     (long)src_stride, l1rows_cf, width, height, m0, m1, frag, map64, mpitch, scale1,
+                                                     c->stream));
+            else if (io.f32)   // float planes in: one launcher for both forms of the map
                 HIP_TRY(c, launch_spatial_l1f(C, zero, split, sff, (long)src_stride, (long)ch_step, width, height, m0, m1, frag, map64,
                                               mpitch, scale1, c->stream));
-            if (io.rows)       // a stripe: one launcher for both forms of the map, rows from src and the halo buffers
+            else if (io.rows)  // a stripe: one launcher for both forms of the map, rows from src and the halo buffers
                 HIP_TRY(c, launch_spatial_l1_rows(zero, split, sf, (long)src_stride, l1rows, width, height, m0, m1, frag, map64,
                                                   mpitch, scale1, c->stream));
             if (split) {       // the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
@@ -326,7 +349,7 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
                                              c->stream));
             }
             if (io.f32) {      // float planes out, the 1-channel replicate model included (no float form of MODE_L3)
-                HIP_TRY(c, launch_spatial_l3f(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, dff,
+                HIP_TRY(c, launch_spatial_l3f(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, dff - dst_off,
                                               (long)dst_stride, (long)io.dst_ch_pitch, c->stream));
                 continue;
             }
@@ -497,83 +520,121 @@ int srcnn_forward_color(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uin
     return SRCNN_OK;
 }
 
-/* ---- row stripes of every 1-channel model (include/srcnn_amd.h) ---- */
+/* ---- row stripes of every whole model (include/srcnn_amd.h) ---- */
 
 int srcnn_model_halo_rows(const srcnn_ctx *c) { return c ? kHaloRows + (c->f2 - 1) / 2 : SRCNN_ERR_INVALID; }
 
-// Both stripe calls.  src_rows < 0: srcnn_model_rows_dev, d_src holds every row the range needs
-static int model_rows(srcnn_ctx *c, const char *what, const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
-                      const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride, uint8_t *d_dst, size_t dst_stride,
-                      int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
+static bool f32_planes_disjoint(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames);
+
+// Every stripe call.  kind: what the planes are -- one byte channel, interleaved 3-byte pixels, or float planes of the loaded
+// model's channel count; strides and pitches in elements (bytes, or floats).  src_rows < 0: the plain form, src holds every row
+// the range needs
+struct RowsCall {
+    const char *what;
+    StripeKind kind;
+    const void *src;
+    size_t src_stride, src_ch_pitch;
+    int src_row0, src_rows;
+    const void *halo_top, *halo_bot;
+    size_t halo_stride, halo_ch_pitch;
+    void *dst;
+    size_t dst_stride, dst_ch_pitch;
+    int dst_row0, width, height, row_begin, row_end;
+    float *pre;
+};
+
+static int model_rows(srcnn_ctx *c, const RowsCall &a)
 {
     BIND_KEEP(c);
     int rc;
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
-    const bool halo = src_rows >= 0;
-    if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) || width > (1 << 28) ||
-        row_begin < 0 || row_end > height || row_begin >= row_end || src_row0 < 0 || dst_row0 < 0 || dst_row0 > row_begin ||
-        (halo && (src_rows == 0 || src_rows > height - src_row0 || ((d_halo_top || d_halo_bot) && halo_stride < (size_t)width) ||
-                  halo_stride >= ((size_t)1 << 30))))
+    const char *what = a.what;
+    const bool halo = a.src_rows >= 0, f32 = a.kind == STRIPE_F32;
+    const int width = a.width, height = a.height, row_begin = a.row_begin, row_end = a.row_end, src_row0 = a.src_row0;
+    const int planes = f32 ? c->channels : 1;                     // channel planes (the bytes of a colour pixel share a row)
+    const size_t es = f32 ? sizeof(float) : 1;                    // bytes per element
+    const int roww = a.kind == STRIPE_COLOR ? 3 * std::min(width, 1 << 28) : width;      // elements of a row
+    const size_t src_ch_pitch = planes > 1 ? a.src_ch_pitch : 0, dst_ch_pitch = planes > 1 ? a.dst_ch_pitch : 0;
+    const size_t halo_ch_pitch = planes > 1 ? a.halo_ch_pitch : 0;
+    constexpr size_t kMaxPitch = (size_t)1 << 40;      // (elements: every offset the kernels form stays far inside 63 bits)
+    if (bad_plane(a.src, a.src_stride, roww, height) || bad_plane(a.dst, a.dst_stride, roww, height) || width > (1 << 28) ||
+        row_begin < 0 || row_end > height || row_begin >= row_end || src_row0 < 0 || a.dst_row0 < 0 || a.dst_row0 > row_begin ||
+        src_ch_pitch >= kMaxPitch || dst_ch_pitch >= kMaxPitch || halo_ch_pitch >= kMaxPitch ||
+        (halo && (a.src_rows == 0 || a.src_rows > height - src_row0 ||
+                  ((a.halo_top || a.halo_bot) && a.halo_stride < (size_t)roww) || a.halo_stride >= ((size_t)1 << 30))))
         return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
-    if ((rc = model_rows_refusal(c))) return rc;         // a colour model, layers from per-filter calls, the banded path's gate
+    // a model of the wrong channel count, layers from per-filter calls, the banded path's gate
+    if ((rc = model_rows_refusal(c, a.kind))) return rc;
     // the receptive field of rows [row_begin, row_end) must lie in src (halo form: in top | src | bot)
     const int R = srcnn_model_halo_rows(c);
     const int need0 = std::max(0, row_begin - R), need1 = std::min(height, row_end + R);
-    const int src_row1 = halo ? src_row0 + src_rows : height;
+    const int src_row1 = halo ? src_row0 + a.src_rows : height;
     if (!halo && src_row0 > need0)
         return fail(c, SRCNN_ERR_INVALID, "%s: rows [%d,%d) need input rows [%d,%d) (a halo of %d rows); src starts at row %d", what,
                     row_begin, row_end, need0, need1, R, src_row0);
-    if (halo && ((need0 < src_row0 && (!d_halo_top || src_row0 < R || need0 < src_row0 - R)) ||
-                 (need1 > src_row1 && (!d_halo_bot || need1 > src_row1 + R))))
+    if (halo && ((need0 < src_row0 && (!a.halo_top || src_row0 < R || need0 < src_row0 - R)) ||
+                 (need1 > src_row1 && (!a.halo_bot || need1 > src_row1 + R))))
         return fail(c, SRCNN_ERR_INVALID, "%s: rows [%d,%d) need input rows [%d,%d); src holds [%d,%d) and the halo buffers %d rows "
                                           "either side", what, row_begin, row_end, need0, need1, src_row0, src_row1, R);
-    // a side the call reads nothing from keeps a null pointer: with both null this is srcnn_model_rows_dev
-    const uint8_t *top = halo && need0 < src_row0 ? d_halo_top : nullptr, *bot = halo && need1 > src_row1 ? d_halo_bot : nullptr;
-    if (luma_path_ok(c)) {      // the strip path runs this model: the stripe calls of that path, R = 6, the same bytes
-        if (d_preclamp)
+    // a side the call reads nothing from keeps a null pointer: with both null this is the plain form
+    const void *top = halo && need0 < src_row0 ? a.halo_top : nullptr, *bot = halo && need1 > src_row1 ? a.halo_bot : nullptr;
+    if (a.kind == STRIPE_Y && luma_path_ok(c)) {      // the strip path runs this model: the stripe calls of that path, R = 6, the same bytes
+        const uint8_t *d_src = static_cast<const uint8_t *>(a.src);
+        uint8_t *d_dst = static_cast<uint8_t *>(a.dst);
+        if (a.pre)
             return fail(c, SRCNN_ERR_STATE, "%s: the replicate-padded 9-1-5 model runs its stripes on the strip path, which has no "
                                             "pre-clamp output (srcnn_forward_y_dev has one)", what);
         if (!halo)
-            return srcnn_forward_y_rows_dev(c, d_src, src_stride, src_row0, d_dst, dst_stride, dst_row0, width, height, row_begin,
+            return srcnn_forward_y_rows_dev(c, d_src, a.src_stride, src_row0, d_dst, a.dst_stride, a.dst_row0, width, height, row_begin,
                                             row_end);
-        return srcnn_forward_y_rows_halo_dev(c, d_src, src_stride, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, d_dst,
-                                             dst_stride, dst_row0, width, height, row_begin, row_end);
+        return srcnn_forward_y_rows_halo_dev(c, d_src, a.src_stride, src_row0, a.src_rows, static_cast<const uint8_t *>(a.halo_top),
+                                             static_cast<const uint8_t *>(a.halo_bot), a.halo_stride, d_dst, a.dst_stride, a.dst_row0,
+                                             width, height, row_begin, row_end);
     }
-    {   // like srcnn_forward_y_dev: the path cannot run in place -- the rows written must overlap none of the rows read
-        const size_t row_bytes = (size_t)width;
-        const uint8_t *out0 = d_dst + (size_t)(row_begin - dst_row0) * dst_stride;
-        const size_t out_bytes = (size_t)(row_end - row_begin - 1) * dst_stride + row_bytes;
+    if (planes > 1 && !f32_planes_disjoint(planes, a.dst_stride, dst_ch_pitch, 0, width, row_end - row_begin, 1))
+        return fail(c, SRCNN_ERR_INVALID, "%s: the output planes overlap each other (channel pitch %zu floats for %d rows of stride "
+                                          "%zu)", what, dst_ch_pitch, row_end - row_begin, a.dst_stride);
+    {   // like the whole-image calls: the path cannot run in place -- the rows written must overlap none of the rows read
+        // (float planes: the span from the first channel's first row to the last channel's last)
+        const size_t row_elems = (size_t)roww;
+        const uint8_t *out0 = static_cast<const uint8_t *>(a.dst) + es * (size_t)(row_begin - a.dst_row0) * a.dst_stride;
+        const size_t out_bytes = es * ((size_t)(planes - 1) * dst_ch_pitch + (size_t)(row_end - row_begin - 1) * a.dst_stride + row_elems);
         const int s0 = top ? src_row0 : need0, s1 = bot ? src_row1 : need1;         // the rows read from src
-        const size_t halo_bytes = (size_t)(R - 1) * halo_stride + row_bytes;
-        if ((s1 > s0 && ranges_overlap(out0, out_bytes, d_src + (size_t)(s0 - src_row0) * src_stride,
-                                       (size_t)(s1 - s0 - 1) * src_stride + row_bytes)) ||
+        const size_t halo_bytes = es * ((size_t)(planes - 1) * halo_ch_pitch + (size_t)(R - 1) * a.halo_stride + row_elems);
+        if ((s1 > s0 && ranges_overlap(out0, out_bytes, static_cast<const uint8_t *>(a.src) + es * (size_t)(s0 - src_row0) * a.src_stride,
+                                       es * ((size_t)(planes - 1) * src_ch_pitch + (size_t)(s1 - s0 - 1) * a.src_stride + row_elems))) ||
             (top && ranges_overlap(out0, out_bytes, top, halo_bytes)) || (bot && ranges_overlap(out0, out_bytes, bot, halo_bytes)))
             return fail(c, SRCNN_ERR_INVALID, "%s: the output rows overlap the input (src or a halo buffer)", what);
     }
     if ((rc = flush_seams(c))) return rc;
     BandedPlanes io;
-    io.src = d_src;
-    io.src_stride = src_stride;
-    io.dst = d_dst;
-    io.dst_stride = dst_stride;
-    io.pre = d_preclamp;
+    io.f32 = f32;
+    io.src = a.src;
+    io.src_stride = a.src_stride;
+    io.px_step = a.kind == STRIPE_COLOR ? 3 : 1;
+    io.ch_step = a.kind == STRIPE_COLOR ? 1 : src_ch_pitch;
+    io.dst = a.dst;
+    io.dst_stride = a.dst_stride;
+    io.dst_ch_pitch = dst_ch_pitch;
+    io.pre = a.pre;
     io.rows = true;
     io.row_begin = row_begin;
     io.row_end = row_end;
     io.src_row0 = src_row0;
     io.src_rows = src_row1 - src_row0;
-    io.dst_row0 = dst_row0;
+    io.dst_row0 = a.dst_row0;
     io.halo_top = top;
     io.halo_bot = bot;
-    io.halo_stride = halo_stride;
+    io.halo_stride = a.halo_stride;
+    io.halo_ch_pitch = halo_ch_pitch;
     return forward_banded(c, io, width, height, 1);
 }
 
 int srcnn_model_rows_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, int src_row0, uint8_t *d_dst, size_t dst_stride,
                          int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
 {
-    return model_rows(c, "model_rows_dev", d_src, src_stride, src_row0, -1, nullptr, nullptr, 0, d_dst, dst_stride, dst_row0, width,
-                      height, row_begin, row_end, d_preclamp);
+    return model_rows(c, RowsCall{"model_rows_dev", STRIPE_Y, d_src, src_stride, 0, src_row0, -1, nullptr, nullptr, 0, 0, d_dst,
+                                  dst_stride, 0, dst_row0, width, height, row_begin, row_end, d_preclamp});
 }
 
 int srcnn_model_rows_halo_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
@@ -581,8 +642,46 @@ int srcnn_model_rows_halo_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_str
                               size_t dst_stride, int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
 {
     if (c && src_rows < 0) return fail(c, SRCNN_ERR_INVALID, "model_rows_halo_dev: bad arguments");
-    return model_rows(c, "model_rows_halo_dev", d_src, src_stride, src_row0, src_rows, d_halo_top, d_halo_bot, halo_stride, d_dst,
-                      dst_stride, dst_row0, width, height, row_begin, row_end, d_preclamp);
+    return model_rows(c, RowsCall{"model_rows_halo_dev", STRIPE_Y, d_src, src_stride, 0, src_row0, src_rows, d_halo_top, d_halo_bot,
+                                  halo_stride, 0, d_dst, dst_stride, 0, dst_row0, width, height, row_begin, row_end, d_preclamp});
+}
+
+/* ---- row stripes of a colour model and of float planes (include/srcnn_amd.h) ---- */
+
+int srcnn_model_color_rows_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, int src_row0, uint8_t *d_dst, size_t dst_stride,
+                               int dst_row0, int width, int height, int row_begin, int row_end, float *d_preclamp)
+{
+    return model_rows(c, RowsCall{"model_color_rows_dev", STRIPE_COLOR, d_src, src_stride, 0, src_row0, -1, nullptr, nullptr, 0, 0,
+                                  d_dst, dst_stride, 0, dst_row0, width, height, row_begin, row_end, d_preclamp});
+}
+
+int srcnn_model_color_rows_halo_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, int src_row0, int src_rows,
+                                    const uint8_t *d_halo_top, const uint8_t *d_halo_bot, size_t halo_stride, uint8_t *d_dst,
+                                    size_t dst_stride, int dst_row0, int width, int height, int row_begin, int row_end,
+                                    float *d_preclamp)
+{
+    if (c && src_rows < 0) return fail(c, SRCNN_ERR_INVALID, "model_color_rows_halo_dev: bad arguments");
+    return model_rows(c, RowsCall{"model_color_rows_halo_dev", STRIPE_COLOR, d_src, src_stride, 0, src_row0, src_rows, d_halo_top,
+                                  d_halo_bot, halo_stride, 0, d_dst, dst_stride, 0, dst_row0, width, height, row_begin, row_end,
+                                  d_preclamp});
+}
+
+int srcnn_model_rows_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, int src_row0, float *d_dst,
+                             size_t dst_stride, size_t dst_ch_pitch, int dst_row0, int width, int height, int row_begin, int row_end)
+{
+    return model_rows(c, RowsCall{"model_rows_f32_dev", STRIPE_F32, d_src, src_stride, src_ch_pitch, src_row0, -1, nullptr, nullptr, 0,
+                                  0, d_dst, dst_stride, dst_ch_pitch, dst_row0, width, height, row_begin, row_end, nullptr});
+}
+
+int srcnn_model_rows_halo_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, int src_row0, int src_rows,
+                                  const float *d_halo_top, const float *d_halo_bot, size_t halo_stride, size_t halo_ch_pitch,
+                                  float *d_dst, size_t dst_stride, size_t dst_ch_pitch, int dst_row0, int width, int height,
+                                  int row_begin, int row_end)
+{
+    if (c && src_rows < 0) return fail(c, SRCNN_ERR_INVALID, "model_rows_halo_f32_dev: bad arguments");
+    return model_rows(c, RowsCall{"model_rows_halo_f32_dev", STRIPE_F32, d_src, src_stride, src_ch_pitch, src_row0, src_rows,
+                                  d_halo_top, d_halo_bot, halo_stride, halo_ch_pitch, d_dst, dst_stride, dst_ch_pitch, dst_row0, width,
+                                  height, row_begin, row_end, nullptr});
 }
 
 int srcnn_set_input_range(srcnn_ctx *c, float r)

@@ -26,7 +26,10 @@
 // Row stripes (srcnn_model_rows_dev, srcnn_model_rows_halo_dev, srcnn_model_striped*) run the same launches on a row range of
 // the image with one more compile-time form of layer 1, spatial_l1_kernel<1, ZERO, Scale, uint8_t, L1Rows> (srcnn_spatial_rows.hip):
 // the image's rows come from up to three buffers, and no row outside the ones the launch's map rows need is read.  Layers 2
-// and 3 read the context's own band maps only and have no such form.
+// and 3 read the context's own band maps only and have no such form.  The stripes of a colour model and of float planes
+// (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev, srcnn_model_color_striped*, srcnn_model_striped_f32*) are the same
+// with the forms spatial_l1_kernel<C, ZERO, Scale, In, L1RowsCF> (srcnn_spatial_rows_cf.hip) for 3 interleaved byte channels
+// and for 1 or 3 float planes.
 //
 // The input is read at src[y * sstride + x * px_step + c * ch_step]: px_step = 3, ch_step = 1 for interleaved 3-byte pixels
 // (srcnn_forward_color*), px_step = 1, ch_step = plane pitch for the three resized planes of srcnn_process_bgr, and a plain
@@ -117,6 +120,23 @@ __device__ __forceinline__ const uint8_t *l1_row(const uint8_t *src, long sstrid
     return src + (long)(y - rs.src_row0) * sstride;
 }
 __device__ __forceinline__ const L1Rows &l1_rows_of(const L1Rows &rs) { return rs; }
+// ... and for the three other inputs (Steps = L1RowsCF: 3 interleaved byte channels, 1 or 3 float planes; strides in elements):
+// the row's base address and, in *ch_pitch, the channel pitch of the buffer it lives in (float planes)
+template <typename In>
+__device__ __forceinline__ const In *l1_row(const In *src, long sstride, int y, const L1RowsCF &rs, long *ch_pitch)
+{
+    if (rs.top && y < rs.src_row0) {
+        *ch_pitch = rs.halo_ch_pitch;
+        return static_cast<const In *>(rs.top) + (long)(y - (rs.src_row0 - rs.halo_rows)) * rs.halo_stride;
+    }
+    if (rs.bot && y >= rs.src_row1) {
+        *ch_pitch = rs.halo_ch_pitch;
+        return static_cast<const In *>(rs.bot) + (long)(y - rs.src_row1) * rs.halo_stride;
+    }
+    *ch_pitch = rs.src_ch_pitch;
+    return src + (long)(y - rs.src_row0) * sstride;
+}
+__device__ __forceinline__ const L1RowsCF &l1_rows_of(const L1RowsCF &rs) { return rs; }
 
 template <int C, bool ZERO, typename Scale, typename In, typename... Steps>
 __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ src, long sstride, Steps... steps, int W, int H,
@@ -126,8 +146,10 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
     constexpr bool SPLIT = std::is_same_v<Scale, float>;
     constexpr bool F32 = std::is_same_v<In, float>;            // float planes in (px_step = 1, ch_step = the plane pitch)
     constexpr bool ROWS = (std::is_same_v<Steps, L1Rows> || ...);    // the stripe form: rows from src and two halo buffers
-    static_assert(ROWS ? (sizeof...(Steps) == 1 && C == 1 && !F32) : sizeof...(Steps) == (C == 1 ? 0 : 2),
-                  "px_step and ch_step for 3 channels only; the stripe form for one byte channel only");
+    constexpr bool ROWS_CF = (std::is_same_v<Steps, L1RowsCF> || ...);   // ... of 3 byte channels, of 1 or 3 float planes
+    static_assert(ROWS_CF ? (sizeof...(Steps) == 1 && (C == 3 || F32))
+                          : ROWS ? (sizeof...(Steps) == 1 && C == 1 && !F32) : sizeof...(Steps) == (C == 1 ? 0 : 2),
+                  "px_step and ch_step for 3 channels only; L1Rows for one byte channel only, L1RowsCF for the other inputs");
     using T = std::conditional_t<C == 1 || F32, float, uint8_t>;      // the window's element type
     float *as;
     T *ys;
@@ -142,7 +164,33 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * SL1_COLS, y0 = m0 + blockIdx.y * SL1_ROWS;
-    if constexpr (ROWS) {
+    if constexpr (ROWS_CF) {
+        // The stripe form of the other inputs: the rows as below (image row y0 - 4 + rr, clamped to the image, then to y_last; the
+        // select is uniform over the workgroup), the elements of a row in the order of the whole-image form of the same input --
+        // bytes channel fastest (consecutive threads read consecutive bytes of the row's interleaved pixels),
+        // float planes channel slowest (consecutive floats of a plane's row) -- into the same places of the same window.
+        const L1RowsCF &rs = l1_rows_of(steps...);
+        const int y_last = min(H - 1, m1 + 3);
+        for (int rr = 0; rr < SL1_YR; ++rr) {
+            const int yi = sclamp(y0 - 4 + rr, 0, H - 1);
+            long chp;
+            const In *row = l1_row(src, sstride, min(yi, y_last), rs, &chp);     // uniform over the workgroup
+            for (int e = tid; e < C * SL1_YP; e += 256) {
+                int cc, ch;
+                if constexpr (F32) {
+                    ch = e / SL1_YP;
+                    cc = e - ch * SL1_YP;
+                } else {
+                    cc = e / C;
+                    ch = e - C * cc;
+                }
+                const int xx = sclamp(x0 - 4 + cc, 0, W - 1);
+                const T v = F32 ? row[xx + (C == 1 ? 0 : ch * chp)] : row[(long)xx * C + ch];
+                if constexpr (ZERO) ys[ch * SL1_YC + rr * SL1_YP + cc] = (T)(v * ((yi == y0 - 4 + rr && xx == x0 - 4 + cc) ? (T)1 : (T)0));
+                else ys[ch * SL1_YC + rr * SL1_YP + cc] = v;
+            }
+        }
+    } else if constexpr (ROWS) {
         // The stripe form stages the window row by row: window row rr is image row y0 - 4 + rr, clamped to the IMAGE (yi: what
         // replicate and zero padding refer to, exactly as below), and then to y_last, the last input row this launch may read.
         // Computed row y reads window rows y - y0 .. y - y0 + 8, i.e. image rows y - 4 .. y + 4, and the row loop below stops at
@@ -239,7 +287,7 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
 // A channel plane of the window is SL2_PS floats, = 32 mod 64: the two lane-halves (channels 2p, 2p + 1) read disjoint banks.
 constexpr int SL2_COLS = 64, SL2_ROWS = 16, SL2_CC = 8, SL2_XP = 72;
 __host__ __device__ constexpr int sl2_ps(int r2) { return ((((SL2_ROWS + 2 * r2) * SL2_XP) + 31) / 64) * 64 + 32; }
-#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT)
+#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT) && !defined(SRCNN_SPATIAL_ROWS_CF_UNIT)
 size_t spatial_l2_lds_bytes(int f2)
 {
     return ((size_t)SL2_CC * sl2_ps((f2 - 1) / 2) + (size_t)f2 * f2 * (SL2_CC / 2) * 64) * sizeof(float);
@@ -567,8 +615,9 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
 // The launchers.  This file is compiled twice (srcnn_cpp_amd/build.py): as itself it instantiates the kernels of the byte entry
 // points, and through srcnn_spatial_f32.hip (which defines SRCNN_SPATIAL_F32_UNIT and includes it) the float forms of layers 1
 // and 3 and nothing else -- the kernels of this unit stay the ones they were, one for one.  srcnn_spatial_rows.hip (which
-// defines SRCNN_SPATIAL_ROWS_UNIT) includes it for the templates alone and instantiates the stripe forms of layer 1 itself.
-#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT)
+// defines SRCNN_SPATIAL_ROWS_UNIT) includes it for the templates alone and instantiates the stripe forms of layer 1 itself, and
+// so does srcnn_spatial_rows_cf.hip (SRCNN_SPATIAL_ROWS_CF_UNIT) for the stripe forms of the colour and float inputs.
+#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT) && !defined(SRCNN_SPATIAL_ROWS_CF_UNIT)
 template <int C, bool ZERO>
 static void launch_l1(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
                       const float *frag, float *map, long mpitch, hipStream_t st)
