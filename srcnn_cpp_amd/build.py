@@ -47,16 +47,8 @@ UNITS = [
     # the resize's vertical pass is OpenCV's float32 multiply-then-add (every product and sum rounded on its own):
     # __fmul_rn / __fadd_rn are plain * and + in HIP's headers, so contraction must be off here too
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
-    # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models
+    # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models, float planes and row stripes -- every form
     ("srcnn_spatial_kernels.hip", []),
-    # the float image path (srcnn_forward_f32*): the float forms of that file's layer-1 and layer-3 templates, a unit of their own
-    ("srcnn_spatial_f32.hip", []),
-    # row stripes of the banded models (srcnn_model_rows*_dev, srcnn_model_striped*): the stripe forms of that file's layer-1
-    # template, again a unit of their own
-    ("srcnn_spatial_rows.hip", []),
-    # ... and of the colour models and the float planes (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev and their
-    # striped calls): the stripe forms of the other three inputs of layer 1, once more a unit of their own
-    ("srcnn_spatial_rows_cf.hip", []),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),
@@ -120,8 +112,7 @@ TUNING_LIB = PKG / "libsrcnn_amd_tuning.so"
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [CSRC / "srcnn_kernels.h", CSRC / "srcnn_ctx.h", CSRC / "srcnn_spatial_kernels.hip",
-               PKG.parent / "include" / "srcnn_amd.h", Path(__file__)]
+    headers = [CSRC / "srcnn_kernels.h", CSRC / "srcnn_ctx.h", PKG.parent / "include" / "srcnn_amd.h", Path(__file__)]
     objs, tuning_objs = [], []
     for unit in UNITS:
         src, extra = unit[0], unit[1]

@@ -262,79 +262,59 @@ __host__ __device__ constexpr size_t spatial_l2_offset(int C) { return (size_t)C
 __host__ __device__ constexpr size_t spatial_l3_offset(int C, int f2) { return spatial_l2_offset(C) + (size_t)f2 * f2 * 2048 + 32; }
 __host__ __device__ constexpr size_t spatial_table_floats(int C, int f2) { return spatial_l3_offset(C, f2) + (size_t)C * SPATIAL_NFRAG_L3 * 64; }
 size_t spatial_l2_lds_bytes(int f2);
-// 64 planar maps (plane pitch mpitch, row stride W) of image rows [m0, m1) from `channels` u8 channels at src[y * sstride + x *
-// px_step + c * ch_step] (1 channel: a plane, the steps unused); zero: input outside the image is 0 (SRCNN_PAD_ZERO), else replicated
-hipError_t launch_spatial_l1(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
-                             int m0, int m1, const float *frag, float *map, long mpitch, hipStream_t st);
-// 32 planar maps (row stride W) of rows [o0, o1) from the 64 maps of rows [m0, m1) (which must hold rows o0 - r2 .. o1 + r2 - 1,
-// clamped to the image); zero: the map outside the image is 0, else replicated (f2 = 1, 3, 5)
-hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                             const float *frag, const float *bias, float *out, long opitch, hipStream_t st);
-// Layer 3: rows [b0, b1) of dst, pixels of `channels` bytes (row stride dstride; pre: the values before truncation at the same
-// element offsets, or null) from the 32 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch), which must hold every
-// image row of [b0 - 2, b1 + 2).  frag: the layer-3 part of the table above, b3: `channels` floats.  1 channel under replicate
-// padding is not a form of this kernel (the MODE_L3 strip kernel runs it).
-hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                             const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st);
-// SRCNN_MODE_BANDED16: layer 2 in split f16 (spatial_l2h_kernel).  launch_spatial_l1h is launch_spatial_l1 with the split-output
-// epilogue: `map` (the same bytes) holds 8 planes of 32-byte pixels, every activation times `scale` (a power of two) as an f16
-// (hi, lo) pair; launch_spatial_l2h is launch_spatial_l2 on that map with frag = the split W2 table
-// (spatial_l2h_table_bytes(f2): [4 K steps][f2 * f2 taps][hi, lo][64 lanes][8 f16], lane l: output channel l & 31, element e:
-// layer-1 channel spatial_l2h_channel(step, l >> 5, e)) and unscale = 1 / (scale x the W2 scale).
-// WEAK declarations: a host-only build of srcnn_spatial.cpp that defines just the three launchers above still links, and
-// forward_banded() refuses the mode where these two are null.
+// The split W2 table of SRCNN_MODE_BANDED16 (spatial_l2h_table_bytes(f2): [4 K steps][f2 * f2 taps][hi, lo][64 lanes][8 f16],
+// lane l: output channel l & 31, element e: layer-1 channel spatial_l2h_channel(step, l >> 5, e))
 __host__ __device__ constexpr int spatial_l2h_channel(int step, int h, int e) { return 32 * (step >> 1) + acc_row(8 * (step & 1) + e, h); }
 __host__ __device__ constexpr size_t spatial_l2h_table_bytes(int f2) { return (size_t)4 * f2 * f2 * 2 * 64 * 16; }
-hipError_t launch_spatial_l1h(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
-                              int m0, int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
-    __attribute__((weak));
-hipError_t launch_spatial_l2h(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                              const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
-    __attribute__((weak));
-// The float image path (srcnn_forward_f32*).  launch_spatial_l1f is launch_spatial_l1 / launch_spatial_l1h (split: the f16 pair
-// map, every activation times `scale`) on `channels` float planes, channel c of pixel (y, x) at src[y * sstride + x + c * ch_step],
-// in the model's own units (finite values); launch_spatial_l3f is launch_spatial_l3 writing the value before truncation to
-// `channels` float planes, dst[y * dstride + x + o * ch_pitch], and no byte -- 1 channel under replicate padding included.
-// WEAK declarations, as the two above: forward_banded() refuses a float call where they are null.
-hipError_t launch_spatial_l1f(int channels, bool zero, bool split, const float *src, long sstride, long ch_step, int W, int H, int m0,
-                              int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
-    __attribute__((weak));
-hipError_t launch_spatial_l3f(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                              const float *frag, const float *b3, float *dst, long dstride, long ch_pitch, hipStream_t st)
-    __attribute__((weak));
-// Row stripes of a 1-channel model (srcnn_model_rows_dev, srcnn_model_rows_halo_dev, srcnn_model_striped*; srcnn_spatial_rows.hip).
-// L1Rows: where the image's rows are.  src (the launcher's argument, row stride sstride) starts at image row src_row0; with
-// `top` the halo_rows rows above src_row0 come from it, with `bot` the halo_rows rows from src_row1 on, both with row stride
-// halo_stride (a null pointer: no buffer on that side, src holds those rows too).  launch_spatial_l1_rows is launch_spatial_l1
-// (split: launch_spatial_l1h) for one byte channel with rows from there, and it reads no input row outside
-// [max(0, m0 - 4), min(H, m1 + 4)); padding refers to the image (0, H - 1, 0, W - 1), never to the stripe.  Same arithmetic as the
-// whole-image forms, same order.  A WEAK declaration, as the four above: the stripe entry points refuse where it is null.
-struct L1Rows {
-    const uint8_t *top, *bot;
-    long halo_stride;
-    int src_row0, src_row1, halo_rows;
-};
-hipError_t launch_spatial_l1_rows(bool zero, bool split, const uint8_t *src, long sstride, const L1Rows &rows, int W, int H, int m0,
-                                  int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
-    __attribute__((weak));
-// Row stripes of a colour model and of float planes (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev,
-// srcnn_model_color_striped*, srcnn_model_striped_f32*; srcnn_spatial_rows_cf.hip).  L1RowsCF is L1Rows for the three other
-// inputs of layer 1, every stride and pitch in ELEMENTS of the input (bytes, or floats):
-//   3 byte channels   a row holds interleaved pixels (byte c of pixel x at row[3 x + c]); the channel pitches are unused
-//   1 float plane     a plain plane; the channel pitches are unused
-//   3 float planes    channel c of a row of src at + c * src_ch_pitch, of a row of a halo buffer at + c * halo_ch_pitch: a
-//                     halo buffer has a pitch of its own, so that a neighbour's stripe can be read where it lies
-// launch_spatial_l1_rows_cf is launch_spatial_l1 / launch_spatial_l1h / launch_spatial_l1f (f32: float planes; split: the f16
-// pair map) with rows from there; it reads no input row outside [max(0, m0 - 4), min(H, m1 + 4)) and no column beyond W - 1.
-// Same arithmetic as the whole-image forms, same order.  A WEAK declaration, as the five above.
-struct L1RowsCF {
+// One launcher per layer; each picks the kernel form from what it is given and returns hipErrorInvalidValue where there is none.
+// Every form of a layer does the same arithmetic in the same order.
+//
+// Where layer 1 reads the image: `channels` = 1 or 3 channels of bytes or (f32) floats in the model's own units (finite values),
+// channel c of pixel (y, x) at src[y * sstride + x * px_step + c * ch_step], strides and pitches in elements (1 channel: a plane,
+// the steps unused; floats: planes, px_step 1).  rows: a row stripe (one byte channel, 3 interleaved byte channels -- px_step 3,
+// ch_step 1 -- or float planes): src starts at image row src_row0; with `top` the halo_rows rows above src_row0 come from it, with
+// `bot` the halo_rows rows from src_row1 on, both with row stride halo_stride and, for 3 float planes, a channel pitch of their
+// own, halo_ch_pitch, so that a neighbour's stripe can be read where it lies (a null pointer: no buffer on that side, src holds
+// those rows too).
+struct L1Input {
+    const void *src;
+    bool f32;
+    int channels;
+    long sstride;
+    int px_step;
+    long ch_step;
+    bool rows;
     const void *top, *bot;
-    long halo_stride, halo_ch_pitch, src_ch_pitch;
+    long halo_stride, halo_ch_pitch;
     int src_row0, src_row1, halo_rows;
 };
-hipError_t launch_spatial_l1_rows_cf(int channels, bool zero, bool split, bool f32, const void *src, long sstride, const L1RowsCF &rows,
-                                     int W, int H, int m0, int m1, const float *frag, void *map, long mpitch, float scale,
-                                     hipStream_t st) __attribute__((weak));
+// Layer 1: the 64 maps of image rows [m0, m1).  zero: input outside the image is 0 (SRCNN_PAD_ZERO), else replicated; padding
+// refers to the image (0, H - 1, 0, W - 1), never to a stripe.  split (SRCNN_MODE_BANDED16): `map` holds 8 planes of 32-byte
+// pixels, every activation times `scale` (a power of two) as an f16 (hi, lo) pair; else 64 planar f32 maps (plane pitch mpitch,
+// row stride W; the same bytes) and `scale` is unused.  A stripe reads no input row outside [max(0, m0 - 4), min(H, m1 + 4)) and
+// no column beyond W - 1.
+hipError_t launch_spatial_l1(const L1Input &in, bool zero, bool split, float scale, int W, int H, int m0, int m1, const float *frag,
+                             void *map, long mpitch, hipStream_t st);
+// Layer 2 (f2 = 1, 3, 5): 32 planar f32 maps (row stride W) of rows [o0, o1) from the layer-1 map of rows [m0, m1) (which must
+// hold rows o0 - r2 .. o1 + r2 - 1, clamped to the image); zero: the map outside the image is 0, else replicated.  split: the
+// f16 pair map, frag = the split W2 table above and unscale = 1 / (layer 1's scale x the W2 scale), on the f16 MFMA
+// (spatial_l2h_kernel); else the f32 maps, frag = the layer-2 part of the fragment table, unscale unused.
+hipError_t launch_spatial_l2(int f2, bool zero, bool split, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                             const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st);
+// What layer 3 writes: pixels of `channels` bytes (row stride dstride; pre: the values before truncation at the same element
+// offsets, or null), or (f32) the value before truncation to `channels` float planes, dst[y * dstride + x + o * ch_pitch], and
+// no byte.
+struct L3Output {
+    void *dst;
+    bool f32;
+    long dstride, ch_pitch;
+    float *pre;
+};
+// Layer 3: rows [b0, b1) of the output from the 32 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch), which must
+// hold every image row of [b0 - 2, b1 + 2).  frag: the layer-3 part of the table above, b3: `channels` floats.  Bytes of 1 channel
+// under replicate padding are not a form of this kernel (the MODE_L3 strip kernel runs them); floats of it are.
+hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                             const float *frag, const float *b3, const L3Output &out, hipStream_t st);
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

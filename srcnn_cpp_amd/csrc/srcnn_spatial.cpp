@@ -162,25 +162,15 @@ static int upload_table16(srcnn_ctx *c)
 static int banded_refusal(srcnn_ctx *c, bool f32 = false, bool rows = false)
 {
     const bool zero = c->padding == SRCNN_PAD_ZERO;
-    if (rows && (f32 || c->channels != 1)) {
-        if (!launch_spatial_l1_rows_cf)
-            return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows: built without the colour / float stripe kernels");
-    } else if (rows && !launch_spatial_l1_rows) {
-        return fail(c, SRCNN_ERR_STATE, "srcnn_model_rows: built without the stripe kernels");
-    }
     if (f32) {
         if (c->mode != SRCNN_MODE_MFMA && c->mode != SRCNN_MODE_BANDED16)
             return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 runs in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only (mode %d has no "
                                             "float image path)", c->mode);
-        if (!launch_spatial_l1f || !launch_spatial_l3f)
-            return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32: built without the float-plane banded kernels");
         if (!c->whole_model)
             return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 needs a model loaded by srcnn_set_weights / srcnn_set_model(_color): "
                                             "the loaded layers came from per-filter calls");
     }
     if (c->mode == SRCNN_MODE_BANDED16) {      // every whole model, in either padding
-        if (!launch_spatial_l1h || !launch_spatial_l2h)
-            return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16: built without the split-f16 banded kernels");
         if (!c->whole_model)
             return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16 needs a model loaded by srcnn_set_weights / srcnn_set_model(_color): "
                                             "the loaded layers came from per-filter calls");
@@ -296,66 +286,32 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     const float *frag2 = frag + spatial_l2_offset(C), *bias2 = frag2 + (size_t)c->f2 * c->f2 * 2048;
     const float *frag3 = frag + spatial_l3_offset(C, c->f2);
     float *map64 = static_cast<float *>(c->sp_map64.p), *map32 = static_cast<float *>(c->sp_map32.p);
-    const size_t src_stride = io.src_stride, ch_step = io.ch_step, dst_stride = io.dst_stride;
-    const int px_step = io.px_step;
-    // a stripe: where the image's rows are for layer 1, and dst / pre addressed by image row from dst_row0
-    const L1Rows l1rows{static_cast<const uint8_t *>(io.halo_top), static_cast<const uint8_t *>(io.halo_bot), (long)io.halo_stride,
-                        io.src_row0, io.src_row0 + io.src_rows, kHaloRows + r2};
-    // ... of a colour model or of float planes: the halo buffers have a channel pitch of their own
-    const bool rows_cf = io.rows && (io.f32 || C != 1);
-    const L1RowsCF l1rows_cf{io.halo_top, io.halo_bot, (long)io.halo_stride, (long)io.halo_ch_pitch, (long)ch_step, io.src_row0,
-                             io.src_row0 + io.src_rows, kHaloRows + r2};
+    const size_t dst_stride = io.dst_stride;
+    // where layer 1 reads the image (a stripe: the image's rows in src and the halo buffers) and what layer 3 writes (a stripe:
+    // dst / pre addressed by image row from dst_row0); src, dst and pre are set per frame
+    L1Input in{nullptr, io.f32, C, (long)io.src_stride, io.px_step, (long)io.ch_step, io.rows, io.halo_top, io.halo_bot,
+               (long)io.halo_stride, (long)io.halo_ch_pitch, io.src_row0, io.src_row0 + io.src_rows, kHaloRows + r2};
+    L3Output out{nullptr, io.f32, (long)dst_stride, (long)io.dst_ch_pitch, nullptr};
     const long dst_off = io.rows ? (long)io.dst_row0 * (long)dst_stride : 0;
+    const size_t es = io.f32 ? sizeof(float) : 1;      // bytes per element of the call's planes
     for (int f = 0; f < n_frames; ++f) {
-        // frame f of the call's planes: bytes, or floats (the float image path); the other pair stays null
-        const uint8_t *sf = nullptr;
-        uint8_t *df = nullptr;
-        float *pf = nullptr;
-        const float *sff = nullptr;
-        float *dff = nullptr;
-        if (io.f32) {
-            sff = static_cast<const float *>(io.src) + (size_t)f * io.src_frame_pitch;
-            dff = static_cast<float *>(io.dst) + (size_t)f * io.dst_frame_pitch;
-        } else {
-            sf = static_cast<const uint8_t *>(io.src) + (size_t)f * io.src_frame_pitch;
-            df = static_cast<uint8_t *>(io.dst) + (size_t)f * io.dst_frame_pitch;
-            pf = io.pre ? io.pre + (size_t)f * io.dst_frame_pitch : nullptr;
-        }
+        // frame f of the call's planes: bytes, or floats (the float image path, which has no pre)
+        in.src = static_cast<const uint8_t *>(io.src) + es * f * io.src_frame_pitch;
+        uint8_t *df = static_cast<uint8_t *>(io.dst) + es * f * io.dst_frame_pitch;
+        float *pf = io.pre && !io.f32 ? io.pre + (size_t)f * io.dst_frame_pitch : nullptr;
+        out.dst = df - (long)es * dst_off;
+        out.pre = pf ? pf - dst_off : nullptr;
         for (int b0 = row_begin; b0 < row_end; b0 += band) {
             const int b1 = std::min(row_end, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
-            if (rows_cf)       // a stripe of a colour model or of float planes: one launcher for every form
-                HIP_TRY(c, launch_spatial_l1_rows_cf(C, zero, split, io.f32, io.f32 ? (const void *)sff : (const void *)sf,
-                                                     (long)src_stride, l1rows_cf, width, height, m0, m1, frag, map64, mpitch, scale1,
-                                                     c->stream));
-            else if (io.f32)   // float planes in: one launcher for both forms of the map
-                HIP_TRY(c, launch_spatial_l1f(C, zero, split, sff, (long)src_stride, (long)ch_step, width, height, m0, m1, frag, map64,
-                                              mpitch, scale1, c->stream));
-            else if (io.rows)  // a stripe: one launcher for both forms of the map, rows from src and the halo buffers
-                HIP_TRY(c, launch_spatial_l1_rows(zero, split, sf, (long)src_stride, l1rows, width, height, m0, m1, frag, map64,
-                                                  mpitch, scale1, c->stream));
-            if (split) {       // the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
-                if (!io.f32 && !io.rows)
-                    HIP_TRY(c, launch_spatial_l1h(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
-                                                  map64, mpitch, scale1, c->stream));
-                HIP_TRY(c, launch_spatial_l2h(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, c->sp16_table.p, bias2,
-                                              unscale, map32, opitch, c->stream));
-            } else {
-                if (!io.f32 && !io.rows)
-                    HIP_TRY(c, launch_spatial_l1(C, zero, sf, (long)src_stride, px_step, (long)ch_step, width, height, m0, m1, frag,
-                                                 map64, mpitch, c->stream));
-                HIP_TRY(c, launch_spatial_l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, map32, opitch,
-                                             c->stream));
-            }
-            if (io.f32) {      // float planes out, the 1-channel replicate model included (no float form of MODE_L3)
-                HIP_TRY(c, launch_spatial_l3f(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, dff - dst_off,
-                                              (long)dst_stride, (long)io.dst_ch_pitch, c->stream));
-                continue;
-            }
-            if (C > 1 || zero) {
-                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, df - dst_off,
-                                             (long)dst_stride, pf ? pf - dst_off : nullptr, c->stream));
+            // split: the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
+            HIP_TRY(c, launch_spatial_l1(in, zero, split, scale1, width, height, m0, m1, frag, map64, mpitch, c->stream));
+            HIP_TRY(c, launch_spatial_l2(c->f2, zero, split, map64, mpitch, m0, m1, width, height, o0, o1,
+                                         split ? c->sp16_table.p : (const void *)frag2, bias2, unscale, map32, opitch, c->stream));
+            // float planes out, the 1-channel replicate model included (no float form of MODE_L3)
+            if (io.f32 || C > 1 || zero) {
+                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, c->stream));
                 continue;
             }
             StripParams q{};

@@ -24,12 +24,14 @@
 // 32 planar f32 maps, layer 3 is unchanged.
 //
 // Row stripes (srcnn_model_rows_dev, srcnn_model_rows_halo_dev, srcnn_model_striped*) run the same launches on a row range of
-// the image with one more compile-time form of layer 1, spatial_l1_kernel<1, ZERO, Scale, uint8_t, L1Rows> (srcnn_spatial_rows.hip):
-// the image's rows come from up to three buffers, and no row outside the ones the launch's map rows need is read.  Layers 2
-// and 3 read the context's own band maps only and have no such form.  The stripes of a colour model and of float planes
+// the image with one more compile-time form of layer 1, spatial_l1_kernel<1, ZERO, Scale, uint8_t, L1Rows>: the image's rows
+// come from up to three buffers, and no row outside the ones the launch's map rows need is read.  Layers 2 and 3 read the
+// context's own band maps only and have no such form.  The stripes of a colour model and of float planes
 // (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev, srcnn_model_color_striped*, srcnn_model_striped_f32*) are the same
-// with the forms spatial_l1_kernel<C, ZERO, Scale, In, L1RowsCF> (srcnn_spatial_rows_cf.hip) for 3 interleaved byte channels
-// and for 1 or 3 float planes.
+// with the forms spatial_l1_kernel<C, ZERO, Scale, In, L1RowsCF> for 3 interleaved byte channels and for 1 or 3 float planes.
+//
+// Every form lives in this one translation unit, 55 kernels behind the three launchers at its end (srcnn_kernels.h), which
+// choose the form from what they are given.
 //
 // The input is read at src[y * sstride + x * px_step + c * ch_step]: px_step = 3, ch_step = 1 for interleaved 3-byte pixels
 // (srcnn_forward_color*), px_step = 1, ch_step = plane pitch for the three resized planes of srcnn_process_bgr, and a plain
@@ -70,6 +72,8 @@ __device__ __forceinline__ int sclamp(int v, int lo, int hi) { return v < lo ? l
 constexpr int SL1_COLS = 128, SL1_ROWS = 8;
 constexpr int SL1_YP = SL1_COLS + 8, SL1_YR = SL1_ROWS + 8, SL1_YC = SL1_YR * SL1_YP;
 constexpr size_t SL1_LDS3 = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC;
+// 3 float planes: the three tables and an f32 window of the three channels, 61.5 + 25.5 KiB, one workgroup per CU
+constexpr size_t SL1_LDS3F = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC * sizeof(float);
 
 // Kernel arguments are passed as they always were, so that each form compiles to the instructions it had: layer 1 takes the
 // steps of the input (int px_step, long ch_step) for 3 channels and none for 1, layer 3 takes its C biases as C floats.
@@ -110,7 +114,27 @@ __device__ __forceinline__ void l1_store_split(uint4 *o, const f32x16 &acc, int 
 
 struct NoScale {};         // the last argument of the forms that write plain f32 maps: nothing
 
-// The stripe form (Steps = L1Rows, srcnn_kernels.h): where image row y lives -- the R rows above src_row0 in `top`, the R rows
+// The stripe forms' row source, a kernel argument (launch_spatial_l1 fills it from an L1Input with `rows`).  L1Rows, one byte
+// channel: src (row stride sstride) starts at image row src_row0; with `top` the halo_rows rows above src_row0 come from it,
+// with `bot` the halo_rows rows from src_row1 on, both with row stride halo_stride (a null pointer: no buffer on that side, src
+// holds those rows too).
+struct L1Rows {
+    const uint8_t *top, *bot;
+    long halo_stride;
+    int src_row0, src_row1, halo_rows;
+};
+// L1RowsCF is L1Rows for the three other inputs of layer 1, every stride and pitch in ELEMENTS of the input (bytes, or floats):
+//   3 byte channels   a row holds interleaved pixels (byte c of pixel x at row[3 x + c]); the channel pitches are unused
+//   1 float plane     a plain plane; the channel pitches are unused
+//   3 float planes    channel c of a row of src at + c * src_ch_pitch, of a row of a halo buffer at + c * halo_ch_pitch: a
+//                     halo buffer has a pitch of its own, so that a neighbour's stripe can be read where it lies
+struct L1RowsCF {
+    const void *top, *bot;
+    long halo_stride, halo_ch_pitch, src_ch_pitch;
+    int src_row0, src_row1, halo_rows;
+};
+
+// The stripe form (Steps = L1Rows): where image row y lives -- the R rows above src_row0 in `top`, the R rows
 // from src_row1 on in `bot` (a null pointer: no such buffer, the row is in src), every other row in src, whose first row is
 // image row src_row0.  y is uniform over the workgroup, so the select and the row's base address are scalar.
 __device__ __forceinline__ const uint8_t *l1_row(const uint8_t *src, long sstride, int y, const L1Rows &rs)
@@ -287,12 +311,10 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
 // A channel plane of the window is SL2_PS floats, = 32 mod 64: the two lane-halves (channels 2p, 2p + 1) read disjoint banks.
 constexpr int SL2_COLS = 64, SL2_ROWS = 16, SL2_CC = 8, SL2_XP = 72;
 __host__ __device__ constexpr int sl2_ps(int r2) { return ((((SL2_ROWS + 2 * r2) * SL2_XP) + 31) / 64) * 64 + 32; }
-#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT) && !defined(SRCNN_SPATIAL_ROWS_CF_UNIT)
 size_t spatial_l2_lds_bytes(int f2)
 {
     return ((size_t)SL2_CC * sl2_ps((f2 - 1) / 2) + (size_t)f2 * f2 * (SL2_CC / 2) * 64) * sizeof(float);
 }
-#endif
 
 template <int F2, bool ZERO>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void spatial_l2_kernel(const float *__restrict__ map, long mpitch, int m0, int m1,
@@ -612,148 +634,104 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
     }
 }
 
-// The launchers.  This file is compiled twice (srcnn_cpp_amd/build.py): as itself it instantiates the kernels of the byte entry
-// points, and through srcnn_spatial_f32.hip (which defines SRCNN_SPATIAL_F32_UNIT and includes it) the float forms of layers 1
-// and 3 and nothing else -- the kernels of this unit stay the ones they were, one for one.  srcnn_spatial_rows.hip (which
-// defines SRCNN_SPATIAL_ROWS_UNIT) includes it for the templates alone and instantiates the stripe forms of layer 1 itself, and
-// so does srcnn_spatial_rows_cf.hip (SRCNN_SPATIAL_ROWS_CF_UNIT) for the stripe forms of the colour and float inputs.
-#if !defined(SRCNN_SPATIAL_F32_UNIT) && !defined(SRCNN_SPATIAL_ROWS_UNIT) && !defined(SRCNN_SPATIAL_ROWS_CF_UNIT)
-template <int C, bool ZERO>
-static void launch_l1(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
-                      const float *frag, float *map, long mpitch, hipStream_t st)
+// ---- the launchers (srcnn_kernels.h states what each one reads and writes) ----------------------------------------------------
+// (n, zero) as compile-time constants: calls f(std::integral_constant<int, n>, std::bool_constant<zero>) for the one of Ns that
+// n is and returns what f returns; n is none of them: hipErrorInvalidValue, there is no such kernel
+template <int... Ns, typename F>
+static hipError_t with_form(int n, bool zero, F f)
 {
-    if constexpr (C == 1) {
-        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, NoScale, uint8_t>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch,
-                           NoScale{});
-    } else {
-        // (68 KiB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, NoScale, uint8_t, int, long>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
-        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, NoScale, uint8_t, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step,
-                           ch_step, W, H, m0, m1, frag, map, mpitch, NoScale{});
-    }
+    hipError_t e = hipErrorInvalidValue;
+    auto one = [&](auto N) {
+        if (n == N.value) e = zero ? f(N, std::true_type{}) : f(N, std::false_type{});
+    };
+    (one(std::integral_constant<int, Ns>{}), ...);
+    return e;
 }
 
-hipError_t launch_spatial_l1(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
-                             int m0, int m1, const float *frag, float *map, long mpitch, hipStream_t st)
+hipError_t launch_spatial_l1(const L1Input &in, bool zero, bool split, float scale, int W, int H, int m0, int m1, const float *frag,
+                             void *map, long mpitch, hipStream_t st)
 {
     const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
-    if (channels == 1 && !zero) launch_l1<1, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
-    else if (channels == 1) launch_l1<1, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
-    else if (channels == 3 && !zero) launch_l1<3, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
-    else if (channels == 3) launch_l1<3, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, map, mpitch, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    // one form: spatial_l1_kernel<C, ZERO, Scale, In, Steps...> by the types of sc, src and steps
+    auto launch = [&](auto C, auto ZERO, auto sc, auto *src, auto... steps) {
+        using In = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
+        auto *kernel = spatial_l1_kernel<decltype(C)::value, decltype(ZERO)::value, decltype(sc), In, decltype(steps)...>;
+        // (3 channels: 68 KiB for bytes, 87 KiB for floats exceed the default dynamic-LDS limit; set per call: the attribute is
+        // per device)
+        const size_t lds = decltype(C)::value == 1 ? 0 : std::is_same_v<In, float> ? SL1_LDS3F : SL1_LDS3;
+        if (lds) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, src, in.sstride, steps..., W, H, m0, m1, frag, static_cast<float *>(map),
+                           mpitch, sc);
+        return hipGetLastError();
+    };
+    const uint8_t *bytes = static_cast<const uint8_t *>(in.src);
+    const float *floats = static_cast<const float *>(in.src);
+    // the form of the input, for a map of one kind (sc: the scale of the split map, or NoScale)
+    auto input = [&](auto C, auto ZERO, auto sc) -> hipError_t {
+        constexpr bool one = decltype(C)::value == 1;
+        if (in.rows) {
+            const L1RowsCF cf{in.top, in.bot, in.halo_stride, in.halo_ch_pitch, in.ch_step, in.src_row0, in.src_row1, in.halo_rows};
+            if (in.f32) return launch(C, ZERO, sc, floats, cf);
+            if constexpr (one)
+                return launch(C, ZERO, sc, bytes, L1Rows{static_cast<const uint8_t *>(in.top), static_cast<const uint8_t *>(in.bot),
+                                                         in.halo_stride, in.src_row0, in.src_row1, in.halo_rows});
+            else       // (3 byte planes have no stripe form)
+                return in.px_step == 3 && in.ch_step == 1 ? launch(C, ZERO, sc, bytes, cf) : hipErrorInvalidValue;
+        }
+        if constexpr (one) return in.f32 ? launch(C, ZERO, sc, floats) : launch(C, ZERO, sc, bytes);
+        else return in.f32 ? launch(C, ZERO, sc, floats, 1, in.ch_step) : launch(C, ZERO, sc, bytes, in.px_step, in.ch_step);
+    };
+    return with_form<1, 3>(in.channels, zero,
+                           [&](auto C, auto ZERO) { return split ? input(C, ZERO, scale) : input(C, ZERO, NoScale{}); });
 }
 
-template <int F2, bool ZERO>
-static void launch_l2(dim3 grid, size_t lds, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                      const float *frag, const float *bias, float *out, long opitch, hipStream_t st)
-{
-    // (the 9-5-5 kernel's 70 KB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l2_kernel<F2, ZERO>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    hipLaunchKernelGGL((spatial_l2_kernel<F2, ZERO>), grid, dim3(256), lds, st, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out,
-                       opitch);
-}
-
-hipError_t launch_spatial_l2(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                             const float *frag, const float *bias, float *out, long opitch, hipStream_t st)
+hipError_t launch_spatial_l2(int f2, bool zero, bool split, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                             const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
 {
     const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS));
-    const size_t lds = spatial_l2_lds_bytes(f2);
-    if (f2 == 1 && !zero) launch_l2<1, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else if (f2 == 3 && !zero) launch_l2<3, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else if (f2 == 5 && !zero) launch_l2<5, false>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else if (f2 == 1 && zero) launch_l2<1, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else if (f2 == 3 && zero) launch_l2<3, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else if (f2 == 5 && zero) launch_l2<5, true>(grid, lds, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, out, opitch, st);
-    else return hipErrorInvalidValue;
     // (f2 = 1 under replicate padding: the colour 9-1-5 model; the 1-channel one runs on the strip kernels)
-    return hipGetLastError();
-}
-
-// ---- SRCNN_MODE_BANDED16: the split-output layer 1 and the split-f16 layer 2 -------------------------------------------------
-template <int C, bool ZERO>
-static void launch_l1h(dim3 grid, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H, int m0, int m1,
-                       const float *frag, float *map, long mpitch, float scale, hipStream_t st)
-{
-    if constexpr (C == 1) {
-        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, float, uint8_t>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch, scale);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, float, uint8_t, int, long>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3);
-        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, float, uint8_t, int, long>), grid, dim3(256), SL1_LDS3, st, src, sstride, px_step, ch_step, W,
-                           H, m0, m1, frag, map, mpitch, scale);
-    }
-}
-
-hipError_t launch_spatial_l1h(int channels, bool zero, const uint8_t *src, long sstride, int px_step, long ch_step, int W, int H,
-                              int m0, int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
-{
-    const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
-    float *m = static_cast<float *>(map);
-    if (channels == 1 && !zero) launch_l1h<1, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
-    else if (channels == 1) launch_l1h<1, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
-    else if (channels == 3 && !zero) launch_l1h<3, false>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
-    else if (channels == 3) launch_l1h<3, true>(grid, src, sstride, px_step, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-template <int F2, bool ZERO>
-static void launch_l2h(dim3 grid, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1, const void *frag,
-                       const float *bias, float unscale, float *out, long opitch, hipStream_t st)
-{
-    const size_t lds = spatial_l2h_lds_bytes(F2);
-    // (more than the default dynamic-LDS limit; set per call: the attribute is per device)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l2h_kernel<F2, ZERO>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    hipLaunchKernelGGL((spatial_l2h_kernel<F2, ZERO>), grid, dim3(256), lds, st, static_cast<const uint4 *>(map), mpitch, m0, m1, W, H,
-                       o0, o1, static_cast<const uint4 *>(frag), bias, unscale, out, opitch);
-}
-
-hipError_t launch_spatial_l2h(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                              const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
-{
-    const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS));
-    if (f2 == 1 && !zero) launch_l2h<1, false>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
-    else if (f2 == 3 && !zero) launch_l2h<3, false>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
-    else if (f2 == 5 && !zero) launch_l2h<5, false>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
-    else if (f2 == 1 && zero) launch_l2h<1, true>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
-    else if (f2 == 3 && zero) launch_l2h<3, true>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
-    else if (f2 == 5 && zero) launch_l2h<5, true>(grid, map, mpitch, m0, m1, W, H, o0, o1, frag, bias, unscale, out, opitch, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-template <int C, bool ZERO, typename... B3>
-static void launch_l3(dim3 grid, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, int nx, int n_tiles,
-                      const float *frag, uint8_t *dst, long dstride, float *pre, hipStream_t st, B3... b3)
-{
-    if (pre)
-        hipLaunchKernelGGL((spatial_l3_kernel<C, true, ZERO, uint8_t, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
-                           n_tiles, frag, b3..., dst, dstride, pre);
-    else
-        hipLaunchKernelGGL((spatial_l3_kernel<C, false, ZERO, uint8_t, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
-                           n_tiles, frag, b3..., dst, dstride, pre);
+    return with_form<1, 3, 5>(f2, zero, [&](auto F2, auto ZERO) {
+        // (the 9-5-5 kernel's 70 KB and every split form exceed the default dynamic-LDS limit; set per call: the attribute is
+        // per device)
+        if (split) {
+            auto *kernel = spatial_l2h_kernel<decltype(F2)::value, decltype(ZERO)::value>;
+            const size_t lds = spatial_l2h_lds_bytes(F2);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, static_cast<const uint4 *>(map), mpitch, m0, m1, W, H, o0, o1,
+                               static_cast<const uint4 *>(frag), bias, unscale, out, opitch);
+        } else {
+            auto *kernel = spatial_l2_kernel<decltype(F2)::value, decltype(ZERO)::value>;
+            const size_t lds = spatial_l2_lds_bytes(F2);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, static_cast<const float *>(map), mpitch, m0, m1, W, H, o0, o1,
+                               static_cast<const float *>(frag), bias, out, opitch);
+        }
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                             const float *frag, const float *b3, uint8_t *dst, long dstride, float *pre, hipStream_t st)
+                             const float *frag, const float *b3, const L3Output &out, hipStream_t st)
 {
     const int nx = (W + SL3_OUT - 1) / SL3_OUT, ny = (b1 - b0 + SL3_SEG - 1) / SL3_SEG, n_tiles = nx * ny;
     const dim3 grid((unsigned)(SL3_XCDS * ((n_tiles + SL3_XCDS - 1) / SL3_XCDS)));
-    // (1 channel under replicate padding: MODE_L3)
-    if (channels == 1 && zero)
-        launch_l3<1, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, pre, st, b3[0]);
-    else if (channels == 3 && zero)
-        launch_l3<3, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, pre, st, b3[0], b3[1], b3[2]);
-    else if (channels == 3)
-        launch_l3<3, false>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, pre, st, b3[0], b3[1], b3[2]);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    // one form: spatial_l3_kernel<C, PRE, ZERO, Out, float x C> by the type of dst; last: the kernel's last argument
+    auto launch = [&](auto C, auto ZERO, auto PRE, auto *dst, auto last, auto... b) {
+        using Out = std::remove_pointer_t<decltype(dst)>;
+        hipLaunchKernelGGL((spatial_l3_kernel<decltype(C)::value, decltype(PRE)::value, decltype(ZERO)::value, Out, decltype(b)...>), grid,
+                           dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, b..., dst, out.dstride, last);
+        return hipGetLastError();
+    };
+    return with_form<1, 3>(channels, zero, [&](auto C, auto ZERO) -> hipError_t {
+        auto biases = [&](auto PRE, auto *dst, auto last) {
+            if constexpr (decltype(C)::value == 1) return launch(C, ZERO, PRE, dst, last, b3[0]);
+            else return launch(C, ZERO, PRE, dst, last, b3[0], b3[1], b3[2]);
+        };
+        if (out.f32) return biases(std::false_type{}, static_cast<float *>(out.dst), out.ch_pitch);
+        if constexpr (decltype(C)::value == 1 && !decltype(ZERO)::value) return hipErrorInvalidValue;      // (MODE_L3 runs it)
+        else if (out.pre) return biases(std::true_type{}, static_cast<uint8_t *>(out.dst), out.pre);
+        else return biases(std::false_type{}, static_cast<uint8_t *>(out.dst), out.pre);
+    });
 }
 
 // ---- srcnn_process_bgr: interleaved BGR -> three planes (before the planar bicubic resize) ------------------------------
@@ -775,74 +753,5 @@ hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t
                        ppitch);
     return hipGetLastError();
 }
-
-#elif defined(SRCNN_SPATIAL_F32_UNIT)
-// ---- the float image path (srcnn_forward_f32*): layer 1 on float planes, layer 3 writing float planes ---------------------
-// the three tables and an f32 window of the three channels: 61.5 + 25.5 KiB, one workgroup per CU
-constexpr size_t SL1_LDS3F = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC * sizeof(float);
-
-template <int C, bool ZERO, typename Scale>
-static void launch_l1f(dim3 grid, const float *src, long sstride, long ch_step, int W, int H, int m0, int m1, const float *frag,
-                       float *map, long mpitch, Scale scale, hipStream_t st)
-{
-    if constexpr (C == 1) {
-        hipLaunchKernelGGL((spatial_l1_kernel<1, ZERO, Scale, float>), grid, dim3(256), 0, st, src, sstride, W, H, m0, m1, frag, map, mpitch,
-                           scale);
-    } else {
-        // (87 KiB exceed the default dynamic-LDS limit; set per call: the attribute is per device)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spatial_l1_kernel<C, ZERO, Scale, float, int, long>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SL1_LDS3F);
-        hipLaunchKernelGGL((spatial_l1_kernel<C, ZERO, Scale, float, int, long>), grid, dim3(256), SL1_LDS3F, st, src, sstride, 1, ch_step,
-                           W, H, m0, m1, frag, map, mpitch, scale);
-    }
-}
-
-template <typename Scale>
-static hipError_t launch_l1f_any(int channels, bool zero, dim3 grid, const float *src, long sstride, long ch_step, int W, int H, int m0,
-                                 int m1, const float *frag, float *map, long mpitch, Scale scale, hipStream_t st)
-{
-    if (channels == 1 && !zero) launch_l1f<1, false>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
-    else if (channels == 1) launch_l1f<1, true>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
-    else if (channels == 3 && !zero) launch_l1f<3, false>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
-    else if (channels == 3) launch_l1f<3, true>(grid, src, sstride, ch_step, W, H, m0, m1, frag, map, mpitch, scale, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_spatial_l1f(int channels, bool zero, bool split, const float *src, long sstride, long ch_step, int W, int H, int m0,
-                              int m1, const float *frag, void *map, long mpitch, float scale, hipStream_t st)
-{
-    const dim3 grid((unsigned)((W + SL1_COLS - 1) / SL1_COLS), (unsigned)((m1 - m0 + SL1_ROWS - 1) / SL1_ROWS));
-    float *m = static_cast<float *>(map);
-    if (split) return launch_l1f_any(channels, zero, grid, src, sstride, ch_step, W, H, m0, m1, frag, m, mpitch, scale, st);
-    return launch_l1f_any(channels, zero, grid, src, sstride, ch_step, W, H, m0, m1, frag, m, mpitch, NoScale{}, st);
-}
-
-template <int C, bool ZERO, typename... B3>
-static void launch_l3f(dim3 grid, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1, int nx, int n_tiles,
-                       const float *frag, float *dst, long dstride, long ch_pitch, hipStream_t st, B3... b3)
-{
-    hipLaunchKernelGGL((spatial_l3_kernel<C, false, ZERO, float, B3...>), grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx,
-                       n_tiles, frag, b3..., dst, dstride, ch_pitch);
-}
-
-hipError_t launch_spatial_l3f(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                              const float *frag, const float *b3, float *dst, long dstride, long ch_pitch, hipStream_t st)
-{
-    const int nx = (W + SL3_OUT - 1) / SL3_OUT, ny = (b1 - b0 + SL3_SEG - 1) / SL3_SEG, n_tiles = nx * ny;
-    const dim3 grid((unsigned)(SL3_XCDS * ((n_tiles + SL3_XCDS - 1) / SL3_XCDS)));
-    if (channels == 1 && zero)
-        launch_l3f<1, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0]);
-    else if (channels == 1)
-        launch_l3f<1, false>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0]);
-    else if (channels == 3 && zero)
-        launch_l3f<3, true>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0], b3[1], b3[2]);
-    else if (channels == 3)
-        launch_l3f<3, false>(grid, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, dst, dstride, ch_pitch, st, b3[0], b3[1], b3[2]);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-#endif  // SRCNN_SPATIAL_F32_UNIT
 
 }  // namespace srcnn

@@ -36,9 +36,9 @@ hipError_t launch_resize_cubic(const uint8_t *, long, long, int, int, uint8_t *,
 bool fused_pipeline_ok(int, int, int, int, const void *, long, const void *, long) { return false; }
 hipError_t launch_bgr_to_y_resized(const uint8_t *, long, int, int, uint8_t *, long, int, int, const int *, const short *, const int *, const short *, hipStream_t) { return never(); }
 hipError_t launch_resize_merge(const uint8_t *, long, int, int, const uint8_t *, long, uint8_t *, long, int, int, const int *, const short *, const int *, const short *, hipStream_t) { return never(); }
-hipError_t launch_spatial_l1(int, bool, const uint8_t *, long, int, long, int, int, int, int, const float *, float *, long, hipStream_t) { return never(); }
-hipError_t launch_spatial_l2(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, float *, long, hipStream_t) { return never(); }
-hipError_t launch_spatial_l3(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, uint8_t *, long, float *, hipStream_t) { return never(); }
+hipError_t launch_spatial_l1(const L1Input &, bool, bool, float, int, int, int, int, const float *, void *, long, hipStream_t) { return never(); }
+hipError_t launch_spatial_l2(int, bool, bool, const void *, long, int, int, int, int, int, int, const void *, const float *, float, float *, long, hipStream_t) { return never(); }
+hipError_t launch_spatial_l3(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, const L3Output &, hipStream_t) { return never(); }
 hipError_t launch_split3(const uint8_t *, long, int, int, uint8_t *, long, hipStream_t) { return never(); }
 }  // namespace srcnn
 

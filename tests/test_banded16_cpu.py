@@ -9,7 +9,6 @@ layer 3 in float32.  The same model with the lo parts dropped -- plain f16 opera
 9-5-5 cases: the test can tell the split from a single f16 product."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -17,8 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import spatial_listing as L
 import srcnn_cpp_amd as S
-from srcnn_cpp_amd import build as B
 from srcnn_cpp_amd.synth import synth_luma
 from color_reference import random_color_model, synth_color, torch_forward_color
 from spatial_reference import as_model, pre_tolerance, random_model, torch_forward
@@ -187,28 +186,16 @@ def test_split_arithmetic_meets_the_mfma_tolerance_colour(f2, padding):
 
 
 # ---- the device code ----------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def unit_asm(tmp_path_factory):
-    unit = "srcnn_spatial_kernels.hip"
-    flags = [u[1] for u in B.UNITS if u[0] == unit and len(u) == 2][0]
-    out = tmp_path_factory.mktemp("banded16") / "unit.s"
-    subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, f"-I{B.CSRC}", "-S", "--cuda-device-only",
-                    "-o", str(out), str(B.CSRC / unit)], check=True, stderr=subprocess.DEVNULL)
-    return out.read_text()
+def test_no_kernel_of_the_unit_uses_scratch_memory():
+    assert len(L.kernels("spatial_l2h_kernel")) == 6                # f2 = 1, 3, 5 x replicate, zero
+    assert len(L.kernels(L.L1_BYTES)) == 8                          # 1, 3 channels x replicate, zero x f32, split output
+    for name, desc, _ in L.kernels():
+        assert L.private_bytes(desc) == 0, name
 
 
-def test_no_kernel_of_the_unit_uses_scratch_memory(unit_asm):
-    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", unit_asm, re.S)
-    names = [n for n, _ in kernels]
-    assert sum("spatial_l2h_kernel" in n for n in names) == 6       # f2 = 1, 3, 5 x replicate, zero
-    assert sum("spatial_l1_kernel" in n for n in names) == 8        # 1, 3 channels x replicate, zero x f32, split output
-    for name, body in kernels:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
-
-
-def test_layer2_kernel_runs_on_the_f16_mfma_only(unit_asm):
-    bodies = re.findall(r"^(_ZN5srcnn\w*spatial_l2h_kernel\w+):.*?^\.Lfunc_end", unit_asm, re.S | re.M)
-    assert len(bodies) == 6
-    for m in re.finditer(r"^(_ZN5srcnn\w*spatial_l2h_kernel\w+):(.*?)^\.Lfunc_end", unit_asm, re.S | re.M):
-        assert "v_mfma_f32_32x32x16_f16" in m.group(2), m.group(1)
-        assert "v_mfma_f32_32x32x2_f32" not in m.group(2), m.group(1)
+def test_layer2_kernel_runs_on_the_f16_mfma_only():
+    found = L.kernels("spatial_l2h_kernel")
+    assert len(found) == 6
+    for name, _, body in found:
+        assert "v_mfma_f32_32x32x16_f16" in body, name
+        assert "v_mfma_f32_32x32x2_f32" not in body, name

@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import spatial_listing as L
 import srcnn_cpp_amd as S
 from srcnn_cpp_amd import build as B
 from srcnn_cpp_amd.synth import synth_luma
@@ -322,38 +323,30 @@ def ten_bit_plane(w, h):
 
 
 # ---- the device code ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def unit_asm(tmp_path_factory):
-    unit = "srcnn_spatial_f32.hip"
-    flags = [u[1] for u in B.UNITS if u[0] == unit and len(u) == 2][0]
-    out = tmp_path_factory.mktemp("f32") / "unit.s"
-    subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, f"-I{B.CSRC}", "-S", "--cuda-device-only",
-                    "-o", str(out), str(B.CSRC / unit)], check=True, stderr=subprocess.DEVNULL)
-    return out.read_text()
+def float_kernels():
+    """The whole-image float forms of layers 1 and 3 (the stripe forms of float planes carry L1RowsCF in their names)."""
+    return L.kernels(L.L1_FLOATS), L.kernels(L.L3_FLOATS)
 
 
-def test_the_float_unit_holds_the_twelve_new_kernels_without_scratch_memory(unit_asm):
-    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", unit_asm, re.S)
-    names = [n for n, _ in kernels]
-    assert sum("spatial_l1_kernel" in n for n in names) == 8        # 1, 3 channels x replicate, zero x f32, split map
-    assert sum("spatial_l3_kernel" in n for n in names) == 4        # 1, 3 channels x replicate, zero
-    assert len(names) == 12, names
-    for name, body in kernels:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
+def test_the_float_unit_holds_the_twelve_new_kernels_without_scratch_memory():
+    l1, l3 = float_kernels()
+    assert len(l1) == 8                                             # 1, 3 channels x replicate, zero x f32, split map
+    assert len(l3) == 4                                             # 1, 3 channels x replicate, zero
+    assert not any("L1Rows" in name for name, _, _ in l1)
+    assert len({name for name, _, _ in l1 + l3}) == 12
+    for name, desc, _ in l1 + l3:
+        assert L.private_bytes(desc) == 0, name
     # the colour layer-1 forms stage an f32 window beside the three tables: 3 * 82 * 64 * 4 + 3 * 16 * 136 * 4 bytes, dynamic
     # (no static LDS ahead of it), i.e. one workgroup per CU
-    for name, body in kernels:
-        static = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1))
+    for name, desc, _ in l1 + l3:
         if "spatial_l1_kernelILi3" in name:
-            assert static == 0, name
+            assert L.static_lds_bytes(desc) == 0, name
+    assert sum("spatial_l1_kernelILi3" in name for name, _, _ in l1) == 4
 
 
-def test_the_float_kernels_run_on_the_f32_mfma_and_store_no_byte(unit_asm):
-    n = 0
-    for m in re.finditer(r"^(_ZN5srcnn\w*spatial_l[13]_kernel\w+):(.*?)^\.Lfunc_end", unit_asm, re.S | re.M):
-        n += 1
-        body = m.group(2)
-        mfma = set(re.findall(r"\b(v_mfma_\w+)", body))
-        assert mfma == {"v_mfma_f32_32x32x2_f32"}, (m.group(1), mfma)
-        assert "global_store_byte" not in body and "global_load_ubyte" not in body, m.group(1)
-    assert n == 12
+def test_the_float_kernels_run_on_the_f32_mfma_and_store_no_byte():
+    l1, l3 = float_kernels()
+    for name, _, body in l1 + l3:
+        assert L.mfma_kinds(body) == {"v_mfma_f32_32x32x2_f32"}, (name, L.mfma_kinds(body))
+        assert "global_store_byte" not in body and "global_load_ubyte" not in body, name
+    assert len(l1 + l3) == 12

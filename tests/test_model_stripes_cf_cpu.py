@@ -9,6 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import spatial_listing as L
 import srcnn_cpp_amd as S
 from srcnn_cpp_amd import build as B
 
@@ -16,7 +17,6 @@ ROOT = Path(__file__).resolve().parent.parent
 NEW_SYMBOLS = ["srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped_dev",
                "srcnn_model_color_striped", "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev",
                "srcnn_model_striped_f32_dev", "srcnn_model_striped_f32"]
-UNIT = "srcnn_spatial_rows_cf.hip"
 
 
 @pytest.fixture(scope="module")
@@ -50,14 +50,6 @@ def test_null_contexts_are_invalid(lib):
         assert lib.srcnn_model_color_striped_dev(ctxs, n, None, 12, None, 12, 4, 4) == S.ERR_INVALID
         assert lib.srcnn_model_striped_f32(ctxs, n, x.ctypes.data_as(f32p), 4, 0, x.ctypes.data_as(f32p), 4, 0, 4, 4) == S.ERR_INVALID
         assert lib.srcnn_model_striped_f32_dev(ctxs, n, None, 4, 0, None, 4, 0, 4, 4) == S.ERR_INVALID
-
-
-def test_the_host_layer_links_without_the_new_launcher():
-    """The launcher is a weak declaration: a host-only build (tests/checks/san_host.cpp) defines none of the stripe kernels."""
-    text = (B.CSRC / "srcnn_kernels.h").read_text()
-    decl = re.search(r"hipError_t launch_spatial_l1_rows_cf\([^;]*;", text, re.S).group(0)
-    assert "__attribute__((weak))" in decl
-    assert "built without the colour / float stripe kernels" in (B.CSRC / "srcnn_spatial.cpp").read_text()
 
 
 # ---- the Python bindings validate before any call into the library --------------------------------------------------------
@@ -184,21 +176,11 @@ def test_striped_bindings_reject_mismatched_shapes_before_the_library(monkeypatc
 
 
 # ---- the device code ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def unit_asm(tmp_path_factory):
-    flags = [u[1] for u in B.UNITS if u[0] == UNIT and len(u) == 2][0]
-    same = [u[1] for u in B.UNITS if u[0] == "srcnn_spatial_rows.hip"][0]
-    assert flags == same                                      # the flags of the other side units of the template
-    out = tmp_path_factory.mktemp("rows_cf") / "unit.s"
-    subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, f"-I{B.CSRC}", "-S", "--cuda-device-only",
-                    "-o", str(out), str(B.CSRC / UNIT)], check=True, stderr=subprocess.DEVNULL)
-    return out.read_text()
-
-
-def test_the_unit_holds_the_twelve_new_kernels_without_scratch_memory(unit_asm):
-    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", unit_asm, re.S)
-    names = [n for n, _ in kernels]
+def test_the_unit_holds_the_twelve_new_kernels_without_scratch_memory():
+    found = L.kernels("L1RowsCF")
+    names = [n for n, _, _ in found]
     assert len(names) == 12 and len(set(names)) == 12, names
+    assert names == [n for n, _, _ in L.kernels(L.L1_ROWS_CF)]
     assert all("spatial_l1_kernel" in n and "L1RowsCF" in n for n in names), names
     # (C, In) x ZERO x Scale: In follows Scale in the mangled name -- NoScale is NS_7NoScaleE, float is f; bytes h, floats f
     forms = {}
@@ -208,26 +190,39 @@ def test_the_unit_holds_the_twelve_new_kernels_without_scratch_memory(unit_asm):
         forms.setdefault((int(m.group(1)), m.group(4)), set()).add((m.group(2), m.group(3)))
     assert set(forms) == {(3, "h"), (1, "f"), (3, "f")}
     assert all(len(v) == 4 for v in forms.values()), forms
-    for name, body in kernels:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
-        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1))
+    for name, desc, _ in found:
+        assert L.private_bytes(desc) == 0, name
         # one float plane: the window and the layer-1 table, all static, 16 x 136 x 4 + 82 x 64 x 4 bytes as the whole-image
         # form; three channels: all dynamic (68 KiB bytes, 87 KiB floats), so no static LDS shifts it
+        lds = L.static_lds_bytes(desc)
         assert lds == (29696 if "kernelILi1E" in name else 0), (name, lds)
     assert sum("kernelILi1E" in n for n in names) == 4
 
 
-def test_the_new_kernels_run_on_the_f32_mfma_only(unit_asm):
-    n = 0
-    for m in re.finditer(r"^(_ZN5srcnn\w*spatial_l1_kernel\w+):(.*?)^\.Lfunc_end", unit_asm, re.S | re.M):
-        n += 1
-        mfma = re.findall(r"\b(v_mfma_\w+)", m.group(2))
-        assert set(mfma) == {"v_mfma_f32_32x32x2_f32"}, (m.group(1), set(mfma))
-    assert n == 12
+def test_the_new_kernels_run_on_the_f32_mfma_only():
+    found = L.kernels("L1RowsCF")
+    for name, _, body in found:
+        assert L.mfma_kinds(body) == {"v_mfma_f32_32x32x2_f32"}, (name, L.mfma_kinds(body))
+    assert len(found) == 12
 
 
-def test_the_other_units_keep_their_kernel_sets():
-    """The new forms live in a unit of their own: the unit is in the build, and it switches the template's launchers off."""
-    assert sum(u[0] == UNIT for u in B.UNITS) == 1
-    text = (B.CSRC / UNIT).read_text()
-    assert "#define SRCNN_SPATIAL_ROWS_CF_UNIT 1" in text and '#include "srcnn_spatial_kernels.hip"' in text
+def test_one_unit_holds_every_form_and_no_launcher_is_weak():
+    """What the side units and the weak launchers stood for: the kernel set of the banded path is exactly the one it was, and
+    the host layer depends on no optional symbol (tests/checks/san_host.cpp links it against three stubs)."""
+    names = [n for n, _, _ in L.kernels()]
+    assert len(names) == 55 and len(set(names)) == 55, names
+    families = [("split3_kernel", 1), (L.L1_BYTES, 8), (L.L1_ROWS, 4), (L.L1_ROWS_CF, 12), (L.L1_FLOATS, 8),
+                ("spatial_l2_kernel", 6), ("spatial_l2h_kernel", 6), (L.L3_BYTES, 6), (L.L3_FLOATS, 4)]
+    picked = []
+    for pattern, count in families:
+        family = [n for n, _, _ in L.kernels(pattern)]
+        assert len(family) == count, (pattern, family)
+        picked += family
+    assert sorted(picked) == sorted(names)                     # every kernel is in exactly one family
+    header = (B.CSRC / "srcnn_kernels.h").read_text()
+    assert "weak" not in header
+    assert len(re.findall(r"^hipError_t launch_spatial_\w+\(", header, re.M)) == 3
+    units = [u[0] for u in B.UNITS]
+    assert units.count(L.UNIT) == 1
+    for gone in ("srcnn_spatial_f32.hip", "srcnn_spatial_rows.hip", "srcnn_spatial_rows_cf.hip"):
+        assert gone not in units and not (B.CSRC / gone).exists()

@@ -8,6 +8,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import spatial_listing as L
 import srcnn_cpp_amd as S
 from srcnn_cpp_amd import build as B
 
@@ -116,33 +117,22 @@ def test_striped_bindings_reject_mismatched_shapes_before_the_library(monkeypatc
 
 
 # ---- the device code ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def unit_asm(tmp_path_factory):
-    unit = "srcnn_spatial_rows.hip"
-    flags = [u[1] for u in B.UNITS if u[0] == unit and len(u) == 2][0]
-    out = tmp_path_factory.mktemp("rows") / "unit.s"
-    subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, f"-I{B.CSRC}", "-S", "--cuda-device-only",
-                    "-o", str(out), str(B.CSRC / unit)], check=True, stderr=subprocess.DEVNULL)
-    return out.read_text()
-
-
-def test_the_stripe_unit_holds_the_four_new_kernels_without_scratch_memory(unit_asm):
-    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", unit_asm, re.S)
-    names = [n for n, _ in kernels]
+def test_the_stripe_unit_holds_the_four_new_kernels_without_scratch_memory():
+    found = L.kernels("L1RowsE")
+    names = [n for n, _, _ in found]
     assert len(names) == 4 and len(set(names)) == 4, names
+    assert names == [n for n, _, _ in L.kernels(L.L1_ROWS)]
     # one byte channel, the row source in the argument pack: replicate, zero x f32, split map
     assert all("spatial_l1_kernelILi1E" in n and "L1Rows" in n for n in names), names
     assert sum("Lb1E" in n for n in names) == 2 and sum("NoScale" in n for n in names) == 2
-    for name, body in kernels:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
+    for name, desc, _ in found:
+        assert L.private_bytes(desc) == 0, name
         # the window and the layer-1 table, all static: 16 x 136 x 4 + 82 x 64 x 4 bytes, as the whole-image 1-channel form
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1)) == 29696, name
+        assert L.static_lds_bytes(desc) == 29696, name
 
 
-def test_the_stripe_kernels_run_on_the_f32_mfma_only(unit_asm):
-    n = 0
-    for m in re.finditer(r"^(_ZN5srcnn\w*spatial_l1_kernel\w+):(.*?)^\.Lfunc_end", unit_asm, re.S | re.M):
-        n += 1
-        mfma = set(re.findall(r"\b(v_mfma_\w+)", m.group(2)))
-        assert mfma == {"v_mfma_f32_32x32x2_f32"}, (m.group(1), mfma)
-    assert n == 4
+def test_the_stripe_kernels_run_on_the_f32_mfma_only():
+    found = L.kernels("L1RowsE")
+    for name, _, body in found:
+        assert L.mfma_kinds(body) == {"v_mfma_f32_32x32x2_f32"}, (name, L.mfma_kinds(body))
+    assert len(found) == 4
