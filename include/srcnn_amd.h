@@ -350,6 +350,46 @@ int srcnn_forward_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_
 int srcnn_set_input_range(srcnn_ctx *ctx, float r);
 float srcnn_get_input_range(const srcnn_ctx *ctx);
 
+/* The step in front of the float image path: a bicubic resize of float32 planes, and resize + model in one call.  An SRCNN does
+ * not change resolution, so a low-resolution image is first resized to the target size; this is that resize as
+ * torch.nn.functional.interpolate(x, size=(dst_h, dst_w), mode="bicubic", align_corners=False, antialias=False) defines it.
+ *   - Arithmetic, per axis with s source and n output samples: r = (s / n) * (d + 0.5) - 0.5, i = floor(r), t = r - i; the taps
+ *     are source samples i - 1 .. i + 2, each INDEX clamped to [0, s - 1] (never the coefficient), with the Keys coefficients
+ *     c2(t + 1), c1(t), c1(1 - t), c2(2 - t), c1(x) = ((A + 2) x - (A + 3)) x^2 + 1, c2(x) = ((A x - 5 A) x + 8 A) x - 4 A,
+ *     A = -0.75.  r, i, t and the coefficients are computed on the host in float64 and the coefficients rounded once to float32
+ *     (torch computes the coordinates in float32: its own result drifts from this formula by up to ~3e-5 x max|x| at non-dyadic
+ *     ratios, by ~2e-7 at x2).  The horizontal pass comes first, then the vertical one; each sums its four products in ascending
+ *     tap order in float32, every product and sum rounded on its own (no fused multiply-add), in every kernel form.  A resize to
+ *     the same size is an exact copy; down-scaling is plain 4-tap sampling without antialiasing; the output is not clamped and
+ *     may overshoot the input's range.  Non-finite input is allowed and spreads over the outputs whose 4 x 4 support holds it.
+ *   - srcnn_cubic_f32_taps: the table of one axis, host only (no context, no GPU) and the table the kernels run on:
+ *     first[d] = i (unclamped), coef[4 d .. 4 d + 3] the four coefficients.  SRCNN_ERR_INVALID for sizes <= 0 or a null pointer.
+ *   - Layout: that of srcnn_forward_f32_dev -- planar, element (frame f, channel c, row y, column x) at p[f * frame_pitch +
+ *     c * ch_pitch + y * stride + x], strides and pitches in floats, for source and destination separately.
+ *   - srcnn_resize_cubic_f32(_dev) need no model and run in every mode, on `channels` >= 1 planes (x n_frames frames) in one
+ *     launch.  _dev: device memory, asynchronous on the context's stream; the other form takes one image in host memory, staged
+ *     on the device, and returns when dst is complete.
+ *   - srcnn_process_f32(_dev): the resize of every channel of the loaded model (1 or 3, the channel pitches are ignored for 1)
+ *     into a workspace of one frame that the context owns (channels x dst_w x dst_h floats, grown on demand, freed with the
+ *     context), then the model on that frame as srcnn_forward_f32_dev runs it; frames one after another.  It equals the two
+ *     calls made separately bit for bit.  Its gate is that of srcnn_forward_f32: SRCNN_MODE_MFMA or SRCNN_MODE_BANDED16 and a
+ *     whole model, else SRCNN_ERR_STATE and srcnn_last_error() names the reason.
+ *   - SRCNN_ERR_INVALID for null pointers, sizes <= 0, a stride below the width, channels or n_frames <= 0, and output planes
+ *     that overlap each other or the input.  A refused call launches nothing and leaves the context usable. */
+int srcnn_cubic_f32_taps(int src_n, int dst_n, int *first /*[dst_n]*/, float *coef /*[dst_n][4]*/);
+int srcnn_resize_cubic_f32_dev(srcnn_ctx *ctx,
+                               const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w, int src_h,
+                               float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                               int channels, int n_frames);
+int srcnn_resize_cubic_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h,
+                           float *dst, size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h, int channels);
+int srcnn_process_f32_dev(srcnn_ctx *ctx,
+                          const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w, int src_h,
+                          float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                          int n_frames);
+int srcnn_process_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h,
+                      float *dst, size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

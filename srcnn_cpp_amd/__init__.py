@@ -35,6 +35,7 @@ __all__ = [
     "stripe_rows", "forward_y_frames_multi", "forward_y_lanes_dev", "forward_y_striped", "forward_y_striped_dev",
     "model_striped", "model_striped_dev",
     "model_color_striped", "model_color_striped_dev", "model_striped_f32", "model_striped_f32_dev",
+    "cubic_f32_taps",
 ]
 
 _PKG = Path(__file__).resolve().parent
@@ -137,6 +138,11 @@ def load_library() -> C.CDLL:
         "srcnn_forward_color_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
         "srcnn_forward_f32": ([vp, _f32p, sz, sz, _f32p, sz, sz, i, i], i),
         "srcnn_forward_f32_dev": ([vp, vp, sz, sz, sz, vp, sz, sz, sz, i, i, i], i),
+        "srcnn_cubic_f32_taps": ([i, i, C.POINTER(i), _f32p], i),
+        "srcnn_resize_cubic_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, i], i),
+        "srcnn_resize_cubic_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i, i], i),
+        "srcnn_process_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i], i),
+        "srcnn_process_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i], i),
         "srcnn_set_input_range": ([vp, C.c_float], i),
         "srcnn_get_input_range": ([vp], C.c_float),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
@@ -213,6 +219,7 @@ ABI_SYMBOLS = (
     "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
+    "srcnn_cubic_f32_taps", "srcnn_resize_cubic_f32", "srcnn_resize_cubic_f32_dev", "srcnn_process_f32", "srcnn_process_f32_dev",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -384,6 +391,18 @@ def _f32_planes(a, name, writable=False):
     if writable and not a.flags.writeable:
         raise ValueError(f"{name}: output array is read-only")
     return a4
+
+
+def _f32_image(a, name, dst_w, dst_h):
+    """One float32 image (H, W) or (C, H, W) as its (C, H, W) view, and the output size of a resize as two positive ints
+    (TypeError / ValueError otherwise, before any call into the library)."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim not in (2, 3):
+        raise TypeError(f"{name}: expected a float32 numpy array of shape (H, W) or (C, H, W)")
+    a3 = _f32_planes(a, name)[0]
+    for what, v in (("dst_w", dst_w), ("dst_h", dst_h)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError(f"{what}: expected a positive integer, got {v!r}")
+    return a3, int(dst_w), int(dst_h)
 
 
 def _same_shape(name, got, want):
@@ -579,6 +598,49 @@ class Context:
         context's stream; the channel pitches are ignored for a 1-channel model."""
         self._check(self._lib.srcnn_forward_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, d_dst, dst_stride,
                                                     dst_ch_pitch, dst_frame_pitch, width, height, n_frames))
+
+    def resize_cubic_f32(self, x, dst_w, dst_h):
+        """Bicubic resize of float32 planes as torch.nn.functional.interpolate(mode="bicubic", align_corners=False) defines it
+        (srcnn_resize_cubic_f32): x is (H, W) or (C, H, W), rows contiguous, row and channel strides free; returns a new
+        (dst_h, dst_w) or (C, dst_h, dst_w) array.  Needs no model and runs in every mode."""
+        x3, dst_w, dst_h = _f32_image(x, "x", dst_w, dst_h)
+        c, h, w = x3.shape
+        out = np.empty((c, dst_h, dst_w), np.float32)
+        self._check(self._lib.srcnn_resize_cubic_f32(self._h, _fp(x3), x3.strides[1] // 4 if h > 1 else w,
+                                                     x3.strides[0] // 4 if c > 1 else 0, w, h, _fp(out), dst_w, dst_w * dst_h,
+                                                     dst_w, dst_h, c))
+        return out if x.ndim == 3 else out[0]
+
+    def resize_cubic_f32_dev(self, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride,
+                             dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels=1, n_frames=1):
+        """srcnn_resize_cubic_f32_dev: device addresses of float32 planes, strides and pitches in floats, `channels` planes of
+        n_frames frames in one launch, asynchronous on the context's stream."""
+        self._check(self._lib.srcnn_resize_cubic_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h,
+                                                         d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels,
+                                                         n_frames))
+
+    def process_f32(self, x, dst_w, dst_h):
+        """resize_cubic_f32 to (dst_h, dst_w), then the loaded whole model on the result (srcnn_process_f32): x is (C, H, W)
+        with C the model's channel count, or (H, W) for a 1-channel model; returns an array of the resized shape.  MODE_MFMA
+        and MODE_BANDED16 only, like forward_f32."""
+        x3, dst_w, dst_h = _f32_image(x, "x", dst_w, dst_h)
+        c, h, w = x3.shape
+        channels = self.model_channels()
+        if c != channels:
+            raise ValueError(f"x: shape {tuple(x.shape)} for a model of {channels} channel(s): expected ({channels}, H, W)"
+                             + (" or (H, W)" if channels == 1 else ""))
+        out = np.empty((c, dst_h, dst_w), np.float32)
+        self._check(self._lib.srcnn_process_f32(self._h, _fp(x3), x3.strides[1] // 4 if h > 1 else w,
+                                                x3.strides[0] // 4 if c > 1 else 0, w, h, _fp(out), dst_w, dst_w * dst_h, dst_w,
+                                                dst_h))
+        return out if x.ndim == 3 else out[0]
+
+    def process_f32_dev(self, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
+                        dst_frame_pitch, dst_w, dst_h, n_frames=1):
+        """srcnn_process_f32_dev: resize + model on device memory, the channel count from the loaded model, asynchronous on
+        the context's stream; equals resize_cubic_f32_dev followed by forward_f32_dev bit for bit."""
+        self._check(self._lib.srcnn_process_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                                                    dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, n_frames))
 
     def set_input_range(self, r: float):
         """The largest |input| of a float call (srcnn_set_input_range): 255 by default, 1.0 for [0, 1] data.  A setting of the
@@ -954,6 +1016,20 @@ def process_bgr(self, bgr, scale):
 def process_bgr_dev(self, d_bgr, stride, width, height, scale, d_out, out_stride):
     self._check(self._lib.srcnn_process_bgr_dev(self._h, d_bgr, stride, width, height, float(scale),
                                                 d_out, out_stride))
+
+
+def cubic_f32_taps(src_n: int, dst_n: int):
+    """The float resize's table of one axis (srcnn_cubic_f32_taps; host only, needs no GPU): (first, coef) with first[d] the
+    unclamped floor of the source coordinate of output d (int32, taps first - 1 .. first + 2) and coef[d] its four float32
+    coefficients."""
+    if src_n <= 0 or dst_n <= 0:
+        raise ValueError(f"cubic_f32_taps: sizes {src_n} -> {dst_n} (both must be positive)")
+    first = np.empty(dst_n, np.int32)
+    coef = np.empty((dst_n, 4), np.float32)
+    rc = load_library().srcnn_cubic_f32_taps(int(src_n), int(dst_n), first.ctypes.data_as(C.POINTER(C.c_int)), _fp(coef))
+    if rc != 0:
+        raise SrcnnError(rc, "cubic_f32_taps")
+    return first, coef
 
 
 def stripe_rows(height: int, n_parts: int, index: int):

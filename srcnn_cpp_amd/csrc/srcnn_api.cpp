@@ -131,7 +131,8 @@ void srcnn_destroy(srcnn_ctx *c)
     (void)hipDeviceSynchronize();          // work on any stream the context was given may still use its buffers
     for (DevBuf *b : {&c->wfrag, &c->wraw, &c->in_u8, &c->out_u8, &c->pre_f32, &c->planes, &c->plane1, &c->kern, &c->sink,
                       &c->bgr_in, &c->bgr_out, &c->ycc_lo, &c->ycc_hi, &c->y_sr, &c->tables, &c->wfrag16,
-                      &c->band_top, &c->band_bot, &c->stripe_ext, &c->sp_table, &c->sp16_table, &c->sp_map64, &c->sp_map32})
+                      &c->band_top, &c->band_bot, &c->stripe_ext, &c->sp_table, &c->sp16_table, &c->sp_map64, &c->sp_map32,
+                      &c->f32_tables, &c->f32_lo, &c->f32_hi, &c->f32_work})
         release(*b);
     if (c->sp_done) (void)hipEventDestroy(c->sp_done);
     for (int k = 0; k < srcnn_ctx::kHaloSets; ++k) {
@@ -421,6 +422,22 @@ int srcnn_debug_resize_variant(int sw, int sh, int dw, int dh, int dword_ok)
 {
     if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return SRCNN_ERR_INVALID;
     return resize_variant(sw, sh, dw, dh, dword_ok != 0);
+}
+
+/* ... and the same for the float32 resize: 1 tiled, 0 direct (resize_f32_variant(), what launch_resize_cubic_f32 asks); F32_RT,
+ * F32_RMAX, F32_SMAX, columns per tile. */
+int srcnn_debug_resize_f32_variant(int sw, int sh, int dw, int dh)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return SRCNN_ERR_INVALID;
+    return resize_f32_variant(sw, sh, dw, dh);
+}
+
+int srcnn_debug_resize_f32_limits(int *out4)
+{
+    if (!out4) return SRCNN_ERR_INVALID;
+    const int v[4] = {F32_RT, F32_RMAX, F32_SMAX, 256};
+    for (int k = 0; k < 4; ++k) out4[k] = v[k];
+    return SRCNN_OK;
 }
 
 int srcnn_debug_resize_limits(int *out6)

@@ -7,6 +7,7 @@
 //   srcnn_host.cpp    host-buffer entry points: staging, band / frame pipelines, the reference call surface, the pipeline steps
 //   srcnn_multi.cpp   several GPUs from one host process: row-striped plane, frame ranges
 //   srcnn_spatial.cpp the banded path (9-3-5 / 9-5-5, zero padding, colour models): weight table, gate, band loop, entry points
+//   srcnn_resize_f32.cpp the cubic resize of float32 planes in front of the float image path: tap tables, entry points
 #pragma once
 #include "../../include/srcnn_amd.h"
 #include "srcnn_kernels.h"
@@ -223,6 +224,12 @@ struct srcnn_ctx {
     // pipeline steps around the conv path
     srcnn::host::DevBuf bgr_in, bgr_out, ycc_lo, ycc_hi, y_sr, tables;
     int tab_sw = 0, tab_sh = 0, tab_dw = 0, tab_dh = 0;   // geometry the uploaded cubic tables are for
+    // The float32 cubic resize (srcnn_resize_cubic_f32*, srcnn_process_f32*): the tables of one geometry and the stream of the
+    // last launch that read them (ensure_tables_f32), the staging of the host-memory forms, and the one-frame workspace of
+    // srcnn_process_f32* (channels x dst_w x dst_h floats, grown on demand)
+    srcnn::host::DevBuf f32_tables, f32_lo, f32_hi, f32_work;
+    int ftab_sw = 0, ftab_sh = 0, ftab_dw = 0, ftab_dh = 0;
+    hipStream_t ftab_stream = nullptr;
     // second lane of the host-frame pipeline (srcnn_forward_y_frames)
     // explicit work items of single-round launches (build_items): a small cache of device tables, one per
     // launch geometry, so that a caller alternating between a few plane sizes never waits for an upload
@@ -407,6 +414,11 @@ int forward_banded(srcnn_ctx *c, const uint8_t *src, size_t src_stride, int px_s
 // the gate of the stripe entry points: SRCNN_OK, or SRCNN_ERR_STATE and the reason.  kind: what the entry point takes
 enum StripeKind { STRIPE_Y = 0, STRIPE_COLOR = 1, STRIPE_F32 = 2 };    // one byte channel, 3-byte pixels, 1 or 3 float planes
 int model_rows_refusal(srcnn_ctx *c, StripeKind kind = STRIPE_Y);
+// the float planes of a call (C channels x n_frames frames): elements spanned from the first, and whether the planes the call
+// WRITES are disjoint; the gate of srcnn_forward_f32 for srcnn_process_f32*
+size_t f32_span(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames);
+bool f32_planes_disjoint(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames);
+int forward_f32_refusal(srcnn_ctx *c);
 constexpr size_t kSpatialWorkBytes = (size_t)512 << 20;     // bound of the two band maps (include/srcnn_amd.h, srcnn_set_model)
 extern const char *const kNoModel;
 
@@ -452,6 +464,15 @@ bool bad_pitch(size_t plane_pitch);
 // may_defer: the caller is one of the device entry points whose contract allows seam deferral (srcnn_set_seam_deferral)
 int run_strip(srcnn_ctx *c, int mode, StripParams p, int n_frames, int fix_frame = 0, int fix_frames = 1, bool may_defer = false);
 int flush_seams(srcnn_ctx *c);
+
+// ---- srcnn_resize_f32.cpp: the float32 cubic resize ----
+// the one table builder (also srcnn_cubic_f32_taps), and the tables of a geometry on the device
+void cubic_f32_taps(int n_src, int n_dst, int *first, float *coef);
+struct ResizeTablesF32 {
+    const int *xfirst, *yfirst;
+    const float *xcoef, *ycoef;
+};
+int ensure_tables_f32(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResizeTablesF32 *t);
 
 // ---- srcnn_host.cpp ----
 void cubic_table(int n_src, int n_dst, int *ofs, short *coef);

@@ -345,6 +345,31 @@ inline int resize_variant(int sw, int sh, int dw, int dh, bool dword_ok)
     return RESIZE_DIRECT;
 }
 
+// The float32 cubic resize (srcnn_resize_cubic_f32*, torch's bicubic with half-pixel centres) has two forms.  tiled: a workgroup
+// produces F32_RT output rows x 256 columns (four row groups of F32_RPT rows, four adjacent columns per thread) from at most
+// F32_RMAX source rows x F32_SMAX source columns held in LDS: 2 x 20 KB per workgroup, three workgroups per CU.  direct: one
+// output element per lane, its 16 taps from global memory -- every ratio whose tile span does not fit (down-scaling below 1).
+constexpr int F32_RT = 16;         // output rows per workgroup
+constexpr int F32_RPT = F32_RT / 4;
+constexpr int F32_RMAX = 20;       // source rows a tile may span (ratio 1: 16 + 4)
+constexpr int F32_SMAX = 264;      // source columns a 256-wide tile may span (ratio 1: 256 + 5)
+enum { RESIZE_F32_DIRECT = 0, RESIZE_F32_TILED = 1 };
+// Which form resizes (sw x sh) -> (dw x dh): the ONE place that keeps a float tile inside its LDS arrays, by the span bound
+// of resize_variant() above (the first tap of output d is floor((d + 0.5) * s / n - 0.5) - 1 on both paths).
+inline int resize_f32_variant(int sw, int sh, int dw, int dh)
+{
+    const long span = ((long)F32_RT * sh + dh - 1) / dh + 4;
+    const long cspan = (256L * sw + dw - 1) / dw + 5;
+    return (span <= F32_RMAX && cspan <= F32_SMAX) ? RESIZE_F32_TILED : RESIZE_F32_DIRECT;
+}
+// `channels` planes x n_frames frames of float32 in one launch; strides and pitches in floats, for source and destination
+// separately.  xfirst / yfirst: first[d] = floor(r), unclamped (the taps are first - 1 .. first + 2, each clamped to the plane
+// by the kernels); xcoef / ycoef: four float32 coefficients per output column / row (srcnn_cubic_f32_taps).  Both forms sum
+// in the same order and give the same bits.
+hipError_t launch_resize_cubic_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *dst,
+                                   long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int channels, int n_frames,
+                                   const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st);
+
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);
 hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8_t *planes, long pstride,
                             long ppitch, hipStream_t st);

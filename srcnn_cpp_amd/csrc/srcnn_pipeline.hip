@@ -9,6 +9,8 @@
 // oracle/opencv_steps.c; it is integer work, so the kernels are bit-exact
 // against that restatement.  One byte in, one byte out per element: no reuse,
 // no LDS, consecutive lanes on consecutive bytes.
+// At the end of the file: the cubic resize of float32 planes, torch's bicubic
+// (srcnn_resize_cubic_f32*, the step in front of the float image path).
 #include "srcnn_kernels.h"
 
 // No FMA contraction anywhere in this file (also given on the command line, srcnn_cpp_amd/build.py): the vertical pass of
@@ -452,6 +454,149 @@ hipError_t launch_resize_cubic(const uint8_t *src, long sstride, long spitch, in
     else
         hipLaunchKernelGGL(resize_cubic_kernel, dim3((dw + 255) / 256, dh, n_planes), dim3(256), 0, st, src, sstride,
                            spitch, sw, sh, dst, dstride, dpitch, dw, dh, xofs, alpha, yofs, beta);
+    return hipGetLastError();
+}
+
+// ---- cubic resize of float32 planes (srcnn_resize_cubic_f32*, srcnn_process_f32*) --------------------------------------
+// torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=False) on planar float32: Keys cubic,
+// A = -0.75, half-pixel centres, tap indices clamped to the plane.  The first-tap indices and the coefficients come from the
+// host in tables (srcnn_cubic_f32_taps: float64 arithmetic, coefficients rounded once to float32).
+// Summation order, the same in both kernels: the horizontal pass first, then the vertical pass, each four products summed in
+// ascending tap order, ((c0 s0 + c1 s1) + c2 s2) + c3 s3, all float32.  The sums are SEPARATE multiplies and adds, every
+// product and every sum rounded on its own (this unit is built without FMA contraction), so both kernels give the same bits.
+// Nothing is clamped but the tap INDEX: the output may overshoot the input's range, and a non-finite input spreads over the
+// outputs whose 4 x 4 support holds it and no further.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float cubic_sum4(float s0, float s1, float s2, float s3, const f32x4 c)
+{
+    float r = __fmul_rn(s0, c[0]);
+    r = __fadd_rn(r, __fmul_rn(s1, c[1]));
+    r = __fadd_rn(r, __fmul_rn(s2, c[2]));
+    return __fadd_rn(r, __fmul_rn(s3, c[3]));
+}
+
+// Where the planes of a call lie: plane z = frame * channels + channel (strides and pitches in floats)
+struct F32ResizeArgs {
+    const float *src;
+    long sstride, sch_pitch, sframe_pitch;
+    int sw, sh;
+    float *dst;
+    long dstride, dch_pitch, dframe_pitch;
+    int dw, dh;
+    int channels, n_planes;
+    const int *xfirst, *yfirst;
+    const float *xcoef, *ycoef;     // 16-byte aligned: one f32x4 per output column / row
+};
+
+// Direct form: one output element per lane, the 16 taps from global memory.  Every index is clamped before it is used; lanes
+// beyond the last column do nothing.  Rows and planes beyond the grid's y / z limits are walked by the same blocks.
+__global__ __launch_bounds__(256) void resize_cubic_f32_direct_kernel(const F32ResizeArgs p)
+{
+    const int dx = blockIdx.x * 256 + threadIdx.x;
+    if (dx >= p.dw) return;
+    const int x0 = p.xfirst[dx] - 1;
+    int xs[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xs[k] = min(max(x0 + k, 0), p.sw - 1);
+    const f32x4 a = *reinterpret_cast<const f32x4 *>(p.xcoef + 4L * dx);
+    for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
+        const int frame = z / p.channels, ch = z - frame * p.channels;
+        const float *s = p.src + frame * p.sframe_pitch + ch * p.sch_pitch;
+        float *d = p.dst + frame * p.dframe_pitch + ch * p.dch_pitch;
+        for (int dy = blockIdx.y; dy < p.dh; dy += gridDim.y) {
+            const int y0 = p.yfirst[dy] - 1;
+            float hs[4];
+#pragma unroll
+            for (int ky = 0; ky < 4; ++ky) {
+                const float *row = s + (long)min(max(y0 + ky, 0), p.sh - 1) * p.sstride;
+                hs[ky] = cubic_sum4(row[xs[0]], row[xs[1]], row[xs[2]], row[xs[3]], a);
+            }
+            d[(long)dy * p.dstride + dx] = cubic_sum4(hs[0], hs[1], hs[2], hs[3], *reinterpret_cast<const f32x4 *>(p.ycoef + 4L * dy));
+        }
+    }
+}
+
+// Tiled form: a workgroup produces F32_RT output rows x 256 columns.  The source rows and columns the tile spans are loaded
+// into LDS once (consecutive lanes on consecutive floats, the replicate border applied by clamping the index), the horizontal
+// pass of every one of those rows is done once from LDS (thread = output column), the vertical pass reads the horizontal
+// results (thread = four adjacent columns of F32_RPT rows) and stores 16 bytes per lane where the address allows it: scalar
+// stores at a ragged right edge and wherever base, stride and column leave the four floats unaligned.
+// (at most F32_RMAX source rows x F32_SMAX source columns: srcnn_kernels.h, where resize_f32_variant() checks a geometry
+// against them before this kernel is chosen)
+__global__ __launch_bounds__(256) void resize_cubic_f32_tiled_kernel(const F32ResizeArgs p)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    const int tid = threadIdx.x;
+    const int dx0 = blockIdx.x * 256;
+    const int c_lo = p.xfirst[dx0] - 1, c_hi = p.xfirst[min(dx0 + 255, p.dw - 1)] + 2;     // unclamped source columns of the tile
+    const int ncol = c_hi - c_lo + 1;
+    const int dxc = min(dx0 + tid, p.dw - 1);
+    const int x0 = p.xfirst[dxc] - 1 - c_lo;
+    const f32x4 a = *reinterpret_cast<const f32x4 *>(p.xcoef + 4L * dxc);
+    const int tx = tid & 63, ty = tid >> 6, dx = dx0 + 4 * tx;
+    const int n_row_tiles = (p.dh + F32_RT - 1) / F32_RT;
+    for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
+        const int frame = z / p.channels, ch = z - frame * p.channels;
+        const float *s = p.src + frame * p.sframe_pitch + ch * p.sch_pitch;
+        float *d = p.dst + frame * p.dframe_pitch + ch * p.dch_pitch;
+        for (int rt = blockIdx.y; rt < n_row_tiles; rt += gridDim.y) {
+            const int dy0 = rt * F32_RT, dy1 = min(dy0 + F32_RT, p.dh);
+            const int r_lo = p.yfirst[dy0] - 1, r_hi = p.yfirst[dy1 - 1] + 2;              // ... and rows
+            const int nrow = r_hi - r_lo + 1;
+            // (a thread still in the vertical pass of the tile before has not reached the barrier below: hbuf is not written
+            // yet, and sbuf was last read before that tile's second barrier)
+            for (int e = tid; e < nrow * ncol; e += 256) {
+                const int rr = e / ncol, cc = e - rr * ncol;
+                sbuf[rr][cc] = s[(long)min(max(r_lo + rr, 0), p.sh - 1) * p.sstride + min(max(c_lo + cc, 0), p.sw - 1)];
+            }
+            __syncthreads();
+            for (int rr = 0; rr < nrow; ++rr)
+                hbuf[rr][tid] = cubic_sum4(sbuf[rr][x0], sbuf[rr][x0 + 1], sbuf[rr][x0 + 2], sbuf[rr][x0 + 3], a);
+            __syncthreads();
+            if (dx < p.dw) {
+#pragma unroll
+                for (int r = 0; r < F32_RPT; ++r) {
+                    const int dy = dy0 + F32_RPT * ty + r;
+                    if (dy >= dy1) break;
+                    const int j = p.yfirst[dy] - 1 - r_lo;
+                    const f32x4 b = *reinterpret_cast<const f32x4 *>(p.ycoef + 4L * dy);
+                    f32x4 h[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) h[k] = *reinterpret_cast<const f32x4 *>(&hbuf[j + k][4 * tx]);
+                    f32x4 v;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[c] = cubic_sum4(h[0][c], h[1][c], h[2][c], h[3][c], b);
+                    float *o = d + (long)dy * p.dstride + dx;
+                    if (dx + 3 < p.dw && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+                        *reinterpret_cast<f32x4 *>(o) = v;
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            if (dx + c < p.dw) o[c] = v[c];
+                    }
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_resize_cubic_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *dst,
+                                   long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int channels, int n_frames,
+                                   const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels <= 0 || n_frames <= 0 || (long)channels * n_frames > 0x7fffffffL)
+        return hipErrorInvalidValue;
+    const F32ResizeArgs p{src, sstride, sch_pitch, sframe_pitch, sw, sh, dst, dstride, dch_pitch, dframe_pitch, dw, dh,
+                          channels, channels * n_frames, xfirst, yfirst, xcoef, ycoef};
+    auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };      // grid y and z: the kernels walk what lies beyond
+    const unsigned gz = cap(p.n_planes);
+    if (resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED)      // the tile's LDS limits: srcnn_kernels.h
+        hipLaunchKernelGGL(resize_cubic_f32_tiled_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), gz),
+                           dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL(resize_cubic_f32_direct_kernel, dim3((dw + 255) / 256, cap(dh), gz), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

@@ -1,0 +1,226 @@
+// srcnn_resize_f32.cpp -- the step in front of the float image path: the cubic resize of float32 planes as torch's bicubic
+// interpolation defines it (srcnn_cubic_f32_taps, srcnn_resize_cubic_f32*), and resize + model in one call (srcnn_process_f32*).
+// The tap tables are built here, on the host in float64; the kernels are in srcnn_pipeline.hip (launch_resize_cubic_f32).
+#include "srcnn_ctx.h"
+
+using namespace srcnn;
+using namespace srcnn::host;
+
+namespace srcnn {
+namespace host {
+
+// Keys cubic (A = -0.75) taps of one axis as torch.nn.functional.interpolate(mode="bicubic", align_corners=False) defines
+// them, for float32 planes: r = (n_src / n_dst) * (d + 0.5) - 0.5, first[d] = floor(r) (unclamped: the taps are first - 1 ..
+// first + 2, the kernels clamp each index), t = r - first[d], coef[d] = c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with
+// c1(x) = ((A + 2) x - (A + 3)) x^2 + 1 and c2(x) = ((A x - 5 A) x + 8 A) x - 4 A.  All of it in float64, the coefficients
+// rounded once to float32 (torch does the coordinates in float32 and drifts from this at non-dyadic ratios).
+void cubic_f32_taps(int n_src, int n_dst, int *first, float *coef)
+{
+    const double scale = (double)n_src / (double)n_dst, A = -0.75;
+    auto c1 = [A](double x) { return ((A + 2) * x - (A + 3)) * x * x + 1; };
+    auto c2 = [A](double x) { return ((A * x - 5 * A) * x + 8 * A) * x - 4 * A; };
+    for (int d = 0; d < n_dst; ++d) {
+        const double r = scale * (d + 0.5) - 0.5;
+        const double i = std::floor(r), t = r - i;
+        first[d] = (int)i;
+        coef[4 * (size_t)d + 0] = (float)c2(t + 1);
+        coef[4 * (size_t)d + 1] = (float)c1(t);
+        coef[4 * (size_t)d + 2] = (float)c1(1 - t);
+        coef[4 * (size_t)d + 3] = (float)c2(2 - t);
+    }
+}
+
+// The float tables of a (sw x sh) -> (dw x dh) resize on the device, cached like the 8-bit ones above.  Layout: float
+// xcoef[4 dw], ycoef[4 dh] (16-byte aligned: the kernels load a row of four at once), then int xfirst[dw], yfirst[dh].
+int ensure_tables_f32(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResizeTablesF32 *t)
+{
+    const size_t n = (size_t)dw + dh;
+    if (!(c->f32_tables.p && c->ftab_sw == sw && c->ftab_sh == sh && c->ftab_dw == dw && c->ftab_dh == dh)) {
+        std::vector<float> coef(4 * n);
+        std::vector<int> first(n);
+        cubic_f32_taps(sw, dw, first.data(), coef.data());
+        cubic_f32_taps(sh, dh, first.data() + dw, coef.data() + 4 * (size_t)dw);
+        // an earlier launch may still read the old tables, on this stream or on the one the context had then
+        if (c->ftab_stream && c->ftab_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->ftab_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->ftab_sw = 0;
+        int rc;
+        if ((rc = reserve(c, c->f32_tables, n * 20))) return rc;
+        HIP_TRY(c, hipMemcpy(c->f32_tables.p, coef.data(), n * 16, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(static_cast<char *>(c->f32_tables.p) + n * 16, first.data(), n * 4, hipMemcpyHostToDevice));
+        c->ftab_sw = sw; c->ftab_sh = sh; c->ftab_dw = dw; c->ftab_dh = dh;
+    }
+    c->ftab_stream = c->stream;
+    t->xcoef = static_cast<const float *>(c->f32_tables.p);
+    t->ycoef = t->xcoef + 4 * (size_t)dw;
+    t->xfirst = reinterpret_cast<const int *>(t->xcoef + 4 * n);
+    t->yfirst = t->xfirst + dw;
+    return SRCNN_OK;
+}
+
+}  // namespace host
+}  // namespace srcnn
+
+// SRCNN_OK, or SRCNN_ERR_INVALID and the reason: the planes of a float resize (C channels x n_frames frames each side)
+static int resize_f32_refusal(srcnn_ctx *c, const char *what, const float *src, size_t src_stride, size_t src_ch_pitch,
+                              size_t src_frame_pitch, int src_w, int src_h, const float *dst, size_t dst_stride, size_t dst_ch_pitch,
+                              size_t dst_frame_pitch, int dst_w, int dst_h, int C, int n_frames)
+{
+    constexpr size_t kMaxPitch = (size_t)1 << 40;      // (elements: every offset the kernels form stays far inside 63 bits)
+    if (bad_plane(src, src_stride, src_w, src_h) || bad_plane(dst, dst_stride, dst_w, dst_h) || C <= 0 || n_frames <= 0 ||
+        (long)C * n_frames > 0x7fffffffL || src_ch_pitch >= kMaxPitch || dst_ch_pitch >= kMaxPitch || src_frame_pitch >= kMaxPitch ||
+        dst_frame_pitch >= kMaxPitch)
+        return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    if (!f32_planes_disjoint(C, dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, n_frames))
+        return fail(c, SRCNN_ERR_INVALID, "%s: the output planes overlap each other (channel pitch %zu, frame pitch %zu floats for %d "
+                                          "channel(s) and %d frame(s))", what, dst_ch_pitch, dst_frame_pitch, C, n_frames);
+    if (ranges_overlap(src, sizeof(float) * f32_span(C, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, n_frames), dst,
+                       sizeof(float) * f32_span(C, dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, n_frames)))
+        return fail(c, SRCNN_ERR_INVALID, "%s: src and dst overlap (the resize cannot run in place)", what);
+    return SRCNN_OK;
+}
+
+// the launch behind every float resize: checked arguments, device memory, the context's stream
+static int resize_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
+                          int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                          int C, int n_frames)
+{
+    ResizeTablesF32 t;
+    int rc;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    HIP_TRY(c, launch_resize_cubic_f32(d_src, (long)src_stride, (long)src_ch_pitch, (long)src_frame_pitch, src_w, src_h, d_dst,
+                                       (long)dst_stride, (long)dst_ch_pitch, (long)dst_frame_pitch, dst_w, dst_h, C, n_frames, t.xfirst,
+                                       t.xcoef, t.yfirst, t.ycoef, c->stream));
+    return SRCNN_OK;
+}
+
+// Resize + model on device memory: every channel of a frame into the context's one-frame workspace, then the model on that
+// frame exactly as srcnn_forward_f32_dev runs it; frame after frame on the context's stream.
+static int process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
+                           int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                           int n_frames)
+{
+    const int C = c->channels;
+    const size_t plane = (size_t)dst_w * dst_h;
+    int rc;
+    // the workspace (and the band maps) were last used on another stream: wait for that work before the resize overwrites it
+    if (c->sp_done && c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
+    if ((rc = reserve(c, c->f32_work, C * plane * sizeof(float)))) return rc;      // (growing waits for the device)
+    float *work = static_cast<float *>(c->f32_work.p);
+    for (int f = 0; f < n_frames; ++f) {
+        if ((rc = resize_f32_dev(c, d_src + (size_t)f * src_frame_pitch, src_stride, src_ch_pitch, 0, src_w, src_h, work, (size_t)dst_w,
+                                 plane, 0, dst_w, dst_h, C, 1)))
+            return rc;
+        BandedPlanes io;
+        io.f32 = true;
+        io.src = work;
+        io.src_stride = (size_t)dst_w;
+        io.ch_step = C == 1 ? 0 : plane;
+        io.dst = d_dst + (size_t)f * dst_frame_pitch;
+        io.dst_stride = dst_stride;
+        io.dst_ch_pitch = C == 1 ? 0 : dst_ch_pitch;
+        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
+    }
+    return SRCNN_OK;
+}
+
+extern "C" {
+
+int srcnn_cubic_f32_taps(int src_n, int dst_n, int *first, float *coef)
+{
+    if (src_n <= 0 || dst_n <= 0 || !first || !coef) return SRCNN_ERR_INVALID;
+    cubic_f32_taps(src_n, dst_n, first, coef);
+    return SRCNN_OK;
+}
+
+int srcnn_resize_cubic_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
+                               int src_w, int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch,
+                               int dst_w, int dst_h, int channels, int n_frames)
+{
+    BIND(c);
+    int rc;
+    if ((rc = resize_f32_refusal(c, "resize_cubic_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                                 dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels, n_frames)))
+        return rc;
+    return resize_f32_dev(c, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
+                          dst_frame_pitch, dst_w, dst_h, channels, n_frames);
+}
+
+// one image of `C` planes between host memory and the packed device buffers lo (src_w x src_h) / hi (dst_w x dst_h)
+static int f32_stage_in(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int w, int h, int C, float **d_lo)
+{
+    const size_t plane = (size_t)w * h, row = (size_t)w * sizeof(float);
+    int rc;
+    if ((rc = reserve(c, c->f32_lo, C * plane * sizeof(float)))) return rc;
+    *d_lo = static_cast<float *>(c->f32_lo.p);
+    for (int ch = 0; ch < C; ++ch)
+        HIP_TRY(c, hipMemcpy2DAsync(*d_lo + ch * plane, row, src + ch * src_ch_pitch, src_stride * sizeof(float), row, h,
+                                    hipMemcpyHostToDevice, c->stream));
+    return SRCNN_OK;
+}
+static int f32_stage_out(srcnn_ctx *c, float *dst, size_t dst_stride, size_t dst_ch_pitch, int w, int h, int C, const float *d_hi)
+{
+    const size_t plane = (size_t)w * h, row = (size_t)w * sizeof(float);
+    for (int ch = 0; ch < C; ++ch)
+        HIP_TRY(c, hipMemcpy2DAsync(dst + ch * dst_ch_pitch, dst_stride * sizeof(float), d_hi + ch * plane, row, row, h,
+                                    hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SRCNN_OK;
+}
+
+int srcnn_resize_cubic_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
+                           size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h, int channels)
+{
+    BIND(c);
+    int rc;
+    if ((rc = resize_f32_refusal(c, "resize_cubic_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch,
+                                 0, dst_w, dst_h, channels, 1)))
+        return rc;
+    const size_t hi = (size_t)dst_w * dst_h;
+    float *d_lo = nullptr;
+    if ((rc = reserve(c, c->f32_hi, channels * hi * sizeof(float)))) return rc;
+    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, channels, &d_lo))) return rc;
+    float *d_hi = static_cast<float *>(c->f32_hi.p);
+    if ((rc = resize_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h,
+                             channels, 1)))
+        return rc;
+    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels, d_hi);
+}
+
+int srcnn_process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
+                          int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                          int n_frames)
+{
+    BIND(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    if ((rc = resize_f32_refusal(c, "process_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                                 dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, c->channels, n_frames)))
+        return rc;
+    if ((rc = forward_f32_refusal(c))) return rc;      // the gate of srcnn_forward_f32, before anything is launched
+    return process_f32_dev(c, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
+                           dst_frame_pitch, dst_w, dst_h, n_frames);
+}
+
+int srcnn_process_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
+                      size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h)
+{
+    BIND(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const int C = c->channels;
+    if ((rc = resize_f32_refusal(c, "process_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch, 0,
+                                 dst_w, dst_h, C, 1)))
+        return rc;
+    if ((rc = forward_f32_refusal(c))) return rc;      // before anything is staged
+    const size_t hi = (size_t)dst_w * dst_h;
+    float *d_lo = nullptr;
+    if ((rc = reserve(c, c->f32_hi, C * hi * sizeof(float)))) return rc;
+    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, C, &d_lo))) return rc;
+    float *d_hi = static_cast<float *>(c->f32_hi.p);
+    if ((rc = process_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h, 1)))
+        return rc;
+    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, C, d_hi);
+}
+
+}  // extern "C"

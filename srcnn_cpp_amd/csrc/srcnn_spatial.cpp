@@ -334,6 +334,24 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     return SRCNN_OK;
 }
 
+// the float planes of a call: elements spanned from the first, and whether the planes the call WRITES are disjoint (frames of
+// channels, or channels of frames)
+size_t f32_span(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames)
+{
+    return (size_t)(n_frames - 1) * frame_pitch + (size_t)(C - 1) * ch_pitch + (size_t)(height - 1) * stride + (size_t)width;
+}
+bool f32_planes_disjoint(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames)
+{
+    const size_t plane = (size_t)(height - 1) * stride + (size_t)width;
+    if (C == 1) return n_frames == 1 || frame_pitch >= plane;
+    if (n_frames == 1) return ch_pitch >= plane;
+    return (ch_pitch >= plane && frame_pitch >= (size_t)(C - 1) * ch_pitch + plane) ||
+           (frame_pitch >= plane && ch_pitch >= (size_t)(n_frames - 1) * frame_pitch + plane);
+}
+
+// the gate of the float image path for the callers outside this file (srcnn_process_f32*)
+int forward_f32_refusal(srcnn_ctx *c) { return banded_refusal(c, true); }
+
 }  // namespace host
 }  // namespace srcnn
 
@@ -479,8 +497,6 @@ int srcnn_forward_color(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uin
 /* ---- row stripes of every whole model (include/srcnn_amd.h) ---- */
 
 int srcnn_model_halo_rows(const srcnn_ctx *c) { return c ? kHaloRows + (c->f2 - 1) / 2 : SRCNN_ERR_INVALID; }
-
-static bool f32_planes_disjoint(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames);
 
 // Every stripe call.  kind: what the planes are -- one byte channel, interleaved 3-byte pixels, or float planes of the loaded
 // model's channel count; strides and pitches in elements (bytes, or floats).  src_rows < 0: the plain form, src holds every row
@@ -650,21 +666,6 @@ int srcnn_set_input_range(srcnn_ctx *c, float r)
 }
 
 float srcnn_get_input_range(const srcnn_ctx *c) { return c ? c->input_range : (float)SRCNN_ERR_INVALID; }
-
-// the float planes of a call: elements spanned from the first, and whether the planes the call WRITES are disjoint (frames of
-// channels, or channels of frames)
-static size_t f32_span(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames)
-{
-    return (size_t)(n_frames - 1) * frame_pitch + (size_t)(C - 1) * ch_pitch + (size_t)(height - 1) * stride + (size_t)width;
-}
-static bool f32_planes_disjoint(int C, size_t stride, size_t ch_pitch, size_t frame_pitch, int width, int height, int n_frames)
-{
-    const size_t plane = (size_t)(height - 1) * stride + (size_t)width;
-    if (C == 1) return n_frames == 1 || frame_pitch >= plane;
-    if (n_frames == 1) return ch_pitch >= plane;
-    return (ch_pitch >= plane && frame_pitch >= (size_t)(C - 1) * ch_pitch + plane) ||
-           (frame_pitch >= plane && ch_pitch >= (size_t)(n_frames - 1) * frame_pitch + plane);
-}
 
 int srcnn_forward_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
                           float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int width, int height,

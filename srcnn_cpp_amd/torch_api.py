@@ -3,6 +3,7 @@
     from srcnn_cpp_amd.torch_api import compile_module
     fast = compile_module(module)              # an nn.Module with conv1, conv2, conv3 (9-f2-5, 1 or 3 channels)
     y = fast(x)                                # x: float32 (N, C, H, W) or (C, H, W) on that GPU; y ~ module(x)
+    z = fast.upscale(lr, scale=2)              # ~ module(F.interpolate(lr, size, mode="bicubic", align_corners=False))
 
 The weights go in as they are (the data is already in the model's units), the module's padding mode is the context's padding,
 the call runs on torch.cuda.current_stream() and reads the tensor where it lies: data_ptr() and strides, no copy.  torch is
@@ -46,6 +47,18 @@ def check_input(x, channels: int, device_index: int):
     return n, h, w, (sh if h > 1 else w), (sc if c > 1 else 0), (sn if n > 1 else 0)
 
 
+def check_size(size):
+    """ValueError unless size is (H, W), two positive integers; returns them as ints."""
+    try:
+        dh, dw = size
+    except (TypeError, ValueError):
+        raise ValueError(f"size {size!r}: expected (H, W)") from None
+    for v in (dh, dw):
+        if isinstance(v, bool) or int(v) != v or v <= 0:
+            raise ValueError(f"size {size!r}: expected two positive integers (H, W)")
+    return int(dh), int(dw)
+
+
 class CompiledModule:
     """What compile_module returns: a callable that owns its Context (one GPU, the module's weights and padding)."""
 
@@ -53,26 +66,58 @@ class CompiledModule:
         self.ctx, self.channels, self.device = ctx, channels, device
         self._side = None
 
+    def _on_current_stream(self, device, launch):
+        """Run launch() -- calls on self.ctx -- as if on torch.cuda.current_stream(device).
+        The library takes a stream handle and reads 0 as "the context's own stream", so torch's default stream (handle 0)
+        cannot be handed over: the call then runs on a side stream of this callable, ordered after and before the default
+        stream by events, which for the caller is the same as running on it."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        run_on = cur
+        if cur.cuda_stream == 0:
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=device)
+            run_on = self._side
+            run_on.wait_stream(cur)
+        self.ctx.set_stream(run_on.cuda_stream)
+        launch()
+        if run_on is not cur:
+            cur.wait_stream(run_on)
+
     def __call__(self, x):
         import torch
         n, h, w, stride, ch_pitch, frame_pitch = check_input(x, self.channels, self.device)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        cur = torch.cuda.current_stream(x.device)
-        # The library takes a stream handle and reads 0 as "the context's own stream", so torch's default stream (handle 0)
-        # cannot be handed over: the call then runs on a side stream of this callable, ordered after and before the default
-        # stream by events, which for the caller is the same as running on it.
-        run_on = cur
-        if cur.cuda_stream == 0:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=x.device)
-            run_on = self._side
-            run_on.wait_stream(cur)
-        self.ctx.set_stream(run_on.cuda_stream)
-        self.ctx.forward_f32_dev(x.data_ptr(), stride, ch_pitch, frame_pitch, out.data_ptr(), w, h * w, self.channels * h * w,
-                                 w, h, n)
-        if run_on is not cur:
-            cur.wait_stream(run_on)
+        self._on_current_stream(x.device, lambda: self.ctx.forward_f32_dev(
+            x.data_ptr(), stride, ch_pitch, frame_pitch, out.data_ptr(), w, h * w, self.channels * h * w, w, h, n))
         return out
+
+    def _resized(self, x, size, call):
+        import torch
+        n, h, w, stride, ch_pitch, frame_pitch = check_input(x, self.channels, self.device)
+        dh, dw = check_size(size)
+        out = torch.empty(tuple(x.shape[:-2]) + (dh, dw), dtype=torch.float32, device=x.device)
+        self._on_current_stream(x.device, lambda: call(x.data_ptr(), stride, ch_pitch, frame_pitch, w, h, out.data_ptr(), dw,
+                                                       dh * dw, self.channels * dh * dw, dw, dh, n))
+        return out
+
+    def resize(self, x, size):
+        """F.interpolate(x, size=size, mode="bicubic", align_corners=False) with this library's kernel: size = (H, W) of the
+        result.  The same tensors as __call__ takes, read where they lie, on the current stream."""
+        return self._resized(x, size, lambda *a: self.ctx.resize_cubic_f32_dev(*a[:-1], self.channels, a[-1]))
+
+    def upscale(self, x, scale=None, size=None):
+        """module(F.interpolate(x, size, mode="bicubic", align_corners=False)): the bicubic resize of a low-resolution tensor
+        and the module on the result, in one call and without a full-size intermediate tensor per batch.  Exactly one of
+        scale (size = (int(h * scale), int(w * scale))) and size = (H, W) is given.  Equals self(self.resize(x, size))."""
+        if (scale is None) == (size is None):
+            raise ValueError("upscale: give exactly one of scale and size")
+        if size is None:
+            from . import scaled_size
+            check_input(x, self.channels, self.device)
+            ow, oh = scaled_size(int(x.shape[-1]), int(x.shape[-2]), float(scale))
+            size = (oh, ow)
+        return self._resized(x, size, lambda *a: self.ctx.process_f32_dev(*a))
 
     def close(self):
         self.ctx.close()
