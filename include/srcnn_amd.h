@@ -390,6 +390,44 @@ int srcnn_process_f32_dev(srcnn_ctx *ctx,
 int srcnn_process_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h,
                       float *dst, size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h);
 
+/* A 3-plane float image (RGB, BGR, any order) through a 1-CHANNEL model: what a program around a luma SRCNN does -- resize the
+ * three planes, convert to Y'CbCr, run the model on Y, convert back -- in one call and two launches around the model.
+ *   - Arithmetic.  A Y'CbCr whose chroma rows sum to zero has (1, 1, 1) / (w0 + w1 + w2) as the first column of its inverse, and
+ *     the cubic coefficients sum to 1, so that program collapses to
+ *         out_c = up(x_c) + g (Ysr - Yup),   g = 1 / (w0 + w1 + w2),   Yup = up(Y_lr),   Ysr = model(Yup):
+ *     chroma scale, offsets and matrix cancel and only the luma row matters.  `luma` is that row as data, {w0, w1, w2, offset}
+ *     for the planes in the order given (BT.601 full range on RGB: {0.299, 0.587, 0.114, 0}; reverse the weights for BGR).
+ *     Every step in float32, every product and sum rounded on its own (no fused multiply-add):
+ *       1. Y_lr = ((w0 x0 + w1 x1) + w2 x2) + offset at the SOURCE resolution;
+ *       2. Yup = srcnn_resize_cubic_f32 of Y_lr (same tables, same summation order);
+ *       3. Ysr = the loaded model on Yup, exactly as srcnn_forward_f32_dev runs it;
+ *       4. out_c = U_c + (Ysr - Yup) * g with U_c = srcnn_resize_cubic_f32 of x_c and g = (float)(1.0 / ((double)w0 + w1 + w2));
+ *          with a clamp {lo, hi}: a value below lo becomes lo, one above hi becomes hi (min(max(out_c, lo), hi); a NaN stays).
+ *     The result equals those calls composed, bit for bit.
+ *   - srcnn_luma_gain: g of step 4, host only (no context, no GPU).  SRCNN_ERR_INVALID for a null pointer, a non-finite entry of
+ *     luma, w0 + w1 + w2 <= 0, or a sum so small that g is not finite.
+ *   - The model sees Yup in the image's own units (offset included): load weights for those units, and in SRCNN_MODE_BANDED16
+ *     srcnn_set_input_range must bound |Y| (the resize may overshoot the source's range by a few percent).
+ *   - Layout: that of srcnn_resize_cubic_f32_dev with 3 channels each side.  srcnn_process_rgb_f32_dev: device memory, n_frames
+ *     images one after another, asynchronous on the context's stream; srcnn_process_rgb_f32: one image in host memory, staged
+ *     on the device, returns when dst is complete.  The context keeps a workspace of two planes (Yup, Ysr: 2 x dst_w x dst_h
+ *     floats, the buffer srcnn_process_f32 uses, grown on demand).
+ *   - Gate: that of srcnn_forward_f32 -- SRCNN_ERR_STATE without a model, in a mode other than SRCNN_MODE_MFMA and
+ *     SRCNN_MODE_BANDED16, for per-filter layers -- and SRCNN_ERR_STATE for a loaded 3-channel model (srcnn_process_f32 runs
+ *     that one, on the planes themselves).  SRCNN_ERR_INVALID for what srcnn_resize_cubic_f32 refuses (null pointers, sizes <= 0,
+ *     a stride below the width, n_frames <= 0, output planes that overlap each other or the input), a bad luma (as
+ *     srcnn_luma_gain), a clamp with lo > hi or a NaN, and dst_w < src_w or dst_h < src_h: a super-resolution call does not
+ *     shrink (the same size is allowed: an image that is already up-sampled).  A refused call launches nothing and leaves the
+ *     context usable. */
+int srcnn_luma_gain(const float luma[4], float *g);
+int srcnn_process_rgb_f32_dev(srcnn_ctx *ctx,
+                              const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w, int src_h,
+                              float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                              const float luma[4], const float *clamp /* NULL or {lo, hi} */, int n_frames);
+int srcnn_process_rgb_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h,
+                          float *dst, size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h,
+                          const float luma[4], const float *clamp /* NULL or {lo, hi} */);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

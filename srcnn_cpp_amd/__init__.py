@@ -35,7 +35,7 @@ __all__ = [
     "stripe_rows", "forward_y_frames_multi", "forward_y_lanes_dev", "forward_y_striped", "forward_y_striped_dev",
     "model_striped", "model_striped_dev",
     "model_color_striped", "model_color_striped_dev", "model_striped_f32", "model_striped_f32_dev",
-    "cubic_f32_taps",
+    "cubic_f32_taps", "luma_gain", "luma_for_order", "luma_bt601_studio", "LUMA_BT601",
 ]
 
 _PKG = Path(__file__).resolve().parent
@@ -59,6 +59,8 @@ PAD_ZERO = 1
 _PADDINGS = {"replicate": PAD_REPLICATE, "zero": PAD_ZERO}
 # 2 x (64*81 + 32*64 + 32*25) MAC per output pixel
 FLOP_PER_PIXEL = 16064
+# luma rows {w0, w1, w2, offset} of process_rgb_f32 (srcnn_process_rgb_f32) for planes in R, G, B order: BT.601 full range
+LUMA_BT601 = (0.299, 0.587, 0.114, 0.0)
 
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_NODEVICE, ERR_STATE = -1, -2, -3, -4, -5      # include/srcnn_amd.h
 _ERR = {-1: "invalid argument", -2: "HIP runtime error", -3: "out of memory",
@@ -143,6 +145,9 @@ def load_library() -> C.CDLL:
         "srcnn_resize_cubic_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i, i], i),
         "srcnn_process_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i], i),
         "srcnn_process_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i], i),
+        "srcnn_luma_gain": ([_f32p, _f32p], i),
+        "srcnn_process_rgb_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, _f32p, _f32p], i),
+        "srcnn_process_rgb_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, _f32p, _f32p, i], i),
         "srcnn_set_input_range": ([vp, C.c_float], i),
         "srcnn_get_input_range": ([vp], C.c_float),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
@@ -220,6 +225,7 @@ ABI_SYMBOLS = (
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
     "srcnn_cubic_f32_taps", "srcnn_resize_cubic_f32", "srcnn_resize_cubic_f32_dev", "srcnn_process_f32", "srcnn_process_f32_dev",
+    "srcnn_luma_gain", "srcnn_process_rgb_f32", "srcnn_process_rgb_f32_dev",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -642,6 +648,33 @@ class Context:
         self._check(self._lib.srcnn_process_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
                                                     dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, n_frames))
 
+    def process_rgb_f32(self, x, dst_w, dst_h, luma=LUMA_BT601, clamp=None):
+        """A 3-plane float32 image through the loaded 1-CHANNEL model (srcnn_process_rgb_f32): x is (3, H, W), rows contiguous;
+        returns (3, dst_h, dst_w) = resize(x_c) + g (model(Yup) - Yup) per plane, Yup the resize of the luma
+        ((w0 x0 + w1 x1) + w2 x2) + offset, g = luma_gain(luma); clamp = (lo, hi) bounds the result.  Never shrinks; the same
+        size is allowed.  MODE_MFMA and MODE_BANDED16 only (set_input_range must then bound |Y|)."""
+        x3, dst_w, dst_h = _f32_image(x, "x", dst_w, dst_h)
+        if x.ndim != 3 or x3.shape[0] != 3:
+            raise ValueError(f"x: shape {tuple(x.shape)}: expected (3, H, W)")
+        _, h, w = x3.shape
+        _not_shrinking(w, h, dst_w, dst_h)
+        luma4, clamp2 = _luma4(luma), _clamp2(clamp)
+        out = np.empty((3, dst_h, dst_w), np.float32)
+        self._check(self._lib.srcnn_process_rgb_f32(self._h, _fp(x3), x3.strides[1] // 4 if h > 1 else w, x3.strides[0] // 4, w, h,
+                                                    _fp(out), dst_w, dst_w * dst_h, dst_w, dst_h, luma4, clamp2))
+        return out
+
+    def process_rgb_f32_dev(self, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
+                            dst_frame_pitch, dst_w, dst_h, luma=LUMA_BT601, clamp=None, n_frames=1):
+        """srcnn_process_rgb_f32_dev: device addresses of 3 float32 planes each side, strides and pitches in floats,
+        asynchronous on the context's stream; equals resize_cubic_f32_dev of the planes and of the luma, forward_f32_dev and
+        three float32 operations, bit for bit."""
+        _not_shrinking(src_w, src_h, dst_w, dst_h)
+        luma4, clamp2 = _luma4(luma), _clamp2(clamp)
+        self._check(self._lib.srcnn_process_rgb_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                                                        dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, luma4, clamp2,
+                                                        n_frames))
+
     def set_input_range(self, r: float):
         """The largest |input| of a float call (srcnn_set_input_range): 255 by default, 1.0 for [0, 1] data.  A setting of the
         context; only MODE_BANDED16 reads it, and only in forward_f32 / forward_f32_dev."""
@@ -1030,6 +1063,63 @@ def cubic_f32_taps(src_n: int, dst_n: int):
     if rc != 0:
         raise SrcnnError(rc, "cubic_f32_taps")
     return first, coef
+
+
+def luma_bt601_studio(value_range: float = 1.0):
+    """The luma row of BT.601 studio range (MATLAB's rgb2ycbcr) for R, G, B planes holding [0, value_range]:
+    (65.481, 128.553, 24.966) / 255 with the offset 16 / 255 * value_range."""
+    return (65.481 / 255.0, 128.553 / 255.0, 24.966 / 255.0, 16.0 / 255.0 * float(value_range))
+
+
+def luma_for_order(luma, order: str = "rgb"):
+    """A luma row given for R, G, B planes as the row for planes in `order`: "rgb" (unchanged) or "bgr" (the three weights
+    reversed, the offset kept)."""
+    w0, w1, w2, off = luma
+    if order == "rgb":
+        return (w0, w1, w2, off)
+    if order == "bgr":
+        return (w2, w1, w0, off)
+    raise ValueError(f"order {order!r}: expected 'rgb' or 'bgr'")
+
+
+def _luma4(luma):
+    """{w0, w1, w2, offset} as a C array of four floats: ValueError unless four finite numbers whose weights (as float32) sum to
+    more than 0, before any call into the library."""
+    try:
+        a = np.asarray(luma, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"luma {luma!r}: expected four numbers (w0, w1, w2, offset)") from None
+    if a.size != 4 or not np.isfinite(a).all() or not float(a[:3].astype(np.float64).sum()) > 0.0:
+        raise ValueError(f"luma {luma!r}: expected four finite numbers (w0, w1, w2, offset) with w0 + w1 + w2 > 0")
+    return (C.c_float * 4)(*a.tolist())
+
+
+def _clamp2(clamp):
+    """None, or (lo, hi) as a C array of two floats: ValueError unless lo <= hi and neither is a NaN."""
+    if clamp is None:
+        return None
+    try:
+        lo, hi = (float(np.float32(v)) for v in clamp)
+    except (TypeError, ValueError):
+        raise ValueError(f"clamp {clamp!r}: expected None or (lo, hi)") from None
+    if not lo <= hi:
+        raise ValueError(f"clamp {clamp!r}: expected lo <= hi, neither a NaN")
+    return (C.c_float * 2)(lo, hi)
+
+
+def _not_shrinking(w, h, dst_w, dst_h):
+    if dst_w < w or dst_h < h:
+        raise ValueError(f"{h} x {w} -> {dst_h} x {dst_w} (H x W) shrinks the image: a super-resolution call resizes up or not at all")
+
+
+def luma_gain(luma) -> float:
+    """g = 1 / (w0 + w1 + w2) of a luma row as process_rgb_f32 uses it (srcnn_luma_gain; host only, needs no GPU): the sum in
+    float64 over the float32 weights, rounded once to float32."""
+    g = C.c_float()
+    rc = load_library().srcnn_luma_gain(_luma4(luma), C.byref(g))
+    if rc != 0:
+        raise SrcnnError(rc, "luma_gain")
+    return float(g.value)
 
 
 def stripe_rows(height: int, n_parts: int, index: int):

@@ -7,7 +7,8 @@
 //   srcnn_host.cpp    host-buffer entry points: staging, band / frame pipelines, the reference call surface, the pipeline steps
 //   srcnn_multi.cpp   several GPUs from one host process: row-striped plane, frame ranges
 //   srcnn_spatial.cpp the banded path (9-3-5 / 9-5-5, zero padding, colour models): weight table, gate, band loop, entry points
-//   srcnn_resize_f32.cpp the cubic resize of float32 planes in front of the float image path: tap tables, entry points
+//   srcnn_resize_f32.cpp the cubic resize of float32 planes in front of the float image path: tap tables, entry points, and a
+//                     3-plane float image through a 1-channel model (srcnn_process_rgb_f32*)
 #pragma once
 #include "../../include/srcnn_amd.h"
 #include "srcnn_kernels.h"
@@ -226,7 +227,7 @@ struct srcnn_ctx {
     int tab_sw = 0, tab_sh = 0, tab_dw = 0, tab_dh = 0;   // geometry the uploaded cubic tables are for
     // The float32 cubic resize (srcnn_resize_cubic_f32*, srcnn_process_f32*): the tables of one geometry and the stream of the
     // last launch that read them (ensure_tables_f32), the staging of the host-memory forms, and the one-frame workspace of
-    // srcnn_process_f32* (channels x dst_w x dst_h floats, grown on demand)
+    // srcnn_process_f32* (channels x dst_w x dst_h floats, grown on demand) and of srcnn_process_rgb_f32* (two planes: Yup, Ysr)
     srcnn::host::DevBuf f32_tables, f32_lo, f32_hi, f32_work;
     int ftab_sw = 0, ftab_sh = 0, ftab_dw = 0, ftab_dh = 0;
     hipStream_t ftab_stream = nullptr;

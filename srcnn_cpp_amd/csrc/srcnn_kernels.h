@@ -370,6 +370,20 @@ hipError_t launch_resize_cubic_f32(const float *src, long sstride, long sch_pitc
                                    long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int channels, int n_frames,
                                    const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st);
 
+// A 3-plane float image through a 1-channel model (srcnn_process_rgb_f32*): the two launches around the banded path, both the
+// tiled form above with the same tables (hipErrorInvalidValue for a geometry resize_f32_variant() does not send there: the call
+// never shrinks, and every up-scale fits the tile).  Front: Yup = the resize of Y = ((w0 x0 + w1 x1) + w2 x2) + off, luma =
+// {w0, w1, w2, off}, the three source planes sch_pitch apart.  Back: dst_c = resize(x_c) + (Ysr - Yup) g for c = 0, 1, 2,
+// clamped to [clamp[0], clamp[1]] unless clamp is null.  Strides and pitches in floats; every product and sum rounded on its own.
+hipError_t launch_luma_resize_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *yup,
+                                  long ystride, long yframe_pitch, int dw, int dh, int n_frames, const float luma[4],
+                                  const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st);
+hipError_t launch_resize_merge_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, const float *ysr,
+                                   long ysr_stride, long ysr_frame_pitch, const float *yup, long yup_stride, long yup_frame_pitch,
+                                   float *dst, long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int n_frames, float g,
+                                   const float *clamp, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
+                                   hipStream_t st);
+
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);
 hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8_t *planes, long pstride,
                             long ppitch, hipStream_t st);

@@ -10,7 +10,8 @@
 // against that restatement.  One byte in, one byte out per element: no reuse,
 // no LDS, consecutive lanes on consecutive bytes.
 // At the end of the file: the cubic resize of float32 planes, torch's bicubic
-// (srcnn_resize_cubic_f32*, the step in front of the float image path).
+// (srcnn_resize_cubic_f32*, the step in front of the float image path), and the
+// two kernels of srcnn_process_rgb_f32* built from its tile.
 #include "srcnn_kernels.h"
 
 // No FMA contraction anywhere in this file (also given on the command line, srcnn_cpp_amd/build.py): the vertical pass of
@@ -524,18 +525,130 @@ __global__ __launch_bounds__(256) void resize_cubic_f32_direct_kernel(const F32R
 // stores at a ragged right edge and wherever base, stride and column leave the four floats unaligned.
 // (at most F32_RMAX source rows x F32_SMAX source columns: srcnn_kernels.h, where resize_f32_variant() checks a geometry
 // against them before this kernel is chosen)
-__global__ __launch_bounds__(256) void resize_cubic_f32_tiled_kernel(const F32ResizeArgs p)
+// The three steps are functions of their own, shared with the two kernels of srcnn_process_rgb_f32* below: the fill may
+// compute the luma of three planes instead of loading one, and the vertical pass may add a term to what it stores.
+
+// What srcnn_process_rgb_f32* adds to a resize.  Y = ((w0 x0 + w1 x1) + w2 x2) + off at the source resolution, the three
+// planes sch_pitch apart; out_c = U_c + (Ysr - Yup) g, then min(max(., lo), hi) when clamp is set.  Every product and every
+// sum is rounded on its own, like the resize's (this unit is built without FMA contraction).
+struct F32LumaArgs {
+    float w0, w1, w2, off;
+    float g, lo, hi;
+    int clamp;
+    const float *ysr, *yup;         // the model's output and its input, dw x dh each (merge kernel only)
+    long ysr_stride, ysr_frame_pitch, yup_stride, yup_frame_pitch;
+};
+
+// the columns of a tile: what a thread keeps for every row tile and plane it walks
+struct F32TileCols {
+    int c_lo, ncol;      // unclamped first source column of the tile, and how many it spans
+    int x0;              // horizontal pass, thread = output column: its first tap in sbuf, and its coefficients
+    f32x4 a;
+    int tx, ty, dx;      // vertical pass: four columns from dx, rows F32_RPT * ty ...
+};
+
+__device__ __forceinline__ F32TileCols f32_tile_cols(const F32ResizeArgs &p)
 {
-    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
-    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    F32TileCols t;
     const int tid = threadIdx.x;
     const int dx0 = blockIdx.x * 256;
-    const int c_lo = p.xfirst[dx0] - 1, c_hi = p.xfirst[min(dx0 + 255, p.dw - 1)] + 2;     // unclamped source columns of the tile
-    const int ncol = c_hi - c_lo + 1;
+    t.c_lo = p.xfirst[dx0] - 1;
+    const int c_hi = p.xfirst[min(dx0 + 255, p.dw - 1)] + 2;     // unclamped source columns of the tile
+    t.ncol = c_hi - t.c_lo + 1;
     const int dxc = min(dx0 + tid, p.dw - 1);
-    const int x0 = p.xfirst[dxc] - 1 - c_lo;
-    const f32x4 a = *reinterpret_cast<const f32x4 *>(p.xcoef + 4L * dxc);
-    const int tx = tid & 63, ty = tid >> 6, dx = dx0 + 4 * tx;
+    t.x0 = p.xfirst[dxc] - 1 - t.c_lo;
+    t.a = *reinterpret_cast<const f32x4 *>(p.xcoef + 4L * dxc);
+    t.tx = tid & 63;
+    t.ty = tid >> 6;
+    t.dx = dx0 + 4 * t.tx;
+    return t;
+}
+
+// source rows [r_lo, r_lo + nrow) x columns [c_lo, c_lo + ncol) into sbuf, every index clamped to the plane before it is
+// used.  LUMA: the element is the luma of the three planes at that place (three loads), not the plane's own.
+template <bool LUMA>
+__device__ __forceinline__ void f32_tile_fill(float (*sbuf)[F32_SMAX], const float *s, const F32ResizeArgs &p, const F32LumaArgs &q,
+                                              int r_lo, int nrow, int c_lo, int ncol)
+{
+    for (int e = threadIdx.x; e < nrow * ncol; e += 256) {
+        const int rr = e / ncol, cc = e - rr * ncol;
+        const long at = (long)min(max(r_lo + rr, 0), p.sh - 1) * p.sstride + min(max(c_lo + cc, 0), p.sw - 1);
+        if (LUMA) {
+            float y = __fadd_rn(__fmul_rn(q.w0, s[at]), __fmul_rn(q.w1, s[at + p.sch_pitch]));
+            y = __fadd_rn(y, __fmul_rn(q.w2, s[at + 2 * p.sch_pitch]));
+            sbuf[rr][cc] = __fadd_rn(y, q.off);
+        } else {
+            sbuf[rr][cc] = s[at];
+        }
+    }
+}
+
+__device__ __forceinline__ void f32_tile_hpass(float (*hbuf)[256], const float (*sbuf)[F32_SMAX], int nrow, const F32TileCols t)
+{
+    for (int rr = 0; rr < nrow; ++rr)
+        hbuf[rr][threadIdx.x] = cubic_sum4(sbuf[rr][t.x0], sbuf[rr][t.x0 + 1], sbuf[rr][t.x0 + 2], sbuf[rr][t.x0 + 3], t.a);
+}
+
+// four floats of a row from o, of which the first n (1 .. 4 and more) exist: one 16-byte load where all four exist and the
+// address is aligned, else a load per float that exists (the others 0)
+__device__ __forceinline__ f32x4 f32_load4(const float *o, int n)
+{
+    if (n >= 4 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) return *reinterpret_cast<const f32x4 *>(o);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < n) v[c] = o[c];
+    return v;
+}
+
+// The vertical pass of the thread's rows of the tile [dy0, dy1) into plane d.  MERGE: add[r] is added to row r's four sums
+// and the result clamped when q.clamp is set (a NaN stays a NaN, as in numpy and torch).
+template <bool MERGE>
+__device__ __forceinline__ void f32_tile_vpass(const float (*hbuf)[256], float *d, const F32ResizeArgs &p, const F32LumaArgs &q,
+                                               const f32x4 *add, int dy0, int dy1, int r_lo, const F32TileCols t)
+{
+    if (t.dx < p.dw) {
+#pragma unroll
+        for (int r = 0; r < F32_RPT; ++r) {
+            const int dy = dy0 + F32_RPT * t.ty + r;
+            if (dy >= dy1) break;
+            const int j = p.yfirst[dy] - 1 - r_lo;
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(p.ycoef + 4L * dy);
+            f32x4 h[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) h[k] = *reinterpret_cast<const f32x4 *>(&hbuf[j + k][4 * t.tx]);
+            f32x4 v;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = cubic_sum4(h[0][c], h[1][c], h[2][c], h[3][c], b);
+            if (MERGE) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    float m = __fadd_rn(v[c], add[r][c]);
+                    if (q.clamp) {
+                        m = m < q.lo ? q.lo : m;
+                        m = m > q.hi ? q.hi : m;
+                    }
+                    v[c] = m;
+                }
+            }
+            float *o = d + (long)dy * p.dstride + t.dx;
+            if (t.dx + 3 < p.dw && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+                *reinterpret_cast<f32x4 *>(o) = v;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (t.dx + c < p.dw) o[c] = v[c];
+            }
+        }
+    }
+}
+
+// the resize of p.n_planes planes, tile after tile; LUMA: every "plane" is the luma of the frame's three (p.channels = 1)
+template <bool LUMA>
+__device__ __forceinline__ void resize_f32_tiled(const F32ResizeArgs p, const F32LumaArgs q, float (*hbuf)[256],
+                                                 float (*sbuf)[F32_SMAX])
+{
+    const F32TileCols t = f32_tile_cols(p);
     const int n_row_tiles = (p.dh + F32_RT - 1) / F32_RT;
     for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
         const int frame = z / p.channels, ch = z - frame * p.channels;
@@ -547,36 +660,71 @@ __global__ __launch_bounds__(256) void resize_cubic_f32_tiled_kernel(const F32Re
             const int nrow = r_hi - r_lo + 1;
             // (a thread still in the vertical pass of the tile before has not reached the barrier below: hbuf is not written
             // yet, and sbuf was last read before that tile's second barrier)
-            for (int e = tid; e < nrow * ncol; e += 256) {
-                const int rr = e / ncol, cc = e - rr * ncol;
-                sbuf[rr][cc] = s[(long)min(max(r_lo + rr, 0), p.sh - 1) * p.sstride + min(max(c_lo + cc, 0), p.sw - 1)];
-            }
+            f32_tile_fill<LUMA>(sbuf, s, p, q, r_lo, nrow, t.c_lo, t.ncol);
             __syncthreads();
-            for (int rr = 0; rr < nrow; ++rr)
-                hbuf[rr][tid] = cubic_sum4(sbuf[rr][x0], sbuf[rr][x0 + 1], sbuf[rr][x0 + 2], sbuf[rr][x0 + 3], a);
+            f32_tile_hpass(hbuf, sbuf, nrow, t);
             __syncthreads();
-            if (dx < p.dw) {
+            f32_tile_vpass<false>(hbuf, d, p, q, nullptr, dy0, dy1, r_lo, t);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void resize_cubic_f32_tiled_kernel(const F32ResizeArgs p)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    resize_f32_tiled<false>(p, F32LumaArgs{}, hbuf, sbuf);
+}
+
+// ---- a 3-plane float image through a 1-channel model (srcnn_process_rgb_f32*) -------------------------------------------
+// out_c = up(x_c) + g (Ysr - Yup), Yup = up(Y_lr), Ysr = model(Yup): two kernels around the banded path, both the tiled resize
+// above (a call never shrinks the image, so every geometry fits the tile).
+// Front: the tiled resize whose fill computes Y_lr from the frame's three planes; one plane out, Yup.
+__global__ __launch_bounds__(256) void luma_resize_f32_kernel(const F32ResizeArgs p, const F32LumaArgs q)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    resize_f32_tiled<true>(p, q, hbuf, sbuf);
+}
+
+// Back: a workgroup produces its tile of all three output planes in turn.  (Ysr - Yup) g of the thread's F32_RPT rows x 4
+// columns is loaded once and kept in registers; then, channel after channel, fill, horizontal pass and a vertical pass that
+// adds it.  p.n_planes counts FRAMES here (grid z), p.channels is 3.
+// (between two channels no barrier is needed beyond the two of a tile, for the reason given in resize_f32_tiled: a thread
+// that refills sbuf has left the vertical pass, which reads hbuf only, and nobody writes hbuf before the next first barrier)
+__global__ __launch_bounds__(256) void resize_merge_f32_kernel(const F32ResizeArgs p, const F32LumaArgs q)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    const F32TileCols t = f32_tile_cols(p);
+    const int n_row_tiles = (p.dh + F32_RT - 1) / F32_RT;
+    for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
+        const float *s = p.src + z * p.sframe_pitch;
+        float *d = p.dst + z * p.dframe_pitch;
+        const float *ysr = q.ysr + z * q.ysr_frame_pitch, *yup = q.yup + z * q.yup_frame_pitch;
+        for (int rt = blockIdx.y; rt < n_row_tiles; rt += gridDim.y) {
+            const int dy0 = rt * F32_RT, dy1 = min(dy0 + F32_RT, p.dh);
+            const int r_lo = p.yfirst[dy0] - 1, r_hi = p.yfirst[dy1 - 1] + 2;
+            const int nrow = r_hi - r_lo + 1;
+            f32x4 add[F32_RPT];
 #pragma unroll
-                for (int r = 0; r < F32_RPT; ++r) {
-                    const int dy = dy0 + F32_RPT * ty + r;
-                    if (dy >= dy1) break;
-                    const int j = p.yfirst[dy] - 1 - r_lo;
-                    const f32x4 b = *reinterpret_cast<const f32x4 *>(p.ycoef + 4L * dy);
-                    f32x4 h[4];
+            for (int r = 0; r < F32_RPT; ++r) {
+                const int dy = dy0 + F32_RPT * t.ty + r;
+                add[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (t.dx < p.dw && dy < dy1) {
+                    const f32x4 sr = f32_load4(ysr + (long)dy * q.ysr_stride + t.dx, p.dw - t.dx);
+                    const f32x4 up = f32_load4(yup + (long)dy * q.yup_stride + t.dx, p.dw - t.dx);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) h[k] = *reinterpret_cast<const f32x4 *>(&hbuf[j + k][4 * tx]);
-                    f32x4 v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = cubic_sum4(h[0][c], h[1][c], h[2][c], h[3][c], b);
-                    float *o = d + (long)dy * p.dstride + dx;
-                    if (dx + 3 < p.dw && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-                        *reinterpret_cast<f32x4 *>(o) = v;
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c)
-                            if (dx + c < p.dw) o[c] = v[c];
-                    }
+                    for (int c = 0; c < 4; ++c) add[r][c] = __fmul_rn(__fsub_rn(sr[c], up[c]), q.g);
                 }
+            }
+#pragma unroll 1
+            for (int ch = 0; ch < 3; ++ch) {
+                f32_tile_fill<false>(sbuf, s + ch * p.sch_pitch, p, q, r_lo, nrow, t.c_lo, t.ncol);
+                __syncthreads();
+                f32_tile_hpass(hbuf, sbuf, nrow, t);
+                __syncthreads();
+                f32_tile_vpass<true>(hbuf, d + ch * p.dch_pitch, p, q, add, dy0, dy1, r_lo, t);
             }
         }
     }
@@ -597,6 +745,48 @@ hipError_t launch_resize_cubic_f32(const float *src, long sstride, long sch_pitc
                            dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL(resize_cubic_f32_direct_kernel, dim3((dw + 255) / 256, cap(dh), gz), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+// the two launches of srcnn_process_rgb_f32* for n_frames frames: hipErrorInvalidValue for a geometry outside the tile
+static bool rgb_f32_geometry_ok(int sw, int sh, int dw, int dh, int n_frames)
+{
+    return sw > 0 && sh > 0 && dw > 0 && dh > 0 && n_frames > 0 && resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED;
+}
+
+hipError_t launch_luma_resize_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *yup,
+                                  long ystride, long yframe_pitch, int dw, int dh, int n_frames, const float luma[4],
+                                  const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st)
+{
+    if (!rgb_f32_geometry_ok(sw, sh, dw, dh, n_frames)) return hipErrorInvalidValue;
+    const F32ResizeArgs p{src, sstride, sch_pitch, sframe_pitch, sw, sh, yup, ystride, 0, yframe_pitch, dw, dh,
+                          1, n_frames, xfirst, yfirst, xcoef, ycoef};
+    F32LumaArgs q{};
+    q.w0 = luma[0]; q.w1 = luma[1]; q.w2 = luma[2]; q.off = luma[3];
+    auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };
+    hipLaunchKernelGGL(luma_resize_f32_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), cap(n_frames)), dim3(256), 0,
+                       st, p, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_merge_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, const float *ysr,
+                                   long ysr_stride, long ysr_frame_pitch, const float *yup, long yup_stride, long yup_frame_pitch,
+                                   float *dst, long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int n_frames, float g,
+                                   const float *clamp, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
+                                   hipStream_t st)
+{
+    if (!rgb_f32_geometry_ok(sw, sh, dw, dh, n_frames)) return hipErrorInvalidValue;
+    const F32ResizeArgs p{src, sstride, sch_pitch, sframe_pitch, sw, sh, dst, dstride, dch_pitch, dframe_pitch, dw, dh,
+                          3, n_frames, xfirst, yfirst, xcoef, ycoef};
+    F32LumaArgs q{};
+    q.g = g;
+    q.clamp = clamp != nullptr;
+    if (clamp) { q.lo = clamp[0]; q.hi = clamp[1]; }
+    q.ysr = ysr; q.ysr_stride = ysr_stride; q.ysr_frame_pitch = ysr_frame_pitch;
+    q.yup = yup; q.yup_stride = yup_stride; q.yup_frame_pitch = yup_frame_pitch;
+    auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };
+    hipLaunchKernelGGL(resize_merge_f32_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), cap(n_frames)), dim3(256), 0,
+                       st, p, q);
     return hipGetLastError();
 }
 

@@ -1,6 +1,8 @@
 // srcnn_resize_f32.cpp -- the step in front of the float image path: the cubic resize of float32 planes as torch's bicubic
-// interpolation defines it (srcnn_cubic_f32_taps, srcnn_resize_cubic_f32*), and resize + model in one call (srcnn_process_f32*).
-// The tap tables are built here, on the host in float64; the kernels are in srcnn_pipeline.hip (launch_resize_cubic_f32).
+// interpolation defines it (srcnn_cubic_f32_taps, srcnn_resize_cubic_f32*), resize + model in one call (srcnn_process_f32*), and a
+// 3-plane image through a 1-channel model (srcnn_luma_gain, srcnn_process_rgb_f32*).
+// The tap tables are built here, on the host in float64; the kernels are in srcnn_pipeline.hip (launch_resize_cubic_f32,
+// launch_luma_resize_f32, launch_resize_merge_f32).
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
@@ -124,6 +126,80 @@ static int process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, 
     return SRCNN_OK;
 }
 
+// g = 1 / (w0 + w1 + w2) of a luma row {w0, w1, w2, off}: the sum in float64, rounded once.  False for a non-finite entry or a
+// sum that is not positive.
+static bool luma_gain(const float *luma, float *g)
+{
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(luma[k])) return false;
+    const double sum = (double)luma[0] + (double)luma[1] + (double)luma[2];
+    if (!(sum > 0.0)) return false;
+    *g = (float)(1.0 / sum);
+    return std::isfinite(*g) && *g > 0.f;
+}
+
+// The gate of srcnn_process_rgb_f32*, before anything is staged or launched: SRCNN_OK and the gain, or the code and the reason
+static int process_rgb_refusal(srcnn_ctx *c, const char *what, const float *src, size_t src_stride, size_t src_ch_pitch,
+                               size_t src_frame_pitch, int src_w, int src_h, const float *dst, size_t dst_stride, size_t dst_ch_pitch,
+                               size_t dst_frame_pitch, int dst_w, int dst_h, const float *luma, const float *clamp, int n_frames, float *g)
+{
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    if ((rc = resize_f32_refusal(c, what, src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, dst, dst_stride, dst_ch_pitch,
+                                 dst_frame_pitch, dst_w, dst_h, 3, n_frames)))
+        return rc;
+    if (!luma || !luma_gain(luma, g))
+        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset} with w0 + w1 + w2 > 0", what);
+    if (clamp && !(clamp[0] <= clamp[1]))
+        return fail(c, SRCNN_ERR_INVALID, "%s: clamp {%g, %g}: expected lo <= hi, neither a NaN", what, (double)clamp[0], (double)clamp[1]);
+    if (dst_w < src_w || dst_h < src_h)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d shrinks the image (a super-resolution call resizes up or not at all)",
+                    what, src_w, src_h, dst_w, dst_h);
+    // (what that bound implies, and what the two kernels rest on: every such geometry fits the resize's tile)
+    if (resize_f32_variant(src_w, src_h, dst_w, dst_h) != RESIZE_F32_TILED)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d does not fit the resize's tile", what, src_w, src_h, dst_w, dst_h);
+    if (c->channels != 1)
+        return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model on the luma of the image: the context holds a colour model (3 "
+                                        "channels, 9-%d-5), which srcnn_process_f32 runs on the three planes themselves", what, c->f2);
+    return forward_f32_refusal(c);      // the gate of srcnn_forward_f32
+}
+
+// A 3-plane image through the loaded 1-channel model, on device memory.  Per frame: Yup = resize(luma of the three planes) into
+// the first plane of the workspace, Ysr = the model on Yup -- exactly as srcnn_forward_f32_dev runs it -- into the second,
+// then every output plane = resize of its source plane + (Ysr - Yup) g.  Frame after frame on the context's stream.
+static int process_rgb_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
+                               int src_w, int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch,
+                               int dst_w, int dst_h, const float *luma, float g, const float *clamp, int n_frames)
+{
+    const size_t plane = (size_t)dst_w * dst_h;
+    int rc;
+    // the workspace (and the band maps) were last used on another stream: wait for that work before the resize overwrites it
+    if (c->sp_done && c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
+    if ((rc = reserve(c, c->f32_work, 2 * plane * sizeof(float)))) return rc;      // (growing waits for the device)
+    float *yup = static_cast<float *>(c->f32_work.p), *ysr = yup + plane;
+    ResizeTablesF32 t;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    for (int f = 0; f < n_frames; ++f) {
+        const float *s = d_src + (size_t)f * src_frame_pitch;
+        HIP_TRY(c, launch_luma_resize_f32(s, (long)src_stride, (long)src_ch_pitch, 0, src_w, src_h, yup, dst_w, 0, dst_w, dst_h, 1, luma,
+                                          t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
+        BandedPlanes io;
+        io.f32 = true;
+        io.src = yup;
+        io.src_stride = (size_t)dst_w;
+        io.dst = ysr;
+        io.dst_stride = (size_t)dst_w;
+        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
+        HIP_TRY(c, launch_resize_merge_f32(s, (long)src_stride, (long)src_ch_pitch, 0, src_w, src_h, ysr, dst_w, 0, yup, dst_w, 0,
+                                           d_dst + (size_t)f * dst_frame_pitch, (long)dst_stride, (long)dst_ch_pitch, 0, dst_w, dst_h, 1,
+                                           g, clamp, t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
+    }
+    // the merge reads the workspace behind forward_banded's event: the next user on another stream waits for it too
+    HIP_TRY(c, hipEventRecord(c->sp_done, c->stream));
+    c->sp_stream = c->stream;
+    return SRCNN_OK;
+}
+
 extern "C" {
 
 int srcnn_cubic_f32_taps(int src_n, int dst_n, int *first, float *coef)
@@ -221,6 +297,48 @@ int srcnn_process_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t 
     if ((rc = process_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h, 1)))
         return rc;
     return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, C, d_hi);
+}
+
+int srcnn_luma_gain(const float *luma, float *g)
+{
+    float v;
+    if (!luma || !g || !luma_gain(luma, &v)) return SRCNN_ERR_INVALID;
+    *g = v;
+    return SRCNN_OK;
+}
+
+int srcnn_process_rgb_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
+                              int src_w, int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch,
+                              int dst_w, int dst_h, const float *luma, const float *clamp, int n_frames)
+{
+    BIND(c);
+    int rc;
+    float g = 0.f;
+    if ((rc = process_rgb_refusal(c, "process_rgb_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                                  dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, luma, clamp, n_frames, &g)))
+        return rc;
+    return process_rgb_f32_dev(c, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
+                               dst_frame_pitch, dst_w, dst_h, luma, g, clamp, n_frames);
+}
+
+int srcnn_process_rgb_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
+                          size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h, const float *luma, const float *clamp)
+{
+    BIND(c);
+    int rc;
+    float g = 0.f;
+    if ((rc = process_rgb_refusal(c, "process_rgb_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch, 0,
+                                  dst_w, dst_h, luma, clamp, 1, &g)))
+        return rc;
+    const size_t hi = (size_t)dst_w * dst_h;
+    float *d_lo = nullptr;
+    if ((rc = reserve(c, c->f32_hi, 3 * hi * sizeof(float)))) return rc;
+    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, 3, &d_lo))) return rc;
+    float *d_hi = static_cast<float *>(c->f32_hi.p);
+    if ((rc = process_rgb_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h,
+                                  luma, g, clamp, 1)))
+        return rc;
+    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, 3, d_hi);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
     fast = compile_module(module)              # an nn.Module with conv1, conv2, conv3 (9-f2-5, 1 or 3 channels)
     y = fast(x)                                # x: float32 (N, C, H, W) or (C, H, W) on that GPU; y ~ module(x)
     z = fast.upscale(lr, scale=2)              # ~ module(F.interpolate(lr, size, mode="bicubic", align_corners=False))
+    rgb = fast.upscale_rgb(lr_rgb, scale=2)    # a 1-channel module on the luma of an RGB tensor, chroma resized, merged
 
 The weights go in as they are (the data is already in the model's units), the module's padding mode is the context's padding,
 the call runs on torch.cuda.current_stream() and reads the tensor where it lies: data_ptr() and strides, no copy.  torch is
@@ -11,7 +12,7 @@ imported when compile_module is called, not when this module is.
 """
 from __future__ import annotations
 
-from . import MODE_BANDED16, MODE_MFMA, Context, model_from_module
+from . import LUMA_BT601, MODE_BANDED16, MODE_MFMA, Context, _clamp2, _luma4, model_from_module
 
 __all__ = ["compile_module", "CompiledModule"]
 
@@ -118,6 +119,33 @@ class CompiledModule:
             ow, oh = scaled_size(int(x.shape[-1]), int(x.shape[-2]), float(scale))
             size = (oh, ow)
         return self._resized(x, size, lambda *a: self.ctx.process_f32_dev(*a))
+
+    def upscale_rgb(self, x, scale=None, size=None, luma=LUMA_BT601, clamp=None):
+        """A 1-channel module on the luma of a 3-channel tensor, the usual script around a luma SRCNN in one call: bicubic
+        resize of the three planes, RGB -> Y'CbCr, the module on Y, Y'CbCr -> RGB, clamp.  x: float32 (N, 3, H, W) or (3, H, W)
+        on the module's GPU, read where it lies; exactly one of scale and size = (H, W), never smaller than x (size equal to
+        x's: an image that is already up-sampled).  luma = (w0, w1, w2, offset), the luma row of the colour convention for the
+        planes in the order given (LUMA_BT601, luma_bt601_studio(), luma_for_order()); clamp = (lo, hi) or None.  Per plane
+        the result is resize(x_c) + (module(Yup) - Yup) / (w0 + w1 + w2), Yup = resize(luma of x)."""
+        import torch
+        if self.channels != 1:
+            raise ValueError(f"upscale_rgb runs a 1-channel module on the luma of the tensor: this module has {self.channels} "
+                             "channels (upscale runs it on the planes themselves)")
+        if (scale is None) == (size is None):
+            raise ValueError("upscale_rgb: give exactly one of scale and size")
+        n, h, w, stride, ch_pitch, frame_pitch = check_input(x, 3, self.device)
+        if size is None:
+            from . import scaled_size
+            ow, oh = scaled_size(w, h, float(scale))
+            size = (oh, ow)
+        dh, dw = check_size(size)
+        if dh < h or dw < w:
+            raise ValueError(f"size {(dh, dw)} is smaller than the tensor's {(h, w)}: upscale_rgb resizes up or not at all")
+        _luma4(luma), _clamp2(clamp)      # refused here, before anything is allocated or the library is reached
+        out = torch.empty(tuple(x.shape[:-2]) + (dh, dw), dtype=torch.float32, device=x.device)
+        self._on_current_stream(x.device, lambda: self.ctx.process_rgb_f32_dev(
+            x.data_ptr(), stride, ch_pitch, frame_pitch, w, h, out.data_ptr(), dw, dh * dw, 3 * dh * dw, dw, dh, luma, clamp, n))
+        return out
 
     def close(self):
         self.ctx.close()
