@@ -428,6 +428,54 @@ int srcnn_process_rgb_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, s
                           float *dst, size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h,
                           const float luma[4], const float *clamp /* NULL or {lo, hi} */);
 
+/* Images as they are stored: the four device calls of the float image path on interleaved or planar pixels of float32, float16,
+ * bfloat16 or uint8, in and out (srcnn_forward_image_dev, srcnn_resize_cubic_image_dev, srcnn_process_image_dev,
+ * srcnn_process_rgb_image_dev), and the host-only check of a descriptor (srcnn_image_check).
+ *   - Address rule.  Element (frame f, channel c, row y, column x) of an srcnn_image lies at
+ *         data + f * frame_pitch + c * ch_pitch + y * stride + x * px_step        (all in ELEMENTS of `elem`):
+ *     planar NCHW is px_step = 1; channels-last or H x W x C is px_step = C, ch_pitch = 1; RGBA with the alpha skipped is
+ *     px_step = 4, ch_pitch = 1 and three channels; one channel of an interleaved image is one channel with px_step = 3.  A step
+ *     whose count is 1 is ignored.  data is aligned to its element size and to nothing more.
+ *   - Load: every load yields a float32.  F32 as it is; F16 and BF16 widen exactly; U8 is (float)b * scale, one rounded multiply
+ *     (torch: x.float() * scale).
+ *   - Store of a float32 v.  F32 as it is; F16 rounds to nearest even with IEEE overflow to +-inf; BF16 rounds to nearest even;
+ *     both keep a NaN a NaN; U8 computes t = v * scale with one rounding and stores rint_half_even(min(max(t, 0), 255)), 0 for a
+ *     NaN (torch: (y * scale).clamp(0, 255).round().to(torch.uint8)).  The {lo, hi} clamp of srcnn_process_rgb_image_dev stays in
+ *     float32 ahead of the store.
+ *   - The rule.  Each call equals store(its _f32_dev counterpart(load(x))) bit for bit: summation order, band structure, tap
+ *     tables, the luma formula, the gain and the clamp are those of srcnn_forward_f32_dev, srcnn_resize_cubic_f32_dev,
+ *     srcnn_process_f32_dev and srcnn_process_rgb_f32_dev.  In SRCNN_MODE_BANDED16 srcnn_set_input_range bounds the LOADED
+ *     values (after the U8 scale).  With both descriptors planar F32 (px_step = 1) a call IS its counterpart: same kernels.
+ *   - srcnn_image_check (no context, no GPU): SRCNN_OK, or SRCNN_ERR_INVALID for a null descriptor or data, an unknown elem, a U8
+ *     scale that is not finite and > 0, a size or count <= 0, a step of 0 in a dimension whose count is above 1, an offset of the
+ *     last element that does not fit in 63 bits (in bytes), data not aligned to the element size, and -- is_dst != 0 -- an address
+ *     map that the following rule does not show injective: sort the used dimensions by step; each step must exceed the sum of
+ *     (n_j - 1) * step_j over the dimensions with smaller steps.  (Sufficient, not necessary.)  A source may alias itself.
+ *   - Gate of each call: that of its counterpart (SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only, a whole model, a 1-channel model
+ *     and no shrinking for srcnn_process_rgb_image_dev), SRCNN_ERR_INVALID for a descriptor srcnn_image_check refuses and for a
+ *     destination byte range that overlaps the source's.  A refused call launches nothing and leaves the context usable.
+ *     Asynchronous on the context's stream; the workspace is the one srcnn_process_f32_dev uses, grown on demand.
+ *     srcnn_forward_image_dev and srcnn_process_image_dev run the model on float32 planes in that workspace: a format other than
+ *     planar F32 is converted into and out of it by a kernel of its own (one pass each side, exact).
+ *   Out of scope: host-memory forms, row stripes and several GPUs, the byte entry points (srcnn_forward_y*, srcnn_process_bgr*),
+ *   uint16 elements, a command-line option; the existing calls are unchanged. */
+enum { SRCNN_ELEM_F32 = 0, SRCNN_ELEM_F16 = 1, SRCNN_ELEM_BF16 = 2, SRCNN_ELEM_U8 = 3 };
+typedef struct srcnn_image {
+    void  *data;      /* device pointer to element (frame 0, channel 0, row 0, column 0) */
+    int    elem;      /* SRCNN_ELEM_* */
+    float  scale;     /* SRCNN_ELEM_U8 only, finite and > 0; ignored otherwise */
+    size_t px_step, stride, ch_pitch, frame_pitch;   /* in ELEMENTS of `elem` */
+} srcnn_image;
+int srcnn_image_check(const srcnn_image *im, int width, int height, int channels, int n_frames, int is_dst);
+int srcnn_forward_image_dev(srcnn_ctx *ctx, const srcnn_image *src, const srcnn_image *dst, int width, int height, int n_frames);
+int srcnn_resize_cubic_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                                 const srcnn_image *dst, int dst_w, int dst_h, int channels, int n_frames);
+int srcnn_process_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                            const srcnn_image *dst, int dst_w, int dst_h, int n_frames);
+int srcnn_process_rgb_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                                const srcnn_image *dst, int dst_w, int dst_h,
+                                const float luma[4], const float *clamp /* NULL or {lo, hi} */, int n_frames);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */
@@ -634,7 +682,8 @@ int srcnn_model_striped(srcnn_ctx *const *ctxs, int n_ctx,
  *     built without the colour / float stripe kernels;
  *   - SRCNN_ERR_INVALID: null pointers, sizes <= 0, a stride below the row, a range outside the image, src or the halo buffers
  *     not covering the rows the range needs, float output planes that overlap each other, output rows that overlap the input.
- * Out of scope: interleaved float pixels, a pipelined form, a several-GPU form of the torch module. */
+ * Out of scope: interleaved float pixels in a stripe (whole images: the srcnn_*_image_dev calls), a pipelined form, a several-GPU
+ * form of the torch module. */
 int srcnn_model_color_rows_dev(srcnn_ctx *ctx,
                                const uint8_t *d_src, size_t src_stride, int src_row0,
                                uint8_t *d_dst, size_t dst_stride, int dst_row0,

@@ -36,6 +36,7 @@ __all__ = [
     "model_striped", "model_striped_dev",
     "model_color_striped", "model_color_striped_dev", "model_striped_f32", "model_striped_f32_dev",
     "cubic_f32_taps", "luma_gain", "luma_for_order", "luma_bt601_studio", "LUMA_BT601",
+    "ELEM_F32", "ELEM_F16", "ELEM_BF16", "ELEM_U8", "ELEM_SIZE", "Image", "image_check",
 ]
 
 _PKG = Path(__file__).resolve().parent
@@ -62,6 +63,10 @@ FLOP_PER_PIXEL = 16064
 # luma rows {w0, w1, w2, offset} of process_rgb_f32 (srcnn_process_rgb_f32) for planes in R, G, B order: BT.601 full range
 LUMA_BT601 = (0.299, 0.587, 0.114, 0.0)
 
+# element kinds of an Image (SRCNN_ELEM_*) and their sizes in bytes
+ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = 0, 1, 2, 3
+ELEM_SIZE = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
+
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_NODEVICE, ERR_STATE = -1, -2, -3, -4, -5      # include/srcnn_amd.h
 _ERR = {-1: "invalid argument", -2: "HIP runtime error", -3: "out of memory",
         -4: "no gfx950 device", -5: "bad state"}
@@ -70,6 +75,11 @@ _u8p = C.POINTER(C.c_uint8)
 _f32p = C.POINTER(C.c_float)
 _f32pp = C.POINTER(_f32p)
 _lib = None
+
+
+class _CImage(C.Structure):      # srcnn_image
+    _fields_ = [("data", C.c_void_p), ("elem", C.c_int), ("scale", C.c_float), ("px_step", C.c_size_t), ("stride", C.c_size_t),
+                ("ch_pitch", C.c_size_t), ("frame_pitch", C.c_size_t)]
 
 
 class SrcnnError(RuntimeError):
@@ -114,7 +124,7 @@ def load_library() -> C.CDLL:
     if "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
         import torch  # noqa: F401
     lib = C.CDLL(str(_LIB_PATH))
-    sz, i, vp = C.c_size_t, C.c_int, C.c_void_p
+    sz, i, vp, imp = C.c_size_t, C.c_int, C.c_void_p, C.POINTER(_CImage)
     sigs = {
         "srcnn_abi_version": ([], i),
         "srcnn_create": ([C.POINTER(vp), i], i),
@@ -148,6 +158,11 @@ def load_library() -> C.CDLL:
         "srcnn_luma_gain": ([_f32p, _f32p], i),
         "srcnn_process_rgb_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, _f32p, _f32p], i),
         "srcnn_process_rgb_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, _f32p, _f32p, i], i),
+        "srcnn_image_check": ([imp, i, i, i, i, i], i),
+        "srcnn_forward_image_dev": ([vp, imp, imp, i, i, i], i),
+        "srcnn_resize_cubic_image_dev": ([vp, imp, i, i, imp, i, i, i, i], i),
+        "srcnn_process_image_dev": ([vp, imp, i, i, imp, i, i, i], i),
+        "srcnn_process_rgb_image_dev": ([vp, imp, i, i, imp, i, i, _f32p, _f32p, i], i),
         "srcnn_set_input_range": ([vp, C.c_float], i),
         "srcnn_get_input_range": ([vp], C.c_float),
         "srcnn_forward_y": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
@@ -226,6 +241,8 @@ ABI_SYMBOLS = (
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
     "srcnn_cubic_f32_taps", "srcnn_resize_cubic_f32", "srcnn_resize_cubic_f32_dev", "srcnn_process_f32", "srcnn_process_f32_dev",
     "srcnn_luma_gain", "srcnn_process_rgb_f32", "srcnn_process_rgb_f32_dev",
+    "srcnn_image_check", "srcnn_forward_image_dev", "srcnn_resize_cubic_image_dev", "srcnn_process_image_dev",
+    "srcnn_process_rgb_image_dev",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -675,6 +692,29 @@ class Context:
                                                         dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, luma4, clamp2,
                                                         n_frames))
 
+    def forward_image_dev(self, src: "Image", dst: "Image", width, height, n_frames=1):
+        """srcnn_forward_image_dev: forward_f32_dev on images as they are stored (Image: element kind, pixel step, strides);
+        equals store(forward_f32_dev(load(src))) bit for bit, asynchronous on the context's stream."""
+        self._check(self._lib.srcnn_forward_image_dev(self._h, C.byref(src.c()), C.byref(dst.c()), width, height, n_frames))
+
+    def resize_cubic_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, channels, n_frames=1):
+        """srcnn_resize_cubic_image_dev: resize_cubic_f32_dev on stored images; the same size is a pure format conversion."""
+        self._check(self._lib.srcnn_resize_cubic_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
+                                                           channels, n_frames))
+
+    def process_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, n_frames=1):
+        """srcnn_process_image_dev: process_f32_dev (resize + model) on stored images."""
+        self._check(self._lib.srcnn_process_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
+                                                      n_frames))
+
+    def process_rgb_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, luma=LUMA_BT601, clamp=None, n_frames=1):
+        """srcnn_process_rgb_image_dev: process_rgb_f32_dev (a 3-channel image through the loaded 1-channel model) on stored
+        images; the clamp applies in float32, ahead of the store."""
+        _not_shrinking(src_w, src_h, dst_w, dst_h)
+        luma4, clamp2 = _luma4(luma), _clamp2(clamp)
+        self._check(self._lib.srcnn_process_rgb_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
+                                                          luma4, clamp2, n_frames))
+
     def set_input_range(self, r: float):
         """The largest |input| of a float call (srcnn_set_input_range): 255 by default, 1.0 for [0, 1] data.  A setting of the
         context; only MODE_BANDED16 reads it, and only in forward_f32 / forward_f32_dev."""
@@ -1110,6 +1150,35 @@ def _clamp2(clamp):
 def _not_shrinking(w, h, dst_w, dst_h):
     if dst_w < w or dst_h < h:
         raise ValueError(f"{h} x {w} -> {dst_h} x {dst_w} (H x W) shrinks the image: a super-resolution call resizes up or not at all")
+
+
+class Image:
+    """Where an image lies and what its elements are (srcnn_image): element (f, c, y, x) at ptr + f * frame_pitch + c * ch_pitch
+    + y * stride + x * px_step, all in elements of `elem` (ELEM_*).  Planar NCHW: px_step 1; channels-last or H x W x C: px_step
+    C, ch_pitch 1; RGBA with the alpha skipped: px_step 4, ch_pitch 1, three channels.  scale: ELEM_U8 only -- a load is byte *
+    scale, a store rint(clamp(value * scale, 0, 255)).  A pitch whose count is 1 is ignored."""
+    __slots__ = ("ptr", "elem", "px_step", "stride", "ch_pitch", "frame_pitch", "scale")
+
+    def __init__(self, ptr, elem=ELEM_F32, px_step=1, stride=0, ch_pitch=0, frame_pitch=0, scale=1.0):
+        self.ptr, self.elem, self.px_step, self.stride = int(ptr), int(elem), int(px_step), int(stride)
+        self.ch_pitch, self.frame_pitch, self.scale = int(ch_pitch), int(frame_pitch), float(scale)
+
+    def c(self) -> _CImage:
+        for v in (self.px_step, self.stride, self.ch_pitch, self.frame_pitch):
+            if v < 0:
+                raise ValueError(f"{self!r}: steps and pitches must not be negative")
+        return _CImage(self.ptr, self.elem, self.scale, self.px_step, self.stride, self.ch_pitch, self.frame_pitch)
+
+    def __repr__(self):
+        return (f"Image(ptr={self.ptr:#x}, elem={self.elem}, px_step={self.px_step}, stride={self.stride}, ch_pitch={self.ch_pitch}, "
+                f"frame_pitch={self.frame_pitch}, scale={self.scale})")
+
+
+def image_check(image: Image, width: int, height: int, channels: int, n_frames: int = 1, is_dst: bool = False) -> bool:
+    """srcnn_image_check (host only, needs no GPU): whether the library accepts the descriptor for an image of that size -- as a
+    destination only where its address map is shown injective (every step, sorted, exceeds what the smaller ones reach)."""
+    return load_library().srcnn_image_check(C.byref(image.c()), int(width), int(height), int(channels), int(n_frames),
+                                            int(bool(is_dst))) == 0
 
 
 def luma_gain(luma) -> float:

@@ -57,9 +57,10 @@ UNITS = [
     ("srcnn_multi.cpp", ["-x", "hip"]),
     ("srcnn_spatial.cpp", ["-x", "hip"]),
     ("srcnn_resize_f32.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_f32_taps(): float64 as written, nothing contracted
+    ("srcnn_image.cpp", ["-x", "hip"]),      # images as they are stored: the descriptor check and the four srcnn_*_image_dev calls
 ]
 HOST_UNITS = {"srcnn_api.cpp", "srcnn_model.cpp", "srcnn_plan.cpp", "srcnn_launch.cpp", "srcnn_host.cpp", "srcnn_multi.cpp",
-              "srcnn_spatial.cpp", "srcnn_resize_f32.cpp"}
+              "srcnn_spatial.cpp", "srcnn_resize_f32.cpp", "srcnn_image.cpp"}
 
 
 def kernel_sources_fingerprint() -> str:
@@ -113,7 +114,7 @@ TUNING_LIB = PKG / "libsrcnn_amd_tuning.so"
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [CSRC / "srcnn_kernels.h", CSRC / "srcnn_ctx.h", PKG.parent / "include" / "srcnn_amd.h", Path(__file__)]
+    headers = [CSRC / "srcnn_kernels.h", CSRC / "srcnn_ctx.h", CSRC / "srcnn_image.h", PKG.parent / "include" / "srcnn_amd.h", Path(__file__)]
     objs, tuning_objs = [], []
     for unit in UNITS:
         src, extra = unit[0], unit[1]

@@ -1,0 +1,306 @@
+// srcnn_image.cpp -- images as they are stored: the descriptor check (srcnn_image_check) and the four device calls of the float
+// image path on interleaved or planar pixels of float32, float16, bfloat16 or uint8 (srcnn_forward_image_dev,
+// srcnn_resize_cubic_image_dev, srcnn_process_image_dev, srcnn_process_rgb_image_dev).
+// Each call equals store(its _f32_dev counterpart(load(x))) bit for bit.  With both descriptors planar float32 a call IS that
+// counterpart; otherwise the resize, the luma front and the merge back run their accessor forms (srcnn_pipeline.hip), and the
+// model itself runs on float32 planes in the context's workspace, converted in and out by convert_image_kernel where the
+// stored format is not planar float32 already.
+#include "srcnn_ctx.h"
+#include "srcnn_image.h"
+
+using namespace srcnn;
+using namespace srcnn::host;
+
+namespace {
+
+size_t elem_size(int elem) { return elem == SRCNN_ELEM_F32 ? 4 : elem == SRCNN_ELEM_U8 ? 1 : 2; }
+
+struct Dim {
+    uint64_t n, step;
+};
+// the dimensions of an image that are used (count above 1): x, y, channel, frame
+int used_dims(const srcnn_image *im, int width, int height, int channels, int n_frames, Dim out[4])
+{
+    const Dim all[4] = {{(uint64_t)width, im->px_step}, {(uint64_t)height, im->stride}, {(uint64_t)channels, im->ch_pitch},
+                        {(uint64_t)n_frames, im->frame_pitch}};
+    int k = 0;
+    for (const Dim &d : all)
+        if (d.n > 1) out[k++] = d;
+    return k;
+}
+
+// offset of the last element, in elements; false when it (times the element size) does not fit in 63 bits
+bool last_offset(const Dim *dims, int k, size_t es, uint64_t *last)
+{
+    unsigned __int128 sum = 0;
+    for (int i = 0; i < k; ++i) sum += (unsigned __int128)(dims[i].n - 1) * dims[i].step;
+    if ((sum + 1) * es > (unsigned __int128)INT64_MAX) return false;
+    *last = (uint64_t)sum;
+    return true;
+}
+
+int image_check(const srcnn_image *im, int width, int height, int channels, int n_frames, int is_dst)
+{
+    if (!im || !im->data || width <= 0 || height <= 0 || channels <= 0 || n_frames <= 0) return SRCNN_ERR_INVALID;
+    if (im->elem < SRCNN_ELEM_F32 || im->elem > SRCNN_ELEM_U8) return SRCNN_ERR_INVALID;
+    if (im->elem == SRCNN_ELEM_U8 && !(std::isfinite(im->scale) && im->scale > 0.f)) return SRCNN_ERR_INVALID;
+    const size_t es = elem_size(im->elem);
+    if (reinterpret_cast<uintptr_t>(im->data) % es) return SRCNN_ERR_INVALID;
+    Dim d[4];
+    const int k = used_dims(im, width, height, channels, n_frames, d);
+    for (int i = 0; i < k; ++i)
+        if (d[i].step == 0) return SRCNN_ERR_INVALID;
+    uint64_t last;
+    if (!last_offset(d, k, es, &last)) return SRCNN_ERR_INVALID;
+    if (is_dst) {
+        // injective where, sorted by step, every step exceeds the largest offset the smaller ones reach (sufficient)
+        std::sort(d, d + k, [](const Dim &a, const Dim &b) { return a.step < b.step; });
+        unsigned __int128 reach = 0;
+        for (int i = 0; i < k; ++i) {
+            if (!((unsigned __int128)d[i].step > reach)) return SRCNN_ERR_INVALID;
+            reach += (unsigned __int128)(d[i].n - 1) * d[i].step;
+        }
+    }
+    return SRCNN_OK;
+}
+
+size_t image_bytes(const srcnn_image *im, int width, int height, int channels, int n_frames)
+{
+    Dim d[4];
+    const int k = used_dims(im, width, height, channels, n_frames, d);
+    uint64_t last = 0;
+    (void)last_offset(d, k, elem_size(im->elem), &last);      // (checked before)
+    return (size_t)(last + 1) * elem_size(im->elem);
+}
+
+// a pitch whose count is 1 is ignored: the kernels multiply it by 0 only, but keep every field they see small and defined
+ImageRef image_ref(const srcnn_image *im, int width, int height, int channels, int n_frames)
+{
+    return ImageRef{im->data, im->elem, im->elem == SRCNN_ELEM_U8 ? im->scale : 0.f, width > 1 ? (long)im->px_step : 1,
+                    height > 1 ? (long)im->stride : 0, channels > 1 ? (long)im->ch_pitch : 0, n_frames > 1 ? (long)im->frame_pitch : 0};
+}
+// frame f of an image, as an image of one frame
+ImageRef frame_of(const ImageRef &im, int f)
+{
+    ImageRef r = im;
+    r.data = static_cast<char *>(im.data) + (size_t)f * (size_t)im.frame_pitch * elem_size(im.elem);
+    r.frame_pitch = 0;
+    return r;
+}
+// a packed float32 image of `channels` planes in the workspace
+ImageRef packed_f32(float *p, int width, int height)
+{
+    return ImageRef{p, ELEM_F32, 0.f, 1, (long)width, (long)width * height, 0};
+}
+
+// planar float32 whose rows do not overlap: what the existing calls take, and (f32_row) the row stride they expect
+bool planar_f32(const ImageRef &im, int width) { return image_is_planar_f32(im) && (im.stride == 0 || im.stride >= width); }
+size_t f32_row(const ImageRef &im, int width) { return im.stride ? (size_t)im.stride : (size_t)width; }
+// ... as a DESTINATION of the existing calls and of the banded path: their own gate on top (planes apart from each other, pitches
+// in range).  A planar float32 destination that srcnn_image_check accepts and this refuses -- a channel pitch inside the row
+// stride, say -- is written through the workspace and the converting kernel like any other layout, whatever the source is.
+bool f32_direct_dst(const ImageRef &im, int C, int width, int height, int n_frames)
+{
+    constexpr long kMaxPitch = 1L << 40;
+    return planar_f32(im, width) && im.ch_pitch < kMaxPitch && im.frame_pitch < kMaxPitch &&
+           f32_planes_disjoint(C, f32_row(im, width), (size_t)im.ch_pitch, (size_t)im.frame_pitch, width, height, n_frames);
+}
+bool f32_direct_src(const ImageRef &im, int width) { return planar_f32(im, width) && im.ch_pitch < (1L << 40) && im.frame_pitch < (1L << 40); }
+
+// the descriptors of a call: both checked, and the destination's bytes apart from the source's
+int images_refusal(srcnn_ctx *c, const char *what, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
+                   int dst_h, int channels, int n_frames)
+{
+    if (image_check(src, src_w, src_h, channels, n_frames, 0))
+        return fail(c, SRCNN_ERR_INVALID, "%s: bad source image (srcnn_image_check)", what);
+    if (image_check(dst, dst_w, dst_h, channels, n_frames, 1))
+        return fail(c, SRCNN_ERR_INVALID, "%s: bad destination image: a descriptor srcnn_image_check refuses, or an address map "
+                                          "it cannot show injective", what);
+    if ((long)channels * n_frames > 0x7fffffffL) return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    if (ranges_overlap(src->data, image_bytes(src, src_w, src_h, channels, n_frames), dst->data,
+                       image_bytes(dst, dst_w, dst_h, channels, n_frames)))
+        return fail(c, SRCNN_ERR_INVALID, "%s: src and dst overlap (the call cannot run in place)", what);
+    return SRCNN_OK;
+}
+
+int luma_refusal(srcnn_ctx *c, const char *what, const float *luma, const float *clamp, float *g)
+{
+    if (!luma || srcnn_luma_gain(luma, g) != SRCNN_OK)
+        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset} with w0 + w1 + w2 > 0", what);
+    if (clamp && !(clamp[0] <= clamp[1]))
+        return fail(c, SRCNN_ERR_INVALID, "%s: clamp {%g, %g}: expected lo <= hi, neither a NaN", what, (double)clamp[0], (double)clamp[1]);
+    return SRCNN_OK;
+}
+
+// the workspace (and the band maps) were last used on another stream: wait for that work before this call overwrites it
+int claim_workspace(srcnn_ctx *c, size_t floats, float **work)
+{
+    int rc;
+    if (c->sp_done && c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
+    if ((rc = reserve(c, c->f32_work, floats * sizeof(float)))) return rc;      // (growing waits for the device)
+    *work = static_cast<float *>(c->f32_work.p);
+    return SRCNN_OK;
+}
+int release_workspace(srcnn_ctx *c)      // the last kernel read the workspace behind forward_banded's event
+{
+    HIP_TRY(c, hipEventRecord(c->sp_done, c->stream));
+    c->sp_stream = c->stream;
+    return SRCNN_OK;
+}
+
+// The model on one frame: `in` (packed float32 planes) -> frame `dst`; direct: dst is planar float32 the banded path can write
+// itself, else through `out` (a second set of packed planes in the workspace) and a converting pass
+int model_frame(srcnn_ctx *c, const float *in, float *out, const ImageRef &dst, bool direct, int width, int height)
+{
+    const int C = c->channels;
+    const size_t plane = (size_t)width * height;
+    int rc;
+    BandedPlanes io;
+    io.f32 = true;
+    io.src = in;
+    io.src_stride = (size_t)width;
+    io.ch_step = C == 1 ? 0 : plane;
+    io.dst = direct ? dst.data : out;
+    io.dst_stride = direct ? (height > 1 ? (size_t)dst.stride : (size_t)width) : (size_t)width;
+    io.dst_ch_pitch = C == 1 ? 0 : direct ? (size_t)dst.ch_pitch : plane;
+    if ((rc = forward_banded(c, io, width, height, 1))) return rc;
+    if (!direct) HIP_TRY(c, launch_convert_image(packed_f32(out, width, height), dst, width, height, C, 1, c->stream));
+    return SRCNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srcnn_image_check(const srcnn_image *im, int width, int height, int channels, int n_frames, int is_dst)
+{
+    return image_check(im, width, height, channels, n_frames, is_dst);
+}
+
+int srcnn_forward_image_dev(srcnn_ctx *c, const srcnn_image *src, const srcnn_image *dst, int width, int height, int n_frames)
+{
+    BIND(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const int C = c->channels;
+    if ((rc = images_refusal(c, "forward_image_dev", src, width, height, dst, width, height, C, n_frames))) return rc;
+    const ImageRef s = image_ref(src, width, height, C, n_frames), d = image_ref(dst, width, height, C, n_frames);
+    const bool direct = f32_direct_dst(d, C, width, height, n_frames);
+    if (f32_direct_src(s, width) && direct)
+        return srcnn_forward_f32_dev(c, static_cast<const float *>(s.data), f32_row(s, width), s.ch_pitch, s.frame_pitch,
+                                     static_cast<float *>(d.data), f32_row(d, width), d.ch_pitch, d.frame_pitch, width, height,
+                                     n_frames);
+    if ((rc = forward_f32_refusal(c))) return rc;      // the gate of srcnn_forward_f32, before anything is launched
+    const size_t plane = (size_t)width * height;
+    // the workspace holds what the call needs: C planes for a source that is not packed float32 already, C for a destination the
+    // banded path cannot write itself
+    const bool packed = image_is_planar_f32(s) && (height == 1 || (size_t)s.stride == (size_t)width) && (C == 1 || (size_t)s.ch_pitch == plane);
+    float *work = nullptr;
+    if ((rc = claim_workspace(c, ((packed ? 0 : 1) + (direct ? 0 : 1)) * C * plane, &work))) return rc;
+    float *out = work + (packed ? 0 : C * plane);
+    for (int f = 0; f < n_frames; ++f) {
+        const float *in = work;
+        if (packed)
+            in = static_cast<const float *>(frame_of(s, f).data);
+        else
+            HIP_TRY(c, launch_convert_image(frame_of(s, f), packed_f32(work, width, height), width, height, C, 1, c->stream));
+        if ((rc = model_frame(c, in, out, frame_of(d, f), direct, width, height))) return rc;
+    }
+    return release_workspace(c);
+}
+
+int srcnn_resize_cubic_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
+                                 int dst_h, int channels, int n_frames)
+{
+    BIND(c);
+    int rc;
+    if ((rc = images_refusal(c, "resize_cubic_image_dev", src, src_w, src_h, dst, dst_w, dst_h, channels, n_frames))) return rc;
+    const ImageRef s = image_ref(src, src_w, src_h, channels, n_frames), d = image_ref(dst, dst_w, dst_h, channels, n_frames);
+    if (f32_direct_src(s, src_w) && f32_direct_dst(d, channels, dst_w, dst_h, n_frames))
+        return srcnn_resize_cubic_f32_dev(c, static_cast<const float *>(s.data), f32_row(s, src_w), s.ch_pitch, s.frame_pitch, src_w,
+                                          src_h, static_cast<float *>(d.data), f32_row(d, dst_w), d.ch_pitch, d.frame_pitch, dst_w,
+                                          dst_h, channels, n_frames);
+    ResizeTablesF32 t;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    HIP_TRY(c, launch_resize_cubic_image(s, src_w, src_h, d, dst_w, dst_h, channels, n_frames, t.xfirst, t.xcoef, t.yfirst, t.ycoef,
+                                         c->stream));
+    return SRCNN_OK;
+}
+
+int srcnn_process_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w, int dst_h,
+                            int n_frames)
+{
+    BIND(c);
+    int rc;
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const int C = c->channels;
+    if ((rc = images_refusal(c, "process_image_dev", src, src_w, src_h, dst, dst_w, dst_h, C, n_frames))) return rc;
+    const ImageRef s = image_ref(src, src_w, src_h, C, n_frames), d = image_ref(dst, dst_w, dst_h, C, n_frames);
+    const bool direct = f32_direct_dst(d, C, dst_w, dst_h, n_frames);
+    if (f32_direct_src(s, src_w) && direct)
+        return srcnn_process_f32_dev(c, static_cast<const float *>(s.data), f32_row(s, src_w), s.ch_pitch, s.frame_pitch, src_w, src_h,
+                                     static_cast<float *>(d.data), f32_row(d, dst_w), d.ch_pitch, d.frame_pitch, dst_w, dst_h,
+                                     n_frames);
+    if ((rc = forward_f32_refusal(c))) return rc;
+    const size_t plane = (size_t)dst_w * dst_h;
+    float *work = nullptr;
+    if ((rc = claim_workspace(c, (direct ? 1 : 2) * C * plane, &work))) return rc;      // the resized frame, and the model's output
+    ResizeTablesF32 t;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    for (int f = 0; f < n_frames; ++f) {
+        HIP_TRY(c, launch_resize_cubic_image(frame_of(s, f), src_w, src_h, packed_f32(work, dst_w, dst_h), dst_w, dst_h, C, 1,
+                                             t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
+        if ((rc = model_frame(c, work, work + C * plane, frame_of(d, f), direct, dst_w, dst_h))) return rc;
+    }
+    return release_workspace(c);
+}
+
+int srcnn_process_rgb_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
+                                int dst_h, const float *luma, const float *clamp, int n_frames)
+{
+    BIND(c);
+    int rc;
+    const char *what = "process_rgb_image_dev";
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    if ((rc = images_refusal(c, what, src, src_w, src_h, dst, dst_w, dst_h, 3, n_frames))) return rc;
+    const ImageRef s = image_ref(src, src_w, src_h, 3, n_frames), d = image_ref(dst, dst_w, dst_h, 3, n_frames);
+    if (f32_direct_src(s, src_w) && f32_direct_dst(d, 3, dst_w, dst_h, n_frames))
+        return srcnn_process_rgb_f32_dev(c, static_cast<const float *>(s.data), f32_row(s, src_w), s.ch_pitch, s.frame_pitch, src_w,
+                                         src_h, static_cast<float *>(d.data), f32_row(d, dst_w), d.ch_pitch, d.frame_pitch, dst_w,
+                                         dst_h, luma, clamp, n_frames);
+    float g = 0.f;
+    if ((rc = luma_refusal(c, what, luma, clamp, &g))) return rc;
+    if (dst_w < src_w || dst_h < src_h)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d shrinks the image (a super-resolution call resizes up or not at all)",
+                    what, src_w, src_h, dst_w, dst_h);
+    if (resize_f32_variant(src_w, src_h, dst_w, dst_h) != RESIZE_F32_TILED)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d does not fit the resize's tile", what, src_w, src_h, dst_w, dst_h);
+    if (c->channels != 1)
+        return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model on the luma of the image: the context holds a colour model (3 "
+                                        "channels, 9-%d-5), which srcnn_process_image_dev runs on the three channels themselves",
+                    what, c->f2);
+    if ((rc = forward_f32_refusal(c))) return rc;
+    const size_t plane = (size_t)dst_w * dst_h;
+    float *yup = nullptr;
+    if ((rc = claim_workspace(c, 2 * plane, &yup))) return rc;
+    float *ysr = yup + plane;
+    ResizeTablesF32 t;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    for (int f = 0; f < n_frames; ++f) {
+        const ImageRef sf = frame_of(s, f);
+        HIP_TRY(c, launch_luma_resize_image(sf, src_w, src_h, yup, dst_w, 0, dst_w, dst_h, 1, luma, t.xfirst, t.xcoef, t.yfirst,
+                                            t.ycoef, c->stream));
+        BandedPlanes io;
+        io.f32 = true;
+        io.src = yup;
+        io.src_stride = (size_t)dst_w;
+        io.dst = ysr;
+        io.dst_stride = (size_t)dst_w;
+        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
+        HIP_TRY(c, launch_resize_merge_image(sf, src_w, src_h, ysr, dst_w, 0, yup, dst_w, 0, frame_of(d, f), dst_w, dst_h, 1, g, clamp,
+                                             t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
+    }
+    return release_workspace(c);
+}
+
+}  // extern "C"

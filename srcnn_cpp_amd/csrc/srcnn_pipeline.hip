@@ -11,8 +11,9 @@
 // no LDS, consecutive lanes on consecutive bytes.
 // At the end of the file: the cubic resize of float32 planes, torch's bicubic
 // (srcnn_resize_cubic_f32*, the step in front of the float image path), and the
-// two kernels of srcnn_process_rgb_f32* built from its tile.
-#include "srcnn_kernels.h"
+// two kernels of srcnn_process_rgb_f32* built from its tile; then the accessor
+// forms of those four kernels for images as they are stored (srcnn_*_image_dev).
+#include "srcnn_image.h"
 
 // No FMA contraction anywhere in this file (also given on the command line, srcnn_cpp_amd/build.py): the vertical pass of
 // the resize reproduces OpenCV's separately rounded float32 products and sums.
@@ -787,6 +788,499 @@ hipError_t launch_resize_merge_f32(const float *src, long sstride, long sch_pitc
     auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };
     hipLaunchKernelGGL(resize_merge_f32_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), cap(n_frames)), dim3(256), 0,
                        st, p, q);
+    return hipGetLastError();
+}
+
+// ---- images as they are stored (srcnn_*_image_dev): accessor forms of the four kernels above ------------------------------
+// The same tables, tile (F32_RT, F32_RMAX, F32_SMAX: the same LDS), variant choice and cubic_sum4 order; f32_tile_cols and
+// f32_tile_hpass are the ones above.  Only the fill's load and the vertical pass's store differ: they go through an ImageRef.
+// The element kind is a workgroup-uniform switch, not a template parameter: 4 source x 4 destination kinds x 4 kernels would be
+// 64 kernels for a branch that is scalar (s_cmp on a kernel argument) and sits beside a global load or store.
+// Everything between load and store is float32 as above, so a call equals store(f32 call(load(x))) bit for bit.
+__device__ __forceinline__ float image_load(const ImageRef &im, long at)
+{
+    switch (im.elem) {
+    case ELEM_F32: return static_cast<const float *>(im.data)[at];
+    case ELEM_F16: return (float)static_cast<const _Float16 *>(im.data)[at];                           // exact
+    case ELEM_BF16: return __uint_as_float((unsigned)static_cast<const uint16_t *>(im.data)[at] << 16);  // exact
+    default: return __fmul_rn((float)static_cast<const uint8_t *>(im.data)[at], im.scale);
+    }
+}
+
+// float32 -> bfloat16 bits, round to nearest even; a NaN stays a NaN (quiet, sign kept)
+__device__ __forceinline__ unsigned bf16_bits(float v)
+{
+    const unsigned u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// float32 -> float16 bits: v_cvt_f16_f32, round to nearest even, overflow to +-inf, f16 subnormals kept
+__device__ __forceinline__ unsigned f16_bits(float v)
+{
+    const _Float16 h = (_Float16)v;
+    return (unsigned)__builtin_bit_cast(unsigned short, h);
+}
+// float32 -> byte: rint_half_even(min(max(v scale, 0), 255)), 0 for a NaN (neither comparison holds for one)
+__device__ __forceinline__ unsigned u8_bits(float v, float scale)
+{
+    float t = __fmul_rn(v, scale);
+    t = t >= 0.f ? t : 0.f;
+    t = t > 255.f ? 255.f : t;
+    return (unsigned)(int)rintf(t);
+}
+
+__device__ __forceinline__ void image_store(const ImageRef &im, long at, float v)
+{
+    switch (im.elem) {
+    case ELEM_F32: static_cast<float *>(im.data)[at] = v; break;
+    case ELEM_F16: static_cast<uint16_t *>(im.data)[at] = (uint16_t)f16_bits(v); break;
+    case ELEM_BF16: static_cast<uint16_t *>(im.data)[at] = (uint16_t)bf16_bits(v); break;
+    default: static_cast<uint8_t *>(im.data)[at] = (uint8_t)u8_bits(v, im.scale); break;
+    }
+}
+
+// Four CONTIGUOUS elements from element offset `at`: one store of 16 (F32), 8 (F16, BF16) or 4 (U8) bytes where the ADDRESS
+// is aligned to that, else element by element.
+__device__ __forceinline__ void image_store_run4(const ImageRef &im, long at, const f32x4 v)
+{
+    if (im.elem == ELEM_F32) {
+        float *o = static_cast<float *>(im.data) + at;
+        if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) { *reinterpret_cast<f32x4 *>(o) = v; return; }
+    } else if (im.elem == ELEM_U8) {
+        uint8_t *o = static_cast<uint8_t *>(im.data) + at;
+        if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+            *reinterpret_cast<unsigned *>(o) = u8_bits(v[0], im.scale) | u8_bits(v[1], im.scale) << 8 |
+                                               u8_bits(v[2], im.scale) << 16 | u8_bits(v[3], im.scale) << 24;
+            return;
+        }
+    } else {
+        uint16_t *o = static_cast<uint16_t *>(im.data) + at;
+        if ((reinterpret_cast<uintptr_t>(o) & 7) == 0) {
+            const bool h = im.elem == ELEM_F16;
+            uint2 w;
+            w.x = (h ? f16_bits(v[0]) : bf16_bits(v[0])) | (h ? f16_bits(v[1]) : bf16_bits(v[1])) << 16;
+            w.y = (h ? f16_bits(v[2]) : bf16_bits(v[2])) | (h ? f16_bits(v[3]) : bf16_bits(v[3])) << 16;
+            *reinterpret_cast<uint2 *>(o) = w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) image_store(im, at + c, v[c]);
+}
+
+// ... and the load of four contiguous elements, by the same rule
+__device__ __forceinline__ f32x4 image_load_run4(const ImageRef &im, long at)
+{
+    f32x4 v;
+    if (im.elem == ELEM_F32) {
+        const float *o = static_cast<const float *>(im.data) + at;
+        if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) return *reinterpret_cast<const f32x4 *>(o);
+    } else if (im.elem == ELEM_U8) {
+        const uint8_t *o = static_cast<const uint8_t *>(im.data) + at;
+        if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+            const unsigned w = *reinterpret_cast<const unsigned *>(o);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = __fmul_rn((float)((w >> (8 * c)) & 0xffu), im.scale);
+            return v;
+        }
+    } else {
+        const uint16_t *o = static_cast<const uint16_t *>(im.data) + at;
+        if ((reinterpret_cast<uintptr_t>(o) & 7) == 0) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(o);
+            const unsigned b[4] = {w.x & 0xffffu, w.x >> 16, w.y & 0xffffu, w.y >> 16};
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                v[c] = im.elem == ELEM_F16 ? (float)__builtin_bit_cast(_Float16, (unsigned short)b[c]) : __uint_as_float(b[c] << 16);
+            return v;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = image_load(im, at + c);
+    return v;
+}
+
+// Four columns of a row from element offset `at`, px_step apart, of which the first n (>= 1) exist: planar rows (px_step 1)
+// with all four present as one run, everything else element by element.
+__device__ __forceinline__ void image_store4(const ImageRef &im, long at, const f32x4 v, int n)
+{
+    if (im.px_step == 1 && n >= 4) {
+        image_store_run4(im, at, v);
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < n) image_store(im, at + c * im.px_step, v[c]);
+}
+
+// Four pixels of three channels (v[channel][column]) into an image whose pixels are three adjacent elements (px_step 3,
+// ch_pitch 1): twelve contiguous elements from `at`, as three runs
+__device__ __forceinline__ void image_store_pixels4(const ImageRef &im, long at, const f32x4 v0, const f32x4 v1, const f32x4 v2)
+{
+    image_store_run4(im, at, f32x4{v0[0], v1[0], v2[0], v0[1]});
+    image_store_run4(im, at + 4, f32x4{v1[1], v2[1], v0[2], v1[2]});
+    image_store_run4(im, at + 8, f32x4{v2[2], v0[3], v1[3], v2[3]});
+}
+__host__ __device__ __forceinline__ bool image_pixels_of_3(const ImageRef &im) { return im.px_step == 3 && im.ch_pitch == 1; }
+
+// geometry and tables as the kernels above take them (g.src, g.dst and their strides unused), and the two images
+struct ImageResizeArgs {
+    F32ResizeArgs g;
+    ImageRef src, dst;
+};
+
+__global__ __launch_bounds__(256) void resize_cubic_image_direct_kernel(const ImageResizeArgs a)
+{
+    const F32ResizeArgs &p = a.g;
+    const int dx = blockIdx.x * 256 + threadIdx.x;
+    if (dx >= p.dw) return;
+    const int x0 = p.xfirst[dx] - 1;
+    long xs[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xs[k] = (long)min(max(x0 + k, 0), p.sw - 1) * a.src.px_step;
+    const f32x4 ca = *reinterpret_cast<const f32x4 *>(p.xcoef + 4L * dx);
+    for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
+        const int frame = z / p.channels, ch = z - frame * p.channels;
+        const long s = frame * a.src.frame_pitch + ch * a.src.ch_pitch;
+        const long d = frame * a.dst.frame_pitch + ch * a.dst.ch_pitch + dx * a.dst.px_step;
+        for (int dy = blockIdx.y; dy < p.dh; dy += gridDim.y) {
+            const int y0 = p.yfirst[dy] - 1;
+            float hs[4];
+#pragma unroll
+            for (int ky = 0; ky < 4; ++ky) {
+                const long row = s + (long)min(max(y0 + ky, 0), p.sh - 1) * a.src.stride;
+                hs[ky] = cubic_sum4(image_load(a.src, row + xs[0]), image_load(a.src, row + xs[1]), image_load(a.src, row + xs[2]),
+                                    image_load(a.src, row + xs[3]), ca);
+            }
+            image_store(a.dst, d + (long)dy * a.dst.stride,
+                        cubic_sum4(hs[0], hs[1], hs[2], hs[3], *reinterpret_cast<const f32x4 *>(p.ycoef + 4L * dy)));
+        }
+    }
+}
+
+// f32_tile_fill through the accessor; s: element offset of the plane (LUMA: of the first of the pixel's three channels, which
+// lie ch_pitch apart -- adjacent in an interleaved image).  Consecutive lanes take consecutive columns: memory order.
+template <bool LUMA>
+__device__ __forceinline__ void image_tile_fill(float (*sbuf)[F32_SMAX], const ImageRef &im, long s, const F32ResizeArgs &p,
+                                                const F32LumaArgs &q, int r_lo, int nrow, int c_lo, int ncol)
+{
+    for (int e = threadIdx.x; e < nrow * ncol; e += 256) {
+        const int rr = e / ncol, cc = e - rr * ncol;
+        const long at = s + (long)min(max(r_lo + rr, 0), p.sh - 1) * im.stride + (long)min(max(c_lo + cc, 0), p.sw - 1) * im.px_step;
+        if (LUMA) {
+            float y = __fadd_rn(__fmul_rn(q.w0, image_load(im, at)), __fmul_rn(q.w1, image_load(im, at + im.ch_pitch)));
+            y = __fadd_rn(y, __fmul_rn(q.w2, image_load(im, at + 2 * im.ch_pitch)));
+            sbuf[rr][cc] = __fadd_rn(y, q.off);
+        } else {
+            sbuf[rr][cc] = image_load(im, at);
+        }
+    }
+}
+
+// The vertical pass of f32_tile_vpass for one row dy of the thread's four columns (r: its place among the thread's rows)
+template <bool MERGE>
+__device__ __forceinline__ f32x4 image_tile_vsum(const float (*hbuf)[256], const F32ResizeArgs &p, const F32LumaArgs &q,
+                                                 const f32x4 *add, int r, int dy, int r_lo, const F32TileCols &t)
+{
+    const int j = p.yfirst[dy] - 1 - r_lo;
+    const f32x4 b = *reinterpret_cast<const f32x4 *>(p.ycoef + 4L * dy);
+    f32x4 h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h[k] = *reinterpret_cast<const f32x4 *>(&hbuf[j + k][4 * t.tx]);
+    f32x4 v;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = cubic_sum4(h[0][c], h[1][c], h[2][c], h[3][c], b);
+    if (MERGE) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float m = __fadd_rn(v[c], add[r][c]);
+            if (q.clamp) {
+                m = m < q.lo ? q.lo : m;
+                m = m > q.hi ? q.hi : m;
+            }
+            v[c] = m;
+        }
+    }
+    return v;
+}
+
+// f32_tile_vpass through the accessor; d: element offset of the plane in im
+template <bool MERGE>
+__device__ __forceinline__ void image_tile_vpass(const float (*hbuf)[256], const ImageRef &im, long d, const F32ResizeArgs &p,
+                                                 const F32LumaArgs &q, const f32x4 *add, int dy0, int dy1, int r_lo,
+                                                 const F32TileCols t)
+{
+    if (t.dx < p.dw) {
+#pragma unroll
+        for (int r = 0; r < F32_RPT; ++r) {
+            const int dy = dy0 + F32_RPT * t.ty + r;
+            if (dy >= dy1) break;
+            image_store4(im, d + (long)dy * im.stride + t.dx * im.px_step, image_tile_vsum<MERGE>(hbuf, p, q, add, r, dy, r_lo, t),
+                         p.dw - t.dx);
+        }
+    }
+}
+
+template <bool LUMA>
+__device__ __forceinline__ void resize_image_tiled(const ImageResizeArgs &a, const F32LumaArgs q, float (*hbuf)[256],
+                                                   float (*sbuf)[F32_SMAX])
+{
+    const F32ResizeArgs &p = a.g;
+    const F32TileCols t = f32_tile_cols(p);
+    const int n_row_tiles = (p.dh + F32_RT - 1) / F32_RT;
+    for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
+        const int frame = z / p.channels, ch = z - frame * p.channels;
+        const long s = frame * a.src.frame_pitch + ch * a.src.ch_pitch;
+        const long d = frame * a.dst.frame_pitch + ch * a.dst.ch_pitch;
+        for (int rt = blockIdx.y; rt < n_row_tiles; rt += gridDim.y) {
+            const int dy0 = rt * F32_RT, dy1 = min(dy0 + F32_RT, p.dh);
+            const int r_lo = p.yfirst[dy0] - 1, r_hi = p.yfirst[dy1 - 1] + 2;
+            const int nrow = r_hi - r_lo + 1;
+            image_tile_fill<LUMA>(sbuf, a.src, s, p, q, r_lo, nrow, t.c_lo, t.ncol);      // (barriers: as in resize_f32_tiled)
+            __syncthreads();
+            f32_tile_hpass(hbuf, sbuf, nrow, t);
+            __syncthreads();
+            image_tile_vpass<false>(hbuf, a.dst, d, p, q, nullptr, dy0, dy1, r_lo, t);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void resize_cubic_image_tiled_kernel(const ImageResizeArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    resize_image_tiled<false>(a, F32LumaArgs{}, hbuf, sbuf);
+}
+
+// Front of srcnn_process_rgb_image_dev: Yup (a packed float32 plane, a.dst) from the luma of the stored image
+__global__ __launch_bounds__(256) void luma_resize_image_kernel(const ImageResizeArgs a, const F32LumaArgs q)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    resize_image_tiled<true>(a, q, hbuf, sbuf);
+}
+
+// Back: as resize_merge_f32_kernel, in one of two store orders.  PIXELS false: channel after channel, each channel's tile
+// stored on its own pass (any destination).  PIXELS true, for a destination whose pixels are three adjacent elements: the three
+// channels' results of the thread's F32_RPT rows x 4 columns are kept in registers and stored pixel-contiguous, twelve elements per row as three runs.  Same sums in the same order either way.
+template <bool PIXELS>
+__device__ __forceinline__ void resize_merge_image(const ImageResizeArgs &a, const F32LumaArgs &q, float (*hbuf)[256],
+                                                   float (*sbuf)[F32_SMAX])
+{
+    const F32ResizeArgs &p = a.g;
+    const F32TileCols t = f32_tile_cols(p);
+    const int n_row_tiles = (p.dh + F32_RT - 1) / F32_RT;
+    for (int z = blockIdx.z; z < p.n_planes; z += gridDim.z) {
+        const long s = z * a.src.frame_pitch, d = z * a.dst.frame_pitch;
+        const float *ysr = q.ysr + z * q.ysr_frame_pitch, *yup = q.yup + z * q.yup_frame_pitch;
+        for (int rt = blockIdx.y; rt < n_row_tiles; rt += gridDim.y) {
+            const int dy0 = rt * F32_RT, dy1 = min(dy0 + F32_RT, p.dh);
+            const int r_lo = p.yfirst[dy0] - 1, r_hi = p.yfirst[dy1 - 1] + 2;
+            const int nrow = r_hi - r_lo + 1;
+            f32x4 add[F32_RPT];
+#pragma unroll
+            for (int r = 0; r < F32_RPT; ++r) {
+                const int dy = dy0 + F32_RPT * t.ty + r;
+                add[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (t.dx < p.dw && dy < dy1) {
+                    const f32x4 sr = f32_load4(ysr + (long)dy * q.ysr_stride + t.dx, p.dw - t.dx);
+                    const f32x4 up = f32_load4(yup + (long)dy * q.yup_stride + t.dx, p.dw - t.dx);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) add[r][c] = __fmul_rn(__fsub_rn(sr[c], up[c]), q.g);
+                }
+            }
+            if constexpr (PIXELS) {
+                // (the channel loop stays rolled -- unrolled it takes more than 256 registers -- and the results shift through
+                // three register sets instead of being indexed by the channel: k0 ends as channel 0, k2 as channel 2)
+                f32x4 k0[F32_RPT], k1[F32_RPT], k2[F32_RPT];
+#pragma unroll
+                for (int r = 0; r < F32_RPT; ++r) k0[r] = k1[r] = k2[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+                for (int ch = 0; ch < 3; ++ch) {
+                    image_tile_fill<false>(sbuf, a.src, s + ch * a.src.ch_pitch, p, q, r_lo, nrow, t.c_lo, t.ncol);
+                    __syncthreads();
+                    f32_tile_hpass(hbuf, sbuf, nrow, t);
+                    __syncthreads();
+#pragma unroll
+                    for (int r = 0; r < F32_RPT; ++r) {
+                        const int dy = min(dy0 + F32_RPT * t.ty + r, dy1 - 1);      // (rows beyond the tile: computed, not stored)
+                        k0[r] = k1[r];
+                        k1[r] = k2[r];
+                        k2[r] = image_tile_vsum<true>(hbuf, p, q, add, r, dy, r_lo, t);
+                    }
+                }
+                if (t.dx < p.dw) {
+#pragma unroll
+                    for (int r = 0; r < F32_RPT; ++r) {
+                        const int dy = dy0 + F32_RPT * t.ty + r;
+                        if (dy >= dy1) break;
+                        const long at = d + (long)dy * a.dst.stride + 3L * t.dx;
+                        if (t.dx + 3 < p.dw) {
+                            image_store_pixels4(a.dst, at, k0[r], k1[r], k2[r]);
+                        } else {
+                            image_store4(a.dst, at, k0[r], p.dw - t.dx);
+                            image_store4(a.dst, at + 1, k1[r], p.dw - t.dx);
+                            image_store4(a.dst, at + 2, k2[r], p.dw - t.dx);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll 1
+                for (int ch = 0; ch < 3; ++ch) {
+                    image_tile_fill<false>(sbuf, a.src, s + ch * a.src.ch_pitch, p, q, r_lo, nrow, t.c_lo, t.ncol);
+                    __syncthreads();
+                    f32_tile_hpass(hbuf, sbuf, nrow, t);
+                    __syncthreads();
+                    image_tile_vpass<true>(hbuf, a.dst, d + ch * a.dst.ch_pitch, p, q, add, dy0, dy1, r_lo, t);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void resize_merge_image_kernel(const ImageResizeArgs a, const F32LumaArgs q)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    resize_merge_image<false>(a, q, hbuf, sbuf);
+}
+
+__global__ __launch_bounds__(256) void resize_merge_image_pixels_kernel(const ImageResizeArgs a, const F32LumaArgs q)
+{
+    __shared__ __attribute__((aligned(16))) float hbuf[F32_RMAX][256];
+    __shared__ float sbuf[F32_RMAX][F32_SMAX];
+    resize_merge_image<true>(a, q, hbuf, sbuf);
+}
+
+// dst = store(load(src)) for images of C = 1 or 3 channels: a lane converts four adjacent pixels of every channel.  A side
+// whose pixels are C adjacent elements is read / written as 4 C contiguous elements (C runs of four), a planar side as a run of
+// four per channel, each run one access of 4 ... 16 bytes where its address is aligned; any other layout, and the last columns
+// of a row, element by element.  Rows and frames beyond the grid's limits are walked by the same blocks.
+template <int C>
+__global__ __launch_bounds__(256) void convert_image_kernel(const ImageRef src, const ImageRef dst, int width, int height, int n_frames)
+{
+    const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x >= width) return;
+    const int n = width - x;
+    const bool s_px = C > 1 && src.px_step == C && src.ch_pitch == 1, d_px = C > 1 && dst.px_step == C && dst.ch_pitch == 1;
+    for (int f = blockIdx.z; f < n_frames; f += gridDim.z) {
+        for (int y = blockIdx.y; y < height; y += gridDim.y) {
+            const long s = f * src.frame_pitch + y * src.stride + x * src.px_step;
+            const long d = f * dst.frame_pitch + y * dst.stride + x * dst.px_step;
+            f32x4 v[C];      // v[channel][column]
+            if (n >= 4 && s_px) {
+                float e[4 * C];
+#pragma unroll
+                for (int k = 0; k < C; ++k) {
+                    const f32x4 r = image_load_run4(src, s + 4 * k);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) e[4 * k + c] = r[c];
+                }
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[ch][c] = e[c * C + ch];
+            } else if (n >= 4 && src.px_step == 1) {
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) v[ch] = image_load_run4(src, s + ch * src.ch_pitch);
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[ch][c] = c < n ? image_load(src, s + ch * src.ch_pitch + c * src.px_step) : 0.f;
+            }
+            if (n >= 4 && d_px) {
+                float e[4 * C];
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) e[c * C + ch] = v[ch][c];
+#pragma unroll
+                for (int k = 0; k < C; ++k) image_store_run4(dst, d + 4 * k, f32x4{e[4 * k], e[4 * k + 1], e[4 * k + 2], e[4 * k + 3]});
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) image_store4(dst, d + ch * dst.ch_pitch, v[ch], n);
+            }
+        }
+    }
+}
+
+// Which store order the merge kernel takes for a destination of 3-element pixels (DESIGN.md 4.14 has both orders' times);
+// -DSRCNN_MERGE_CHANNEL_PASSES builds the other one for an A/B run
+#ifdef SRCNN_MERGE_CHANNEL_PASSES
+constexpr bool kMergePixelOrder = false;
+#else
+constexpr bool kMergePixelOrder = true;
+#endif
+
+static unsigned grid_cap(int v) { return (unsigned)(v < 65535 ? v : 65535); }      // grid y and z: the kernels walk what lies beyond
+
+static ImageResizeArgs image_args(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_planes,
+                                  const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef)
+{
+    return ImageResizeArgs{F32ResizeArgs{nullptr, 0, 0, 0, sw, sh, nullptr, 0, 0, 0, dw, dh, channels, n_planes, xfirst, yfirst, xcoef,
+                                         ycoef}, src, dst};
+}
+
+hipError_t launch_resize_cubic_image(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels,
+                                     int n_frames, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
+                                     hipStream_t st)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels <= 0 || n_frames <= 0 || (long)channels * n_frames > 0x7fffffffL)
+        return hipErrorInvalidValue;
+    const ImageResizeArgs a = image_args(src, sw, sh, dst, dw, dh, channels, channels * n_frames, xfirst, xcoef, yfirst, ycoef);
+    const unsigned gz = grid_cap(a.g.n_planes);
+    if (resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED)
+        hipLaunchKernelGGL(resize_cubic_image_tiled_kernel, dim3((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), gz),
+                           dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(resize_cubic_image_direct_kernel, dim3((dw + 255) / 256, grid_cap(dh), gz), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_luma_resize_image(const ImageRef &src, int sw, int sh, float *yup, long ystride, long yframe_pitch, int dw, int dh,
+                                    int n_frames, const float luma[4], const int *xfirst, const float *xcoef, const int *yfirst,
+                                    const float *ycoef, hipStream_t st)
+{
+    if (!rgb_f32_geometry_ok(sw, sh, dw, dh, n_frames)) return hipErrorInvalidValue;
+    const ImageRef dst{yup, ELEM_F32, 0.f, 1, ystride, 0, yframe_pitch};
+    const ImageResizeArgs a = image_args(src, sw, sh, dst, dw, dh, 1, n_frames, xfirst, xcoef, yfirst, ycoef);
+    F32LumaArgs q{};
+    q.w0 = luma[0]; q.w1 = luma[1]; q.w2 = luma[2]; q.off = luma[3];
+    hipLaunchKernelGGL(luma_resize_image_kernel, dim3((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), grid_cap(n_frames)),
+                       dim3(256), 0, st, a, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_merge_image(const ImageRef &src, int sw, int sh, const float *ysr, long ysr_stride, long ysr_frame_pitch,
+                                     const float *yup, long yup_stride, long yup_frame_pitch, const ImageRef &dst, int dw, int dh,
+                                     int n_frames, float g, const float *clamp, const int *xfirst, const float *xcoef,
+                                     const int *yfirst, const float *ycoef, hipStream_t st)
+{
+    if (!rgb_f32_geometry_ok(sw, sh, dw, dh, n_frames)) return hipErrorInvalidValue;
+    const ImageResizeArgs a = image_args(src, sw, sh, dst, dw, dh, 3, n_frames, xfirst, xcoef, yfirst, ycoef);
+    F32LumaArgs q{};
+    q.g = g;
+    q.clamp = clamp != nullptr;
+    if (clamp) { q.lo = clamp[0]; q.hi = clamp[1]; }
+    q.ysr = ysr; q.ysr_stride = ysr_stride; q.ysr_frame_pitch = ysr_frame_pitch;
+    q.yup = yup; q.yup_stride = yup_stride; q.yup_frame_pitch = yup_frame_pitch;
+    const dim3 grid((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), grid_cap(n_frames));
+    if (kMergePixelOrder && image_pixels_of_3(dst))
+        hipLaunchKernelGGL(resize_merge_image_pixels_kernel, grid, dim3(256), 0, st, a, q);
+    else
+        hipLaunchKernelGGL(resize_merge_image_kernel, grid, dim3(256), 0, st, a, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_convert_image(const ImageRef &src, const ImageRef &dst, int width, int height, int channels, int n_frames,
+                                hipStream_t st)
+{
+    if (width <= 0 || height <= 0 || (channels != 1 && channels != 3) || n_frames <= 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((width + 1023) / 1024), grid_cap(height), grid_cap(n_frames));
+    if (channels == 1)
+        hipLaunchKernelGGL(convert_image_kernel<1>, grid, dim3(256), 0, st, src, dst, width, height, n_frames);
+    else
+        hipLaunchKernelGGL(convert_image_kernel<3>, grid, dim3(256), 0, st, src, dst, width, height, n_frames);
     return hipGetLastError();
 }
 

@@ -5,6 +5,12 @@
     y = fast(x)                                # x: float32 (N, C, H, W) or (C, H, W) on that GPU; y ~ module(x)
     z = fast.upscale(lr, scale=2)              # ~ module(F.interpolate(lr, size, mode="bicubic", align_corners=False))
     rgb = fast.upscale_rgb(lr_rgb, scale=2)    # a 1-channel module on the luma of an RGB tensor, chroma resized, merged
+    out = fast.upscale_rgb_image(torch.from_numpy(hwc_u8).cuda().permute(2, 0, 1), scale=2)   # H x W x 3 uint8 in and out
+
+The *_image methods (forward_image, resize_image, upscale_image, upscale_rgb_image) take the tensor in the format it is stored
+in: float32, float16, bfloat16 or uint8, any positive strides (a permuted H x W x C view, channels_last, padded rows), and write
+the dtype and layout asked for.  A uint8 tensor is read as byte * in_scale (1 / 255) and written as
+round(clamp(value * out_scale, 0, 255)) (255); between load and store the arithmetic is that of the float32 methods, bit for bit.
 
 The weights go in as they are (the data is already in the model's units), the module's padding mode is the context's padding,
 the call runs on torch.cuda.current_stream() and reads the tensor where it lies: data_ptr() and strides, no copy.  torch is
@@ -12,7 +18,8 @@ imported when compile_module is called, not when this module is.
 """
 from __future__ import annotations
 
-from . import LUMA_BT601, MODE_BANDED16, MODE_MFMA, Context, _clamp2, _luma4, model_from_module
+from . import (ELEM_BF16, ELEM_F16, ELEM_F32, ELEM_U8, LUMA_BT601, MODE_BANDED16, MODE_MFMA, Context, Image, _clamp2, _luma4,
+               model_from_module)
 
 __all__ = ["compile_module", "CompiledModule"]
 
@@ -46,6 +53,76 @@ def check_input(x, channels: int, device_index: int):
     if x.device.index != device_index:
         raise ValueError(f"expected a tensor on cuda:{device_index}, got one on {x.device}")
     return n, h, w, (sh if h > 1 else w), (sc if c > 1 else 0), (sn if n > 1 else 0)
+
+
+def _elem_of(dtype):
+    import torch
+    return {torch.float32: ELEM_F32, torch.float16: ELEM_F16, torch.bfloat16: ELEM_BF16, torch.uint8: ELEM_U8}.get(dtype)
+
+
+def _u8_scale(name, scale, default):
+    scale = default if scale is None else float(scale)
+    if not (scale > 0.0 and scale != float("inf")):
+        raise ValueError(f"{name} {scale!r}: expected a finite number > 0")
+    return scale
+
+
+def describe_image(x, channels: int, in_scale=None):
+    """The Image of a tensor as it is stored: x is (N, C, H, W) or (C, H, W) with C = channels, dtype float32, float16, bfloat16
+    or uint8, every stride of a dimension longer than 1 positive -- a permuted H x W x C view and a channels_last tensor have a
+    pixel step of C and a channel pitch of 1.  Returns (image, n, h, w); ValueError otherwise.  Looks at shape, dtype and strides
+    only: the device is check_image_device's."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"expected a torch.Tensor, got {type(x).__name__}")
+    elem = _elem_of(x.dtype)
+    if elem is None:
+        raise ValueError(f"expected a float32, float16, bfloat16 or uint8 tensor, got {x.dtype}")
+    if x.dim() not in (3, 4):
+        raise ValueError(f"expected shape (N, {channels}, H, W) or ({channels}, H, W), got {tuple(x.shape)}")
+    shape, strides = tuple(x.shape), tuple(x.stride())
+    if x.dim() == 3:
+        shape, strides = (1,) + shape, (0,) + strides
+    n, c, h, w = shape
+    if c != channels:
+        raise ValueError(f"expected {channels} channel(s), the tensor has {c}: shape {tuple(x.shape)} (an H x W x C image goes in as "
+                         "its view .permute(2, 0, 1))")
+    if 0 in (n, h, w):
+        raise ValueError(f"empty tensor of shape {tuple(x.shape)}")
+    if any(count > 1 and step <= 0 for count, step in zip(shape, strides)):
+        raise ValueError(f"strides {tuple(x.stride())}: every stride of a dimension longer than 1 must be positive")
+    sn, sc, sh, sw = (step if count > 1 else 0 for count, step in zip(shape, strides))
+    scale = _u8_scale("in_scale", in_scale, 1.0 / 255.0) if elem == ELEM_U8 else 1.0
+    return Image(x.data_ptr(), elem, sw if w > 1 else 1, sh, sc, sn, scale), n, h, w
+
+
+def check_image_device(x, device_index: int):
+    if x.device.type != "cuda":
+        raise ValueError(f"expected a tensor on cuda:{device_index}, got one on {x.device} (there is no CPU path)")
+    if x.device.index != device_index:
+        raise ValueError(f"expected a tensor on cuda:{device_index}, got one on {x.device}")
+
+
+def is_channels_last(image: Image, channels: int) -> bool:
+    """Whether the pixels of a described tensor are interleaved: the default layout of a call's result."""
+    return channels > 1 and image.ch_pitch != 0 and image.ch_pitch < image.px_step
+
+
+def empty_image(x, n, channels, h, w, dtype, channels_last, out_scale=None):
+    """A new tensor for a call's result, shaped like x ((N, C, h, w), or (C, h, w) for a 3-dimensional x), and its Image:
+    channels_last allocates N x h x w x C and returns the permuted view."""
+    import torch
+    elem = _elem_of(dtype)
+    if elem is None:
+        raise ValueError(f"out_dtype {dtype}: expected float32, float16, bfloat16 or uint8")
+    scale = _u8_scale("out_scale", out_scale, 255.0) if elem == ELEM_U8 else 1.0
+    if channels_last:
+        out = torch.empty((n, h, w, channels), dtype=dtype, device=x.device).permute(0, 3, 1, 2)
+        image = Image(out.data_ptr(), elem, channels, w * channels, 1, h * w * channels, scale)
+    else:
+        out = torch.empty((n, channels, h, w), dtype=dtype, device=x.device)
+        image = Image(out.data_ptr(), elem, 1, w, h * w, channels * h * w, scale)
+    return (out[0] if x.dim() == 3 else out), image
 
 
 def check_size(size):
@@ -146,6 +223,65 @@ class CompiledModule:
         self._on_current_stream(x.device, lambda: self.ctx.process_rgb_f32_dev(
             x.data_ptr(), stride, ch_pitch, frame_pitch, w, h, out.data_ptr(), dw, dh * dw, 3 * dh * dw, dw, dh, luma, clamp, n))
         return out
+
+    # ---- images as they are stored: any of four dtypes, any positive strides, in and out ----
+    def _image_call(self, x, channels, size, out_dtype, out_channels_last, in_scale, out_scale, call, check=None):
+        src, n, h, w = describe_image(x, channels, in_scale)
+        dh, dw = (h, w) if size is None else size(h, w)
+        if check is not None:
+            check(h, w, dh, dw)
+        check_image_device(x, self.device)
+        last = is_channels_last(src, channels) if out_channels_last is None else bool(out_channels_last) and channels > 1
+        out, dst = empty_image(x, n, channels, dh, dw, x.dtype if out_dtype is None else out_dtype, last, out_scale)
+        self._on_current_stream(x.device, lambda: call(src, w, h, dst, dw, dh, n))
+        return out
+
+    @staticmethod
+    def _target(name, scale, size):
+        if (scale is None) == (size is None):
+            raise ValueError(f"{name}: give exactly one of scale and size")
+        if size is not None:
+            dh, dw = check_size(size)
+            return lambda h, w: (dh, dw)
+        from . import scaled_size
+        return lambda h, w: scaled_size(w, h, float(scale))[::-1]
+
+    def forward_image(self, x, out_dtype=None, out_channels_last=None, in_scale=None, out_scale=None):
+        """self(x) on a tensor as it is stored: float32, float16, bfloat16 or uint8, any positive strides (pass an H x W x C
+        image as its view .permute(2, 0, 1)), read where it lies.  The result has out_dtype (default: x's) and is channels-last
+        where out_channels_last says so (default: where x is).  uint8 is read as byte * in_scale (default 1 / 255) and written
+        as round(clamp(value * out_scale, 0, 255)) (default 255).  Bit for bit store(self(load(x)))."""
+        return self._image_call(x, self.channels, None, out_dtype, out_channels_last, in_scale, out_scale,
+                                lambda s, w, h, d, dw, dh, n: self.ctx.forward_image_dev(s, d, w, h, n))
+
+    def resize_image(self, x, size, out_dtype=None, out_channels_last=None, in_scale=None, out_scale=None):
+        """resize() on a tensor as it is stored (see forward_image); size equal to x's converts the format and nothing else."""
+        dh, dw = check_size(size)
+        return self._image_call(x, self.channels, lambda h, w: (dh, dw), out_dtype, out_channels_last, in_scale, out_scale,
+                                lambda s, w, h, d, dw, dh, n: self.ctx.resize_cubic_image_dev(s, w, h, d, dw, dh, self.channels, n))
+
+    def upscale_image(self, x, scale=None, size=None, out_dtype=None, out_channels_last=None, in_scale=None, out_scale=None):
+        """upscale() on a tensor as it is stored (see forward_image)."""
+        return self._image_call(x, self.channels, self._target("upscale_image", scale, size), out_dtype, out_channels_last, in_scale,
+                                out_scale, lambda *a: self.ctx.process_image_dev(*a))
+
+    def upscale_rgb_image(self, x, scale=None, size=None, luma=LUMA_BT601, clamp=None, out_dtype=None, out_channels_last=None,
+                          in_scale=None, out_scale=None):
+        """upscale_rgb() on a tensor as it is stored (see forward_image): a decoded H x W x 3 uint8 picture goes in as
+        .permute(2, 0, 1) and comes back as uint8 at the target size, the same view of an H' x W' x 3 tensor.  luma and clamp
+        are in the units of the LOADED values ([0, 1] for uint8 with the default in_scale); the clamp applies in float32,
+        ahead of the store."""
+        if self.channels != 1:
+            raise ValueError(f"upscale_rgb_image runs a 1-channel module on the luma of the tensor: this module has {self.channels} "
+                             "channels (upscale_image runs it on the channels themselves)")
+        target = self._target("upscale_rgb_image", scale, size)
+
+        def check(h, w, dh, dw):
+            if dh < h or dw < w:
+                raise ValueError(f"size {(dh, dw)} is smaller than the tensor's {(h, w)}: upscale_rgb_image resizes up or not at all")
+            _luma4(luma), _clamp2(clamp)
+        return self._image_call(x, 3, target, out_dtype, out_channels_last, in_scale, out_scale,
+                                lambda *a: self.ctx.process_rgb_image_dev(*a[:-1], luma, clamp, a[-1]), check)
 
     def close(self):
         self.ctx.close()
