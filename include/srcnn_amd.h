@@ -476,6 +476,58 @@ int srcnn_process_rgb_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_
                                 const srcnn_image *dst, int dst_w, int dst_h,
                                 const float luma[4], const float *clamp /* NULL or {lo, hi} */, int n_frames);
 
+/* Antialiased bicubic resize: the way DOWN.  srcnn_resize_cubic_f32 shrinks by plain 4-tap sampling and aliases; this is the
+ * resize that makes a low-resolution picture -- the degradation in front of every SRCNN evaluation and training pair, previews
+ * and thumbnails -- as torch.nn.functional.interpolate(x, size=(dst_h, dst_w), mode="bicubic", align_corners=False,
+ * antialias=True) defines it, on float32 planes and on images as they are stored.
+ *   - Arithmetic, per axis with s source and n output samples; everything in float64 on the host, in exactly this order of
+ *     operations (every line one rounded operation after the other, left to right; trunc rounds toward zero):
+ *         rho = s / n;   m = rho > 1 ? rho : 1;   support = 2 * m;
+ *         for output d:   c = rho * (d + 0.5)
+ *                         xmin = max(0, trunc((c - support) + 0.5));   xend = min(s, trunc((c + support) + 0.5))
+ *                         count = xend - xmin
+ *                         w_j = k((((j + xmin) - c) + 0.5) / m),   j = 0 .. count - 1
+ *                         total = ((w_0 + w_1) + w_2) + ...;   w_j = w_j / total   (left as it is if total is 0)
+ *         k(x): x = |x|;   x < 1: (((A + 2) * x - (A + 3)) * x) * x + 1;   x < 2: A * ((((x - 5) * x + 8) * x) - 4);   else 0
+ *         A = -0.5   (not the -0.75 of srcnn_resize_cubic_f32)
+ *     and each w_j rounded once to float32.  The taps of output d are source samples xmin .. xmin + count - 1: 4 of them when
+ *     scaling up or at the same size, about 4 rho + 1 when scaling down (8-9 at /2, 12 at /3, 62 for 200 -> 13).  No index is
+ *     clamped anywhere: xmin >= 0 and xmin + count <= s by construction; at the borders the truncated weights are renormalised,
+ *     which is how this differs from srcnn_resize_cubic_f32 even when it scales up.  (Matlab's imresize pads its borders
+ *     differently: agreement with it at the borders is not claimed.)
+ *     The horizontal pass comes first, then the vertical one; each computes acc = x_0 w_0, then acc = acc + x_j w_j for j
+ *     ascending over exactly `count` taps, in float32, every product and sum rounded on its own (no fused multiply-add), in
+ *     every kernel form; the intermediate is float32.  A resize to the same size returns finite input value for value; the
+ *     output is not clamped.  Zero-weight taps at the edge of the support are multiplied like any other, so a non-finite
+ *     sample spreads as it does in torch; only finite input is tested.
+ *   - srcnn_cubic_aa_f32_taps: the table of one axis, host only (no context, no GPU) and the table the kernels run on.  Returns
+ *     the largest count of the axis (> 0).  coef == NULL: that and nothing else (first and count may be NULL), so that a caller
+ *     can size the table.  Otherwise first[d] = xmin, count[d], coef[d * max_taps + j] = w_j, zero for j >= count[d].
+ *     SRCNN_ERR_INVALID for sizes <= 0, a null first or count beside a coef, or max_taps below the largest count.
+ *   - srcnn_resize_cubic_aa_f32(_dev): the layout, the refusals and the stream behaviour of srcnn_resize_cubic_f32(_dev); any
+ *     sizes, up, down or the same; no model needed, every mode.  srcnn_resize_cubic_aa_image_dev: those of
+ *     srcnn_resize_cubic_image_dev; it equals store(srcnn_resize_cubic_aa_f32_dev(load(x))) bit for bit with the load and the
+ *     store stated above for F32, F16, BF16 and U8, which the kernels apply where they read and write: no converting pass.
+ *   - Two kernel forms give the same bits.  Up to a ratio of 4 per axis (and 17 taps) one launch keeps the horizontal results of
+ *     a tile in on-chip memory; beyond it on either axis -- thumbnails, 200 -> 13, n -> 1 -- a horizontal launch writes a
+ *     float32 plane of src_h x dst_w per channel and frame into a workspace the context owns (grown on demand, freed with the
+ *     context) and a vertical launch reads it.
+ *   - SRCNN_ERR_INVALID for null pointers, sizes <= 0, a stride below the width, channels or n_frames <= 0, output planes that
+ *     overlap each other or the input, and descriptors srcnn_image_check refuses.  A refused call launches nothing and leaves
+ *     the context usable.
+ *   Out of scope: other filters, the byte entry point srcnn_resize_cubic, row stripes and several GPUs, a fused
+ *   degrade-then-upscale call; srcnn_process_* and the upscale calls never shrink and have no antialiased form. */
+int srcnn_cubic_aa_f32_taps(int src_n, int dst_n, int *first /*[dst_n]*/, int *count /*[dst_n]*/,
+                            float *coef /*[dst_n][max_taps] or NULL*/, int max_taps);
+int srcnn_resize_cubic_aa_f32_dev(srcnn_ctx *ctx,
+                                  const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w, int src_h,
+                                  float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
+                                  int channels, int n_frames);
+int srcnn_resize_cubic_aa_f32(srcnn_ctx *ctx, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h,
+                              float *dst, size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h, int channels);
+int srcnn_resize_cubic_aa_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                                    const srcnn_image *dst, int dst_w, int dst_h, int channels, int n_frames);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

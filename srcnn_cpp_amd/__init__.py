@@ -35,7 +35,7 @@ __all__ = [
     "stripe_rows", "forward_y_frames_multi", "forward_y_lanes_dev", "forward_y_striped", "forward_y_striped_dev",
     "model_striped", "model_striped_dev",
     "model_color_striped", "model_color_striped_dev", "model_striped_f32", "model_striped_f32_dev",
-    "cubic_f32_taps", "luma_gain", "luma_for_order", "luma_bt601_studio", "LUMA_BT601",
+    "cubic_f32_taps", "cubic_aa_f32_taps", "luma_gain", "luma_for_order", "luma_bt601_studio", "LUMA_BT601",
     "ELEM_F32", "ELEM_F16", "ELEM_BF16", "ELEM_U8", "ELEM_SIZE", "Image", "image_check",
 ]
 
@@ -153,6 +153,10 @@ def load_library() -> C.CDLL:
         "srcnn_cubic_f32_taps": ([i, i, C.POINTER(i), _f32p], i),
         "srcnn_resize_cubic_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, i], i),
         "srcnn_resize_cubic_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i, i], i),
+        "srcnn_cubic_aa_f32_taps": ([i, i, C.POINTER(i), C.POINTER(i), _f32p, i], i),
+        "srcnn_resize_cubic_aa_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, i], i),
+        "srcnn_resize_cubic_aa_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i, i], i),
+        "srcnn_resize_cubic_aa_image_dev": ([vp, imp, i, i, imp, i, i, i, i], i),
         "srcnn_process_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i], i),
         "srcnn_process_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i], i),
         "srcnn_luma_gain": ([_f32p, _f32p], i),
@@ -243,6 +247,7 @@ ABI_SYMBOLS = (
     "srcnn_luma_gain", "srcnn_process_rgb_f32", "srcnn_process_rgb_f32_dev",
     "srcnn_image_check", "srcnn_forward_image_dev", "srcnn_resize_cubic_image_dev", "srcnn_process_image_dev",
     "srcnn_process_rgb_image_dev",
+    "srcnn_cubic_aa_f32_taps", "srcnn_resize_cubic_aa_f32", "srcnn_resize_cubic_aa_f32_dev", "srcnn_resize_cubic_aa_image_dev",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -642,6 +647,25 @@ class Context:
                                                          d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels,
                                                          n_frames))
 
+    def resize_cubic_aa_f32(self, x, dst_w, dst_h):
+        """Antialiased bicubic resize of float32 planes as torch.nn.functional.interpolate(mode="bicubic", align_corners=False,
+        antialias=True) defines it (srcnn_resize_cubic_aa_f32): the resize that shrinks without aliasing.  x, the result and the
+        sizes as resize_cubic_f32 takes them.  Needs no model and runs in every mode."""
+        x3, dst_w, dst_h = _f32_image(x, "x", dst_w, dst_h)
+        c, h, w = x3.shape
+        out = np.empty((c, dst_h, dst_w), np.float32)
+        self._check(self._lib.srcnn_resize_cubic_aa_f32(self._h, _fp(x3), x3.strides[1] // 4 if h > 1 else w,
+                                                        x3.strides[0] // 4 if c > 1 else 0, w, h, _fp(out), dst_w, dst_w * dst_h,
+                                                        dst_w, dst_h, c))
+        return out if x.ndim == 3 else out[0]
+
+    def resize_cubic_aa_f32_dev(self, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride,
+                                dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels=1, n_frames=1):
+        """srcnn_resize_cubic_aa_f32_dev: the arguments of resize_cubic_f32_dev, the antialiased arithmetic."""
+        self._check(self._lib.srcnn_resize_cubic_aa_f32_dev(self._h, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h,
+                                                            d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels,
+                                                            n_frames))
+
     def process_f32(self, x, dst_w, dst_h):
         """resize_cubic_f32 to (dst_h, dst_w), then the loaded whole model on the result (srcnn_process_f32): x is (C, H, W)
         with C the model's channel count, or (H, W) for a 1-channel model; returns an array of the resized shape.  MODE_MFMA
@@ -701,6 +725,11 @@ class Context:
         """srcnn_resize_cubic_image_dev: resize_cubic_f32_dev on stored images; the same size is a pure format conversion."""
         self._check(self._lib.srcnn_resize_cubic_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
                                                            channels, n_frames))
+
+    def resize_cubic_aa_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, channels, n_frames=1):
+        """srcnn_resize_cubic_aa_image_dev: resize_cubic_aa_f32_dev on stored images, read and written in their own format."""
+        self._check(self._lib.srcnn_resize_cubic_aa_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w,
+                                                              dst_h, channels, n_frames))
 
     def process_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, n_frames=1):
         """srcnn_process_image_dev: process_f32_dev (resize + model) on stored images."""
@@ -1103,6 +1132,25 @@ def cubic_f32_taps(src_n: int, dst_n: int):
     if rc != 0:
         raise SrcnnError(rc, "cubic_f32_taps")
     return first, coef
+
+
+def cubic_aa_f32_taps(src_n: int, dst_n: int):
+    """The antialiased resize's table of one axis (srcnn_cubic_aa_f32_taps; host only, needs no GPU): (first, count, coef) with
+    first[d] the first source sample of output d, count[d] its tap count (int32 both) and coef[d, :count[d]] its float32
+    coefficients, zero beyond; coef has as many columns as the largest count."""
+    if src_n <= 0 or dst_n <= 0:
+        raise ValueError(f"cubic_aa_f32_taps: sizes {src_n} -> {dst_n} (both must be positive)")
+    lib = load_library()
+    k = lib.srcnn_cubic_aa_f32_taps(int(src_n), int(dst_n), None, None, None, 0)
+    if k <= 0:
+        raise SrcnnError(k, "cubic_aa_f32_taps")
+    first, count = np.empty(dst_n, np.int32), np.empty(dst_n, np.int32)
+    coef = np.empty((dst_n, k), np.float32)
+    ip = C.POINTER(C.c_int)
+    rc = lib.srcnn_cubic_aa_f32_taps(int(src_n), int(dst_n), first.ctypes.data_as(ip), count.ctypes.data_as(ip), _fp(coef), k)
+    if rc != k:
+        raise SrcnnError(rc, "cubic_aa_f32_taps")
+    return first, count, coef
 
 
 def luma_bt601_studio(value_range: float = 1.0):

@@ -56,7 +56,7 @@ UNITS = [
     ("srcnn_host.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_table(): OpenCV's float arithmetic, nothing contracted
     ("srcnn_multi.cpp", ["-x", "hip"]),
     ("srcnn_spatial.cpp", ["-x", "hip"]),
-    ("srcnn_resize_f32.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_f32_taps(): float64 as written, nothing contracted
+    ("srcnn_resize_f32.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_f32_taps(), cubic_aa_f32_taps(): float64 as written, nothing contracted
     ("srcnn_image.cpp", ["-x", "hip"]),      # images as they are stored: the descriptor check and the four srcnn_*_image_dev calls
 ]
 HOST_UNITS = {"srcnn_api.cpp", "srcnn_model.cpp", "srcnn_plan.cpp", "srcnn_launch.cpp", "srcnn_host.cpp", "srcnn_multi.cpp",

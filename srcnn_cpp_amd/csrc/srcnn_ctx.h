@@ -231,6 +231,12 @@ struct srcnn_ctx {
     srcnn::host::DevBuf f32_tables, f32_lo, f32_hi, f32_work;
     int ftab_sw = 0, ftab_sh = 0, ftab_dw = 0, ftab_dh = 0;
     hipStream_t ftab_stream = nullptr;
+    // The antialiased cubic resize (srcnn_resize_cubic_aa_*): the tables of one geometry with their largest tap counts, the
+    // workspace of the general form (n_planes x src_h x dst_w floats, grown on demand), and the stream of the last launch that
+    // used either (ensure_tables_aa, resample_aa_dev)
+    srcnn::host::DevBuf aa_tables, aa_work;
+    int atab_sw = 0, atab_sh = 0, atab_dw = 0, atab_dh = 0, atab_kx = 0, atab_ky = 0;
+    hipStream_t aa_stream = nullptr;
     // second lane of the host-frame pipeline (srcnn_forward_y_frames)
     // explicit work items of single-round launches (build_items): a small cache of device tables, one per
     // launch geometry, so that a caller alternating between a few plane sizes never waits for an upload
@@ -474,6 +480,10 @@ struct ResizeTablesF32 {
     const float *xcoef, *ycoef;
 };
 int ensure_tables_f32(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResizeTablesF32 *t);
+// the antialiased table of one axis (also srcnn_cubic_aa_f32_taps, where include/srcnn_amd.h writes its float64 operations out):
+// the largest count of the axis; coef null: that and nothing else; else first[d], count[d], coef[d * max_taps + j] (zero beyond
+// count[d]), SRCNN_ERR_INVALID for max_taps below the largest count.  (The device tables and the launch: srcnn_image.h.)
+int cubic_aa_f32_taps(int n_src, int n_dst, int *first, int *count, float *coef, int max_taps);
 
 // ---- srcnn_host.cpp ----
 void cubic_table(int n_src, int n_dst, int *ofs, short *coef);

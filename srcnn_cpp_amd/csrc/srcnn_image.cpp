@@ -1,6 +1,7 @@
 // srcnn_image.cpp -- images as they are stored: the descriptor check (srcnn_image_check) and the four device calls of the float
 // image path on interleaved or planar pixels of float32, float16, bfloat16 or uint8 (srcnn_forward_image_dev,
-// srcnn_resize_cubic_image_dev, srcnn_process_image_dev, srcnn_process_rgb_image_dev).
+// srcnn_resize_cubic_image_dev, srcnn_process_image_dev, srcnn_process_rgb_image_dev), and the antialiased resize on them
+// (srcnn_resize_cubic_aa_image_dev; its launch is resample_aa_dev of srcnn_resize_f32.cpp).
 // Each call equals store(its _f32_dev counterpart(load(x))) bit for bit.  With both descriptors planar float32 a call IS that
 // counterpart; otherwise the resize, the luma front and the merge back run their accessor forms (srcnn_pipeline.hip), and the
 // model itself runs on float32 planes in the context's workspace, converted in and out by convert_image_kernel where the
@@ -225,6 +226,17 @@ int srcnn_resize_cubic_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w
     HIP_TRY(c, launch_resize_cubic_image(s, src_w, src_h, d, dst_w, dst_h, channels, n_frames, t.xfirst, t.xcoef, t.yfirst, t.ycoef,
                                          c->stream));
     return SRCNN_OK;
+}
+
+int srcnn_resize_cubic_aa_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
+                                    int dst_h, int channels, int n_frames)
+{
+    BIND(c);
+    int rc;
+    if ((rc = images_refusal(c, "resize_cubic_aa_image_dev", src, src_w, src_h, dst, dst_w, dst_h, channels, n_frames))) return rc;
+    // (one set of kernels for every format: planar float32 is an element kind like the others)
+    return resample_aa_dev(c, image_ref(src, src_w, src_h, channels, n_frames), src_w, src_h,
+                           image_ref(dst, dst_w, dst_h, channels, n_frames), dst_w, dst_h, channels, n_frames);
 }
 
 int srcnn_process_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w, int dst_h,

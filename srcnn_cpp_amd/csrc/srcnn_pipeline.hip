@@ -1284,4 +1284,177 @@ hipError_t launch_convert_image(const ImageRef &src, const ImageRef &dst, int wi
     return hipGetLastError();
 }
 
+// ---- the antialiased cubic resize (srcnn_resize_cubic_aa_*): resample_aa_* kernels ----------------------------------------
+// Per axis a table gives every output sample its first source sample, its tap count and its coefficients (srcnn_cubic_aa_f32_taps:
+// first + count never leaves the plane, so no index is clamped).  Horizontal pass first, then the vertical one; each computes
+// acc = x_0 w_0, then acc = acc + x_j w_j for j ascending over exactly `count` taps, every product and sum rounded on its own
+// (this unit is built without FMA contraction).  The intermediate is float32.  Tile geometry and the two forms: srcnn_image.h.
+// In both passes a LANE is an output COLUMN.  Horizontal: neighbouring lanes read source columns rho apart with overlapping
+// supports, so the taps of one row come out of the same few cache lines, and the coefficient table is tap-major so that a tap's
+// coefficients are one coalesced load.  Vertical: the row and with it `first`, `count` and the coefficients are the same for a
+// whole wave (scalar loads), and the lanes read neighbouring floats of the intermediate: no LDS bank is hit twice.
+// The source's element kind is a workgroup-uniform switch AROUND the horizontal pass (one kernel, four bodies of its tap loop);
+// the destination's is the switch inside image_store.
+struct AaArgs {
+    ImageRef src, dst;
+    int sw, sh, dw, dh, channels, n_planes;
+    ResampleAaTables t;
+    float *work;      // general form: n_planes x sh x dw floats
+};
+
+template <int ELEM>
+__device__ __forceinline__ float aa_load(const ImageRef &im, long at)      // image_load of a known element kind
+{
+    if (ELEM == ELEM_F32) return static_cast<const float *>(im.data)[at];
+    if (ELEM == ELEM_F16) return (float)static_cast<const _Float16 *>(im.data)[at];
+    if (ELEM == ELEM_BF16) return __uint_as_float((unsigned)static_cast<const uint16_t *>(im.data)[at] << 16);
+    return __fmul_rn((float)static_cast<const uint8_t *>(im.data)[at], im.scale);
+}
+
+// Horizontal pass of a tile: source rows [r_lo, r_lo + nrow) of the plane at element offset s, output column dxc (the lane's,
+// clamped to the plane) -> hbuf[row][lane].  Wave w takes rows w, w + 4, ...; four of them at a time share a coefficient load.
+template <int ELEM>
+__device__ __forceinline__ void aa_tile_hpass(float (*hbuf)[AA_TC], const AaArgs &a, long s, int r_lo, int nrow, int dxc)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int cnt = a.t.xcount[dxc];
+    const float *coef = a.t.xcoef + dxc;
+    const long col = s + (long)a.t.xfirst[dxc] * a.src.px_step;
+    for (int r0 = w; r0 < nrow; r0 += 16) {
+        long row[4];
+        float acc[4];
+        const float w0 = coef[0];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            row[k] = col + (long)min(r_lo + r0 + 4 * k, a.sh - 1) * a.src.stride;      // (rows beyond the tile: computed, not kept)
+            acc[k] = __fmul_rn(aa_load<ELEM>(a.src, row[k]), w0);
+        }
+        for (int j = 1; j < cnt; ++j) {
+            const float wj = coef[(long)j * a.dw];
+            const long o = (long)j * a.src.px_step;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(aa_load<ELEM>(a.src, row[k] + o), wj));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (r0 + 4 * k < nrow) hbuf[r0 + 4 * k][lane] = acc[k];
+    }
+}
+
+// Vertical pass of a tile: output rows [dy0, dy1), wave w takes dy0 + w, dy0 + w + 4, ...; column dx of the plane at element
+// offset d of the destination
+__device__ __forceinline__ void aa_tile_vpass(const float (*hbuf)[AA_TC], const AaArgs &a, long d, int dy0, int dy1, int r_lo, int dx)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int dy = dy0 + w; dy < dy1; dy += 4) {
+        const int j0 = a.t.yfirst[dy] - r_lo, cnt = a.t.ycount[dy];
+        const float *coef = a.t.ycoef + (long)dy * a.t.ky;
+        float acc = __fmul_rn(hbuf[j0][lane], coef[0]);
+        for (int j = 1; j < cnt; ++j) acc = __fadd_rn(acc, __fmul_rn(hbuf[j0 + j][lane], coef[j]));
+        if (dx < a.dw) image_store(a.dst, d + (long)dy * a.dst.stride + (long)dx * a.dst.px_step, acc);
+    }
+}
+
+__global__ __launch_bounds__(256) void resample_aa_tiled_kernel(const AaArgs a)
+{
+    __shared__ float hbuf[AA_RMAX][AA_TC];
+    const int dx = blockIdx.x * AA_TC + (threadIdx.x & 63);
+    const int dxc = min(dx, a.dw - 1);
+    const int n_row_tiles = (a.dh + AA_TR - 1) / AA_TR;
+    for (int z = blockIdx.z; z < a.n_planes; z += gridDim.z) {
+        const int frame = z / a.channels, ch = z - frame * a.channels;
+        const long s = frame * a.src.frame_pitch + ch * a.src.ch_pitch;
+        const long d = frame * a.dst.frame_pitch + ch * a.dst.ch_pitch;
+        for (int rt = blockIdx.y; rt < n_row_tiles; rt += gridDim.y) {
+            const int dy0 = rt * AA_TR, dy1 = min(dy0 + AA_TR, a.dh);
+            const int r_lo = a.t.yfirst[dy0];
+            const int nrow = a.t.yfirst[dy1 - 1] + a.t.ycount[dy1 - 1] - r_lo;      // <= AA_RMAX: resample_aa_variant()
+            switch (a.src.elem) {
+            case ELEM_F32: aa_tile_hpass<ELEM_F32>(hbuf, a, s, r_lo, nrow, dxc); break;
+            case ELEM_F16: aa_tile_hpass<ELEM_F16>(hbuf, a, s, r_lo, nrow, dxc); break;
+            case ELEM_BF16: aa_tile_hpass<ELEM_BF16>(hbuf, a, s, r_lo, nrow, dxc); break;
+            default: aa_tile_hpass<ELEM_U8>(hbuf, a, s, r_lo, nrow, dxc); break;
+            }
+            __syncthreads();
+            aa_tile_vpass(hbuf, a, d, dy0, dy1, r_lo, dx);
+            __syncthreads();      // the next tile's horizontal pass overwrites what this vertical pass reads
+        }
+    }
+}
+
+// General form, first launch: the horizontal pass of every source row into the workspace (thread = output column)
+template <int ELEM>
+__device__ __forceinline__ void aa_rows_hpass(const AaArgs &a, int dx)
+{
+    const int cnt = a.t.xcount[dx];
+    const float *coef = a.t.xcoef + dx;
+    const float w0 = coef[0];
+    const long col = (long)a.t.xfirst[dx] * a.src.px_step;
+    for (int z = blockIdx.z; z < a.n_planes; z += gridDim.z) {
+        const int frame = z / a.channels, ch = z - frame * a.channels;
+        const long s = frame * a.src.frame_pitch + ch * a.src.ch_pitch + col;
+        float *o = a.work + (long)z * a.sh * a.dw + dx;
+        for (int y = blockIdx.y; y < a.sh; y += gridDim.y) {
+            const long row = s + (long)y * a.src.stride;
+            float acc = __fmul_rn(aa_load<ELEM>(a.src, row), w0);
+            for (int j = 1; j < cnt; ++j)
+                acc = __fadd_rn(acc, __fmul_rn(aa_load<ELEM>(a.src, row + (long)j * a.src.px_step), coef[(long)j * a.dw]));
+            o[(long)y * a.dw] = acc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void resample_aa_h_kernel(const AaArgs a)
+{
+    const int dx = blockIdx.x * 256 + threadIdx.x;
+    if (dx >= a.dw) return;
+    switch (a.src.elem) {
+    case ELEM_F32: aa_rows_hpass<ELEM_F32>(a, dx); break;
+    case ELEM_F16: aa_rows_hpass<ELEM_F16>(a, dx); break;
+    case ELEM_BF16: aa_rows_hpass<ELEM_BF16>(a, dx); break;
+    default: aa_rows_hpass<ELEM_U8>(a, dx); break;
+    }
+}
+
+// ... second launch: the vertical pass out of the workspace (thread = output column, a block's row is blockIdx.y's)
+__global__ __launch_bounds__(256) void resample_aa_v_kernel(const AaArgs a)
+{
+    const int dx = blockIdx.x * 256 + threadIdx.x;
+    if (dx >= a.dw) return;
+    for (int z = blockIdx.z; z < a.n_planes; z += gridDim.z) {
+        const int frame = z / a.channels, ch = z - frame * a.channels;
+        const float *h = a.work + (long)z * a.sh * a.dw + dx;
+        const long d = frame * a.dst.frame_pitch + ch * a.dst.ch_pitch + (long)dx * a.dst.px_step;
+        for (int dy = blockIdx.y; dy < a.dh; dy += gridDim.y) {
+            const int cnt = a.t.ycount[dy];
+            const float *coef = a.t.ycoef + (long)dy * a.t.ky;
+            const float *p = h + (long)a.t.yfirst[dy] * a.dw;
+            float acc = __fmul_rn(p[0], coef[0]);
+            for (int j = 1; j < cnt; ++j) acc = __fadd_rn(acc, __fmul_rn(p[(long)j * a.dw], coef[j]));
+            image_store(a.dst, d + (long)dy * a.dst.stride, acc);
+        }
+    }
+}
+
+hipError_t launch_resample_aa(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
+                              const ResampleAaTables &t, int variant, float *work, hipStream_t st)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels <= 0 || n_frames <= 0 || (long)channels * n_frames > 0x7fffffffL ||
+        t.kx <= 0 || t.ky <= 0)
+        return hipErrorInvalidValue;
+    const AaArgs a{src, dst, sw, sh, dw, dh, channels, channels * n_frames, t, work};
+    const unsigned gz = grid_cap(a.n_planes);
+    if (variant == RESAMPLE_AA_TILED) {
+        if (resample_aa_variant(sw, sh, dw, dh, t.kx, t.ky) != RESAMPLE_AA_TILED) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(resample_aa_tiled_kernel, dim3((dw + AA_TC - 1) / AA_TC, grid_cap((dh + AA_TR - 1) / AA_TR), gz), dim3(256),
+                           0, st, a);
+        return hipGetLastError();
+    }
+    if (!work) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resample_aa_h_kernel, dim3((dw + 255) / 256, grid_cap(sh), gz), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(resample_aa_v_kernel, dim3((dw + 255) / 256, grid_cap(dh), gz), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace srcnn

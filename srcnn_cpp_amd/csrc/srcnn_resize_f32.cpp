@@ -3,7 +3,10 @@
 // 3-plane image through a 1-channel model (srcnn_luma_gain, srcnn_process_rgb_f32*).
 // The tap tables are built here, on the host in float64; the kernels are in srcnn_pipeline.hip (launch_resize_cubic_f32,
 // launch_luma_resize_f32, launch_resize_merge_f32).
+// The antialiased down-scaling resize lives here too (srcnn_cubic_aa_f32_taps, srcnn_resize_cubic_aa_f32*, and resample_aa_dev,
+// the launch srcnn_resize_cubic_aa_image_dev shares): its tables have a tap count per output sample; kernels resample_aa_*.
 #include "srcnn_ctx.h"
+#include "srcnn_image.h"
 
 using namespace srcnn;
 using namespace srcnn::host;
@@ -57,6 +60,119 @@ int ensure_tables_f32(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResizeTables
     t->ycoef = t->xcoef + 4 * (size_t)dw;
     t->xfirst = reinterpret_cast<const int *>(t->xcoef + 4 * n);
     t->yfirst = t->xfirst + dw;
+    return SRCNN_OK;
+}
+
+// Keys cubic with A = -0.5 (the antialiased resize; the 4-tap resize above has -0.75)
+static double keys_aa(double x)
+{
+    const double A = -0.5;
+    x = std::fabs(x);
+    if (x < 1.0) return ((A + 2) * x - (A + 3)) * x * x + 1;
+    if (x < 2.0) return A * (((x - 5) * x + 8) * x - 4);
+    return 0.0;
+}
+
+// first and count of output d: xmin = max(0, trunc(c - support + 0.5)), xend = min(s, trunc(c + support + 0.5))
+static void aa_span(double c, double support, int s, int *xmin, int *count)
+{
+    const long long lo = std::max(0LL, (long long)(c - support + 0.5)), hi = std::min((long long)s, (long long)(c + support + 0.5));
+    *xmin = (int)lo;
+    *count = (int)(hi - lo);
+}
+
+// One axis of torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=True), in float64 and in the
+// operation order include/srcnn_amd.h writes out; each coefficient rounded once to float32.
+int cubic_aa_f32_taps(int n_src, int n_dst, int *first, int *count, float *coef, int max_taps)
+{
+    const double rho = (double)n_src / (double)n_dst, m = rho > 1.0 ? rho : 1.0, support = 2.0 * m;
+    int kmax = 0;
+    for (int d = 0; d < n_dst; ++d) {
+        int xmin, cnt;
+        aa_span(rho * (d + 0.5), support, n_src, &xmin, &cnt);
+        kmax = std::max(kmax, cnt);
+    }
+    if (!coef) return kmax;
+    if (max_taps < kmax) return SRCNN_ERR_INVALID;
+    std::vector<double> w((size_t)kmax);
+    for (int d = 0; d < n_dst; ++d) {
+        const double c = rho * (d + 0.5);
+        int xmin, cnt;
+        aa_span(c, support, n_src, &xmin, &cnt);
+        double total = 0.0;
+        for (int j = 0; j < cnt; ++j) {
+            w[(size_t)j] = keys_aa(((double)(j + xmin) - c + 0.5) / m);
+            total += w[(size_t)j];
+        }
+        float *row = coef + (size_t)d * (size_t)max_taps;
+        for (int j = 0; j < max_taps; ++j) row[j] = j < cnt ? (float)(total != 0.0 ? w[(size_t)j] / total : w[(size_t)j]) : 0.f;
+        first[d] = xmin;
+        count[d] = cnt;
+    }
+    return kmax;
+}
+
+// The antialiased tables of a (sw x sh) -> (dw x dh) resize on the device, cached like the float ones above.  Layout: float
+// xcoef[kx][dw] (tap-major), ycoef[dh][ky], then int xfirst[dw], xcount[dw], yfirst[dh], ycount[dh].
+static int ensure_tables_aa(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResampleAaTables *t)
+{
+    if (!(c->aa_tables.p && c->atab_sw == sw && c->atab_sh == sh && c->atab_dw == dw && c->atab_dh == dh)) {
+        const int kx = cubic_aa_f32_taps(sw, dw, nullptr, nullptr, nullptr, 0), ky = cubic_aa_f32_taps(sh, dh, nullptr, nullptr, nullptr, 0);
+        const size_t nx = (size_t)kx * dw, ny = (size_t)ky * dh, n = (size_t)dw + dh;
+        std::vector<float> coef(nx + ny), rows(nx);
+        std::vector<int> ints(2 * n);
+        cubic_aa_f32_taps(sw, dw, ints.data(), ints.data() + dw, rows.data(), kx);
+        for (int d = 0; d < dw; ++d)
+            for (int j = 0; j < kx; ++j) coef[(size_t)j * dw + d] = rows[(size_t)d * kx + j];
+        cubic_aa_f32_taps(sh, dh, ints.data() + 2 * (size_t)dw, ints.data() + 2 * (size_t)dw + dh, coef.data() + nx, ky);
+        // an earlier launch on this stream may still read the old tables (one on another stream: resample_aa_dev has waited)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->atab_sw = 0;
+        int rc;
+        if ((rc = reserve(c, c->aa_tables, (nx + ny + 2 * n) * 4))) return rc;
+        HIP_TRY(c, hipMemcpy(c->aa_tables.p, coef.data(), (nx + ny) * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(static_cast<float *>(c->aa_tables.p) + nx + ny, ints.data(), 2 * n * 4, hipMemcpyHostToDevice));
+        c->atab_sw = sw; c->atab_sh = sh; c->atab_dw = dw; c->atab_dh = dh; c->atab_kx = kx; c->atab_ky = ky;
+    }
+    const size_t nx = (size_t)c->atab_kx * dw, ny = (size_t)c->atab_ky * dh;
+    t->xcoef = static_cast<const float *>(c->aa_tables.p);
+    t->ycoef = t->xcoef + nx;
+    t->xfirst = reinterpret_cast<const int *>(t->ycoef + ny);
+    t->xcount = t->xfirst + dw;
+    t->yfirst = t->xcount + dw;
+    t->ycount = t->yfirst + dh;
+    t->kx = c->atab_kx;
+    t->ky = c->atab_ky;
+    return SRCNN_OK;
+}
+
+#ifdef SRCNN_TUNING_BUILD
+static int g_aa_force_general = 0, g_aa_last_form = -1;      // srcnn_debug_resample_aa_form / _last_form
+#endif
+
+int resample_aa_dev(srcnn_ctx *c, const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames)
+{
+    ResampleAaTables t;
+    int rc;
+    // tables and workspace were last used on another stream: that work ends before this call replaces or overwrites them
+    if (c->aa_stream && c->aa_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->aa_stream));
+    if ((rc = ensure_tables_aa(c, sw, sh, dw, dh, &t))) return rc;
+    int variant = resample_aa_variant(sw, sh, dw, dh, t.kx, t.ky);
+#ifdef SRCNN_TUNING_BUILD
+    if (g_aa_force_general) variant = RESAMPLE_AA_GENERAL;
+    g_aa_last_form = variant;
+#endif
+    float *work = nullptr;
+    if (variant == RESAMPLE_AA_GENERAL) {
+        const unsigned __int128 bytes = (unsigned __int128)channels * n_frames * (size_t)sh * (size_t)dw * sizeof(float);
+        if (bytes > ((unsigned __int128)1 << 46))
+            return fail(c, SRCNN_ERR_NOMEM, "antialiased resize: the workspace of the two-launch form (%d planes of %d x %d floats) is too large",
+                        channels * n_frames, dw, sh);
+        if ((rc = reserve(c, c->aa_work, (size_t)bytes))) return rc;      // (growing waits for the device)
+        work = static_cast<float *>(c->aa_work.p);
+    }
+    c->aa_stream = c->stream;
+    HIP_TRY(c, launch_resample_aa(src, sw, sh, dst, dw, dh, channels, n_frames, t, variant, work, c->stream));
     return SRCNN_OK;
 }
 
@@ -263,6 +379,52 @@ int srcnn_resize_cubic_f32(srcnn_ctx *c, const float *src, size_t src_stride, si
     return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels, d_hi);
 }
 
+// planar float32 planes as the images resample_aa_dev takes
+static ImageRef f32_image(const float *p, size_t stride, size_t ch_pitch, size_t frame_pitch)
+{
+    return ImageRef{const_cast<float *>(p), ELEM_F32, 0.f, 1, (long)stride, (long)ch_pitch, (long)frame_pitch};
+}
+
+int srcnn_cubic_aa_f32_taps(int src_n, int dst_n, int *first, int *count, float *coef, int max_taps)
+{
+    if (src_n <= 0 || dst_n <= 0) return SRCNN_ERR_INVALID;
+    if (!coef) return cubic_aa_f32_taps(src_n, dst_n, nullptr, nullptr, nullptr, 0);
+    if (!first || !count) return SRCNN_ERR_INVALID;
+    return cubic_aa_f32_taps(src_n, dst_n, first, count, coef, max_taps);
+}
+
+int srcnn_resize_cubic_aa_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
+                                  int src_w, int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch,
+                                  int dst_w, int dst_h, int channels, int n_frames)
+{
+    BIND(c);
+    int rc;
+    if ((rc = resize_f32_refusal(c, "resize_cubic_aa_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                                 dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels, n_frames)))
+        return rc;
+    return resample_aa_dev(c, f32_image(d_src, src_stride, src_ch_pitch, src_frame_pitch), src_w, src_h,
+                           f32_image(d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch), dst_w, dst_h, channels, n_frames);
+}
+
+int srcnn_resize_cubic_aa_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
+                              size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h, int channels)
+{
+    BIND(c);
+    int rc;
+    if ((rc = resize_f32_refusal(c, "resize_cubic_aa_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch,
+                                 0, dst_w, dst_h, channels, 1)))
+        return rc;
+    const size_t hi = (size_t)dst_w * dst_h;
+    float *d_lo = nullptr;
+    if ((rc = reserve(c, c->f32_hi, channels * hi * sizeof(float)))) return rc;
+    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, channels, &d_lo))) return rc;
+    float *d_hi = static_cast<float *>(c->f32_hi.p);
+    if ((rc = resample_aa_dev(c, f32_image(d_lo, (size_t)src_w, (size_t)src_w * src_h, 0), src_w, src_h,
+                              f32_image(d_hi, (size_t)dst_w, hi, 0), dst_w, dst_h, channels, 1)))
+        return rc;
+    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels, d_hi);
+}
+
 int srcnn_process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
                           int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
                           int n_frames)
@@ -340,5 +502,34 @@ int srcnn_process_rgb_f32(srcnn_ctx *c, const float *src, size_t src_stride, siz
         return rc;
     return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, 3, d_hi);
 }
+
+#ifdef SRCNN_TUNING_BUILD
+/* Undocumented test hooks (tuning build only, not part of the ABI) of the antialiased resize.  _form: 0 sends every later call of
+ * this library to the general (two-launch) form, anything else gives the choice back to resample_aa_variant(); _last_form: the
+ * form the last call ran (1 tiled, 0 general, -1 none yet); _variant: what resample_aa_variant() says for a geometry with its own
+ * tables' tap counts (host only); _limits: AA_TR, AA_TC, AA_RATIO, AA_KMAX, AA_RMAX. */
+int srcnn_debug_resample_aa_form(int form)
+{
+    g_aa_force_general = form == 0;
+    return SRCNN_OK;
+}
+
+int srcnn_debug_resample_aa_last_form(void) { return g_aa_last_form; }
+
+int srcnn_debug_resample_aa_variant(int sw, int sh, int dw, int dh)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return SRCNN_ERR_INVALID;
+    return resample_aa_variant(sw, sh, dw, dh, cubic_aa_f32_taps(sw, dw, nullptr, nullptr, nullptr, 0),
+                               cubic_aa_f32_taps(sh, dh, nullptr, nullptr, nullptr, 0));
+}
+
+int srcnn_debug_resample_aa_limits(int *out5)
+{
+    if (!out5) return SRCNN_ERR_INVALID;
+    const int v[5] = {AA_TR, AA_TC, AA_RATIO, AA_KMAX, AA_RMAX};
+    for (int k = 0; k < 5; ++k) out5[k] = v[k];
+    return SRCNN_OK;
+}
+#endif  /* SRCNN_TUNING_BUILD */
 
 }  // extern "C"

@@ -4,6 +4,7 @@
     fast = compile_module(module)              # an nn.Module with conv1, conv2, conv3 (9-f2-5, 1 or 3 channels)
     y = fast(x)                                # x: float32 (N, C, H, W) or (C, H, W) on that GPU; y ~ module(x)
     z = fast.upscale(lr, scale=2)              # ~ module(F.interpolate(lr, size, mode="bicubic", align_corners=False))
+    lr = fast.resize(hr, (h // 2, w // 2), antialias=True)   # the way down: F.interpolate(..., antialias=True)
     rgb = fast.upscale_rgb(lr_rgb, scale=2)    # a 1-channel module on the luma of an RGB tensor, chroma resized, merged
     out = fast.upscale_rgb_image(torch.from_numpy(hwc_u8).cuda().permute(2, 0, 1), scale=2)   # H x W x 3 uint8 in and out
 
@@ -137,6 +138,13 @@ def check_size(size):
     return int(dh), int(dw)
 
 
+def check_antialias(antialias, plain, antialiased):
+    """ValueError unless antialias is a bool; the name of the Context call it selects."""
+    if not isinstance(antialias, bool):
+        raise ValueError(f"antialias {antialias!r}: expected True or False")
+    return antialiased if antialias else plain
+
+
 class CompiledModule:
     """What compile_module returns: a callable that owns its Context (one GPU, the module's weights and padding)."""
 
@@ -179,10 +187,12 @@ class CompiledModule:
                                                        dh * dw, self.channels * dh * dw, dw, dh, n))
         return out
 
-    def resize(self, x, size):
-        """F.interpolate(x, size=size, mode="bicubic", align_corners=False) with this library's kernel: size = (H, W) of the
-        result.  The same tensors as __call__ takes, read where they lie, on the current stream."""
-        return self._resized(x, size, lambda *a: self.ctx.resize_cubic_f32_dev(*a[:-1], self.channels, a[-1]))
+    def resize(self, x, size, antialias=False):
+        """F.interpolate(x, size=size, mode="bicubic", align_corners=False, antialias=antialias) with this library's kernels:
+        size = (H, W) of the result.  The same tensors as __call__ takes, read where they lie, on the current stream.
+        antialias=True is the resize that shrinks without aliasing (the degradation in front of an evaluation: hr -> lr)."""
+        call = check_antialias(antialias, "resize_cubic_f32_dev", "resize_cubic_aa_f32_dev")
+        return self._resized(x, size, lambda *a: getattr(self.ctx, call)(*a[:-1], self.channels, a[-1]))
 
     def upscale(self, x, scale=None, size=None):
         """module(F.interpolate(x, size, mode="bicubic", align_corners=False)): the bicubic resize of a low-resolution tensor
@@ -254,11 +264,13 @@ class CompiledModule:
         return self._image_call(x, self.channels, None, out_dtype, out_channels_last, in_scale, out_scale,
                                 lambda s, w, h, d, dw, dh, n: self.ctx.forward_image_dev(s, d, w, h, n))
 
-    def resize_image(self, x, size, out_dtype=None, out_channels_last=None, in_scale=None, out_scale=None):
-        """resize() on a tensor as it is stored (see forward_image); size equal to x's converts the format and nothing else."""
+    def resize_image(self, x, size, out_dtype=None, out_channels_last=None, in_scale=None, out_scale=None, antialias=False):
+        """resize() on a tensor as it is stored (see forward_image); size equal to x's converts the format and nothing else
+        (with antialias=False)."""
+        call = check_antialias(antialias, "resize_cubic_image_dev", "resize_cubic_aa_image_dev")
         dh, dw = check_size(size)
         return self._image_call(x, self.channels, lambda h, w: (dh, dw), out_dtype, out_channels_last, in_scale, out_scale,
-                                lambda s, w, h, d, dw, dh, n: self.ctx.resize_cubic_image_dev(s, w, h, d, dw, dh, self.channels, n))
+                                lambda s, w, h, d, dw, dh, n: getattr(self.ctx, call)(s, w, h, d, dw, dh, self.channels, n))
 
     def upscale_image(self, x, scale=None, size=None, out_dtype=None, out_channels_last=None, in_scale=None, out_scale=None):
         """upscale() on a tensor as it is stored (see forward_image)."""

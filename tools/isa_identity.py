@@ -87,10 +87,12 @@ def main():
             old, new = Path(args.old).read_text(), Path(args.new).read_text()
         else:
             # the unit as the revision has it, with that revision's header and the kernel file a unit may include
-            for f in dict.fromkeys((*old_units, "srcnn_kernels.h", "srcnn_spatial_kernels.hip")):
-                text = subprocess.run(["git", "-C", str(ROOT), "show", f"{args.rev}:srcnn_cpp_amd/csrc/{f}"], check=True,
-                                      capture_output=True, text=True).stdout
-                (d / f).write_text(text)
+            # (srcnn_image.h: what srcnn_pipeline.hip includes besides; a revision from before it has none)
+            for f in dict.fromkeys((*old_units, "srcnn_kernels.h", "srcnn_spatial_kernels.hip", "srcnn_image.h")):
+                shown = subprocess.run(["git", "-C", str(ROOT), "show", f"{args.rev}:srcnn_cpp_amd/csrc/{f}"],
+                                       check=f != "srcnn_image.h", capture_output=True, text=True)
+                if shown.returncode == 0:
+                    (d / f).write_text(shown.stdout)
             old = "".join(listing(d, u, flags_of(u), d / f"old{i}.s") for i, u in enumerate(old_units))
             new = listing(B.CSRC, args.unit, flags, d / "new.s")
     ko, kn = kernels(old), kernels(new)
