@@ -528,6 +528,51 @@ int srcnn_resize_cubic_aa_f32(srcnn_ctx *ctx, const float *src, size_t src_strid
 int srcnn_resize_cubic_aa_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
                                     const srcnn_image *dst, int dst_w, int dst_h, int channels, int n_frames);
 
+/* Full-reference quality metrics: the measurement at the end of an evaluation.  The sum of squared errors (for PSNR) and the
+ * Gaussian-window SSIM of Wang et al. 2004 between two images as they are stored, on the channel planes or on a luma, with a
+ * border shaved off -- raw sums per frame, on the device, deterministic to the bit.
+ *   - Inputs: two srcnn_image descriptors a and b of the same width x height, channels (1 or 3) and n_frames; each has its own
+ *     element kind and strides.  Every element is loaded by the rule above (F32 as it is, F16 and BF16 widened exactly, U8 as
+ *     (float)b * scale) and the loaded float32 is widened to float64.  EVERYTHING AFTER THE LOAD IS FLOAT64, every product and
+ *     sum rounded on its own, but for the window sums below.
+ *   - luma: NULL, or {w0, w1, w2, offset} (3 channels only).  With a luma each frame is measured on
+ *         y = ((w0 c0 + w1 c1) + w2 c2) + offset            (float64, from the float32 weights)
+ *     and gives one result; without, every channel plane gives one.  P = results per frame (1, or channels).
+ *   - border >= 0: that many rows and columns are shaved off every side before either metric (the usual shave = scale).  The
+ *     region is h' = height - 2 border by w' = width - 2 border, both >= 1.
+ *   - SSE = sum of (a - b)^2 over the region; n_px = h' w'.
+ *   - SSIM: the window is 11 taps of a Gaussian with sigma = 1.5, g[i] = exp(-(i - 5)^2 / 4.5) divided by the sum of the eleven
+ *     (float64), applied separably, down the columns first, then along the rows.  Only whole ("valid") windows count:
+ *     (h' - 10) x (w' - 10) of them, so h', w' >= 11.  A window sum is acc = g[0] v[0], then acc = fma(g[j], v[j], acc) for j
+ *     ascending: one rounding per tap.  Per window mu_a, mu_b, E[a^2], E[b^2], E[ab] (the squares and the product formed per
+ *     pixel, before the window), and
+ *         ssim = ((2 mu_a mu_b + C1) (2 (E[ab] - mu_a mu_b) + C2))
+ *                / ((mu_a^2 + mu_b^2 + C1) ((E[a^2] - mu_a^2) + (E[b^2] - mu_b^2) + C2)),
+ *         C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range > 0 in LOADED units (1 for [0, 1] data, 255 for bytes at scale 1).
+ *     The arrangement is symmetric in a and b -- swapping them gives the same bits -- and identical inputs give exactly 1.0 per
+ *     window, so ssim_sum == n_win.
+ *   - Output: four doubles per (frame, result) in device memory, d_out[(f P + p) 4 + ...] = {sse, n_px, ssim_sum, n_win}: raw
+ *     sums, not PSNR or a mean, so that a caller merges frames, stripes or a data set as they choose.  flags selects
+ *     SRCNN_METRIC_SSE, SRCNN_METRIC_SSIM or both; the two fields of a metric that was not selected are 0.
+ *   - Determinism: no floating-point atomic.  Every workgroup writes one partial sum into a workspace the context owns (grown
+ *     on demand, freed with the context), and a finishing kernel adds the partials of a plane in a fixed order.  Tiles and
+ *     orders depend on w' and h' only: the same call twice gives the same bits, and a frame's four doubles do not depend on the
+ *     batch it is in.
+ *   - srcnn_metrics_image_dev is asynchronous on the context's stream and reads nothing back, so it can sit in a stream of
+ *     work.  It needs no model (a fresh context works) and runs in every mode.  a and b may be the same image or overlap.
+ *   - srcnn_metric_psnr: host only (no context, no GPU): 10 log10(L^2 n_px / sse), +infinity for sse == 0, a NaN for a negative
+ *     or NaN sse, n_px <= 0 or data_range <= 0.  Mean SSIM is ssim_sum / n_win.
+ *   - SRCNN_ERR_INVALID, with nothing launched and the context usable: a descriptor srcnn_image_check(.., is_dst = 0) refuses,
+ *     channels other than 1 and 3, a luma with other than 3 channels, a non-finite luma, a data_range that is not finite or not
+ *     > 0, a negative border, an empty region, SSIM on a region under 11 x 11, flags of 0 or with unknown bits, a null d_out.
+ *   Out of scope: MS-SSIM and the uniform-window SSIM; rounding the luma to 8 bits as MATLAB's rgb2ycbcr does on uint8;
+ *   host-memory forms; several GPUs; the command-line tool; returning an SSIM map. */
+enum { SRCNN_METRIC_SSE = 1, SRCNN_METRIC_SSIM = 2 };
+int srcnn_metrics_image_dev(srcnn_ctx *ctx, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
+                            int n_frames, int border, const float *luma /* NULL or [4] */, double data_range, int flags,
+                            double *d_out /* [n_frames][P][4] */);
+double srcnn_metric_psnr(double sse, double n_px, double data_range);
+
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be
  * NULL) receives the float value before truncation/clamp. */

@@ -66,6 +66,9 @@ LUMA_BT601 = (0.299, 0.587, 0.114, 0.0)
 # element kinds of an Image (SRCNN_ELEM_*) and their sizes in bytes
 ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = 0, 1, 2, 3
 ELEM_SIZE = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
+# what metrics_image_dev measures (SRCNN_METRIC_*): flags, and the fields of one result
+METRIC_SSE, METRIC_SSIM = 1, 2
+METRIC_FIELDS = ("sse", "n_px", "ssim_sum", "n_win")
 
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_NODEVICE, ERR_STATE = -1, -2, -3, -4, -5      # include/srcnn_amd.h
 _ERR = {-1: "invalid argument", -2: "HIP runtime error", -3: "out of memory",
@@ -157,6 +160,8 @@ def load_library() -> C.CDLL:
         "srcnn_resize_cubic_aa_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, i], i),
         "srcnn_resize_cubic_aa_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i, i], i),
         "srcnn_resize_cubic_aa_image_dev": ([vp, imp, i, i, imp, i, i, i, i], i),
+        "srcnn_metrics_image_dev": ([vp, imp, imp, i, i, i, i, i, _f32p, C.c_double, i, vp], i),
+        "srcnn_metric_psnr": ([C.c_double, C.c_double, C.c_double], C.c_double),
         "srcnn_process_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i], i),
         "srcnn_process_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i], i),
         "srcnn_luma_gain": ([_f32p, _f32p], i),
@@ -248,6 +253,7 @@ ABI_SYMBOLS = (
     "srcnn_image_check", "srcnn_forward_image_dev", "srcnn_resize_cubic_image_dev", "srcnn_process_image_dev",
     "srcnn_process_rgb_image_dev",
     "srcnn_cubic_aa_f32_taps", "srcnn_resize_cubic_aa_f32", "srcnn_resize_cubic_aa_f32_dev", "srcnn_resize_cubic_aa_image_dev",
+    "srcnn_metrics_image_dev", "srcnn_metric_psnr",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -731,6 +737,14 @@ class Context:
         self._check(self._lib.srcnn_resize_cubic_aa_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w,
                                                               dst_h, channels, n_frames))
 
+    def metrics_image_dev(self, a: "Image", b: "Image", width, height, channels, n_frames, border, luma, data_range, flags, d_out):
+        """srcnn_metrics_image_dev: {sse, n_px, ssim_sum, n_win} per (frame, result) of two stored images, float64 after the
+        load, into device memory at d_out (n_frames * P * 4 doubles; P = 1 with a luma, else channels).  luma: None or
+        (w0, w1, w2, offset); flags: METRIC_SSE | METRIC_SSIM.  Asynchronous on the context's stream; needs no model."""
+        luma4, ca, cb = _metric_luma4(luma), a.c(), b.c()      # refused here, before the library is reached
+        self._check(self._lib.srcnn_metrics_image_dev(self._h, C.byref(ca), C.byref(cb), int(width), int(height), int(channels),
+                                                      int(n_frames), int(border), luma4, float(data_range), int(flags), d_out))
+
     def process_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, n_frames=1):
         """srcnn_process_image_dev: process_f32_dev (resize + model) on stored images."""
         self._check(self._lib.srcnn_process_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
@@ -1180,6 +1194,26 @@ def _luma4(luma):
     if a.size != 4 or not np.isfinite(a).all() or not float(a[:3].astype(np.float64).sum()) > 0.0:
         raise ValueError(f"luma {luma!r}: expected four finite numbers (w0, w1, w2, offset) with w0 + w1 + w2 > 0")
     return (C.c_float * 4)(*a.tolist())
+
+
+def _metric_luma4(luma):
+    """None, or {w0, w1, w2, offset} of a metric as a C array of four floats: ValueError unless four finite numbers (as float32),
+    before any call into the library.  (A metric's luma need not be invertible: the weights may sum to anything.)"""
+    if luma is None:
+        return None
+    try:
+        a = np.asarray(luma, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"luma {luma!r}: expected None or four numbers (w0, w1, w2, offset)") from None
+    if a.size != 4 or not np.isfinite(a).all():
+        raise ValueError(f"luma {luma!r}: expected None or four finite numbers (w0, w1, w2, offset)")
+    return (C.c_float * 4)(*a.tolist())
+
+
+def metric_psnr(sse: float, n_px: float, data_range: float = 1.0) -> float:
+    """10 log10(L^2 n_px / sse) from the sums metrics_image_dev returns (srcnn_metric_psnr; host only, needs no GPU): inf for
+    sse == 0, nan for arguments that are no sums."""
+    return float(load_library().srcnn_metric_psnr(float(sse), float(n_px), float(data_range)))
 
 
 def _clamp2(clamp):

@@ -49,6 +49,9 @@ UNITS = [
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models, float planes and row stripes -- every form
     ("srcnn_spatial_kernels.hip", []),
+    # the metrics: float64 throughout; the SSIM formula and the luma as written, every product and sum rounded on its own (the
+    # window sums use explicit fused multiply-adds), so identical pictures give exactly 1.0 per window
+    ("srcnn_metrics.hip", ["-ffp-contract=off"]),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),
@@ -57,7 +60,7 @@ UNITS = [
     ("srcnn_multi.cpp", ["-x", "hip"]),
     ("srcnn_spatial.cpp", ["-x", "hip"]),
     ("srcnn_resize_f32.cpp", ["-x", "hip", "-ffp-contract=off"]),      # cubic_f32_taps(), cubic_aa_f32_taps(): float64 as written, nothing contracted
-    ("srcnn_image.cpp", ["-x", "hip"]),      # images as they are stored: the descriptor check and the four srcnn_*_image_dev calls
+    ("srcnn_image.cpp", ["-x", "hip"]),      # images as they are stored: the descriptor check, the srcnn_*_image_dev calls, the metrics' host layer
 ]
 HOST_UNITS = {"srcnn_api.cpp", "srcnn_model.cpp", "srcnn_plan.cpp", "srcnn_launch.cpp", "srcnn_host.cpp", "srcnn_multi.cpp",
               "srcnn_spatial.cpp", "srcnn_resize_f32.cpp", "srcnn_image.cpp"}

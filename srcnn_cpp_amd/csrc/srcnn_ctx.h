@@ -237,6 +237,10 @@ struct srcnn_ctx {
     srcnn::host::DevBuf aa_tables, aa_work;
     int atab_sw = 0, atab_sh = 0, atab_dw = 0, atab_dh = 0, atab_kx = 0, atab_ky = 0;
     hipStream_t aa_stream = nullptr;
+    // The metrics (srcnn_metrics_image_dev): the per-workgroup partial sums of one call (grown on demand) and the stream of the
+    // last launch that wrote them
+    srcnn::host::DevBuf metric_work;
+    hipStream_t metric_stream = nullptr;
     // second lane of the host-frame pipeline (srcnn_forward_y_frames)
     // explicit work items of single-round launches (build_items): a small cache of device tables, one per
     // launch geometry, so that a caller alternating between a few plane sizes never waits for an upload

@@ -315,4 +315,76 @@ int srcnn_process_rgb_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w,
     return release_workspace(c);
 }
 
+/* ---- full-reference metrics: {sse, n_px, ssim_sum, n_win} per (frame, result), float64 after the load (srcnn_metrics.hip) ---- */
+int srcnn_metrics_image_dev(srcnn_ctx *c, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
+                            int n_frames, int border, const float *luma, double data_range, int flags, double *d_out)
+{
+    BIND(c);
+    int rc;
+    const char *what = "metrics_image_dev";
+    if (image_check(a, width, height, channels, n_frames, 0)) return fail(c, SRCNN_ERR_INVALID, "%s: bad image a (srcnn_image_check)", what);
+    if (image_check(b, width, height, channels, n_frames, 0)) return fail(c, SRCNN_ERR_INVALID, "%s: bad image b (srcnn_image_check)", what);
+    if (channels != 1 && channels != 3) return fail(c, SRCNN_ERR_INVALID, "%s: %d channels: expected 1 or 3", what, channels);
+    if (luma && channels != 3)
+        return fail(c, SRCNN_ERR_INVALID, "%s: a luma needs 3 channels, the images have %d (pass NULL to measure the plane itself)", what, channels);
+    if (luma && !(std::isfinite(luma[0]) && std::isfinite(luma[1]) && std::isfinite(luma[2]) && std::isfinite(luma[3])))
+        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset}", what);
+    if (!(std::isfinite(data_range) && data_range > 0.0))
+        return fail(c, SRCNN_ERR_INVALID, "%s: data_range %g: expected a finite number > 0", what, data_range);
+    if (border < 0) return fail(c, SRCNN_ERR_INVALID, "%s: border %d: expected >= 0", what, border);
+    const long rw = (long)width - 2L * border, rh = (long)height - 2L * border;
+    if (rw < 1 || rh < 1)
+        return fail(c, SRCNN_ERR_INVALID, "%s: a border of %d leaves nothing of a %d x %d image", what, border, width, height);
+    if (!flags || (flags & ~(SRCNN_METRIC_SSE | SRCNN_METRIC_SSIM)))
+        return fail(c, SRCNN_ERR_INVALID, "%s: flags %#x: expected SRCNN_METRIC_SSE, SRCNN_METRIC_SSIM or both", what, (unsigned)flags);
+    if ((flags & SRCNN_METRIC_SSIM) && (rw < METRIC_WIN || rh < METRIC_WIN))
+        return fail(c, SRCNN_ERR_INVALID, "%s: SSIM needs a region of at least 11 x 11, this one is %ld x %ld", what, rw, rh);
+    if (!d_out) return fail(c, SRCNN_ERR_INVALID, "%s: null output", what);
+    const int per_frame = luma ? 1 : channels;
+    if ((long)per_frame * n_frames > 0x7fffffffL) return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    // the region: the first pixel inside the border becomes element (0, 0)
+    auto region = [&](const srcnn_image *im) {
+        ImageRef r = image_ref(im, width, height, channels, n_frames);
+        r.data = static_cast<char *>(r.data) + ((size_t)border * (size_t)r.stride + (size_t)border * (size_t)r.px_step) * elem_size(r.elem);
+        return r;
+    };
+    // the window in float64: exp(-(i - 5)^2 / 4.5), divided by the sum taken in ascending order
+    double g[METRIC_WIN], total = 0.0;
+    for (int k = 0; k < METRIC_WIN; ++k) {
+        g[k] = std::exp(-(double)((k - 5) * (k - 5)) / 4.5);
+        total += g[k];
+    }
+    for (int k = 0; k < METRIC_WIN; ++k) g[k] /= total;
+    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+    const unsigned __int128 doubles = (unsigned __int128)per_frame * n_frames *
+                                      (size_t)(metric_sse_partials((int)rh) + metric_ssim_partials((int)rw, (int)rh));
+    if (doubles > ((unsigned __int128)1 << 40)) return fail(c, SRCNN_ERR_NOMEM, "%s: the workspace of the partial sums is too large", what);
+    // the partials were last written on another stream: that work ends before this call overwrites them
+    if (c->metric_stream && c->metric_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->metric_stream));
+    if ((rc = reserve(c, c->metric_work, (size_t)doubles * sizeof(double)))) return rc;      // (growing waits for the device)
+    c->metric_stream = c->stream;
+    HIP_TRY(c, launch_metrics(region(a), region(b), (int)rw, (int)rh, channels, n_frames, luma, g, c1, c2, flags,
+                              static_cast<double *>(c->metric_work.p), d_out, c->stream));
+    return SRCNN_OK;
+}
+
+double srcnn_metric_psnr(double sse, double n_px, double data_range)
+{
+    if (!(sse >= 0.0) || !(n_px > 0.0) || !(data_range > 0.0)) return std::nan("");
+    if (sse == 0.0) return HUGE_VAL;
+    return 10.0 * std::log10(data_range * data_range * n_px / sse);
+}
+
+#ifdef SRCNN_TUNING_BUILD
+/* Undocumented test hook (tuning build only, not part of the ABI): METRIC_T, METRIC_B (window columns and rows of one SSIM
+ * workgroup), METRIC_SSE_ROWS, and the LDS bytes of the SSIM kernel. */
+int srcnn_debug_metric_limits(int *out4)
+{
+    if (!out4) return SRCNN_ERR_INVALID;
+    const int v[4] = {METRIC_T, METRIC_B, METRIC_SSE_ROWS, METRIC_LDS_BYTES};
+    for (int k = 0; k < 4; ++k) out4[k] = v[k];
+    return SRCNN_OK;
+}
+#endif
+
 }  // extern "C"

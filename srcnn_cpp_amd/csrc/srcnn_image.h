@@ -18,6 +18,21 @@ struct ImageRef {
 };
 inline bool image_is_planar_f32(const ImageRef &im) { return im.elem == ELEM_F32 && im.px_step == 1; }
 
+#ifdef __HIPCC__
+// The ONE load rule of a stored image (include/srcnn_amd.h, "Load"): every kernel that reads an ImageRef -- the accessor forms and
+// the antialiased resize of srcnn_pipeline.hip, the metric kernels of srcnn_metrics.hip -- reads it through this.  The element
+// kind is uniform over a launch: the switch is a scalar branch beside a global load.
+__device__ __forceinline__ float image_load(const ImageRef &im, long at)
+{
+    switch (im.elem) {
+    case ELEM_F32: return static_cast<const float *>(im.data)[at];
+    case ELEM_F16: return (float)static_cast<const _Float16 *>(im.data)[at];                           // exact
+    case ELEM_BF16: return __uint_as_float((unsigned)static_cast<const uint16_t *>(im.data)[at] << 16);  // exact
+    default: return __fmul_rn((float)static_cast<const uint8_t *>(im.data)[at], im.scale);
+    }
+}
+#endif
+
 // The accessor forms of the float resize (launch_resize_cubic_f32, launch_luma_resize_f32, launch_resize_merge_f32): the same
 // tables, the same tile, the same variant choice and summation order; only the element access of the tile's fill and of the
 // vertical pass's store goes through the load and the store of an ImageRef.  yup / ysr stay packed float32 planes (the
@@ -69,6 +84,34 @@ struct ResampleAaTables {
 // geometry resample_aa_variant() does not send there.
 hipError_t launch_resample_aa(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
                               const ResampleAaTables &t, int variant, float *work, hipStream_t st);
+
+// ---- full-reference metrics (srcnn_metrics_image_dev; include/srcnn_amd.h has the semantics): srcnn_metrics.hip -------------
+// Everything after the load is float64.  Three kernels, no floating-point atomic: metric_sse_kernel and metric_ssim_kernel write
+// one partial sum per workgroup into a workspace, metric_finish_kernel adds the partials of a plane in a fixed order and writes
+// {sse, n_px, ssim_sum, n_win}.  Tiles, partial counts and both reduction orders depend on the region's size only, so a plane's
+// four doubles do not depend on the batch it is measured in.
+//   SSE:  a workgroup of 256 threads takes METRIC_SSE_ROWS rows of the region, thread t the columns 4 t .. 4 t + 3, + 1024, ...
+//   SSIM: a workgroup is ONE wave.  It owns METRIC_T window columns (64 source columns, one per lane) and a band of METRIC_B window
+//         rows, walks down the band's METRIC_B + 10 source rows with a register ring of 11 rows of (a, b) per lane, forms the five
+//         vertical 11-tap sums per row, writes them to LDS (5 x 64 doubles = 2,560 bytes), and lanes 0 .. METRIC_T - 1 form the five
+//         horizontal sums and the window's SSIM.  Source rows re-read: 10 / METRIC_B; source columns re-read: 10 / METRIC_T.
+constexpr int METRIC_WIN = 11;                       // the Gaussian window's taps
+constexpr int METRIC_T = 64 - (METRIC_WIN - 1);      // window columns per workgroup: 54
+constexpr int METRIC_B = 64;                         // window rows per workgroup
+constexpr int METRIC_SSE_ROWS = 4;                   // region rows per workgroup of the SSE kernel
+constexpr int METRIC_LDS_BYTES = 5 * 64 * 8;
+enum { METRIC_FLAG_SSE = 1, METRIC_FLAG_SSIM = 2 };  // SRCNN_METRIC_*
+inline long metric_sse_partials(int rh) { return ((long)rh + METRIC_SSE_ROWS - 1) / METRIC_SSE_ROWS; }
+inline long metric_ssim_partials(int rw, int rh)     // 0 where the region holds no window
+{
+    if (rw < METRIC_WIN || rh < METRIC_WIN) return 0;
+    return (((long)rw - METRIC_WIN + 1 + METRIC_T - 1) / METRIC_T) * (((long)rh - METRIC_WIN + 1 + METRIC_B - 1) / METRIC_B);
+}
+// a, b: the REGION (border already shaved off) of rw x rh, n_frames frames of `channels` channels; luma: null, or the four
+// weights (channels == 3: one result per frame); gauss: the 11 normalised window weights; work: n_frames * P *
+// (metric_sse_partials + metric_ssim_partials) doubles; out: n_frames * P * 4 doubles
+hipError_t launch_metrics(const ImageRef &a, const ImageRef &b, int rw, int rh, int channels, int n_frames, const float *luma,
+                          const double gauss[METRIC_WIN], double c1, double c2, int flags, double *work, double *out, hipStream_t st);
 
 namespace host {
 // The launch behind every antialiased resize (srcnn_resize_f32.cpp): checked arguments, device memory, the context's stream;

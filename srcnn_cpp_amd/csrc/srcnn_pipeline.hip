@@ -797,15 +797,7 @@ hipError_t launch_resize_merge_f32(const float *src, long sstride, long sch_pitc
 // The element kind is a workgroup-uniform switch, not a template parameter: 4 source x 4 destination kinds x 4 kernels would be
 // 64 kernels for a branch that is scalar (s_cmp on a kernel argument) and sits beside a global load or store.
 // Everything between load and store is float32 as above, so a call equals store(f32 call(load(x))) bit for bit.
-__device__ __forceinline__ float image_load(const ImageRef &im, long at)
-{
-    switch (im.elem) {
-    case ELEM_F32: return static_cast<const float *>(im.data)[at];
-    case ELEM_F16: return (float)static_cast<const _Float16 *>(im.data)[at];                           // exact
-    case ELEM_BF16: return __uint_as_float((unsigned)static_cast<const uint16_t *>(im.data)[at] << 16);  // exact
-    default: return __fmul_rn((float)static_cast<const uint8_t *>(im.data)[at], im.scale);
-    }
-}
+// (image_load: srcnn_image.h, shared with the metric kernels of srcnn_metrics.hip)
 
 // float32 -> bfloat16 bits, round to nearest even; a NaN stays a NaN (quiet, sign kept)
 __device__ __forceinline__ unsigned bf16_bits(float v)

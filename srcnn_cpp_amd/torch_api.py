@@ -7,6 +7,7 @@
     lr = fast.resize(hr, (h // 2, w // 2), antialias=True)   # the way down: F.interpolate(..., antialias=True)
     rgb = fast.upscale_rgb(lr_rgb, scale=2)    # a 1-channel module on the luma of an RGB tensor, chroma resized, merged
     out = fast.upscale_rgb_image(torch.from_numpy(hwc_u8).cuda().permute(2, 0, 1), scale=2)   # H x W x 3 uint8 in and out
+    db, q = fast.psnr(sr, hr, border=2), fast.ssim(sr, hr, border=2)   # float64 (N, P): the measurement, on stored tensors
 
 The *_image methods (forward_image, resize_image, upscale_image, upscale_rgb_image) take the tensor in the format it is stored
 in: float32, float16, bfloat16 or uint8, any positive strides (a permuted H x W x C view, channels_last, padded rows), and write
@@ -294,6 +295,68 @@ class CompiledModule:
             _luma4(luma), _clamp2(clamp)
         return self._image_call(x, 3, target, out_dtype, out_channels_last, in_scale, out_scale,
                                 lambda *a: self.ctx.process_rgb_image_dev(*a[:-1], luma, clamp, a[-1]), check)
+
+    # ---- full-reference metrics: the measurement at the end of an evaluation ----
+    def metrics(self, a, b, border=0, luma=None, data_range=1.0, ssim=True, in_scale=None):
+        """The raw sums behind PSNR and SSIM of two pictures as they are stored: a float64 CUDA tensor (N, P, 4) holding
+        (sse, n_px, ssim_sum, n_win) per frame and result.  a and b: (N, C, H, W) or (C, H, W) of the same shape with C = 1 or 3
+        (taken from the tensors, not from the module), each float32, float16, bfloat16 or uint8 with any positive strides;
+        they may differ in dtype and layout.  uint8 is read as byte * in_scale (default 1 / 255).  border rows and columns are
+        shaved off every side first.  luma = (w0, w1, w2, offset) measures the luma of 3-channel pictures (P = 1); None
+        measures every channel plane (P = C).  data_range is L of the SSIM constants, in loaded units.  ssim=False computes
+        the squared error only (the SSIM fields are then 0).  Float64 after the load, no atomics: the same bits every time.
+        Runs on the current stream, with no synchronisation."""
+        import math
+        import torch
+        from . import METRIC_SSE, METRIC_SSIM, _metric_luma4
+        if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor):
+            raise ValueError(f"expected two torch.Tensors, got {type(a).__name__} and {type(b).__name__}")
+        if a.dim() not in (3, 4) or tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"expected two tensors of the same shape (N, C, H, W) or (C, H, W), got {tuple(a.shape)} and {tuple(b.shape)}")
+        channels = int(a.shape[-3])
+        if channels not in (1, 3):
+            raise ValueError(f"expected 1 or 3 channels, the tensors have {channels}: shape {tuple(a.shape)}")
+        ia, n, h, w = describe_image(a, channels, in_scale)
+        ib = describe_image(b, channels, in_scale)[0]
+        if not isinstance(ssim, bool):
+            raise ValueError(f"ssim {ssim!r}: expected True or False")
+        if isinstance(border, bool) or not isinstance(border, int) or border < 0:
+            raise ValueError(f"border {border!r}: expected an integer >= 0")
+        if luma is not None and channels != 3:
+            raise ValueError(f"luma needs 3 channels, the tensors have {channels} (luma=None measures the plane itself)")
+        _metric_luma4(luma)
+        try:
+            data_range = float(data_range)
+        except (TypeError, ValueError):
+            raise ValueError(f"data_range {data_range!r}: expected a finite number > 0") from None
+        if not (data_range > 0.0 and math.isfinite(data_range)):
+            raise ValueError(f"data_range {data_range!r}: expected a finite number > 0")
+        rh, rw = h - 2 * border, w - 2 * border
+        if rh < 1 or rw < 1:
+            raise ValueError(f"a border of {border} leaves nothing of a {h} x {w} picture")
+        if ssim and (rh < 11 or rw < 11):
+            raise ValueError(f"SSIM needs a region of at least 11 x 11, this one is {rh} x {rw} (ssim=False measures the squared error alone)")
+        check_image_device(a, self.device)
+        check_image_device(b, self.device)
+        per_frame = 1 if luma is not None else channels
+        out = torch.empty((n, per_frame, 4), dtype=torch.float64, device=a.device)
+        flags = METRIC_SSE | (METRIC_SSIM if ssim else 0)
+        self._on_current_stream(a.device, lambda: self.ctx.metrics_image_dev(ia, ib, w, h, channels, n, border, luma, data_range, flags,
+                                                                             out.data_ptr()))
+        return out
+
+    def psnr(self, a, b, border=0, luma=None, data_range=1.0, in_scale=None):
+        """10 log10(L^2 n_px / sse) per frame and result from metrics(): a float64 CUDA tensor (N, P), inf where the pictures
+        are equal.  Torch operations on the device, no synchronisation."""
+        import torch
+        m = self.metrics(a, b, border=border, luma=luma, data_range=data_range, ssim=False, in_scale=in_scale)
+        return 10.0 * torch.log10((float(data_range) ** 2) * m[..., 1] / m[..., 0])
+
+    def ssim(self, a, b, border=0, luma=None, data_range=1.0, in_scale=None):
+        """Mean SSIM (11-tap Gaussian window, sigma 1.5, valid windows) per frame and result from metrics(): a float64 CUDA
+        tensor (N, P)."""
+        m = self.metrics(a, b, border=border, luma=luma, data_range=data_range, ssim=True, in_scale=in_scale)
+        return m[..., 2] / m[..., 3]
 
     def close(self):
         self.ctx.close()
