@@ -853,6 +853,10 @@ int srcnn_conv55_dev(srcnn_ctx *ctx, const float *d_planes, size_t plane_stride,
 /* Output size of the reference pipeline: (int)(w*scale) x (int)(h*scale), src/srcnn.cpp:573-575. */
 int srcnn_scaled_size(int width, int height, float scale, int *out_w, int *out_h);
 
+/* The three steps below run kernels that take one row (or one tile of 8 or 32 output rows, in the resize's
+ * tiled forms) per workgroup of grid y and do not walk further: a picture of more than 65,535 rows -- for the
+ * resize, an output of more rows or row tiles than that -- is refused with SRCNN_ERR_INVALID before anything
+ * is launched. */
 /* cvtColor(CV_BGR2YCrCb) + split, src/srcnn.cpp:509,540. */
 int srcnn_bgr2ycrcb(srcnn_ctx *ctx, const uint8_t *bgr, size_t stride, int width, int height,
                     uint8_t *y, uint8_t *cr, uint8_t *cb, size_t plane_stride);

@@ -70,6 +70,13 @@ static int resize_planes_dev(srcnn_ctx *c, const uint8_t *src, long sstride, lon
 {
     ResizeTables t;
     int rc;
+    // (the variant launch_resize_cubic will choose: its kernels take a row or a row tile per block of grid y and do not walk)
+    const bool dword_ok = ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dstride | (uintptr_t)dpitch) & 3) == 0;
+    const long grid_rows = resize_grid_rows(resize_variant(sw, sh, dw, dh, dword_ok), dh);
+    if (grid_rows > kMaxGridYZ || n_planes > kMaxGridYZ)
+        return fail(c, SRCNN_ERR_INVALID, "resize_cubic: %d x %d -> %d x %d on %d plane(s) needs a grid of %ld x %d blocks: at most %d "
+                                          "each (the 8-bit resize does not walk rows or planes beyond the grid)",
+                    sw, sh, dw, dh, n_planes, grid_rows, n_planes, kMaxGridYZ);
     if ((rc = ensure_tables(c, sw, sh, dw, dh, &t))) return rc;
     HIP_TRY(c, launch_resize_cubic(src, sstride, spitch, sw, sh, dst, dstride, dpitch, dw, dh, n_planes, t.xofs, t.alpha,
                                    t.yofs, t.beta, c->stream));
@@ -524,6 +531,9 @@ int srcnn_bgr2ycrcb(srcnn_ctx *c, const uint8_t *bgr, size_t stride, int width, 
     if (!bgr || !y || !cr || !cb || width <= 0 || height <= 0 || stride < 3 * (size_t)width ||
         plane_stride < (size_t)width)
         return fail(c, SRCNN_ERR_INVALID, "bgr2ycrcb: bad arguments");
+    if (height > kMaxGridYZ)
+        return fail(c, SRCNN_ERR_INVALID, "bgr2ycrcb: %d rows: at most %d (the 8-bit colour kernels take one row per block of grid y)",
+                    height, kMaxGridYZ);
     const size_t n = (size_t)width * height;
     if ((rc = reserve(c, c->bgr_in, 3 * n))) return rc;
     if ((rc = reserve(c, c->ycc_lo, 3 * n))) return rc;
@@ -548,6 +558,9 @@ int srcnn_ycrcb2bgr(srcnn_ctx *c, const uint8_t *y, const uint8_t *cr, const uin
     if (!bgr || !y || !cr || !cb || width <= 0 || height <= 0 || stride < 3 * (size_t)width ||
         plane_stride < (size_t)width)
         return fail(c, SRCNN_ERR_INVALID, "ycrcb2bgr: bad arguments");
+    if (height > kMaxGridYZ)
+        return fail(c, SRCNN_ERR_INVALID, "ycrcb2bgr: %d rows: at most %d (the 8-bit colour kernels take one row per block of grid y)",
+                    height, kMaxGridYZ);
     const size_t n = (size_t)width * height;
     if ((rc = reserve(c, c->bgr_out, 3 * n))) return rc;
     if ((rc = reserve(c, c->ycc_hi, 3 * n))) return rc;

@@ -344,6 +344,13 @@ inline int resize_variant(int sw, int sh, int dw, int dh, bool dword_ok)
     if (span <= RMAX && cspan <= SMAX) return RESIZE_TILED;
     return RESIZE_DIRECT;
 }
+// Grid y of that kernel: one block per output row (direct) or per row tile.  These kernels do not walk rows beyond the grid's
+// limit of 65,535, so launch_resize_cubic and the host layer refuse a geometry whose count passes it.
+constexpr int kMaxGridYZ = 65535;
+inline long resize_grid_rows(int variant, int dh)
+{
+    return variant == RESIZE_TILED4 ? ((long)dh + RT4 - 1) / RT4 : variant == RESIZE_TILED ? ((long)dh + RT - 1) / RT : (long)dh;
+}
 
 // The float32 cubic resize (srcnn_resize_cubic_f32*, torch's bicubic with half-pixel centres) has two forms.  tiled: a workgroup
 // produces F32_RT output rows x 256 columns (four row groups of F32_RPT rows, four adjacent columns per thread) from at most

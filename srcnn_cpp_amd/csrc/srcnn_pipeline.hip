@@ -417,9 +417,15 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(uint8_t *__restrict__ ds
     }
 }
 
+// The unsigned 8-bit kernels of this file take a row (or a row tile) from blockIdx.y and a plane from blockIdx.z and do not walk:
+// a geometry whose grid would pass the limit of 65,535 is refused here, before anything is launched (the host layer words the
+// refusal for the public calls that can reach one: srcnn_host.cpp, u8_rows_refusal).
+static bool u8_grid_ok(long y, long z = 1) { return y <= kMaxGridYZ && z <= kMaxGridYZ; }
+
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st)
 {
     if (width <= 0 || rows <= 0) return hipSuccess;
+    if (!u8_grid_ok(rows)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)((width + 1023) / 1024), (unsigned)rows), dim3(256), 0, st, dst, dstride, src,
                        sstride, width);
     return hipGetLastError();
@@ -428,6 +434,7 @@ hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long
 hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8_t *planes, long pstride,
                             long ppitch, hipStream_t st)
 {
+    if (!u8_grid_ok(h)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bgr2ycrcb_kernel, dim3((w + 255) / 256, h), dim3(256), 0, st, bgr, stride, w, h, planes,
                        pstride, ppitch);
     return hipGetLastError();
@@ -436,6 +443,7 @@ hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8
 hipError_t launch_ycrcb2bgr(const uint8_t *y, long ystride, const uint8_t *crcb, long pstride, long ppitch, int w,
                             int h, uint8_t *bgr, long stride, hipStream_t st)
 {
+    if (!u8_grid_ok(h)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ycrcb2bgr_kernel, dim3((w + 255) / 256, h), dim3(256), 0, st, y, ystride, crcb, pstride,
                        ppitch, w, h, bgr, stride);
     return hipGetLastError();
@@ -447,6 +455,7 @@ hipError_t launch_resize_cubic(const uint8_t *src, long sstride, long spitch, in
 {
     const bool dword_ok = ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dstride | (uintptr_t)dpitch) & 3) == 0;
     const int variant = resize_variant(sw, sh, dw, dh, dword_ok);      // the tiles' LDS limits: srcnn_kernels.h
+    if (!u8_grid_ok(resize_grid_rows(variant, dh), n_planes)) return hipErrorInvalidValue;
     if (variant == RESIZE_TILED4)
         hipLaunchKernelGGL(resize_cubic_tiled4_kernel, dim3((dw + 255) / 256, (dh + RT4 - 1) / RT4, n_planes), dim3(256),
                            0, st, src, sstride, spitch, sw, sh, dst, dstride, dpitch, dw, dh, xofs, alpha, yofs, beta);

@@ -102,6 +102,56 @@ def metrics(a, b, border=0, luma=None, data_range=1.0, ssim=True, sse=True):
     return out
 
 
+def _valid_last(p, g, axis):
+    """_valid along axis -2 or -1 of an array with any leading dimensions: the same products and sums in the same order"""
+    n = p.shape[axis] - (WIN - 1)
+    out = 0.0
+    for j in range(WIN):
+        idx = (Ellipsis, slice(j, j + n)) if axis == -1 else (Ellipsis, slice(j, j + n), slice(None))
+        out = out + g[j] * p[idx]
+    return out
+
+
+def _fsum_rows(x):
+    """math.fsum of every plane of x (..., H, W) -> (...)"""
+    flat = x.reshape(-1, x.shape[-2] * x.shape[-1])
+    return np.array([math.fsum(r) for r in flat.tolist()]).reshape(x.shape[:-2])
+
+
+def metrics_batch(a, b, border=0, luma=None, data_range=1.0, ssim=True, sse=True):
+    """metrics() of every frame of a, b: LOADED float64 arrays (N, C, H, W) -> (N, P, 4), the element-wise arithmetic done on
+    all planes at once.  Every value goes through the operations of metrics() in their order and every plane's sum is the same
+    math.fsum, so the result is metrics() of each frame (tests/test_metrics_cpu.py holds it to that)."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    assert a.shape == b.shape and a.ndim == 4
+    if luma is not None:
+        w = np.asarray(luma, np.float32).astype(np.float64)
+        a, b = ((((w[0] * x[:, 0] + w[1] * x[:, 1]) + w[2] * x[:, 2]) + w[3])[:, None] for x in (a, b))
+    if border:
+        a, b = (x[..., border:x.shape[-2] - border, border:x.shape[-1] - border] for x in (a, b))
+    out = np.zeros(a.shape[:2] + (4,))
+    if sse:
+        d = a - b
+        out[..., 0], out[..., 1] = _fsum_rows(d * d), float(a.shape[-2] * a.shape[-1])
+    if ssim:
+        g = window()
+        blur_nd = lambda p: _valid_last(_valid_last(p, g, -2), g, -1)
+        c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+        ma, mb, eaa, ebb, eab = blur_nd(a), blur_nd(b), blur_nd(a * a), blur_nd(b * b), blur_nd(a * b)
+        mab = ma * mb
+        num = (2.0 * mab + c1) * (2.0 * (eab - mab) + c2)
+        den = ((ma * ma + mb * mb) + c1) * (((eaa - ma * ma) + (ebb - mb * mb)) + c2)
+        m = num / den
+        out[..., 2], out[..., 3] = _fsum_rows(m), float(m.shape[-2] * m.shape[-1])
+    return out
+
+
+def periodic_rows(block, rows):
+    """`rows` rows of a picture whose rows repeat `block` (B, W) with period B"""
+    reps = -(-rows // block.shape[0])
+    return np.tile(block, (reps, 1))[:rows]
+
+
 def sse_bound(n_px):
     """relative error of a float64 sum of n non-negative terms, each exact to 2 roundings, in any order"""
     return (n_px + 4) * 2.0 ** -53

@@ -129,6 +129,49 @@ def test_squared_error_alone_on_regions_too_small_for_a_window(mctx):
         check(got, reference(a, b, border=border, ssim=False), f"{h} x {w}, border {border}, SSE only")
 
 
+# ---- the loops inside a workgroup and in the finish: regions past 1,024 columns and past 256 partials -------------------------
+SSE_COLS = 4 * 256          # the columns one pass of the SSE kernel's 256 threads covers
+
+
+@pytest.mark.parametrize("form", ["planar-f32", "interleaved-u8", "luma"])
+@pytest.mark.parametrize("rh,rw", [(4, SSE_COLS + 1), (4, 2 * SSE_COLS + 1), (5, 2 * SSE_COLS + 3)], ids=lambda v: str(v))
+def test_sse_column_groups_beyond_the_first(mctx, rh, rw, form):
+    """A thread's second and third column group (x += 1024).  planar-f32 is the 16-byte form: 1025 and 2049 columns leave its last
+    group one column wide (the scalar tail at x + 3 >= rw), 2051 three; 5 rows leave the second workgroup one row."""
+    assert rw > SSE_COLS and rw % 4 != 0
+    if form == "interleaved-u8":
+        rng = np.random.default_rng(rw)
+        a, b = (torch.from_numpy(rng.integers(0, 256, (2, rh, rw, 3), dtype=np.uint8)).cuda().permute(0, 3, 1, 2) for _ in range(2))
+    else:
+        a, b = pair((2, 3, rh, rw), rw)
+    luma = R.LUMA_BT601 if form == "luma" else None
+    got = measure(mctx, a, b, luma=luma, flags=S.METRIC_SSE)
+    assert (got[..., 1] == rh * rw).all()
+    check(got, reference(a, b, luma=luma, ssim=False), f"{rh} x {rw}, {form}, SSE only")
+
+
+@pytest.mark.parametrize("rh,rw", [(1025, 3), (2052, 5)], ids=lambda v: str(v))
+def test_finish_pass_over_more_than_256_sse_partials(mctx, rh, rw):
+    lib = C.CDLL(str(S.tuning_library_path()))
+    lim = (C.c_int * 4)()
+    assert lib.srcnn_debug_metric_limits(lim) == 0
+    assert -(-rh // lim[2]) in (257, 513), "one and two partials past the finish kernel's 256 threads"
+    a, b = pair((2, 1, rh, rw), rh)
+    check(measure(mctx, a, b, flags=S.METRIC_SSE), reference(a, b, ssim=False), f"{rh} x {rw}, SSE only")
+
+
+@pytest.mark.parametrize("name", ["one-band-257-tiles", "17x16-tiles"])
+def test_finish_pass_over_more_than_256_ssim_partials(mctx, name):
+    T, B = tile()
+    rh, rw = (13, 256 * T + 11) if name == "one-band-257-tiles" else (16 * B + 11, 15 * T + 11)
+    n_bt, n_ct = -(-(rh - 10) // B), -(-(rw - 10) // T)
+    assert (n_bt, n_ct) == ((1, 257) if name == "one-band-257-tiles" else (17, 16)) and n_bt * n_ct > 256
+    a, b = pair((1, 1, rh, rw), rh + rw)
+    got = measure(mctx, a, b, flags=S.METRIC_SSIM)
+    assert got[0, 0, 3] == (rh - 10) * (rw - 10)
+    check(got, reference(a, b, sse=False), f"{name} ({rh} x {rw}), SSIM only")
+
+
 # ---- data ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [1.0, 255.0])
 @pytest.mark.parametrize("data", ["noise", "smooth", "near-constant"])

@@ -91,6 +91,41 @@ def test_float32_cancels_where_float64_does_not(L):
     assert worst > 1e-5
 
 
+@pytest.mark.parametrize("luma,border,shape", [(None, 0, (22, 3, 12, 13)), (R.LUMA_BT601, 1, (64, 3, 14, 15)), (None, 0, (64, 1, 3, 5))])
+def test_batched_reference_equals_the_loop_form(luma, border, shape):
+    """metrics_batch (all planes at once, for the tests that measure 65,538 planes) against metrics() frame by frame, on 64
+    planes or more: the counts to the last bit, the sums within 1e-15 relative."""
+    a, b = R.load(R.noise(shape, 21)), R.load(R.smooth(shape, 22))
+    ssim = shape[-1] - 2 * border >= R.WIN
+    got = R.metrics_batch(a, b, border=border, luma=luma, ssim=ssim)
+    want = np.stack([R.metrics(a[f], b[f], border=border, luma=luma, ssim=ssim) for f in range(shape[0])])
+    assert got.shape == want.shape and got.shape[0] * got.shape[1] >= 64
+    assert np.array_equal(got[..., 1], want[..., 1]) and np.array_equal(got[..., 3], want[..., 3])
+    for k in (0, 2):
+        assert (np.abs(got[..., k] - want[..., k]) <= 1e-15 * np.abs(want[..., k])).all()
+    assert (want[..., 0] > 0).all() and ((want[..., 2] != 0).all() or not ssim)
+
+
+def test_ssim_of_a_row_periodic_picture_is_the_sum_of_its_bands():
+    """The identity the GPU test of the SSIM band walk rests on, here on 5 bands and the window row that closes the picture: a
+    pair whose rows repeat with the band height B = 64 gives every full band the same 74 source rows, so
+    ssim_sum = 5 S(74 x 11) + S(11 x 11).  Both sides are float64 sums of the same window values; they differ by the rounding
+    of one sum against five."""
+    B, W, k = 64, 11, 5
+    rng = np.random.default_rng(31)
+    blocks = [rng.integers(0, 256, (B, W), dtype=np.uint8) for _ in range(2)]
+    rows = k * B + R.WIN
+    a, b = (R.load(R.periodic_rows(x, rows))[None] for x in blocks)
+    whole = R.metrics(a, b, sse=False)[0]
+    band = R.metrics(a[:, :B + R.WIN - 1], b[:, :B + R.WIN - 1], sse=False)[0]
+    last = R.metrics(a[:, :R.WIN], b[:, :R.WIN], sse=False)[0]
+    assert np.array_equal(a[0, k * B:], a[0, :R.WIN]) and band[3] == B and last[3] == 1
+    assert whole[3] == k * band[3] + last[3] == rows - R.WIN + 1
+    want = math.fsum([band[2]] * k + [last[2]])
+    assert abs(whole[2] - want) <= 1e-14 * max(abs(want), abs(band[2])), "three correctly rounded sums: a few 2^-53 apart"
+    assert abs(whole[2] / whole[3]) < 0.5, "two unrelated pictures"
+
+
 # ---- 2: header, exports, ABI, psnr -----------------------------------------------------------------------------------------
 NEW_SYMBOLS = ["srcnn_metrics_image_dev", "srcnn_metric_psnr"]
 
