@@ -424,7 +424,7 @@ int srcnn_debug_resize_variant(int sw, int sh, int dw, int dh, int dword_ok)
     return resize_variant(sw, sh, dw, dh, dword_ok != 0);
 }
 
-/* ... and the same for the float32 resize: 1 tiled, 0 direct (resize_f32_variant(), what launch_resize_cubic_f32 asks); F32_RT,
+/* ... and the same for the float32 resize: 1 tiled, 0 direct (resize_f32_variant(), what launch_resize_cubic_image asks); F32_RT,
  * F32_RMAX, F32_SMAX, columns per tile. */
 int srcnn_debug_resize_f32_variant(int sw, int sh, int dw, int dh)
 {

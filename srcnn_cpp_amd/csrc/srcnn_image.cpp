@@ -2,10 +2,11 @@
 // image path on interleaved or planar pixels of float32, float16, bfloat16 or uint8 (srcnn_forward_image_dev,
 // srcnn_resize_cubic_image_dev, srcnn_process_image_dev, srcnn_process_rgb_image_dev), and the antialiased resize on them
 // (srcnn_resize_cubic_aa_image_dev; its launch is resample_aa_dev of srcnn_resize_f32.cpp).
-// Each call equals store(its _f32_dev counterpart(load(x))) bit for bit.  With both descriptors planar float32 a call IS that
-// counterpart; otherwise the resize, the luma front and the merge back run their accessor forms (srcnn_pipeline.hip), and the
-// model itself runs on float32 planes in the context's workspace, converted in and out by convert_image_kernel where the
-// stored format is not planar float32 already.
+// Each call equals store(its _f32_dev counterpart(load(x))) bit for bit.  With both descriptors planar float32 (and inside that
+// counterpart's own gate) a call IS that counterpart; otherwise it runs the same per-frame routines, which live here and take
+// two ImageRefs (the _f32 entry points of srcnn_resize_f32.cpp call them with float32 descriptors): the resize, the luma front
+// and the merge back in the accessor forms of their kernels (srcnn_pipeline.hip), and the model itself on float32 planes
+// in the context's workspace, converted in and out by convert_image_kernel where the stored format is not planar float32 already.
 #include "srcnn_ctx.h"
 #include "srcnn_image.h"
 
@@ -124,15 +125,6 @@ int images_refusal(srcnn_ctx *c, const char *what, const srcnn_image *src, int s
     return SRCNN_OK;
 }
 
-int luma_refusal(srcnn_ctx *c, const char *what, const float *luma, const float *clamp, float *g)
-{
-    if (!luma || srcnn_luma_gain(luma, g) != SRCNN_OK)
-        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset} with w0 + w1 + w2 > 0", what);
-    if (clamp && !(clamp[0] <= clamp[1]))
-        return fail(c, SRCNN_ERR_INVALID, "%s: clamp {%g, %g}: expected lo <= hi, neither a NaN", what, (double)clamp[0], (double)clamp[1]);
-    return SRCNN_OK;
-}
-
 // the workspace (and the band maps) were last used on another stream: wait for that work before this call overwrites it
 int claim_workspace(srcnn_ctx *c, size_t floats, float **work)
 {
@@ -170,6 +162,98 @@ int model_frame(srcnn_ctx *c, const float *in, float *out, const ImageRef &dst, 
 }
 
 }  // namespace
+
+// ---- what the _f32 entry points (srcnn_resize_f32.cpp) and the _image_dev ones below share: checked arguments, device memory,
+// the context's stream ----
+namespace srcnn {
+namespace host {
+
+ImageRef f32_image(const float *p, size_t stride, size_t ch_pitch, size_t frame_pitch)
+{
+    return ImageRef{const_cast<float *>(p), ELEM_F32, 0.f, 1, (long)stride, (long)ch_pitch, (long)frame_pitch};
+}
+
+int resize_cubic_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src_h, const ImageRef &dst, int dst_w, int dst_h, int channels,
+                     int n_frames)
+{
+    ResizeTablesF32 t;
+    int rc;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    HIP_TRY(c, launch_resize_cubic_image(src, src_w, src_h, dst, dst_w, dst_h, channels, n_frames, t.xfirst, t.xcoef, t.yfirst, t.ycoef,
+                                         c->stream));
+    return SRCNN_OK;
+}
+
+// Resize + model: every channel of a frame into the context's one-frame workspace (packed float32 planes), then the model on that
+// frame exactly as srcnn_forward_f32_dev runs it -- into the destination itself where the banded path can write it
+// (f32_direct_dst), else through a second set of planes and a converting pass; frame after frame on the context's stream.
+int process_frames_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src_h, const ImageRef &dst, int dst_w, int dst_h, int n_frames)
+{
+    const int C = c->channels;
+    const bool direct = f32_direct_dst(dst, C, dst_w, dst_h, n_frames);
+    const size_t plane = (size_t)dst_w * dst_h;
+    int rc;
+    float *work = nullptr;
+    if ((rc = claim_workspace(c, (direct ? 1 : 2) * C * plane, &work))) return rc;      // the resized frame, and the model's output
+    for (int f = 0; f < n_frames; ++f) {
+        if ((rc = resize_cubic_dev(c, frame_of(src, f), src_w, src_h, packed_f32(work, dst_w, dst_h), dst_w, dst_h, C, 1))) return rc;
+        if ((rc = model_frame(c, work, work + C * plane, frame_of(dst, f), direct, dst_w, dst_h))) return rc;
+    }
+    return release_workspace(c);
+}
+
+// What a 3-channel image through a 1-channel model asks beyond its descriptors, in this order: the luma row (and its gain), the
+// clamp, no shrinking (which implies that the geometry fits the resize's tile, what the two kernels rest on), a 1-channel model
+// (`runs_colour`: the call that runs a colour model, and on what), the gate of srcnn_forward_f32.
+int process_rgb_refusal(srcnn_ctx *c, const char *what, const char *runs_colour, int src_w, int src_h, int dst_w, int dst_h,
+                        const float *luma, const float *clamp, float *g)
+{
+    if (!luma || srcnn_luma_gain(luma, g) != SRCNN_OK)
+        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset} with w0 + w1 + w2 > 0", what);
+    if (clamp && !(clamp[0] <= clamp[1]))
+        return fail(c, SRCNN_ERR_INVALID, "%s: clamp {%g, %g}: expected lo <= hi, neither a NaN", what, (double)clamp[0], (double)clamp[1]);
+    if (dst_w < src_w || dst_h < src_h)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d shrinks the image (a super-resolution call resizes up or not at all)",
+                    what, src_w, src_h, dst_w, dst_h);
+    if (resize_f32_variant(src_w, src_h, dst_w, dst_h) != RESIZE_F32_TILED)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d does not fit the resize's tile", what, src_w, src_h, dst_w, dst_h);
+    if (c->channels != 1)
+        return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model on the luma of the image: the context holds a colour model (3 "
+                                        "channels, 9-%d-5), which %s themselves", what, c->f2, runs_colour);
+    return forward_f32_refusal(c);
+}
+
+// Per frame: Yup = resize(luma of the three channels) into the first plane of the workspace, Ysr = the model on Yup -- exactly as
+// srcnn_forward_f32_dev runs it -- into the second, then every output channel = resize of its source channel + (Ysr - Yup) g.
+int process_rgb_frames_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src_h, const ImageRef &dst, int dst_w, int dst_h,
+                           const float *luma, float g, const float *clamp, int n_frames)
+{
+    const size_t plane = (size_t)dst_w * dst_h;
+    int rc;
+    float *yup = nullptr;
+    if ((rc = claim_workspace(c, 2 * plane, &yup))) return rc;
+    float *ysr = yup + plane;
+    ResizeTablesF32 t;
+    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
+    for (int f = 0; f < n_frames; ++f) {
+        const ImageRef sf = frame_of(src, f);
+        HIP_TRY(c, launch_luma_resize_image(sf, src_w, src_h, yup, dst_w, 0, dst_w, dst_h, 1, luma, t.xfirst, t.xcoef, t.yfirst,
+                                            t.ycoef, c->stream));
+        BandedPlanes io;
+        io.f32 = true;
+        io.src = yup;
+        io.src_stride = (size_t)dst_w;
+        io.dst = ysr;
+        io.dst_stride = (size_t)dst_w;
+        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
+        HIP_TRY(c, launch_resize_merge_image(sf, src_w, src_h, ysr, dst_w, 0, yup, dst_w, 0, frame_of(dst, f), dst_w, dst_h, 1, g, clamp,
+                                             t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
+    }
+    return release_workspace(c);      // (the merge read the workspace behind forward_banded's event)
+}
+
+}  // namespace host
+}  // namespace srcnn
 
 extern "C" {
 
@@ -221,11 +305,7 @@ int srcnn_resize_cubic_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w
         return srcnn_resize_cubic_f32_dev(c, static_cast<const float *>(s.data), f32_row(s, src_w), s.ch_pitch, s.frame_pitch, src_w,
                                           src_h, static_cast<float *>(d.data), f32_row(d, dst_w), d.ch_pitch, d.frame_pitch, dst_w,
                                           dst_h, channels, n_frames);
-    ResizeTablesF32 t;
-    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
-    HIP_TRY(c, launch_resize_cubic_image(s, src_w, src_h, d, dst_w, dst_h, channels, n_frames, t.xfirst, t.xcoef, t.yfirst, t.ycoef,
-                                         c->stream));
-    return SRCNN_OK;
+    return resize_cubic_dev(c, s, src_w, src_h, d, dst_w, dst_h, channels, n_frames);
 }
 
 int srcnn_resize_cubic_aa_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
@@ -248,23 +328,12 @@ int srcnn_process_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int
     const int C = c->channels;
     if ((rc = images_refusal(c, "process_image_dev", src, src_w, src_h, dst, dst_w, dst_h, C, n_frames))) return rc;
     const ImageRef s = image_ref(src, src_w, src_h, C, n_frames), d = image_ref(dst, dst_w, dst_h, C, n_frames);
-    const bool direct = f32_direct_dst(d, C, dst_w, dst_h, n_frames);
-    if (f32_direct_src(s, src_w) && direct)
+    if (f32_direct_src(s, src_w) && f32_direct_dst(d, C, dst_w, dst_h, n_frames))
         return srcnn_process_f32_dev(c, static_cast<const float *>(s.data), f32_row(s, src_w), s.ch_pitch, s.frame_pitch, src_w, src_h,
                                      static_cast<float *>(d.data), f32_row(d, dst_w), d.ch_pitch, d.frame_pitch, dst_w, dst_h,
                                      n_frames);
     if ((rc = forward_f32_refusal(c))) return rc;
-    const size_t plane = (size_t)dst_w * dst_h;
-    float *work = nullptr;
-    if ((rc = claim_workspace(c, (direct ? 1 : 2) * C * plane, &work))) return rc;      // the resized frame, and the model's output
-    ResizeTablesF32 t;
-    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
-    for (int f = 0; f < n_frames; ++f) {
-        HIP_TRY(c, launch_resize_cubic_image(frame_of(s, f), src_w, src_h, packed_f32(work, dst_w, dst_h), dst_w, dst_h, C, 1,
-                                             t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
-        if ((rc = model_frame(c, work, work + C * plane, frame_of(d, f), direct, dst_w, dst_h))) return rc;
-    }
-    return release_workspace(c);
+    return process_frames_dev(c, s, src_w, src_h, d, dst_w, dst_h, n_frames);
 }
 
 int srcnn_process_rgb_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
@@ -281,38 +350,10 @@ int srcnn_process_rgb_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w,
                                          src_h, static_cast<float *>(d.data), f32_row(d, dst_w), d.ch_pitch, d.frame_pitch, dst_w,
                                          dst_h, luma, clamp, n_frames);
     float g = 0.f;
-    if ((rc = luma_refusal(c, what, luma, clamp, &g))) return rc;
-    if (dst_w < src_w || dst_h < src_h)
-        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d shrinks the image (a super-resolution call resizes up or not at all)",
-                    what, src_w, src_h, dst_w, dst_h);
-    if (resize_f32_variant(src_w, src_h, dst_w, dst_h) != RESIZE_F32_TILED)
-        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d does not fit the resize's tile", what, src_w, src_h, dst_w, dst_h);
-    if (c->channels != 1)
-        return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model on the luma of the image: the context holds a colour model (3 "
-                                        "channels, 9-%d-5), which srcnn_process_image_dev runs on the three channels themselves",
-                    what, c->f2);
-    if ((rc = forward_f32_refusal(c))) return rc;
-    const size_t plane = (size_t)dst_w * dst_h;
-    float *yup = nullptr;
-    if ((rc = claim_workspace(c, 2 * plane, &yup))) return rc;
-    float *ysr = yup + plane;
-    ResizeTablesF32 t;
-    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
-    for (int f = 0; f < n_frames; ++f) {
-        const ImageRef sf = frame_of(s, f);
-        HIP_TRY(c, launch_luma_resize_image(sf, src_w, src_h, yup, dst_w, 0, dst_w, dst_h, 1, luma, t.xfirst, t.xcoef, t.yfirst,
-                                            t.ycoef, c->stream));
-        BandedPlanes io;
-        io.f32 = true;
-        io.src = yup;
-        io.src_stride = (size_t)dst_w;
-        io.dst = ysr;
-        io.dst_stride = (size_t)dst_w;
-        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
-        HIP_TRY(c, launch_resize_merge_image(sf, src_w, src_h, ysr, dst_w, 0, yup, dst_w, 0, frame_of(d, f), dst_w, dst_h, 1, g, clamp,
-                                             t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
-    }
-    return release_workspace(c);
+    if ((rc = process_rgb_refusal(c, what, "srcnn_process_image_dev runs on the three channels", src_w, src_h, dst_w, dst_h, luma, clamp,
+                                  &g)))
+        return rc;
+    return process_rgb_frames_dev(c, s, src_w, src_h, d, dst_w, dst_h, luma, g, clamp, n_frames);
 }
 
 /* ---- full-reference metrics: {sse, n_px, ssim_sum, n_win} per (frame, result), float64 after the load (srcnn_metrics.hip) ---- */

@@ -33,10 +33,19 @@ __device__ __forceinline__ float image_load(const ImageRef &im, long at)
 }
 #endif
 
-// The accessor forms of the float resize (launch_resize_cubic_f32, launch_luma_resize_f32, launch_resize_merge_f32): the same
-// tables, the same tile, the same variant choice and summation order; only the element access of the tile's fill and of the
-// vertical pass's store goes through the load and the store of an ImageRef.  yup / ysr stay packed float32 planes (the
-// context's workspace).
+// The launchers of the float cubic resize, for float32 planes and for every other stored format: two families of kernels in
+// srcnn_pipeline.hip, the float32 ones and their accessor forms, nine in all.  A call launches the float32 kernel (resize_cubic_f32_*, luma_resize_f32,
+// resize_merge_f32: pointers and strides of the two descriptors) when BOTH sides are planar float32 (image_is_planar_f32; for
+// the luma front the destination always is), the image kernel (element access through the ImageRef's load and store)
+// otherwise: the same tables, tile, variant choice and summation order, and the same bits.
+// `channels` planes x n_frames frames in one launch.  xfirst / yfirst: first[d] = floor(r), unclamped (the taps are first - 1 ..
+// first + 2, each clamped to the plane by the kernels); xcoef / ycoef: four float32 coefficients per output column / row
+// (srcnn_cubic_f32_taps).  The two launches around the banded path of a 3-channel image through a 1-channel model are the
+// tiled form (hipErrorInvalidValue for a geometry resize_f32_variant() does not send there: the call never shrinks, and every
+// up-scale fits the tile).  Front: Yup = the resize of Y = ((w0 x0 + w1 x1) + w2 x2) + off, luma = {w0, w1, w2, off}, the
+// pixel's three channels ch_pitch apart.  Back: dst_c = resize(x_c) + (Ysr - Yup) g for c = 0, 1, 2, clamped to [clamp[0],
+// clamp[1]] unless clamp is null; every product and sum rounded on its own.  yup / ysr are packed float32 planes (the
+// context's workspace), strides and pitches in floats.
 hipError_t launch_resize_cubic_image(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels,
                                      int n_frames, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
                                      hipStream_t st);
@@ -114,6 +123,21 @@ hipError_t launch_metrics(const ImageRef &a, const ImageRef &b, int rw, int rh, 
                           const double gauss[METRIC_WIN], double c1, double c2, int flags, double *work, double *out, hipStream_t st);
 
 namespace host {
+// What the _f32 entry points (srcnn_resize_f32.cpp) and the _image_dev ones (srcnn_image.cpp, where these live) share.  All take
+// checked arguments and device memory and run on the context's stream.
+// planar float32 planes as a descriptor (strides and pitches in floats)
+ImageRef f32_image(const float *p, size_t stride, size_t ch_pitch, size_t frame_pitch);
+// the cubic resize: tables cached per geometry, one launch
+int resize_cubic_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src_h, const ImageRef &dst, int dst_w, int dst_h, int channels,
+                     int n_frames);
+// resize + model, frame after frame through the context's one-frame workspace (claim_workspace / release_workspace)
+int process_frames_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src_h, const ImageRef &dst, int dst_w, int dst_h, int n_frames);
+// a 3-channel image through the 1-channel model: the rules behind the descriptors' own (SRCNN_OK and the gain, or the code and the
+// reason; runs_colour ends the sentence that names the call for a colour model), and luma front, model, merge back per frame
+int process_rgb_refusal(srcnn_ctx *c, const char *what, const char *runs_colour, int src_w, int src_h, int dst_w, int dst_h,
+                        const float *luma, const float *clamp, float *g);
+int process_rgb_frames_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src_h, const ImageRef &dst, int dst_w, int dst_h,
+                           const float *luma, float g, const float *clamp, int n_frames);
 // The launch behind every antialiased resize (srcnn_resize_f32.cpp): checked arguments, device memory, the context's stream;
 // tables cached per geometry, the form chosen by resample_aa_variant(), the general form's workspace grown on demand.
 int resample_aa_dev(srcnn_ctx *c, const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames);

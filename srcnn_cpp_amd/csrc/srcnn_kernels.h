@@ -369,27 +369,7 @@ inline int resize_f32_variant(int sw, int sh, int dw, int dh)
     const long cspan = (256L * sw + dw - 1) / dw + 5;
     return (span <= F32_RMAX && cspan <= F32_SMAX) ? RESIZE_F32_TILED : RESIZE_F32_DIRECT;
 }
-// `channels` planes x n_frames frames of float32 in one launch; strides and pitches in floats, for source and destination
-// separately.  xfirst / yfirst: first[d] = floor(r), unclamped (the taps are first - 1 .. first + 2, each clamped to the plane
-// by the kernels); xcoef / ycoef: four float32 coefficients per output column / row (srcnn_cubic_f32_taps).  Both forms sum
-// in the same order and give the same bits.
-hipError_t launch_resize_cubic_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *dst,
-                                   long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int channels, int n_frames,
-                                   const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st);
-
-// A 3-plane float image through a 1-channel model (srcnn_process_rgb_f32*): the two launches around the banded path, both the
-// tiled form above with the same tables (hipErrorInvalidValue for a geometry resize_f32_variant() does not send there: the call
-// never shrinks, and every up-scale fits the tile).  Front: Yup = the resize of Y = ((w0 x0 + w1 x1) + w2 x2) + off, luma =
-// {w0, w1, w2, off}, the three source planes sch_pitch apart.  Back: dst_c = resize(x_c) + (Ysr - Yup) g for c = 0, 1, 2,
-// clamped to [clamp[0], clamp[1]] unless clamp is null.  Strides and pitches in floats; every product and sum rounded on its own.
-hipError_t launch_luma_resize_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *yup,
-                                  long ystride, long yframe_pitch, int dw, int dh, int n_frames, const float luma[4],
-                                  const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st);
-hipError_t launch_resize_merge_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, const float *ysr,
-                                   long ysr_stride, long ysr_frame_pitch, const float *yup, long yup_stride, long yup_frame_pitch,
-                                   float *dst, long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int n_frames, float g,
-                                   const float *clamp, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
-                                   hipStream_t st);
+// (the launchers take descriptors, float32 planes among them: srcnn_image.h)
 
 hipError_t launch_copy_rows(uint8_t *dst, long dstride, const uint8_t *src, long sstride, int width, int rows, hipStream_t st);
 hipError_t launch_bgr2ycrcb(const uint8_t *bgr, long stride, int w, int h, uint8_t *planes, long pstride,

@@ -740,66 +740,6 @@ __global__ __launch_bounds__(256) void resize_merge_f32_kernel(const F32ResizeAr
     }
 }
 
-hipError_t launch_resize_cubic_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *dst,
-                                   long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int channels, int n_frames,
-                                   const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st)
-{
-    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels <= 0 || n_frames <= 0 || (long)channels * n_frames > 0x7fffffffL)
-        return hipErrorInvalidValue;
-    const F32ResizeArgs p{src, sstride, sch_pitch, sframe_pitch, sw, sh, dst, dstride, dch_pitch, dframe_pitch, dw, dh,
-                          channels, channels * n_frames, xfirst, yfirst, xcoef, ycoef};
-    auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };      // grid y and z: the kernels walk what lies beyond
-    const unsigned gz = cap(p.n_planes);
-    if (resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED)      // the tile's LDS limits: srcnn_kernels.h
-        hipLaunchKernelGGL(resize_cubic_f32_tiled_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), gz),
-                           dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL(resize_cubic_f32_direct_kernel, dim3((dw + 255) / 256, cap(dh), gz), dim3(256), 0, st, p);
-    return hipGetLastError();
-}
-
-// the two launches of srcnn_process_rgb_f32* for n_frames frames: hipErrorInvalidValue for a geometry outside the tile
-static bool rgb_f32_geometry_ok(int sw, int sh, int dw, int dh, int n_frames)
-{
-    return sw > 0 && sh > 0 && dw > 0 && dh > 0 && n_frames > 0 && resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED;
-}
-
-hipError_t launch_luma_resize_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, float *yup,
-                                  long ystride, long yframe_pitch, int dw, int dh, int n_frames, const float luma[4],
-                                  const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef, hipStream_t st)
-{
-    if (!rgb_f32_geometry_ok(sw, sh, dw, dh, n_frames)) return hipErrorInvalidValue;
-    const F32ResizeArgs p{src, sstride, sch_pitch, sframe_pitch, sw, sh, yup, ystride, 0, yframe_pitch, dw, dh,
-                          1, n_frames, xfirst, yfirst, xcoef, ycoef};
-    F32LumaArgs q{};
-    q.w0 = luma[0]; q.w1 = luma[1]; q.w2 = luma[2]; q.off = luma[3];
-    auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };
-    hipLaunchKernelGGL(luma_resize_f32_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), cap(n_frames)), dim3(256), 0,
-                       st, p, q);
-    return hipGetLastError();
-}
-
-hipError_t launch_resize_merge_f32(const float *src, long sstride, long sch_pitch, long sframe_pitch, int sw, int sh, const float *ysr,
-                                   long ysr_stride, long ysr_frame_pitch, const float *yup, long yup_stride, long yup_frame_pitch,
-                                   float *dst, long dstride, long dch_pitch, long dframe_pitch, int dw, int dh, int n_frames, float g,
-                                   const float *clamp, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
-                                   hipStream_t st)
-{
-    if (!rgb_f32_geometry_ok(sw, sh, dw, dh, n_frames)) return hipErrorInvalidValue;
-    const F32ResizeArgs p{src, sstride, sch_pitch, sframe_pitch, sw, sh, dst, dstride, dch_pitch, dframe_pitch, dw, dh,
-                          3, n_frames, xfirst, yfirst, xcoef, ycoef};
-    F32LumaArgs q{};
-    q.g = g;
-    q.clamp = clamp != nullptr;
-    if (clamp) { q.lo = clamp[0]; q.hi = clamp[1]; }
-    q.ysr = ysr; q.ysr_stride = ysr_stride; q.ysr_frame_pitch = ysr_frame_pitch;
-    q.yup = yup; q.yup_stride = yup_stride; q.yup_frame_pitch = yup_frame_pitch;
-    auto cap = [](int v) { return (unsigned)(v < 65535 ? v : 65535); };
-    hipLaunchKernelGGL(resize_merge_f32_kernel, dim3((dw + 255) / 256, cap((dh + F32_RT - 1) / F32_RT), cap(n_frames)), dim3(256), 0,
-                       st, p, q);
-    return hipGetLastError();
-}
-
 // ---- images as they are stored (srcnn_*_image_dev): accessor forms of the four kernels above ------------------------------
 // The same tables, tile (F32_RT, F32_RMAX, F32_SMAX: the same LDS), variant choice and cubic_sum4 order; f32_tile_cols and
 // f32_tile_hpass are the ones above.  Only the fill's load and the vertical pass's store differ: they go through an ImageRef.
@@ -923,7 +863,8 @@ __device__ __forceinline__ void image_store_pixels4(const ImageRef &im, long at,
 }
 __host__ __device__ __forceinline__ bool image_pixels_of_3(const ImageRef &im) { return im.px_step == 3 && im.ch_pitch == 1; }
 
-// geometry and tables as the kernels above take them (g.src, g.dst and their strides unused), and the two images
+// geometry and tables as the kernels above take them (g.src, g.dst and their strides: not read by the image kernels), and the
+// two images
 struct ImageResizeArgs {
     F32ResizeArgs g;
     ImageRef src, dst;
@@ -1215,12 +1156,18 @@ constexpr bool kMergePixelOrder = true;
 
 static unsigned grid_cap(int v) { return (unsigned)(v < 65535 ? v : 65535); }      // grid y and z: the kernels walk what lies beyond
 
+// The arguments of a launch.  g carries the geometry and the tables for every kernel, and the planes' pointers and strides for
+// the float32 kernels, which a launcher takes exactly when both sides are planar float32 (srcnn_image_check's layouts: any
+// row stride and pitches); every other pair of descriptors takes the image kernels, which read the ImageRefs.
 static ImageResizeArgs image_args(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_planes,
                                   const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef)
 {
-    return ImageResizeArgs{F32ResizeArgs{nullptr, 0, 0, 0, sw, sh, nullptr, 0, 0, 0, dw, dh, channels, n_planes, xfirst, yfirst, xcoef,
-                                         ycoef}, src, dst};
+    return ImageResizeArgs{F32ResizeArgs{static_cast<const float *>(src.data), src.stride, src.ch_pitch, src.frame_pitch, sw, sh,
+                                         static_cast<float *>(dst.data), dst.stride, dst.ch_pitch, dst.frame_pitch, dw, dh, channels,
+                                         n_planes, xfirst, yfirst, xcoef, ycoef}, src, dst};
 }
+static bool both_planar_f32(const ImageResizeArgs &a) { return image_is_planar_f32(a.src) && image_is_planar_f32(a.dst); }
+static dim3 tile_grid(int dw, int dh, int nz) { return dim3((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), grid_cap(nz)); }
 
 hipError_t launch_resize_cubic_image(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels,
                                      int n_frames, const int *xfirst, const float *xcoef, const int *yfirst, const float *ycoef,
@@ -1229,13 +1176,23 @@ hipError_t launch_resize_cubic_image(const ImageRef &src, int sw, int sh, const 
     if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels <= 0 || n_frames <= 0 || (long)channels * n_frames > 0x7fffffffL)
         return hipErrorInvalidValue;
     const ImageResizeArgs a = image_args(src, sw, sh, dst, dw, dh, channels, channels * n_frames, xfirst, xcoef, yfirst, ycoef);
-    const unsigned gz = grid_cap(a.g.n_planes);
-    if (resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED)
-        hipLaunchKernelGGL(resize_cubic_image_tiled_kernel, dim3((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), gz),
-                           dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(resize_cubic_image_direct_kernel, dim3((dw + 255) / 256, grid_cap(dh), gz), dim3(256), 0, st, a);
+    const bool f32 = both_planar_f32(a);
+    if (resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED) {      // the tile's LDS limits: srcnn_kernels.h
+        const dim3 grid = tile_grid(dw, dh, a.g.n_planes);
+        if (f32) hipLaunchKernelGGL(resize_cubic_f32_tiled_kernel, grid, dim3(256), 0, st, a.g);
+        else hipLaunchKernelGGL(resize_cubic_image_tiled_kernel, grid, dim3(256), 0, st, a);
+    } else {
+        const dim3 grid((dw + 255) / 256, grid_cap(dh), grid_cap(a.g.n_planes));
+        if (f32) hipLaunchKernelGGL(resize_cubic_f32_direct_kernel, grid, dim3(256), 0, st, a.g);
+        else hipLaunchKernelGGL(resize_cubic_image_direct_kernel, grid, dim3(256), 0, st, a);
+    }
     return hipGetLastError();
+}
+
+// the two launches of srcnn_process_rgb_* for n_frames frames: hipErrorInvalidValue for a geometry outside the tile
+static bool rgb_f32_geometry_ok(int sw, int sh, int dw, int dh, int n_frames)
+{
+    return sw > 0 && sh > 0 && dw > 0 && dh > 0 && n_frames > 0 && resize_f32_variant(sw, sh, dw, dh) == RESIZE_F32_TILED;
 }
 
 hipError_t launch_luma_resize_image(const ImageRef &src, int sw, int sh, float *yup, long ystride, long yframe_pitch, int dw, int dh,
@@ -1247,8 +1204,8 @@ hipError_t launch_luma_resize_image(const ImageRef &src, int sw, int sh, float *
     const ImageResizeArgs a = image_args(src, sw, sh, dst, dw, dh, 1, n_frames, xfirst, xcoef, yfirst, ycoef);
     F32LumaArgs q{};
     q.w0 = luma[0]; q.w1 = luma[1]; q.w2 = luma[2]; q.off = luma[3];
-    hipLaunchKernelGGL(luma_resize_image_kernel, dim3((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), grid_cap(n_frames)),
-                       dim3(256), 0, st, a, q);
+    if (both_planar_f32(a)) hipLaunchKernelGGL(luma_resize_f32_kernel, tile_grid(dw, dh, n_frames), dim3(256), 0, st, a.g, q);
+    else hipLaunchKernelGGL(luma_resize_image_kernel, tile_grid(dw, dh, n_frames), dim3(256), 0, st, a, q);
     return hipGetLastError();
 }
 
@@ -1265,8 +1222,10 @@ hipError_t launch_resize_merge_image(const ImageRef &src, int sw, int sh, const 
     if (clamp) { q.lo = clamp[0]; q.hi = clamp[1]; }
     q.ysr = ysr; q.ysr_stride = ysr_stride; q.ysr_frame_pitch = ysr_frame_pitch;
     q.yup = yup; q.yup_stride = yup_stride; q.yup_frame_pitch = yup_frame_pitch;
-    const dim3 grid((dw + 255) / 256, grid_cap((dh + F32_RT - 1) / F32_RT), grid_cap(n_frames));
-    if (kMergePixelOrder && image_pixels_of_3(dst))
+    const dim3 grid = tile_grid(dw, dh, n_frames);
+    if (both_planar_f32(a))
+        hipLaunchKernelGGL(resize_merge_f32_kernel, grid, dim3(256), 0, st, a.g, q);
+    else if (kMergePixelOrder && image_pixels_of_3(dst))
         hipLaunchKernelGGL(resize_merge_image_pixels_kernel, grid, dim3(256), 0, st, a, q);
     else
         hipLaunchKernelGGL(resize_merge_image_kernel, grid, dim3(256), 0, st, a, q);

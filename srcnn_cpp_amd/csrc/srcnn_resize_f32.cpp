@@ -1,8 +1,9 @@
 // srcnn_resize_f32.cpp -- the step in front of the float image path: the cubic resize of float32 planes as torch's bicubic
 // interpolation defines it (srcnn_cubic_f32_taps, srcnn_resize_cubic_f32*), resize + model in one call (srcnn_process_f32*), and a
 // 3-plane image through a 1-channel model (srcnn_luma_gain, srcnn_process_rgb_f32*).
-// The tap tables are built here, on the host in float64; the kernels are in srcnn_pipeline.hip (launch_resize_cubic_f32,
-// launch_luma_resize_f32, launch_resize_merge_f32).
+// The tap tables are built here, on the host in float64.  The planes of a call become descriptors (f32_image), and the device
+// steps -- the resize, the per-frame loops of resize + model and of luma front, model, merge back -- are the ones the
+// srcnn_*_image_dev calls run (srcnn_image.cpp; launchers and kernels: srcnn_image.h, srcnn_pipeline.hip).
 // The antialiased down-scaling resize lives here too (srcnn_cubic_aa_f32_taps, srcnn_resize_cubic_aa_f32*, and resample_aa_dev,
 // the launch srcnn_resize_cubic_aa_image_dev shares): its tables have a tap count per output sample; kernels resample_aa_*.
 #include "srcnn_ctx.h"
@@ -198,50 +199,6 @@ static int resize_f32_refusal(srcnn_ctx *c, const char *what, const float *src, 
     return SRCNN_OK;
 }
 
-// the launch behind every float resize: checked arguments, device memory, the context's stream
-static int resize_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
-                          int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
-                          int C, int n_frames)
-{
-    ResizeTablesF32 t;
-    int rc;
-    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
-    HIP_TRY(c, launch_resize_cubic_f32(d_src, (long)src_stride, (long)src_ch_pitch, (long)src_frame_pitch, src_w, src_h, d_dst,
-                                       (long)dst_stride, (long)dst_ch_pitch, (long)dst_frame_pitch, dst_w, dst_h, C, n_frames, t.xfirst,
-                                       t.xcoef, t.yfirst, t.ycoef, c->stream));
-    return SRCNN_OK;
-}
-
-// Resize + model on device memory: every channel of a frame into the context's one-frame workspace, then the model on that
-// frame exactly as srcnn_forward_f32_dev runs it; frame after frame on the context's stream.
-static int process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
-                           int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch, int dst_w, int dst_h,
-                           int n_frames)
-{
-    const int C = c->channels;
-    const size_t plane = (size_t)dst_w * dst_h;
-    int rc;
-    // the workspace (and the band maps) were last used on another stream: wait for that work before the resize overwrites it
-    if (c->sp_done && c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
-    if ((rc = reserve(c, c->f32_work, C * plane * sizeof(float)))) return rc;      // (growing waits for the device)
-    float *work = static_cast<float *>(c->f32_work.p);
-    for (int f = 0; f < n_frames; ++f) {
-        if ((rc = resize_f32_dev(c, d_src + (size_t)f * src_frame_pitch, src_stride, src_ch_pitch, 0, src_w, src_h, work, (size_t)dst_w,
-                                 plane, 0, dst_w, dst_h, C, 1)))
-            return rc;
-        BandedPlanes io;
-        io.f32 = true;
-        io.src = work;
-        io.src_stride = (size_t)dst_w;
-        io.ch_step = C == 1 ? 0 : plane;
-        io.dst = d_dst + (size_t)f * dst_frame_pitch;
-        io.dst_stride = dst_stride;
-        io.dst_ch_pitch = C == 1 ? 0 : dst_ch_pitch;
-        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
-    }
-    return SRCNN_OK;
-}
-
 // g = 1 / (w0 + w1 + w2) of a luma row {w0, w1, w2, off}: the sum in float64, rounded once.  False for a non-finite entry or a
 // sum that is not positive.
 static bool luma_gain(const float *luma, float *g)
@@ -255,64 +212,38 @@ static bool luma_gain(const float *luma, float *g)
 }
 
 // The gate of srcnn_process_rgb_f32*, before anything is staged or launched: SRCNN_OK and the gain, or the code and the reason
-static int process_rgb_refusal(srcnn_ctx *c, const char *what, const float *src, size_t src_stride, size_t src_ch_pitch,
-                               size_t src_frame_pitch, int src_w, int src_h, const float *dst, size_t dst_stride, size_t dst_ch_pitch,
-                               size_t dst_frame_pitch, int dst_w, int dst_h, const float *luma, const float *clamp, int n_frames, float *g)
+static int rgb_f32_refusal(srcnn_ctx *c, const char *what, const float *src, size_t src_stride, size_t src_ch_pitch,
+                           size_t src_frame_pitch, int src_w, int src_h, const float *dst, size_t dst_stride, size_t dst_ch_pitch,
+                           size_t dst_frame_pitch, int dst_w, int dst_h, const float *luma, const float *clamp, int n_frames, float *g)
 {
     int rc;
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     if ((rc = resize_f32_refusal(c, what, src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, dst, dst_stride, dst_ch_pitch,
                                  dst_frame_pitch, dst_w, dst_h, 3, n_frames)))
         return rc;
-    if (!luma || !luma_gain(luma, g))
-        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset} with w0 + w1 + w2 > 0", what);
-    if (clamp && !(clamp[0] <= clamp[1]))
-        return fail(c, SRCNN_ERR_INVALID, "%s: clamp {%g, %g}: expected lo <= hi, neither a NaN", what, (double)clamp[0], (double)clamp[1]);
-    if (dst_w < src_w || dst_h < src_h)
-        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d shrinks the image (a super-resolution call resizes up or not at all)",
-                    what, src_w, src_h, dst_w, dst_h);
-    // (what that bound implies, and what the two kernels rest on: every such geometry fits the resize's tile)
-    if (resize_f32_variant(src_w, src_h, dst_w, dst_h) != RESIZE_F32_TILED)
-        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d does not fit the resize's tile", what, src_w, src_h, dst_w, dst_h);
-    if (c->channels != 1)
-        return fail(c, SRCNN_ERR_STATE, "%s runs a 1-channel model on the luma of the image: the context holds a colour model (3 "
-                                        "channels, 9-%d-5), which srcnn_process_f32 runs on the three planes themselves", what, c->f2);
-    return forward_f32_refusal(c);      // the gate of srcnn_forward_f32
+    return process_rgb_refusal(c, what, "srcnn_process_f32 runs on the three planes", src_w, src_h, dst_w, dst_h, luma, clamp, g);
 }
 
-// A 3-plane image through the loaded 1-channel model, on device memory.  Per frame: Yup = resize(luma of the three planes) into
-// the first plane of the workspace, Ysr = the model on Yup -- exactly as srcnn_forward_f32_dev runs it -- into the second,
-// then every output plane = resize of its source plane + (Ysr - Yup) g.  Frame after frame on the context's stream.
-static int process_rgb_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
-                               int src_w, int src_h, float *d_dst, size_t dst_stride, size_t dst_ch_pitch, size_t dst_frame_pitch,
-                               int dst_w, int dst_h, const float *luma, float g, const float *clamp, int n_frames)
+// The host-memory form of a call on one image of `C` planes: the planes into the packed device buffer lo (src_w x src_h), the
+// device step on lo -> hi (dst_w x dst_h, packed), hi back into dst; returns when dst is written.
+template <class Step>
+static int f32_staged(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
+                      size_t dst_stride, size_t dst_ch_pitch, int dst_w, int dst_h, int C, Step step)
 {
-    const size_t plane = (size_t)dst_w * dst_h;
+    const size_t lo = (size_t)src_w * src_h, hi = (size_t)dst_w * dst_h;
+    const size_t lo_row = (size_t)src_w * sizeof(float), hi_row = (size_t)dst_w * sizeof(float);
     int rc;
-    // the workspace (and the band maps) were last used on another stream: wait for that work before the resize overwrites it
-    if (c->sp_done && c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
-    if ((rc = reserve(c, c->f32_work, 2 * plane * sizeof(float)))) return rc;      // (growing waits for the device)
-    float *yup = static_cast<float *>(c->f32_work.p), *ysr = yup + plane;
-    ResizeTablesF32 t;
-    if ((rc = ensure_tables_f32(c, src_w, src_h, dst_w, dst_h, &t))) return rc;
-    for (int f = 0; f < n_frames; ++f) {
-        const float *s = d_src + (size_t)f * src_frame_pitch;
-        HIP_TRY(c, launch_luma_resize_f32(s, (long)src_stride, (long)src_ch_pitch, 0, src_w, src_h, yup, dst_w, 0, dst_w, dst_h, 1, luma,
-                                          t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
-        BandedPlanes io;
-        io.f32 = true;
-        io.src = yup;
-        io.src_stride = (size_t)dst_w;
-        io.dst = ysr;
-        io.dst_stride = (size_t)dst_w;
-        if ((rc = forward_banded(c, io, dst_w, dst_h, 1))) return rc;
-        HIP_TRY(c, launch_resize_merge_f32(s, (long)src_stride, (long)src_ch_pitch, 0, src_w, src_h, ysr, dst_w, 0, yup, dst_w, 0,
-                                           d_dst + (size_t)f * dst_frame_pitch, (long)dst_stride, (long)dst_ch_pitch, 0, dst_w, dst_h, 1,
-                                           g, clamp, t.xfirst, t.xcoef, t.yfirst, t.ycoef, c->stream));
-    }
-    // the merge reads the workspace behind forward_banded's event: the next user on another stream waits for it too
-    HIP_TRY(c, hipEventRecord(c->sp_done, c->stream));
-    c->sp_stream = c->stream;
+    if ((rc = reserve(c, c->f32_hi, C * hi * sizeof(float)))) return rc;
+    if ((rc = reserve(c, c->f32_lo, C * lo * sizeof(float)))) return rc;
+    float *d_lo = static_cast<float *>(c->f32_lo.p), *d_hi = static_cast<float *>(c->f32_hi.p);
+    for (int ch = 0; ch < C; ++ch)
+        HIP_TRY(c, hipMemcpy2DAsync(d_lo + ch * lo, lo_row, src + ch * src_ch_pitch, src_stride * sizeof(float), lo_row, src_h,
+                                    hipMemcpyHostToDevice, c->stream));
+    if ((rc = step(f32_image(d_lo, (size_t)src_w, lo, 0), f32_image(d_hi, (size_t)dst_w, hi, 0)))) return rc;
+    for (int ch = 0; ch < C; ++ch)
+        HIP_TRY(c, hipMemcpy2DAsync(dst + ch * dst_ch_pitch, dst_stride * sizeof(float), d_hi + ch * hi, hi_row, hi_row, dst_h,
+                                    hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SRCNN_OK;
 }
 
@@ -334,30 +265,8 @@ int srcnn_resize_cubic_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stri
     if ((rc = resize_f32_refusal(c, "resize_cubic_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
                                  dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, channels, n_frames)))
         return rc;
-    return resize_f32_dev(c, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
-                          dst_frame_pitch, dst_w, dst_h, channels, n_frames);
-}
-
-// one image of `C` planes between host memory and the packed device buffers lo (src_w x src_h) / hi (dst_w x dst_h)
-static int f32_stage_in(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int w, int h, int C, float **d_lo)
-{
-    const size_t plane = (size_t)w * h, row = (size_t)w * sizeof(float);
-    int rc;
-    if ((rc = reserve(c, c->f32_lo, C * plane * sizeof(float)))) return rc;
-    *d_lo = static_cast<float *>(c->f32_lo.p);
-    for (int ch = 0; ch < C; ++ch)
-        HIP_TRY(c, hipMemcpy2DAsync(*d_lo + ch * plane, row, src + ch * src_ch_pitch, src_stride * sizeof(float), row, h,
-                                    hipMemcpyHostToDevice, c->stream));
-    return SRCNN_OK;
-}
-static int f32_stage_out(srcnn_ctx *c, float *dst, size_t dst_stride, size_t dst_ch_pitch, int w, int h, int C, const float *d_hi)
-{
-    const size_t plane = (size_t)w * h, row = (size_t)w * sizeof(float);
-    for (int ch = 0; ch < C; ++ch)
-        HIP_TRY(c, hipMemcpy2DAsync(dst + ch * dst_ch_pitch, dst_stride * sizeof(float), d_hi + ch * plane, row, row, h,
-                                    hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SRCNN_OK;
+    return resize_cubic_dev(c, f32_image(d_src, src_stride, src_ch_pitch, src_frame_pitch), src_w, src_h,
+                            f32_image(d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch), dst_w, dst_h, channels, n_frames);
 }
 
 int srcnn_resize_cubic_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
@@ -368,21 +277,10 @@ int srcnn_resize_cubic_f32(srcnn_ctx *c, const float *src, size_t src_stride, si
     if ((rc = resize_f32_refusal(c, "resize_cubic_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch,
                                  0, dst_w, dst_h, channels, 1)))
         return rc;
-    const size_t hi = (size_t)dst_w * dst_h;
-    float *d_lo = nullptr;
-    if ((rc = reserve(c, c->f32_hi, channels * hi * sizeof(float)))) return rc;
-    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, channels, &d_lo))) return rc;
-    float *d_hi = static_cast<float *>(c->f32_hi.p);
-    if ((rc = resize_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h,
-                             channels, 1)))
-        return rc;
-    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels, d_hi);
-}
-
-// planar float32 planes as the images resample_aa_dev takes
-static ImageRef f32_image(const float *p, size_t stride, size_t ch_pitch, size_t frame_pitch)
-{
-    return ImageRef{const_cast<float *>(p), ELEM_F32, 0.f, 1, (long)stride, (long)ch_pitch, (long)frame_pitch};
+    return f32_staged(c, src, src_stride, src_ch_pitch, src_w, src_h, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels,
+                      [&](const ImageRef &lo, const ImageRef &hi) {
+                          return resize_cubic_dev(c, lo, src_w, src_h, hi, dst_w, dst_h, channels, 1);
+                      });
 }
 
 int srcnn_cubic_aa_f32_taps(int src_n, int dst_n, int *first, int *count, float *coef, int max_taps)
@@ -414,15 +312,10 @@ int srcnn_resize_cubic_aa_f32(srcnn_ctx *c, const float *src, size_t src_stride,
     if ((rc = resize_f32_refusal(c, "resize_cubic_aa_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch,
                                  0, dst_w, dst_h, channels, 1)))
         return rc;
-    const size_t hi = (size_t)dst_w * dst_h;
-    float *d_lo = nullptr;
-    if ((rc = reserve(c, c->f32_hi, channels * hi * sizeof(float)))) return rc;
-    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, channels, &d_lo))) return rc;
-    float *d_hi = static_cast<float *>(c->f32_hi.p);
-    if ((rc = resample_aa_dev(c, f32_image(d_lo, (size_t)src_w, (size_t)src_w * src_h, 0), src_w, src_h,
-                              f32_image(d_hi, (size_t)dst_w, hi, 0), dst_w, dst_h, channels, 1)))
-        return rc;
-    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels, d_hi);
+    return f32_staged(c, src, src_stride, src_ch_pitch, src_w, src_h, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, channels,
+                      [&](const ImageRef &lo, const ImageRef &hi) {
+                          return resample_aa_dev(c, lo, src_w, src_h, hi, dst_w, dst_h, channels, 1);
+                      });
 }
 
 int srcnn_process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch, int src_w,
@@ -436,8 +329,8 @@ int srcnn_process_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, s
                                  dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, c->channels, n_frames)))
         return rc;
     if ((rc = forward_f32_refusal(c))) return rc;      // the gate of srcnn_forward_f32, before anything is launched
-    return process_f32_dev(c, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
-                           dst_frame_pitch, dst_w, dst_h, n_frames);
+    return process_frames_dev(c, f32_image(d_src, src_stride, src_ch_pitch, src_frame_pitch), src_w, src_h,
+                              f32_image(d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch), dst_w, dst_h, n_frames);
 }
 
 int srcnn_process_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
@@ -451,14 +344,8 @@ int srcnn_process_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t 
                                  dst_w, dst_h, C, 1)))
         return rc;
     if ((rc = forward_f32_refusal(c))) return rc;      // before anything is staged
-    const size_t hi = (size_t)dst_w * dst_h;
-    float *d_lo = nullptr;
-    if ((rc = reserve(c, c->f32_hi, C * hi * sizeof(float)))) return rc;
-    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, C, &d_lo))) return rc;
-    float *d_hi = static_cast<float *>(c->f32_hi.p);
-    if ((rc = process_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h, 1)))
-        return rc;
-    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, C, d_hi);
+    return f32_staged(c, src, src_stride, src_ch_pitch, src_w, src_h, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, C,
+                      [&](const ImageRef &lo, const ImageRef &hi) { return process_frames_dev(c, lo, src_w, src_h, hi, dst_w, dst_h, 1); });
 }
 
 int srcnn_luma_gain(const float *luma, float *g)
@@ -476,11 +363,11 @@ int srcnn_process_rgb_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_strid
     BIND(c);
     int rc;
     float g = 0.f;
-    if ((rc = process_rgb_refusal(c, "process_rgb_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
-                                  dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, luma, clamp, n_frames, &g)))
+    if ((rc = rgb_f32_refusal(c, "process_rgb_f32_dev", d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst,
+                              dst_stride, dst_ch_pitch, dst_frame_pitch, dst_w, dst_h, luma, clamp, n_frames, &g)))
         return rc;
-    return process_rgb_f32_dev(c, d_src, src_stride, src_ch_pitch, src_frame_pitch, src_w, src_h, d_dst, dst_stride, dst_ch_pitch,
-                               dst_frame_pitch, dst_w, dst_h, luma, g, clamp, n_frames);
+    return process_rgb_frames_dev(c, f32_image(d_src, src_stride, src_ch_pitch, src_frame_pitch), src_w, src_h,
+                                  f32_image(d_dst, dst_stride, dst_ch_pitch, dst_frame_pitch), dst_w, dst_h, luma, g, clamp, n_frames);
 }
 
 int srcnn_process_rgb_f32(srcnn_ctx *c, const float *src, size_t src_stride, size_t src_ch_pitch, int src_w, int src_h, float *dst,
@@ -489,18 +376,13 @@ int srcnn_process_rgb_f32(srcnn_ctx *c, const float *src, size_t src_stride, siz
     BIND(c);
     int rc;
     float g = 0.f;
-    if ((rc = process_rgb_refusal(c, "process_rgb_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch, 0,
-                                  dst_w, dst_h, luma, clamp, 1, &g)))
+    if ((rc = rgb_f32_refusal(c, "process_rgb_f32", src, src_stride, src_ch_pitch, 0, src_w, src_h, dst, dst_stride, dst_ch_pitch, 0,
+                              dst_w, dst_h, luma, clamp, 1, &g)))
         return rc;
-    const size_t hi = (size_t)dst_w * dst_h;
-    float *d_lo = nullptr;
-    if ((rc = reserve(c, c->f32_hi, 3 * hi * sizeof(float)))) return rc;
-    if ((rc = f32_stage_in(c, src, src_stride, src_ch_pitch, src_w, src_h, 3, &d_lo))) return rc;
-    float *d_hi = static_cast<float *>(c->f32_hi.p);
-    if ((rc = process_rgb_f32_dev(c, d_lo, (size_t)src_w, (size_t)src_w * src_h, 0, src_w, src_h, d_hi, (size_t)dst_w, hi, 0, dst_w, dst_h,
-                                  luma, g, clamp, 1)))
-        return rc;
-    return f32_stage_out(c, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, 3, d_hi);
+    return f32_staged(c, src, src_stride, src_ch_pitch, src_w, src_h, dst, dst_stride, dst_ch_pitch, dst_w, dst_h, 3,
+                      [&](const ImageRef &lo, const ImageRef &hi) {
+                          return process_rgb_frames_dev(c, lo, src_w, src_h, hi, dst_w, dst_h, luma, g, clamp, 1);
+                      });
 }
 
 #ifdef SRCNN_TUNING_BUILD

@@ -297,6 +297,50 @@ def test_hardened_layouts_and_three_frames(ictx):
         assert varied(many.get())
 
 
+def rows_interleaved_f32(h, w, off=1):
+    """A planar float32 image of three channels interleaved by ROW (stride 3 w, channel pitch w): a layout srcnn_image_check
+    accepts and the gate of the _f32_dev calls refuses, a channel pitch inside the row stride."""
+    b = Buf.__new__(Buf)
+    b.elem, b.shape, b.strides, b.off = R.F32, (1, 3, h, w), (3 * h * w, w, 3 * w, 1), off
+    b.parent = torch.full((off + 3 * h * w + 9,), GUARD[R.F32], dtype=TORCH_BITS[R.F32], device="cuda")
+    b.view = b.parent.as_strided(b.shape, b.strides, off)
+    b.image = S.Image(b.view.data_ptr(), R.F32, 1, 3 * w, w, 3 * h * w, 1.0)
+    return b
+
+
+def test_planar_float32_the_float_gate_refuses_equals_packed_planes(ictx):
+    """Planar float32 on both sides in a layout the _f32_dev gate refuses: resize_cubic_image_dev, process_rgb_image_dev (front
+    and merge) and process_image_dev (the resize into the workspace) on a destination whose channels are interleaved by row.
+    Each equals the same call on packed planes bit for bit, in guard-filled buffers one element off their base; 131 x 40 ->
+    262 x 80 is the tiled form with a ragged right edge and three row tiles, 40 x 30 -> 20 x 15 the direct form.  What this
+    pins is the addressing of such a layout (strides, pitches, the stores' alignment rule); which kernel a launch takes is the
+    launchers' rule (both sides planar float32: the float32 one) and is not observed here, and the arithmetic of either
+    kernel is what the other tests of this file and tests/test_gpu_resize_f32.py pin."""
+    def same_as_packed(call, sh, sw, dh, dw, seed):
+        bits = R.store(np.random.default_rng(seed).random((1, 3, sh, sw), dtype=np.float32), R.F32)
+        s = Buf(PLANAR_F32, 1, 3, sh, sw, off=1).put(bits)
+        packed, rows = Buf(PLANAR_F32, 1, 3, dh, dw, off=1), rows_interleaved_f32(dh, dw)
+        assert S.image_check(rows.image, dw, dh, 3, 1, True)
+        for d in (packed, rows):
+            run(call, s.image, d.image)
+            assert d.guards_intact() and s.guards_intact()
+        want = packed.get()
+        assert np.isfinite(want.view(np.float32)).all() and len(np.unique(want)) > dh, "written, and not one value"
+        assert np.array_equal(rows.get(), want)
+
+    import ctypes as C
+    tuning = C.CDLL(str(S.tuning_library_path()))
+    tuning.srcnn_debug_resize_f32_variant.argtypes = [C.c_int] * 4
+    assert tuning.srcnn_debug_resize_f32_variant(131, 40, 262, 80) == 1 and tuning.srcnn_debug_resize_f32_variant(40, 30, 20, 15) == 0
+    same_as_packed(lambda s, d: ictx.resize_cubic_image_dev(s, 131, 40, d, 262, 80, 3, 1), 40, 131, 80, 262, 91)
+    same_as_packed(lambda s, d: ictx.resize_cubic_image_dev(s, 40, 30, d, 20, 15, 3, 1), 30, 40, 15, 20, 92)
+    load_model(ictx, 1, 5, "replicate", S.MODE_BANDED16)
+    for j, clamp in enumerate((None, CLAMP)):
+        same_as_packed(lambda s, d: ictx.process_rgb_image_dev(s, 131, 40, d, 262, 80, LUMAS[j], clamp, 1), 40, 131, 80, 262, 93 + j)
+    load_model(ictx, 3, 5, "zero", S.MODE_MFMA)
+    same_as_packed(lambda s, d: ictx.process_image_dev(s, 131, 40, d, 262, 80, 1), 40, 131, 80, 262, 95)
+
+
 # ---- 10: against float64 ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("f2,padding,mode", [(1, "replicate", S.MODE_MFMA), (5, "zero", S.MODE_BANDED16)])
 def test_upscale_rgb_image_against_the_classic_script_in_float64(f2, padding, mode):
