@@ -248,6 +248,7 @@ struct srcnn_ctx {
         int key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int count = 0;                  // 0: this geometry uses the regular grid
         int n_seams = 0;
+        int max_rows = 0;               // the tallest item
         srcnn::host::DevBuf dev, dev_seams;
         srcnn::host::DevBuf dev_winmap;              // [n_strips][rows] bytes: 1 = the row lies in a seam window of that strip (separated plans)
         bool separated = false;         // seam windows of neighbouring strips share no row: one seam launch (plan_items_balanced())
@@ -256,6 +257,7 @@ struct srcnn_ctx {
     static constexpr int kItemTables = 32;
     ItemTable item_tables[kItemTables];
     unsigned long item_clock = 0;
+    int last_launch[7] = {0, 0, 0, 0, 0, 0, 0};      // tuning build: geometry_report() of the last strip launch, and its frames
     // host copy of the uploaded tables in convdata.h order: the per-call weight arguments of the reference surface
     // (srcnn_conv99x11 / srcnn_conv55) are compared against it, and equal tables are not packed or uploaded again
     std::vector<float> host_raw = std::vector<float>(8129, 0.f);
@@ -457,10 +459,30 @@ struct ItemPlan {
 };
 ItemPlan plan_items(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int wgs_per_cu = 2, bool want_seams = false,
                     int extra_top = 0, int extra_bot = 0);
-int skew_percent();
+constexpr int kSkewPercent = 10;       // how much taller / shorter than the mean the first- / later-dispatched item of a CU is made
+// report: null for a launch (the context's cache, device tables uploaded); else nothing on the device is touched and the
+// cache stays as it is -- a cached table is returned as found, any other geometry is planned into *report (host fields only)
 int build_items(srcnn_ctx *c, int n_strips, int row_begin, int row_end, int height, int wgs_per_cu, bool want_seams,
-                const srcnn_ctx::ItemTable **table);
-int split16_wgs_per_cu(bool split16, int tune);
+                const srcnn_ctx::ItemTable **table, srcnn_ctx::ItemTable *report = nullptr);
+// The geometry of ONE strip launch, decided in one place (strip_geometry) for run_strip(), which launches from it, and for
+// srcnn_query_plan(), which reports from it.
+struct StripGeometry {
+    bool split16 = false, fused32 = false;          // the fused pass on the split-f16 / the float32 kernel
+    int tune = 0;                                   // the honoured bits of SRCNN_DEBUG_TUNE
+    Plan grid{0, 0, 0};                             // the regular grid: segment rows, strips, segments (items == 0)
+    int strips_total = 0;                           // strips of the plane
+    const srcnn_ctx::ItemTable *table = nullptr;    // the item plan asked for, if any: count, seams, separated, tallest item
+    int items = 0;                                  // explicit work items per frame (table->count); 0: the regular grid
+    int items_per_cu = 0;                           // ... and how many of them share a compute unit
+    bool col_seams = false;                         // strips of FW columns: the launch exports column seams
+};
+// mode: MODE_FUSED / MODE_L12 / MODE_L3; rows [row_begin, row_end) of a width x height plane, n_frames in the launch.
+// report: as build_items() -- null for a launch, else a table to plan into without touching the device or the cache.
+int strip_geometry(srcnn_ctx *c, int mode, int width, int height, int row_begin, int row_end, int n_frames, StripGeometry *g,
+                   srcnn_ctx::ItemTable *report = nullptr);
+// the six numbers of srcnn_query_plan for `frames` frames launched with this geometry
+void geometry_report(const StripGeometry &g, int mode, int frames, int out[6]);
+int split16_wgs_per_cu(bool split16);
 int seam_scratch_for_stream(srcnn_ctx *c, srcnn_ctx::SeamScratch **out);
 bool cseam_pays(int width);
 constexpr int kItemBatchMax = 32, kItemBatchChunk = 8, kGridBatchChunk = 64;

@@ -105,10 +105,9 @@ int process_bgr_dev(srcnn_ctx *c, const uint8_t *d_bgr, size_t stride, int w, in
     uint8_t *y_sr = static_cast<uint8_t *>(c->y_sr.p);
     // Two launches around the conv path instead of three (and 54 MB instead of 93 MB at 1080p -> 4K): the colour conversion
     // happens while the resize stages its source tile, the resized Cr / Cb go straight into the final BGR.  Same integer
-    // arithmetic per value.  SRCNN_DEBUG_PIPE3=1: the three separate kernels (A/B; also the fallback for geometries
-    // outside the tiled resize's limits).
-    static const char *env_pipe3 = SRCNN_DEBUG_ENV("SRCNN_DEBUG_PIPE3");
-    if (!(env_pipe3 && std::atoi(env_pipe3)) && fused_pipeline_ok(w, h, ow, oh, ycc_hi, (long)ow, d_out, (long)out_stride)) {
+    // arithmetic per value.  The three separate kernels below are the fallback for geometries outside the tiled resize's
+    // limits.
+    if (fused_pipeline_ok(w, h, ow, oh, ycc_hi, (long)ow, d_out, (long)out_stride)) {
         ResizeTables t;
         if ((rc = ensure_tables(c, w, h, ow, oh, &t))) return rc;
         HIP_TRY(c, launch_bgr_to_y_resized(d_bgr, (long)stride, w, h, ycc_hi, ow, ow, oh, t.xofs, t.alpha, t.yofs, t.beta,
@@ -312,10 +311,9 @@ int srcnn_forward_y(srcnn_ctx *c, const uint8_t *src, size_t src_stride, uint8_t
     // result comes back while band i computes, so only the first upload and the last download are exposed
     // (copies from / to pageable memory block this thread, not the other streams).  Any partition of the rows
     // computes the same plane (srcnn_forward_y_rows_dev).  EXACT mode and small planes: one upload, one launch.
-    static const char *env_bands = SRCNN_DEBUG_ENV("SRCNN_DEBUG_BANDS");
     // bands of >= 1024 rows: shorter ones lose more in their launches than the overlap wins (measured: 3840x2160 1.35 ms
     // in one piece, 1.27 in two bands, 1.28 in four, 1.40 in eight; 7680x4320 5.20 -> 4.44 in four)
-    int n_bands = env_bands ? std::atoi(env_bands) : ((long)width * height >= (4L << 20) ? std::min(8, height / 1024) : 1);
+    int n_bands = (long)width * height >= (4L << 20) ? std::min(8, height / 1024) : 1;
     if (c->mode == SRCNN_MODE_EXACT || preclamp || n_bands < 1 || !luma_path_ok(c))
         n_bands = 1;        // (bands: row stripes, the replicate-padded 9-1-5 model only)
     n_bands = std::min(n_bands, std::max(1, height / 64));

@@ -219,7 +219,7 @@ hipError_t launch_cseams(const StripParams &p, int n_frames, hipStream_t stream)
 // both in one launch; `winmap` [strips_total][rows] marks the rows inside a seam window of a strip (srcnn_plan.cpp, plan_items_balanced())
 hipError_t launch_seams_merged(const StripParams &p, int n_seams, const int *d_seams, const unsigned char *d_winmap, int n_frames,
                                hipStream_t stream);
-hipError_t launch_strip(int mode, const StripParams &p, int n_frames, hipStream_t stream, size_t lds_pad = 0);
+hipError_t launch_strip(int mode, const StripParams &p, int n_frames, hipStream_t stream);
 // A fused float32 single-plane launch that also carries the seam blocks of the launch BEFORE it (seam deferral, srcnn_mfma.hip):
 // blocks [0, first_block) are p's work items, the n_seams + cblocks behind them finish `prev`'s row and column seams.
 struct FoldParams {
@@ -228,15 +228,15 @@ struct FoldParams {
     const unsigned char *winmap;    // prev's rows inside a seam window, per strip; null: prev has row seams only (cblocks = 0)
     int n_seams, cblocks, first_block;
 };
-hipError_t launch_strip_fold(const StripParams &p, const FoldParams &f, hipStream_t stream, size_t lds_pad = 0);
+hipError_t launch_strip_fold(const StripParams &p, const FoldParams &f, hipStream_t stream);
 // the same kernels with every MFMA <-> vector-ALU hazard visible to the compiler (srcnn_mfma.hip built with -DSRCNN_SAFE_HAZARDS=1)
-hipError_t launch_strip_safe(int mode, const StripParams &p, int n_frames, hipStream_t stream, size_t lds_pad = 0);
+hipError_t launch_strip_safe(int mode, const StripParams &p, int n_frames, hipStream_t stream);
 // Does this device interlock the inline-asm MFMA -> packed multiply -> MFMA sequences of the fast row body?  Runs them with and
 // without wait states (srcnn_probe.hip); returns the number of results that differ (0 = interlocked), negative on a HIP error.
 long interlock_probe_mismatches(int device, hipStream_t stream);
 
 size_t split16_lds_bytes();
-hipError_t launch_split16(const StripParams &p, int n_frames, hipStream_t stream, size_t lds_pad = 0);
+hipError_t launch_split16(const StripParams &p, int n_frames, hipStream_t stream);
 
 // ---- exact (vector-ALU, reference arithmetic) kernels (srcnn_exact.hip) ----
 hipError_t launch_conv99_exact(const uint8_t *src, long sstride, float *dst, long dstride,

@@ -1,4 +1,5 @@
-// srcnn_launch.cpp -- run_strip(): the ONE launch path of the MFMA strip kernels (fused, layers 1-2, layer 3; float32 and
+// srcnn_launch.cpp -- run_strip(), six steps from the geometry of srcnn_plan.cpp's strip_geometry() on: the ONE launch path
+// of the MFMA strip kernels (fused, layers 1-2, layer 3; float32 and
 // split-f16), their seam launches and the SRCNN_MODE_REFBYTES fix-up behind them; and the device-pointer entry points of
 // include/srcnn_amd.h that are thin argument checks over it.
 #include "srcnn_ctx.h"
@@ -75,233 +76,147 @@ static bool fold_is_safe(const StripParams &a, const StripParams &b)
 // S1 is in true units
 static float r16_kl(const srcnn_ctx *c, float strip_kl) { return c->mode == SRCNN_MODE_REFBYTES16 ? strip_kl * 1024.f : strip_kl; }
 
-// Common launch of the three strip modes on device memory.
-// fix_frame / fix_frames (SRCNN_MODE_REFBYTES only): this single-frame launch is frame `fix_frame` of a batch of `fix_frames`
-// whose flagged pixels ONE fix-up finishes, queued behind the batch's last launch (fix_frames = 1: the launch's own fix-up).
-int run_strip(srcnn_ctx *c, int mode, StripParams p, int n_frames, int fix_frame, int fix_frames, bool may_defer)
+// What run_strip() settles before it launches, step by step: the geometry, the seam scratch, the REFBYTES fix-up.
+struct StripLaunch {
+    StripGeometry g;                                // step 1 (strip_geometry(), srcnn_plan.cpp)
+    bool defer = false;                             // seam deferral: this launch's seam work stays pending
+    bool fix = false;                               // SRCNN_MODE_REFBYTES: flags, and a fix-up behind the batch's last frame
+    srcnn_ctx::SeamScratch *fsc = nullptr;          // ... its flag plane, work lists and counters
+    size_t fix_scat_cap = 0, fix_flag_pitch = 0;
+    float fix_delta = 0.f;
+};
+
+// Step 1, the geometry: decided by strip_geometry() -- the value srcnn_query_plan() reports from -- and written into the
+// kernel's parameters, with the context's tables every launch form reads.
+static int strip_geometry_params(srcnn_ctx *c, int mode, StripParams &p, int n_frames, StripLaunch &L)
 {
-    const int halo = (mode == MODE_L12) ? 0 : 2;
-    // Undocumented experiment knobs (never set in production).  Only bits that leave every output byte as it is are honoured:
-    // 2 / 16 = the stamped builds of the split-f16 / float32 production kernel (tools/diag_split16.py, diag_light.py), 8 = no XCD remap,
-    // 128 = small batches on the regular grid.  A stray SRCNN_DEBUG_TUNE cannot change a pixel (tests/test_gpu_hardening.py).
-    static const char *env_tune = SRCNN_DEBUG_ENV("SRCNN_DEBUG_TUNE");
-    static const char *env_pad = SRCNN_DEBUG_ENV("SRCNN_DEBUG_LDS_PAD");
-    constexpr int kTuneHarmless = 2 | 8 | 16 | 128;
-    p.tune = (env_tune ? std::atoi(env_tune) : 0) & kTuneHarmless;
-    const size_t pad = env_pad ? (size_t)std::atol(env_pad) : 0;
-    const bool split16 = mode == MODE_FUSED && (c->mode == SRCNN_MODE_SPLIT16 || c->mode == SRCNN_MODE_REFBYTES16);
-    const int wgs_per_cu = split16_wgs_per_cu(split16, p.tune);
-    Plan pl = make_plan(c, p.width, p.row_end - p.row_begin, n_frames, halo, wgs_per_cu);
-    static const char *env_segs = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEGS");     // experiment knob
-    if (env_segs && std::atoi(env_segs) > 0) {
-        const int rows = p.row_end - p.row_begin, ns = std::min(rows, std::atoi(env_segs));
-        pl.seg_rows = (rows + ns - 1) / ns;
-        pl.n_segs = (rows + pl.seg_rows - 1) / pl.seg_rows;
-    }
-    p.seg_rows = pl.seg_rows;
-    p.n_strips = pl.n_strips;
-    p.n_segs = pl.n_segs;
+    StripGeometry &g = L.g;
+    if (int rc = strip_geometry(c, mode, p.width, p.height, p.row_begin, p.row_end, n_frames, &g)) return rc;
+    p.tune = g.tune;
+    p.seg_rows = g.grid.seg_rows;
+    p.n_strips = g.grid.n_strips;
+    p.n_segs = g.grid.n_segs;
+    p.strips_total = g.strips_total;
     p.items = nullptr;
     p.seam = nullptr;
     p.cseam = nullptr;
-    p.strips_total = pl.n_strips;
-    int grid_items = 0;
-    bool defer = false;                  // seam deferral: leave this launch's seam work pending (see below)
-    const srcnn_ctx::ItemTable *table = nullptr;
-    // Convolution55 alone (MODE_L3) reads 128 B per pixel and is bound by HBM: strips of exactly FW = 128 columns
-    // (column seams instead of 2 halo columns each side), so that the four waves of a workgroup read four whole
-    // 128-byte lines per plane and row -- with 124-column strips every strip start falls inside a line and a fifth
-    // line is fetched: 1.32 x the algorithmic bytes by FETCH_SIZE (profiles/r02) -- and four workgroups per CU
-    // (<= 128 VGPRs, 18 KB of LDS) to keep 64 KB of loads in flight per CU.  SRCNN_DEBUG_L3=0: the round-1 launch.
-    static const char *env_l3 = SRCNN_DEBUG_ENV("SRCNN_DEBUG_L3");
-    const int ns_l3 = (p.width + FW - 1) / FW;
-    const bool l3_aligned = mode == MODE_L3 && !(env_l3 && std::atoi(env_l3) == 0) &&
-                            (p.width - (ns_l3 - 1) * FW >= 4 || ns_l3 == 1);
-    if (l3_aligned) {
-        pl = make_plan(c, p.width, p.row_end - p.row_begin, n_frames, halo, 4, 0);
-        p.seg_rows = pl.seg_rows;
-        p.n_strips = pl.n_strips;
-        p.n_segs = pl.n_segs;
-        p.strips_total = pl.n_strips;
-        srcnn_ctx::SeamScratch *sc = nullptr;
-        int rc;
-        if ((rc = seam_scratch_for_stream(c, &sc))) return rc;
-        const size_t n = (size_t)n_frames * p.strips_total * (p.row_end - p.row_begin) * CSEAM_FLOATS * sizeof(float);
-        if ((rc = reserve(c, sc->cbuf, n))) return rc;
-        p.cseam = static_cast<float *>(sc->cbuf.p);
-    }
-    // One plane that fits the GPU in a single round: size the work items by the speed of the wave
-    // slot they will land in and use every slot (build_items).
-    const bool fused32 = mode == MODE_FUSED && !split16;
-    // A small batch repeats the plane's item plan frame after frame in one launch (no halo rows, and the next frame's
-    // blocks fill the CUs the last items of a frame leave idle): 8 x 3840x2160 0.857 against 0.839 on the regular
-    // grid; from kItemBatchMax frames on the regular grid's tall segments are as good (64 frames: 0.863 vs 0.865).
-    // (srcnn_forward_y_dev hands over at most kItemBatchChunk frames of such a batch per call: frames_per_launch())
-    if (mode != MODE_L12 && (n_frames == 1 || (fused32 && n_frames < kItemBatchMax && !(p.tune & 128))) && !l3_aligned) {   // tune 128: regular grid (A/B)
-        // float32 fused kernel only: seams instead of halo rows between the items of a strip, and column seams
-        // instead of halo columns between strips (srcnn_kernels.h).  SRCNN_DEBUG_SEAMS: 0 = neither, 1 = rows only.
-        static const char *env_seams = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEAMS");
-        const int seam_knob = env_seams ? std::atoi(env_seams) : 3;
-        const bool want_seams = mode == MODE_FUSED && !split16 && (seam_knob & 1);
-        int rc;
-        // a plane too small for two items per CU of useful height: one (taller) item per CU still beats the regular grid
-        // with its halo rows
-        auto items_for = [&](int n_strips_, bool seams_) -> int {
-            int rc2 = build_items(c, n_strips_, p.row_begin, p.row_end, p.height, wgs_per_cu, seams_, &table);
-            if (!rc2 && table->count == 0 && wgs_per_cu == 2 && seams_)
-                rc2 = build_items(c, n_strips_, p.row_begin, p.row_end, p.height, 1, seams_, &table);
-            return rc2;
-        };
-        bool col_seams = false;
-        if (want_seams && (seam_knob & 2) && cseam_pays(p.width)) {
-            // strips of FW output columns; the last strip must hold the 4 columns its left neighbour's pixels need
-            const int ns_cs = (p.width + FW - 1) / FW;
-            if ((rc = items_for(ns_cs, true))) return rc;
-            if (table->count > 0) {
-                p.strips_total = ns_cs;
-                col_seams = true;
-            } else {
-                table = nullptr;
-            }
-        }
-        if (!table && (rc = items_for(pl.n_strips, want_seams))) return rc;
-        grid_items = table->count;
-        if (grid_items > 0) {
-            p.items = static_cast<const int *>(table->dev.p);
-            if (table->n_seams > 0 || col_seams) {
-                srcnn_ctx::SeamScratch *sc = nullptr;
-                for (auto &e : c->seam_scratch)
-                    if (e.used && e.stream == c->stream) sc = &e;
-                for (auto &e : c->seam_scratch)
-                    if (!sc && !e.used) sc = &e;
-                if (!sc) {                  // more streams than slots: wait for everything, start over with slot 0
-                    HIP_TRY(c, hipDeviceSynchronize());
-                    for (auto &e : c->seam_scratch) e.used = false;
-                    sc = &c->seam_scratch[0];
-                }
-                sc->used = true;
-                sc->stream = c->stream;
-                // Seam deferral: this launch's seam blocks will ride behind the NEXT launch's work items, which writes its own
-                // exports meanwhile -- the two scratch sets of the stream are used in turn.
-                defer = may_defer && c->defer_seams && c->defer_block == 0 && !c->safe_hazards && fused32 && n_frames == 1 && !p.pre && !(p.tune & 16) &&
-                        table->n_seams > 0 && (col_seams ? table->separated : true) &&
-                        !(c->mode == SRCNN_MODE_REFBYTES || c->mode == SRCNN_MODE_REFBYTES16);
-                if (defer) sc->flip ^= 1;
-                DevBuf &rbuf = defer && sc->flip ? sc->buf2 : sc->buf, &cbuf = defer && sc->flip ? sc->cbuf2 : sc->cbuf;
-                if (table->n_seams > 0) {
-                    if ((rc = reserve(c, rbuf, (size_t)n_frames * table->n_seams * SEAM_FLOATS * NTHREADS * sizeof(float)))) return rc;
-                    p.seam = static_cast<float *>(rbuf.p);
-                }
-                if (col_seams) {
-                    const size_t n = (size_t)n_frames * p.strips_total * (p.row_end - p.row_begin) * CSEAM_FLOATS * sizeof(float);
-                    if ((rc = reserve(c, cbuf, n))) return rc;
-                    p.cseam = static_cast<float *>(cbuf.p);
-                }
-            }
-            p.n_strips = 1;            // grid = n_strips * n_segs * n_frames blocks
-            p.n_segs = grid_items;
-            p.items_per_frame = grid_items;
-            p.seams_per_frame = std::max(1, table->n_seams);
-        }
-    }
-    // Batches (regular grid): column seams only -- the planner already makes the segments tall, and a row seam
-    // costs 74 KB of scratch.
-    if (fused32 && n_frames > 1 && grid_items == 0) {
-        static const char *env_seams = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEAMS");
-        const int ns_cs = (p.width + FW - 1) / FW;
-        (void)ns_cs;
-        if ((!env_seams || (std::atoi(env_seams) & 2)) && cseam_pays(p.width)) {
-            pl = make_plan(c, p.width, p.row_end - p.row_begin, n_frames, halo, wgs_per_cu, 0);
-            p.seg_rows = pl.seg_rows;
-            p.n_strips = pl.n_strips;
-            p.n_segs = pl.n_segs;
-            p.strips_total = pl.n_strips;
-            srcnn_ctx::SeamScratch *sc = nullptr;
-            for (auto &e : c->seam_scratch)
-                if (e.used && e.stream == c->stream) sc = &e;
-            for (auto &e : c->seam_scratch)
-                if (!sc && !e.used) sc = &e;
-            if (!sc) {
-                HIP_TRY(c, hipDeviceSynchronize());
-                for (auto &e : c->seam_scratch) e.used = false;
-                sc = &c->seam_scratch[0];
-            }
-            sc->used = true;
-            sc->stream = c->stream;
-            const size_t n = (size_t)n_frames * p.strips_total * (p.row_end - p.row_begin) * CSEAM_FLOATS * sizeof(float);
-            int rc;
-            if ((rc = reserve(c, sc->cbuf, n))) return rc;
-            p.cseam = static_cast<float *>(sc->cbuf.p);
-        }
-    }
-    // SRCNN_MODE_REFBYTES: the fused float32 kernel also writes a flag byte per pixel; fix_collect / fix_apply then recompute
-    // the flagged pixels in the reference's arithmetic (srcnn_exact.hip).  One frame per strip launch; the fix-up of up to
-    // FIX_BATCH_FRAMES consecutive frames of a batch is ONE pair of launches behind the last of them (srcnn_forward_y_dev): its
-    // items are drawn from one list, so the draw's tail -- 3.3 rounds of items on a single 3840x2160 plane leave 18 % of the wave
-    // slots empty -- is paid once per batch.
-    const bool fix = mode == MODE_FUSED && (c->mode == SRCNN_MODE_REFBYTES || c->mode == SRCNN_MODE_REFBYTES16) && !p.pre;
-    srcnn_ctx::SeamScratch *fsc = nullptr;
-    size_t fix_scat_cap = 0, fix_dense_cap = 0, fix_flag_pitch = 0;
-    float fix_delta_used = 0.f;
-    if (fix) {
-        if (n_frames != 1 || fix_frame < 0 || fix_frame >= fix_frames || fix_frames > FIX_BATCH_FRAMES)
-            return fail(c, SRCNN_ERR_STATE, "REFBYTES strip launches hold one frame");
-        int rc;
-        if ((rc = seam_scratch_for_stream(c, &fsc))) return rc;
-        const int rows = p.row_end - p.row_begin;
-        fix_scat_cap = fixup_list_entries(p.width, rows, fix_frames, &fix_dense_cap);
-        fix_flag_pitch = (size_t)rows * (size_t)p.dst_stride;
-        // (sized for the whole batch at its first frame: no buffer moves while earlier frames' flags wait for the fix-up)
-        if ((rc = reserve(c, fsc->flag, fix_flag_pitch * (size_t)fix_frames))) return rc;
-        if ((rc = reserve(c, fsc->fix_lists, (fix_scat_cap + fix_dense_cap) * sizeof(unsigned)))) return rc;
-        if ((rc = reserve(c, fsc->fix_counters, FIX_COUNTERS * sizeof(unsigned)))) return rc;
-        if (!c->fix_totals.p) {
-            if ((rc = reserve(c, c->fix_totals, FIX_TOTALS * sizeof(unsigned long long)))) return rc;
-            HIP_TRY(c, hipMemsetAsync(c->fix_totals.p, 0, FIX_TOTALS * sizeof(unsigned long long), c->stream));
-        }
-        // flag[o] for the same element offsets o as dst: o >= (row_begin - dst_row0) * dst_stride
-        p.flag = static_cast<uint8_t *>(fsc->flag.p) + (size_t)fix_frame * fix_flag_pitch - (long)(p.row_begin - p.dst_row0) * p.dst_stride;
-        // (the split-f16 kernel's noise is a little wider than the float32 kernel's -- soak: 4.3e-4 against 3.7e-4 -- and has no
-        // CPU model to take statistics from: 8 * E0 instead of 6 * E0, and the same monitor)
-        fix_delta_used = c->mode == SRCNN_MODE_REFBYTES16 ? c->fix_delta * (8.f / 6.f) : c->fix_delta;
-        p.fix_delta = fix_delta_used;
-        p.fix_scale = 253.f / (2.f * fix_delta_used);
-        // the per-pixel threshold min(delta, kl * S1 + abs) of both strip kernels (srcnn_kernels.h, l3_row_is_scale());
-        // srcnn_set_fixup_local(ctx, 0): the one global threshold of rounds 3-5
-        const bool r16 = c->mode == SRCNN_MODE_REFBYTES16;
-        const bool local = (r16 ? c->fix_local16 : c->fix_local) > 0.f;
-        // (the split-f16 kernel's plane 5 is x 2^10 like its tap partials: the factor carries the 2^-10)
-        p.fix_kl = local ? (r16 ? c->fix_local16 * std::ldexp(1.f, -10) : c->fix_local) * c->fix_margin * std::ldexp(1.f, -24) : 0.f;
-        p.fix_abs = local ? kFixAbsLocal : fix_delta_used;
-        p.fix_counters = static_cast<unsigned *>(fsc->fix_counters.p);
+    if (g.items > 0) {
+        p.items = static_cast<const int *>(g.table->dev.p);
+        p.n_strips = 1;            // grid = n_strips * n_segs * n_frames blocks
+        p.n_segs = g.items;
+        p.items_per_frame = g.items;
+        p.seams_per_frame = std::max(1, g.table->n_seams);
     }
     p.wfrag = static_cast<const float *>(c->wfrag.p);
     p.wfrag16 = static_cast<const uint32_t *>(c->wfrag16.p);
     p.sink = static_cast<float *>(c->sink.p);
     p.b3 = c->b3;
-    if (split16) {
+#ifdef SRCNN_TUNING_BUILD
+    geometry_report(g, mode, n_frames, c->last_launch);      // srcnn_debug_last_launch_plan
+    c->last_launch[6] = n_frames;
+#endif
+    return SRCNN_OK;
+}
+
+// Step 2, the row-seam and column-seam scratch of the stream, and whether the seam work is deferred.
+static int strip_scratch(srcnn_ctx *c, StripParams &p, int n_frames, bool may_defer, StripLaunch &L)
+{
+    const StripGeometry &g = L.g;
+    const bool row_seams = g.items > 0 && g.table->n_seams > 0;
+    if (!row_seams && !g.col_seams) return SRCNN_OK;
+    srcnn_ctx::SeamScratch *sc = nullptr;
+    int rc;
+    if ((rc = seam_scratch_for_stream(c, &sc))) return rc;
+    // Seam deferral: this launch's seam blocks will ride behind the NEXT launch's work items, which writes its own
+    // exports meanwhile -- the two scratch sets of the stream are used in turn.
+    L.defer = may_defer && c->defer_seams && c->defer_block == 0 && !c->safe_hazards && g.fused32 && n_frames == 1 && !p.pre && !(p.tune & 16) &&
+              row_seams && (g.col_seams ? g.table->separated : true) &&
+              !(c->mode == SRCNN_MODE_REFBYTES || c->mode == SRCNN_MODE_REFBYTES16);
+    if (L.defer) sc->flip ^= 1;
+    DevBuf &rbuf = L.defer && sc->flip ? sc->buf2 : sc->buf, &cbuf = L.defer && sc->flip ? sc->cbuf2 : sc->cbuf;
+    if (row_seams) {
+        if ((rc = reserve(c, rbuf, (size_t)n_frames * g.table->n_seams * SEAM_FLOATS * NTHREADS * sizeof(float)))) return rc;
+        p.seam = static_cast<float *>(rbuf.p);
+    }
+    if (g.col_seams) {
+        const size_t n = (size_t)n_frames * p.strips_total * (p.row_end - p.row_begin) * CSEAM_FLOATS * sizeof(float);
+        if ((rc = reserve(c, cbuf, n))) return rc;
+        p.cseam = static_cast<float *>(cbuf.p);
+    }
+    return SRCNN_OK;
+}
+
+// Step 3, SRCNN_MODE_REFBYTES: the fused float32 kernel also writes a flag byte per pixel; fix_collect / fix_apply then recompute
+// the flagged pixels in the reference's arithmetic (srcnn_exact.hip).  One frame per strip launch; the fix-up of up to
+// FIX_BATCH_FRAMES consecutive frames of a batch is ONE pair of launches behind the last of them (srcnn_forward_y_dev): its
+// items are drawn from one list, so the draw's tail -- 3.3 rounds of items on a single 3840x2160 plane leave 18 % of the wave
+// slots empty -- is paid once per batch.
+static int strip_fix_params(srcnn_ctx *c, int mode, StripParams &p, int n_frames, int fix_frame, int fix_frames, StripLaunch &L)
+{
+    L.fix = mode == MODE_FUSED && (c->mode == SRCNN_MODE_REFBYTES || c->mode == SRCNN_MODE_REFBYTES16) && !p.pre;
+    if (!L.fix) return SRCNN_OK;
+    if (n_frames != 1 || fix_frame < 0 || fix_frame >= fix_frames || fix_frames > FIX_BATCH_FRAMES)
+        return fail(c, SRCNN_ERR_STATE, "REFBYTES strip launches hold one frame");
+    int rc;
+    if ((rc = seam_scratch_for_stream(c, &L.fsc))) return rc;
+    const int rows = p.row_end - p.row_begin;
+    size_t fix_dense_cap = 0;
+    L.fix_scat_cap = fixup_list_entries(p.width, rows, fix_frames, &fix_dense_cap);
+    L.fix_flag_pitch = (size_t)rows * (size_t)p.dst_stride;
+    // (sized for the whole batch at its first frame: no buffer moves while earlier frames' flags wait for the fix-up)
+    if ((rc = reserve(c, L.fsc->flag, L.fix_flag_pitch * (size_t)fix_frames))) return rc;
+    if ((rc = reserve(c, L.fsc->fix_lists, (L.fix_scat_cap + fix_dense_cap) * sizeof(unsigned)))) return rc;
+    if ((rc = reserve(c, L.fsc->fix_counters, FIX_COUNTERS * sizeof(unsigned)))) return rc;
+    if (!c->fix_totals.p) {
+        if ((rc = reserve(c, c->fix_totals, FIX_TOTALS * sizeof(unsigned long long)))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->fix_totals.p, 0, FIX_TOTALS * sizeof(unsigned long long), c->stream));
+    }
+    // flag[o] for the same element offsets o as dst: o >= (row_begin - dst_row0) * dst_stride
+    p.flag = static_cast<uint8_t *>(L.fsc->flag.p) + (size_t)fix_frame * L.fix_flag_pitch - (long)(p.row_begin - p.dst_row0) * p.dst_stride;
+    // (the split-f16 kernel's noise is a little wider than the float32 kernel's -- soak: 4.3e-4 against 3.7e-4 -- and has no
+    // CPU model to take statistics from: 8 * E0 instead of 6 * E0, and the same monitor)
+    L.fix_delta = c->mode == SRCNN_MODE_REFBYTES16 ? c->fix_delta * (8.f / 6.f) : c->fix_delta;
+    p.fix_delta = L.fix_delta;
+    p.fix_scale = 253.f / (2.f * L.fix_delta);
+    // the per-pixel threshold min(delta, kl * S1 + abs) of both strip kernels (srcnn_kernels.h, l3_row_is_scale());
+    // srcnn_set_fixup_local(ctx, 0): the one global threshold of rounds 3-5
+    const bool r16 = c->mode == SRCNN_MODE_REFBYTES16;
+    const bool local = (r16 ? c->fix_local16 : c->fix_local) > 0.f;
+    // (the split-f16 kernel's plane 5 is x 2^10 like its tap partials: the factor carries the 2^-10)
+    p.fix_kl = local ? (r16 ? c->fix_local16 * std::ldexp(1.f, -10) : c->fix_local) * c->fix_margin * std::ldexp(1.f, -24) : 0.f;
+    p.fix_abs = local ? kFixAbsLocal : L.fix_delta;
+    p.fix_counters = static_cast<unsigned *>(L.fsc->fix_counters.p);
+    return SRCNN_OK;
+}
+
+// Step 4, the strip launch: split-f16, the fold form that carries the pending seam blocks of the launch before, or plain.
+static int launch_strip_step(srcnn_ctx *c, int mode, const StripParams &p, int n_frames, const StripLaunch &L)
+{
+    if (L.g.split16) {
         if (!c->split16_ok)
             return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_SPLIT16: these weights exceed the f16 ranges of the mode "
                                             "(layer maps must stay below 8192 / 16384 for 8-bit input); use SRCNN_MODE_MFMA");
-        int rc;
-        if ((rc = flush_seams(c))) return rc;
-        HIP_TRY(c, launch_split16(p, n_frames, c->stream, pad));
-    }
-    else if (c->pending.valid && defer && c->pending.stream == c->stream && grid_items > 0 && fold_is_safe(c->pending.f.prev, p)) {
+        if (int rc = flush_seams(c)) return rc;
+        HIP_TRY(c, launch_split16(p, n_frames, c->stream));
+    } else if (c->pending.valid && L.defer && c->pending.stream == c->stream && L.g.items > 0 && fold_is_safe(c->pending.f.prev, p)) {
         // the previous launch's seam blocks ride behind this launch's work items (srcnn_strip_fold_kernel)
-        c->pending.f.first_block = grid_items;
+        c->pending.f.first_block = L.g.items;
         c->pending.valid = false;
-        HIP_TRY(c, launch_strip_fold(p, c->pending.f, c->stream, pad));
+        HIP_TRY(c, launch_strip_fold(p, c->pending.f, c->stream));
     } else {
-        int rc;
-        if ((rc = flush_seams(c))) return rc;
-        HIP_TRY(c, (c->safe_hazards ? launch_strip_safe : launch_strip)(mode, p, n_frames, c->stream, pad));
+        if (int rc = flush_seams(c)) return rc;
+        HIP_TRY(c, (c->safe_hazards ? launch_strip_safe : launch_strip)(mode, p, n_frames, c->stream));
     }
-    // Row seams and column seams in ONE launch when the plan keeps the seam windows of neighbouring strips apart
-    // (plan_items_balanced()): the blocks that finish a row seam then also finish the column-seam pixels of their four
-    // rows, the column-seam blocks skip those rows, and neither waits for the other.
-    static const char *env_merge = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEAM_MERGE");      // experiment knob: 0 = two launches
-    if (defer && !(env_merge && std::atoi(env_merge) == 0)) {
+    return SRCNN_OK;
+}
+
+// Step 5, the seam work: left pending (deferral), or row seams and column seams in ONE launch when the plan keeps the seam
+// windows of neighbouring strips apart (plan_items_balanced()) -- the blocks that finish a row seam then also finish the
+// column-seam pixels of their four rows, the column-seam blocks skip those rows, and neither waits for the other --, or two.
+static int launch_seam_step(srcnn_ctx *c, const StripParams &p, int n_frames, const StripLaunch &L)
+{
+    const srcnn_ctx::ItemTable *table = L.g.table;
+    if (L.defer) {
         FoldParams &f = c->pending.f;
         f.prev = p;
         f.seams = static_cast<const int *>(table->dev_seams.p);
@@ -311,58 +226,78 @@ int run_strip(srcnn_ctx *c, int mode, StripParams p, int n_frames, int fix_frame
         f.first_block = 0;
         c->pending.stream = c->stream;
         c->pending.valid = true;
-    } else if (p.seam && p.cseam && table->separated && !(env_merge && std::atoi(env_merge) == 0)) {
+    } else if (p.seam && p.cseam && table->separated) {
         HIP_TRY(c, launch_seams_merged(p, table->n_seams * n_frames, static_cast<const int *>(table->dev_seams.p),
                                        static_cast<const unsigned char *>(table->dev_winmap.p), n_frames, c->stream));
     } else {
         if (p.seam) HIP_TRY(c, launch_seams(p, table->n_seams * n_frames, static_cast<const int *>(table->dev_seams.p), c->stream));
         if (p.cseam) HIP_TRY(c, launch_cseams(p, n_frames, c->stream));
     }
-    if (fix && fix_frame == fix_frames - 1) {
-        FixParams f{};
-        f.n_frames = fix_frames;                         // frame 0 of the batch lies fix_frame frames before this launch's
-        f.src_frame_pitch = p.src_frame_pitch;
-        f.dst_frame_pitch = p.dst_frame_pitch;
-        f.flag_frame_pitch = (long)fix_flag_pitch;
-        f.src = p.src - (long)fix_frame * p.src_frame_pitch;
-        f.src_stride = p.src_stride;
-        f.src_row0 = p.src_row0;
-        f.src_top = p.src_top;
-        f.src_bot = p.src_bot;
-        f.halo_stride = p.halo_stride;
-        f.src_row1 = p.src_row1;
-        f.dst = p.dst - (long)fix_frame * p.dst_frame_pitch;
-        f.flag = p.flag - (long)fix_frame * (long)fix_flag_pitch;
-        f.dst_stride = p.dst_stride;
-        f.dst_row0 = p.dst_row0;
-        f.width = p.width;
-        f.height = p.height;
-        f.row_begin = p.row_begin;
-        f.row_end = p.row_end;
-        f.wraw = static_cast<const float *>(c->wraw.p);
-        f.counters = p.fix_counters;
-        f.totals = static_cast<unsigned long long *>(c->fix_totals.p);
-        f.scat = static_cast<unsigned *>(fsc->fix_lists.p);
-        f.dense = f.scat + fix_scat_cap;
-        f.delta = fix_delta_used;
-        f.code_step = 2.f * fix_delta_used / 253.f;
-        f.kl = r16_kl(c, p.fix_kl);          // the fix-up's monitor computes S1 in true units
-        f.abs_term = p.fix_abs;
-        // The monitor ACTS, on the device (srcnn_set_fixup_strict, on by default): fix_apply_kernel records the largest
-        // |v_mfma - v_reference| over the pixels it recomputes -- a random ~0.1-0.3 % sample of the launch -- relative to each
-        // pixel's own threshold, and above HALF of it, where the margin the mode rests on is gone for this content / model, fix_rerun_kernel redoes every frame of
-        // the fix-up batch in the reference's arithmetic (no threshold involved).  No host read: the stream is never stalled.
-        static const char *env_rerun = SRCNN_DEBUG_ENV("SRCNN_DEBUG_FORCE_RERUN");     // test knob: every launch is redone
-        f.rerun_above = (env_rerun && std::atoi(env_rerun)) ? -1.f : c->fix_strict ? 0.5f : INFINITY;
-        // fix_apply with both weight tables in LDS (3 workgroups per CU) on planes whose items fit ONE round of the draw: an item
-        // alone on a compute unit is bound by its scalar weight loads (L2 round trips the scalar cache cannot hold back), which five
-        // co-resident workgroups hide and a few hundred items do not -- 1920x1080: fix-up +64 -> +54 us, 1280x720 +52 -> +43; from
-        // ~2.4 MPix on the scalar-load form's higher occupancy wins (3840x2160: +124 against +141 us).  profiles/r06/fix_apply_ab.txt
-        static const char *env_lds = SRCNN_DEBUG_ENV("SRCNN_DEBUG_FIX_LDS");           // A/B knob: 0 / 1 = never / always
-        const bool lds_weights = env_lds ? std::atoi(env_lds) == 1
-                                         : (long)p.width * (p.row_end - p.row_begin) * fix_frames <= 2400000L;
-        HIP_TRY(c, launch_fixup(f, c->n_cu, c->fix_strict, lds_weights, c->stream));
-    }
+    return SRCNN_OK;
+}
+
+// Step 6, the fix-up of a REFBYTES batch, behind the launch of its last frame.
+static int launch_fixup_step(srcnn_ctx *c, const StripParams &p, int fix_frame, int fix_frames, const StripLaunch &L)
+{
+    FixParams f{};
+    f.n_frames = fix_frames;                         // frame 0 of the batch lies fix_frame frames before this launch's
+    f.src_frame_pitch = p.src_frame_pitch;
+    f.dst_frame_pitch = p.dst_frame_pitch;
+    f.flag_frame_pitch = (long)L.fix_flag_pitch;
+    f.src = p.src - (long)fix_frame * p.src_frame_pitch;
+    f.src_stride = p.src_stride;
+    f.src_row0 = p.src_row0;
+    f.src_top = p.src_top;
+    f.src_bot = p.src_bot;
+    f.halo_stride = p.halo_stride;
+    f.src_row1 = p.src_row1;
+    f.dst = p.dst - (long)fix_frame * p.dst_frame_pitch;
+    f.flag = p.flag - (long)fix_frame * (long)L.fix_flag_pitch;
+    f.dst_stride = p.dst_stride;
+    f.dst_row0 = p.dst_row0;
+    f.width = p.width;
+    f.height = p.height;
+    f.row_begin = p.row_begin;
+    f.row_end = p.row_end;
+    f.wraw = static_cast<const float *>(c->wraw.p);
+    f.counters = p.fix_counters;
+    f.totals = static_cast<unsigned long long *>(c->fix_totals.p);
+    f.scat = static_cast<unsigned *>(L.fsc->fix_lists.p);
+    f.dense = f.scat + L.fix_scat_cap;
+    f.delta = L.fix_delta;
+    f.code_step = 2.f * L.fix_delta / 253.f;
+    f.kl = r16_kl(c, p.fix_kl);          // the fix-up's monitor computes S1 in true units
+    f.abs_term = p.fix_abs;
+    // The monitor ACTS, on the device (srcnn_set_fixup_strict, on by default): fix_apply_kernel records the largest
+    // |v_mfma - v_reference| over the pixels it recomputes -- a random ~0.1-0.3 % sample of the launch -- relative to each
+    // pixel's own threshold, and above HALF of it, where the margin the mode rests on is gone for this content / model, fix_rerun_kernel redoes every frame of
+    // the fix-up batch in the reference's arithmetic (no threshold involved).  No host read: the stream is never stalled.
+    static const char *env_rerun = SRCNN_DEBUG_ENV("SRCNN_DEBUG_FORCE_RERUN");     // test knob: every launch is redone
+    f.rerun_above = (env_rerun && std::atoi(env_rerun)) ? -1.f : c->fix_strict ? 0.5f : INFINITY;
+    // fix_apply with both weight tables in LDS (3 workgroups per CU) on planes whose items fit ONE round of the draw: an item
+    // alone on a compute unit is bound by its scalar weight loads (L2 round trips the scalar cache cannot hold back), which five
+    // co-resident workgroups hide and a few hundred items do not -- 1920x1080: fix-up +64 -> +54 us, 1280x720 +52 -> +43; from
+    // ~2.4 MPix on the scalar-load form's higher occupancy wins (3840x2160: +124 against +141 us).  profiles/r06/fix_apply_ab.txt
+    static const char *env_lds = SRCNN_DEBUG_ENV("SRCNN_DEBUG_FIX_LDS");           // A/B knob: 0 / 1 = never / always
+    const bool lds_weights = env_lds ? std::atoi(env_lds) == 1
+                                     : (long)p.width * (p.row_end - p.row_begin) * fix_frames <= 2400000L;
+    HIP_TRY(c, launch_fixup(f, c->n_cu, c->fix_strict, lds_weights, c->stream));
+    return SRCNN_OK;
+}
+
+// Common launch of the three strip modes on device memory.
+// fix_frame / fix_frames (SRCNN_MODE_REFBYTES only): this single-frame launch is frame `fix_frame` of a batch of `fix_frames`
+// whose flagged pixels ONE fix-up finishes, queued behind the batch's last launch (fix_frames = 1: the launch's own fix-up).
+int run_strip(srcnn_ctx *c, int mode, StripParams p, int n_frames, int fix_frame, int fix_frames, bool may_defer)
+{
+    StripLaunch L;
+    int rc;
+    if ((rc = strip_geometry_params(c, mode, p, n_frames, L))) return rc;
+    if ((rc = strip_scratch(c, p, n_frames, may_defer, L))) return rc;
+    if ((rc = strip_fix_params(c, mode, p, n_frames, fix_frame, fix_frames, L))) return rc;
+    if ((rc = launch_strip_step(c, mode, p, n_frames, L))) return rc;
+    if ((rc = launch_seam_step(c, p, n_frames, L))) return rc;
+    if (L.fix && fix_frame == fix_frames - 1 && (rc = launch_fixup_step(c, p, fix_frame, fix_frames, L))) return rc;
     return SRCNN_OK;
 }
 
@@ -377,8 +312,6 @@ int srcnn_conv99x11_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, f
                         size_t plane_stride, size_t plane_pitch, int width, int height)
 {
     BIND(c);
-    int rc = SRCNN_OK;
-    (void)rc;
     if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_conv99x11_dev");
     if (!c->has_l12) return fail(c, SRCNN_ERR_STATE, "layers 1-2 not loaded (srcnn_set_weights / srcnn_conv99x11)");
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_planes, plane_stride, width, height) ||
@@ -407,8 +340,6 @@ int srcnn_conv55_dev(srcnn_ctx *c, const float *d_planes, size_t plane_stride, s
                      uint8_t *d_dst, size_t dst_stride, int width, int height, float *d_preclamp)
 {
     BIND(c);
-    int rc = SRCNN_OK;
-    (void)rc;
     if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_conv55_dev");
     if (!c->has_l3) return fail(c, SRCNN_ERR_STATE, "layer 3 not loaded (srcnn_set_weights / srcnn_conv55)");
     if (bad_plane(d_planes, plane_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) ||
@@ -439,15 +370,13 @@ int srcnn_forward_y_unfused_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_s
                                 int height, int n_frames, float *d_work)
 {
     BIND(c);
-    int rc = SRCNN_OK;
-    (void)rc;
+    int rc;
     if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_forward_y_unfused_dev");
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) || !d_work ||
         n_frames <= 0)
         return fail(c, SRCNN_ERR_INVALID, "forward_y_unfused_dev: bad arguments");
-    static const char *env_plpad = SRCNN_DEBUG_ENV("SRCNN_DEBUG_PLPAD");     // experiment: floats added to the plane pitch
-    const long pitch = (long)width * height + (env_plpad ? std::atol(env_plpad) : 0);
+    const long pitch = (long)width * height;
     if (bad_pitch((size_t)pitch)) return fail(c, SRCNN_ERR_INVALID, "forward_y_unfused_dev: plane too large");
     if (c->mode == SRCNN_MODE_EXACT) {
         HIP_TRY(c, launch_conv99x11_exact(d_src, (long)src_stride, (long)src_frame_pitch, d_work, width, pitch,
@@ -491,8 +420,7 @@ int srcnn_forward_y_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stride, s
                         int n_frames, float *d_preclamp)
 {
     BIND_KEEP(c);
-    int rc = SRCNN_OK;
-    (void)rc;
+    int rc;
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) ||
         n_frames <= 0)
@@ -569,8 +497,6 @@ int srcnn_forward_y_rows_dev(srcnn_ctx *c, const uint8_t *d_src, size_t src_stri
                              int row_begin, int row_end)
 {
     BIND_KEEP(c);
-    int rc = SRCNN_OK;
-    (void)rc;
     if (!luma_path_ok(c)) return refuse_spatial(c, "srcnn_forward_y_rows_dev");
     if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
     if (bad_plane(d_src, src_stride, width, height) || bad_plane(d_dst, dst_stride, width, height) ||

@@ -1048,11 +1048,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void srcnn_strip_fold_kernel(const Str
     fast::strip_body<MODE_FUSED, false, 0, false, HALO3>(p);
 }
 
-hipError_t launch_strip_fold(const StripParams &p, const FoldParams &f, hipStream_t stream, size_t lds_pad)
+hipError_t launch_strip_fold(const StripParams &p, const FoldParams &f, hipStream_t stream)
 {
     if (p.pre || p.flag || f.prev.pre || f.prev.flag || !p.items) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(f.first_block + f.n_seams + f.cblocks)), block(NTHREADS);
-    const size_t lds = strip_lds_bytes(MODE_FUSED) + lds_pad;
+    const size_t lds = strip_lds_bytes(MODE_FUSED);
     if (p.src_top || p.src_bot) hipLaunchKernelGGL((srcnn_strip_fold_kernel<true>), grid, block, lds, stream, p, f);
     else hipLaunchKernelGGL((srcnn_strip_fold_kernel<false>), grid, block, lds, stream, p, f);
     return hipGetLastError();
@@ -1104,12 +1104,12 @@ static size_t strip_lds_bytes_safe(int mode) { return sizeof(float) * ((mode == 
 #define strip_lds_bytes strip_lds_bytes_safe
 #endif
 
-hipError_t launch_strip(int mode, const StripParams &p, int n_frames, hipStream_t stream, size_t lds_pad)
+hipError_t launch_strip(int mode, const StripParams &p, int n_frames, hipStream_t stream)
 {
     // with explicit items, n_segs carries the number of items per strip-set: n_strips * n_segs = item count
     const dim3 grid((unsigned)((long)p.n_strips * p.n_segs * n_frames));
     const dim3 block(NTHREADS);
-    const size_t lds = strip_lds_bytes(mode) + lds_pad;
+    const size_t lds = strip_lds_bytes(mode);
     const bool pre = p.pre != nullptr;
     switch (mode) {
     case MODE_FUSED:

@@ -1,6 +1,7 @@
 // srcnn_plan.cpp -- launch geometry of the strip kernels: the regular strip x segment x frame grid (make_plan), the balanced
 // work items of a plane launched alone and their seams (plan_items*), the per-context cache of device item tables, seam
-// scratch per stream, frames per launch, and srcnn_query_plan.  Nothing here changes a pixel: any plan computes the same plane.
+// scratch per stream, frames per launch, the geometry decision of a launch (strip_geometry) and srcnn_query_plan, which reports
+// from it.  Nothing here changes a pixel: any plan computes the same plane.
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
@@ -51,35 +52,28 @@ Plan make_plan(const srcnn_ctx *c, int width, int rows, int n_frames, int halo, 
 // Here: same item counts per strip (every strip is tiled exactly by ITS items, whatever their order), same pairing
 // to start from, then a local search moves single rows between two items of the same strip while that lowers the
 // estimated finish time of the slower of the two CUs involved -- until the slowest CU cannot be improved.
-// `cu_speed` (optional, one factor per CU) scales the estimate per CU.  It is not used in production: feeding back the
-// per-XCD finish times of earlier launches was tried and made things worse -- which XCD runs 1-2 % slow changes from
-// launch to launch (profiles/r02/ablation.txt).  Placement only affects speed: any plan computes the same plane.
+// Every CU is taken to run at the same speed: feeding back the per-XCD finish times of earlier launches was tried and made
+// things worse -- which XCD runs 1-2 % slow changes from launch to launch (profiles/r02/ablation.txt).  Placement only
+// affects speed: any plan computes the same plane.
 // (round 3: least-squares fit of this model to the finish times of 4,096 CUs over 16 stamped launches with different row splits,
 // profiles/r03/planner_fit.txt -- rms 6.7 us, of which launch-to-launch and per-XCD noise is most; round 2's constants were
 // 6.85 / 8.35 / 4.3 / 3.0 / 7.2 and left 247..254 rows per CU where these leave 251..254)
-double kPairFast = 6.40, kPairSlow = 8.40, kAlone = 3.76, kStartFast = 3.63, kStartSlow = 5.44;   // us
+constexpr double kPairFast = 6.40, kPairSlow = 8.40, kAlone = 3.76, kStartFast = 3.63, kStartSlow = 5.44;   // us
 
-double cu_finish_estimate(int fast_rows, int slow_rows, double speed)
+static double cu_finish_estimate(int fast_rows, int slow_rows)
 {
-    static const bool once = [] {
-        if (const char *e = SRCNN_DEBUG_ENV("SRCNN_DEBUG_RATES"))      // experiment knob: "fast,slow,alone[,start_fast,start_slow]"
-            std::sscanf(e, "%lf,%lf,%lf,%lf,%lf", &kPairFast, &kPairSlow, &kAlone, &kStartFast, &kStartSlow);
-        return true;
-    }();
-    (void)once;
     const double tf = kStartFast + fast_rows * kPairFast, ts = kStartSlow + slow_rows * kPairSlow;
     double t;
     if (tf <= ts) t = tf + std::max(0.0, slow_rows - (tf - kStartSlow) / kPairSlow) * kAlone;     // the slow one is left alone
     else t = ts + std::max(0.0, fast_rows - (ts - kStartFast) / kPairFast) * kAlone;
-    return t / speed;
+    return t;
 }
 
 // extra_top / extra_bot: feature rows the first / last item of every strip computes beyond its own output rows -- the two rows of
 // layer-3 radius when the launch covers rows [row_begin, row_end) of a taller plane (a rank's stripe: srcnn_forward_y_rows*_dev);
 // at the image's own top and bottom those rows replicate and cost nothing.  They weigh like rows of the item in the balance
 // (a middle rank's 540-row stripe of a 7680-wide plane otherwise finishes one row pair late on the 60 CUs that hold such items).
-ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int extra_top, int extra_bot,
-                             const double *cu_speed = nullptr)
+static ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int extra_top, int extra_bot)
 {
     const ItemPlan none;
     constexpr int kMinRows = 10;
@@ -150,11 +144,8 @@ ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end,
     std::stable_sort(fi.begin(), fi.end(), [&](int x, int y) { return items[(size_t)x].rows + items[(size_t)x].extra > items[(size_t)y].rows + items[(size_t)y].extra; });
     std::stable_sort(si.begin(), si.end(), [&](int x, int y) { return items[(size_t)x].rows + items[(size_t)x].extra < items[(size_t)y].rows + items[(size_t)y].extra; });
     for (int c = 0; c < n_cu; ++c) items[(size_t)fi[(size_t)c]].cu = items[(size_t)si[(size_t)c]].cu = c;
-    auto speed = [&](int c) { return cu_speed && cu_speed[c] > 0.5 && cu_speed[c] < 2.0 ? cu_speed[c] : 1.0; };
     auto work = [&](int i) { return items[(size_t)i].rows + items[(size_t)i].extra; };
-    auto finish = [&](int c) { return cu_finish_estimate(work(fi[(size_t)c]), work(si[(size_t)c]), speed(c)); };
-    // local search: take one row from an item of the slowest improvable CU, give it to the item of the same strip
-    // whose CU stays fastest; stop when no such move lowers the pair's maximum
+    auto finish = [&](int c) { return cu_finish_estimate(work(fi[(size_t)c]), work(si[(size_t)c])); };
     std::vector<std::vector<int>> in_strip((size_t)n_strips);
     for (int i = 0; i < (int)items.size(); ++i) in_strip[(size_t)items[(size_t)i].strip].push_back(i);
     std::vector<double> fin((size_t)n_cu);
@@ -168,29 +159,22 @@ ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end,
         for (size_t q = 0; q + 1 < in_strip[(size_t)s_].size(); ++q) b.push_back(y += items[(size_t)in_strip[(size_t)s_][q]].rows);
         return b;
     };
-    auto apart = [&](const std::vector<int> &x, const std::vector<int> &y) {
-        for (int u : x)
-            for (int v : y)
-                if (std::abs(u - v) < SEAM_ROWS) return false;
-        return true;
-    };
-    auto strip_apart = [&](int s_) {
-        const std::vector<int> b = bounds(s_);
-        return (s_ == 0 || apart(b, bounds(s_ - 1))) && (s_ + 1 >= n_strips || apart(b, bounds(s_ + 1)));
-    };
-    // local search: take one row from an item of the slowest improvable CU, give it to the item of the same strip
-    // whose CU stays fastest; stop when no such move lowers the pair's maximum.  `keep_apart`: only moves that leave the
-    // strip's seam windows clear of its neighbours'.
-    // the same test for ONE candidate move of the search, incrementally: a row from item `from` to item `to` of a strip
-    // shifts the boundaries between them by one row (cur[s] = the strip's boundaries, kept in step by move_apply())
-    std::vector<std::vector<int>> cur((size_t)n_strips);
-    std::vector<int> pos(items.size());
-    for (int s_ = 0; s_ < n_strips; ++s_)
-        for (size_t q = 0; q < in_strip[(size_t)s_].size(); ++q) pos[(size_t)in_strip[(size_t)s_][q]] = (int)q;
     auto clear_of = [&](const std::vector<int> &nbr, int b) {       // b keeps SEAM_ROWS rows away from every entry of nbr (sorted)
         const auto it = std::lower_bound(nbr.begin(), nbr.end(), b);
         return (it == nbr.end() || *it - b >= SEAM_ROWS) && (it == nbr.begin() || b - *(it - 1) >= SEAM_ROWS);
     };
+    auto strip_apart = [&](int s_) {
+        const std::vector<int> up = s_ > 0 ? bounds(s_ - 1) : std::vector<int>(), dn = s_ + 1 < n_strips ? bounds(s_ + 1) : std::vector<int>();
+        for (int b : bounds(s_))
+            if (!clear_of(up, b) || !clear_of(dn, b)) return false;
+        return true;
+    };
+    // the same test for ONE candidate move of the search: a row from item `from` to item `to` of a strip shifts the
+    // boundaries between them by one row (cur[s] = the strip's boundaries, kept in step by move_apply())
+    std::vector<std::vector<int>> cur((size_t)n_strips);
+    std::vector<int> pos(items.size());
+    for (int s_ = 0; s_ < n_strips; ++s_)
+        for (size_t q = 0; q < in_strip[(size_t)s_].size(); ++q) pos[(size_t)in_strip[(size_t)s_][q]] = (int)q;
     auto move_ok = [&](int from, int to) {
         const int s_ = items[(size_t)from].strip, pa = pos[(size_t)from], pb = pos[(size_t)to];
         const int lo = std::min(pa, pb), hi = std::max(pa, pb) - 1, delta = pa < pb ? -1 : 1;
@@ -206,6 +190,9 @@ ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end,
         const int lo = std::min(pa, pb), hi = std::max(pa, pb) - 1, delta = pa < pb ? -1 : 1;
         for (int q = lo; q <= hi; ++q) cur[(size_t)s_][(size_t)q] += delta;
     };
+    // local search: take one row from an item of the slowest improvable CU, give it to the item of the same strip
+    // whose CU stays fastest; stop when no such move lowers the pair's maximum.  `keep_apart`: only moves that leave the
+    // strip's seam windows clear of its neighbours'.
     auto search = [&](bool keep_apart) {
         for (int iter = 0; iter < 40 * n_cu; ++iter) {
             for (int c = 0; c < n_cu; ++c) by_time[(size_t)c] = c;
@@ -250,11 +237,8 @@ ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end,
     // slack and keeps the two CUs involved fastest), then balance under that constraint; if that fails, balance freely
     // (two seam launches then)
     const std::vector<Item> start = items;
-    static const char *env_sep = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEPARATE");     // experiment knob: 0 = never keep the seam windows apart
     // (worth trying only with neighbours to keep apart from and items tall enough to give up a few rows)
-    static const char *env_sep_rows = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEP_MINROWS"), *env_sep_saved = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEP_SAVED");   // experiment knobs
-    const int sep_min_rows = env_sep_rows ? std::atoi(env_sep_rows) : kSepMinRows;
-    bool separated = !(env_sep && std::atoi(env_sep) == 0) && n_strips >= 2 && hs / (kbase + 1) >= sep_min_rows;
+    bool separated = n_strips >= 2 && hs / (kbase + 1) >= kSepMinRows;
     constexpr int kSlack = 4;        // preferred extra distance: the search needs room to move boundaries
     for (int s_ = 1; s_ < n_strips && separated; ++s_) {
         const std::vector<int> left = bounds(s_ - 1);
@@ -303,18 +287,8 @@ ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end,
     items = start;
     for (int c = 0; c < n_cu; ++c) fin[(size_t)c] = finish(c);
     search(false);
-    const double launch_saved = env_sep_saved ? std::atof(env_sep_saved) : kLaunchSaved;
-    if (separated && apart_t <= slowest() + launch_saved) {
-        items = apart_items;
-        for (int c = 0; c < n_cu; ++c) fin[(size_t)c] = finish(c);
-    } else {
-        separated = false;
-    }
-    if (SRCNN_DEBUG_ENV("SRCNN_DEBUG_PLANLOG")) {
-        double mx = 0, mn = 1e30;
-        for (int c = 0; c < n_cu; ++c) { mx = std::max(mx, fin[(size_t)c]); mn = std::min(mn, fin[(size_t)c]); }
-        std::fprintf(stderr, "plan: separated=%d finish %.1f..%.1f\n", (int)separated, mn, mx);
-    }
+    if (separated && apart_t <= slowest() + kLaunchSaved) items = apart_items;
+    else separated = false;
     // positions: the items of a strip in creation order; seams between neighbours
     ItemPlan plan;
     plan.separated = separated;
@@ -343,12 +317,19 @@ ItemPlan plan_items_balanced(int n_cu, int n_strips, int row_begin, int row_end,
     return plan;
 }
 
-ItemPlan plan_items_raw(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int wgs_per_cu = 2,
-                        bool want_seams = false, int extra_top = 0, int extra_bot = 0)
+// A seam's WINDOW is the four output rows b-2 .. b+1 around its boundary row b, which the seam kernel finishes.  When no
+// window of a strip shares a row with a window of a NEIGHBOURING strip, the block that finishes a seam can also finish the
+// four column-seam pixels either side of its strip on those rows -- the neighbour's values there are complete exports of the
+// strip kernel -- and the row-seam and column-seam kernels no longer depend on each other: one launch instead of two.
+// The balanced planner builds such plans (ItemPlan::separated) where that costs no balance; other plans keep two launches.
+//
+// The plan of a launch: the balanced one where it applies (two workgroups per CU with seams); one item per CU, plans without
+// seams and the geometries the balanced planner refuses get k or k+1 items of two heights per strip, tall paired with short.
+ItemPlan plan_items(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int wgs_per_cu, bool want_seams, int extra_top,
+                    int extra_bot)
 {
     const ItemPlan none;
-    static const char *env_plan = SRCNN_DEBUG_ENV("SRCNN_DEBUG_PLAN");      // experiment knob: 1 = the round-1 planner
-    if (wgs_per_cu == 2 && want_seams && skew_pct > 0 && !(env_plan && std::atoi(env_plan) == 1)) {
+    if (wgs_per_cu == 2 && want_seams && skew_pct > 0) {
         const ItemPlan balanced = plan_items_balanced(n_cu, n_strips, row_begin, row_end, skew_pct, extra_top, extra_bot);
         if (balanced.count() > 0) return balanced;
     }
@@ -421,45 +402,43 @@ ItemPlan plan_items_raw(int n_cu, int n_strips, int row_begin, int row_end, int 
     return plan.count() == slots ? plan : none;
 }
 
-int skew_percent()
-{
-    static const char *env_skew = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SKEW");     // experiment knob; 0 = regular grid
-    return env_skew ? std::atoi(env_skew) : 10;
-}
-
-// A seam's WINDOW is the four output rows b-2 .. b+1 around its boundary row b, which the seam kernel finishes.  When no
-// window of a strip shares a row with a window of a NEIGHBOURING strip, the block that finishes a seam can also finish the
-// four column-seam pixels either side of its strip on those rows -- the neighbour's values there are complete exports of the
-// strip kernel -- and the row-seam and column-seam kernels no longer depend on each other: one launch instead of two.
-// The balanced planner builds such plans (ItemPlan::separated) where that costs no balance; other plans keep two launches.
-ItemPlan plan_items(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int wgs_per_cu, bool want_seams, int extra_top,
-                    int extra_bot)
-{
-    return plan_items_raw(n_cu, n_strips, row_begin, row_end, skew_pct, wgs_per_cu, want_seams, extra_top, extra_bot);
-}
-
 // Device copy of plan_items() for this geometry, from the context's table cache.  *n_items = 0: use the
 // regular grid.  A table is written once, before its first use, into memory no earlier launch reads
 // (a fresh slot, or an evicted one after its last reader has finished), and never modified afterwards.
+// `report` (srcnn_query_plan): the host side only -- a cached table as it is (its stamp untouched, so no later eviction
+// changes), or the plan's figures in *report; no upload, no wait, nothing evicted.
+static void summarise(srcnn_ctx::ItemTable &t, const int key[8], const ItemPlan &plan)
+{
+    std::memcpy(t.key, key, sizeof(t.key));
+    t.count = plan.count();
+    t.n_seams = plan.n_seams();
+    t.separated = plan.n_seams() > 0 && plan.separated;
+    t.max_rows = 0;
+    for (size_t i = 0; i < plan.items.size(); i += ITEM_INTS) t.max_rows = std::max(t.max_rows, plan.items[i + 2] - plan.items[i + 1]);
+}
+
 int build_items(srcnn_ctx *c, int n_strips, int row_begin, int row_end, int height, int wgs_per_cu, bool want_seams,
-                const srcnn_ctx::ItemTable **table)
+                const srcnn_ctx::ItemTable **table, srcnn_ctx::ItemTable *report)
 {
     *table = nullptr;
-    static const char *env_edge = SRCNN_DEBUG_ENV("SRCNN_DEBUG_PLAN_EDGES");     // experiment knob: 0 = round 4's plans (edge rows not weighed)
-    const bool edges = !(env_edge && std::atoi(env_edge) == 0);
     // a launch on rows of a taller plane computes two more feature rows at either open end (plan_items_balanced())
-    const int extra_top = edges && row_begin > 0 ? 2 : 0, extra_bot = edges && row_end < height ? 2 : 0;
-    const int key[8] = {n_strips, row_begin, row_end, skew_percent(), c->n_cu, wgs_per_cu, want_seams ? 1 : 0, extra_top + 4 * extra_bot};
+    const int extra_top = row_begin > 0 ? 2 : 0, extra_bot = row_end < height ? 2 : 0;
+    const int key[8] = {n_strips, row_begin, row_end, kSkewPercent, c->n_cu, wgs_per_cu, want_seams ? 1 : 0, extra_top + 4 * extra_bot};
     srcnn_ctx::ItemTable *victim = &c->item_tables[0];
     for (auto &t : c->item_tables) {
         if (t.stamp && std::memcmp(key, t.key, sizeof(key)) == 0) {
-            t.stamp = ++c->item_clock;
+            if (!report) t.stamp = ++c->item_clock;
             *table = &t;
             return SRCNN_OK;
         }
         if (t.stamp < victim->stamp) victim = &t;
     }
     const ItemPlan plan = plan_items(c->n_cu, n_strips, row_begin, row_end, key[3], wgs_per_cu, want_seams, extra_top, extra_bot);
+    if (report) {
+        summarise(*report, key, plan);
+        *table = report;
+        return SRCNN_OK;
+    }
     if (victim->stamp) {                                                // evicting: its readers must be done -- and queued
         if (int rc = flush_seams(c)) return rc;                         // (a deferred seam launch may refer to the victim's tables)
         HIP_TRY(c, hipDeviceSynchronize());
@@ -485,17 +464,14 @@ int build_items(srcnn_ctx *c, int n_strips, int row_begin, int row_end, int heig
             }
         }
     }
-    std::memcpy(victim->key, key, sizeof(key));
-    victim->count = plan.count();
-    victim->n_seams = plan.n_seams();
-    victim->separated = plan.n_seams() > 0 && plan.separated;
+    summarise(*victim, key, plan);
     victim->stamp = ++c->item_clock;
     *table = victim;
     return SRCNN_OK;
 }
 
 // The split-f16 kernel is software-pipelined inside a wave and runs one workgroup per CU (srcnn_split16.hip).
-int split16_wgs_per_cu(bool split16, int /*tune*/) { return split16 ? 1 : 2; }
+int split16_wgs_per_cu(bool split16) { return split16 ? 1 : 2; }
 
 // Seam scratch of the stream the context launches on (one buffer set per stream: srcnn_ctx::SeamScratch).
 int seam_scratch_for_stream(srcnn_ctx *c, srcnn_ctx::SeamScratch **out)
@@ -539,14 +515,100 @@ bool cseam_pays(int width)
 bool f32_mfma(const srcnn_ctx *c) { return c->mode == SRCNN_MODE_MFMA || c->mode == SRCNN_MODE_REFBYTES; }
 int frames_per_launch(const srcnn_ctx *c, int width, int height, int n_frames)
 {
-    static const char *env_loop = SRCNN_DEBUG_ENV("SRCNN_DEBUG_FRAMELOOP");      // experiment knob: 0 = never one launch per frame
     const size_t px = (size_t)width * height;
     if (c->mode == SRCNN_MODE_REFBYTES || c->mode == SRCNN_MODE_REFBYTES16) return 1;       // flag planes are compact per frame; the FIX-UP spans up to FIX_BATCH_FRAMES of them (run_strip)
     if (c->mode != SRCNN_MODE_MFMA || n_frames <= 1) return kGridBatchChunk;
-    if (!(env_loop && std::atoi(env_loop) == 0) &&
-        ((px >= ((size_t)4 << 20) && n_frames < kItemBatchMax) || (px >= ((size_t)3 << 19) && n_frames <= 8)))
-        return 1;
+    if ((px >= ((size_t)4 << 20) && n_frames < kItemBatchMax) || (px >= ((size_t)3 << 19) && n_frames <= 8)) return 1;
     return n_frames < kItemBatchMax ? kItemBatchChunk : kGridBatchChunk;
+}
+
+
+// The geometry of one strip launch: the regular strip x segment x frame grid, or the work items of the plane (build_items).
+int strip_geometry(srcnn_ctx *c, int mode, int width, int height, int row_begin, int row_end, int n_frames, StripGeometry *out,
+                   srcnn_ctx::ItemTable *report)
+{
+    StripGeometry &g = *out;
+    g = StripGeometry();
+    const int halo = (mode == MODE_L12) ? 0 : 2, rows = row_end - row_begin;
+    // Undocumented experiment knobs (never set in production).  Only bits that leave every output byte as it is are honoured:
+    // 2 / 16 = the stamped builds of the split-f16 / float32 production kernel (tools/diag_split16.py, diag_light.py), 8 = no XCD remap,
+    // 128 = small batches on the regular grid.  A stray SRCNN_DEBUG_TUNE cannot change a pixel (tests/test_gpu_hardening.py).
+    static const char *env_tune = SRCNN_DEBUG_ENV("SRCNN_DEBUG_TUNE");
+    constexpr int kTuneHarmless = 2 | 8 | 16 | 128;
+    g.tune = (env_tune ? std::atoi(env_tune) : 0) & kTuneHarmless;
+    // float32 fused kernel only: seams instead of halo rows between the items of a strip, and column seams
+    // instead of halo columns between strips (srcnn_kernels.h).  SRCNN_DEBUG_SEAMS: 0 = neither, 1 = rows only.
+    static const char *env_seams = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEAMS");
+    const int seam_knob = env_seams ? std::atoi(env_seams) : 3;
+    g.split16 = mode == MODE_FUSED && (c->mode == SRCNN_MODE_SPLIT16 || c->mode == SRCNN_MODE_REFBYTES16);
+    g.fused32 = mode == MODE_FUSED && !g.split16;
+    const int wgs_per_cu = split16_wgs_per_cu(g.split16);
+    g.grid = make_plan(c, width, rows, n_frames, halo, wgs_per_cu);
+    g.strips_total = g.grid.n_strips;
+    // Convolution55 alone (MODE_L3) reads 128 B per pixel and is bound by HBM: strips of exactly FW = 128 columns
+    // (column seams instead of 2 halo columns each side), so that the four waves of a workgroup read four whole
+    // 128-byte lines per plane and row -- with 124-column strips every strip start falls inside a line and a fifth
+    // line is fetched: 1.32 x the algorithmic bytes by FETCH_SIZE (profiles/r02) -- and four workgroups per CU
+    // (<= 128 VGPRs, 18 KB of LDS) to keep 64 KB of loads in flight per CU.  (A last strip too narrow for the 4 columns its
+    // left neighbour's pixels need: halo columns and two workgroups per CU, as the other modes.)
+    const int ns_fw = (width + FW - 1) / FW;
+    if (mode == MODE_L3 && (width - (ns_fw - 1) * FW >= 4 || ns_fw == 1)) {
+        g.grid = make_plan(c, width, rows, n_frames, halo, 4, 0);
+        g.strips_total = g.grid.n_strips;
+        g.col_seams = true;
+        return SRCNN_OK;
+    }
+    // One plane that fits the GPU in a single round: size the work items by the speed of the wave
+    // slot they will land in and use every slot (build_items).
+    // A small batch repeats the plane's item plan frame after frame in one launch (no halo rows, and the next frame's
+    // blocks fill the CUs the last items of a frame leave idle): 8 x 3840x2160 0.857 against 0.839 on the regular
+    // grid; from kItemBatchMax frames on the regular grid's tall segments are as good (64 frames: 0.863 vs 0.865).
+    // (srcnn_forward_y_dev hands over at most kItemBatchChunk frames of such a batch per call: frames_per_launch())
+    if (mode != MODE_L12 && (n_frames == 1 || (g.fused32 && n_frames < kItemBatchMax && !(g.tune & 128)))) {   // tune 128: regular grid (A/B)
+        const bool want_seams = g.fused32 && (seam_knob & 1);
+        int rc;
+        // a plane too small for two items per CU of useful height: one (taller) item per CU still beats the regular grid
+        // with its halo rows
+        auto items_for = [&](int n_strips_, bool seams_) -> int {
+            g.items_per_cu = wgs_per_cu;
+            int rc2 = build_items(c, n_strips_, row_begin, row_end, height, wgs_per_cu, seams_, &g.table, report);
+            if (!rc2 && g.table->count == 0 && wgs_per_cu == 2 && seams_) {
+                g.items_per_cu = 1;
+                rc2 = build_items(c, n_strips_, row_begin, row_end, height, 1, seams_, &g.table, report);
+            }
+            return rc2;
+        };
+        if (want_seams && (seam_knob & 2) && cseam_pays(width)) {
+            // strips of FW output columns; the last strip must hold the 4 columns its left neighbour's pixels need
+            if ((rc = items_for(ns_fw, true))) return rc;
+            if (g.table->count > 0) {
+                g.strips_total = ns_fw;
+                g.col_seams = true;
+            } else {
+                g.table = nullptr;
+            }
+        }
+        if (!g.table && (rc = items_for(g.grid.n_strips, want_seams))) return rc;
+        g.items = g.table->count;
+    }
+    // Batches (regular grid): column seams only -- the planner already makes the segments tall, and a row seam
+    // costs 74 KB of scratch.
+    if (g.fused32 && n_frames > 1 && g.items == 0 && (seam_knob & 2) && cseam_pays(width)) {
+        g.grid = make_plan(c, width, rows, n_frames, halo, wgs_per_cu, 0);
+        g.strips_total = g.grid.n_strips;
+        g.col_seams = true;
+    }
+    return SRCNN_OK;
+}
+
+void geometry_report(const StripGeometry &g, int mode, int frames, int out[6])
+{
+    out[0] = (g.items > 0 ? g.items : g.grid.n_strips * g.grid.n_segs) * frames;
+    out[1] = g.items > 0 ? g.table->max_rows : g.grid.seg_rows;
+    out[2] = g.strips_total;
+    out[3] = g.items > 0 ? (g.items + g.strips_total - 1) / g.strips_total : g.grid.n_segs;
+    out[4] = (int)(g.split16 ? split16_lds_bytes() : strip_lds_bytes(mode));
+    out[5] = NTHREADS;
 }
 
 }  // namespace host
@@ -557,55 +619,27 @@ extern "C" {
 int srcnn_query_plan(srcnn_ctx *c, int width, int height, int n_frames, int out[6])
 {
     if (!c || !out || width <= 0 || height <= 0 || n_frames <= 0) return SRCNN_ERR_INVALID;
-    static const char *env_seams = SRCNN_DEBUG_ENV("SRCNN_DEBUG_SEAMS");
-    const int wgs_per_cu = split16_wgs_per_cu(c->mode == SRCNN_MODE_SPLIT16 || c->mode == SRCNN_MODE_REFBYTES16, 0);
-    // mirrors srcnn_forward_y_dev() and run_strip(): `nl` frames go into one launch (1 = one single-plane launch per frame);
-    // the float32 fused kernel uses column seams (strips of FW columns) when the geometry allows
+    // `nl` frames go into one launch of the fused pass (1 = one single-plane launch per frame): the geometry run_strip() would
+    // decide for it, planned on the side; the workgroups are those of all launches of the batch
     const int nl = std::min(n_frames, frames_per_launch(c, width, height, n_frames));
-    const int seam_knob = env_seams ? std::atoi(env_seams) : 3;
-    const int ns_cs = (width + FW - 1) / FW;
-    bool col_seams = f32_mfma(c) && (seam_knob & 2) && (nl > 1 || (seam_knob & 1)) && cseam_pays(width);
-    int items_per_cu = wgs_per_cu;
-    const bool row_seams = f32_mfma(c) && (seam_knob & 1);
-    auto fits = [&](int n_strips_, int per_cu) { return !plan_items(c->n_cu, n_strips_, 0, height, skew_percent(), per_cu, row_seams).items.empty(); };
-    if (col_seams && nl == 1 && !fits(ns_cs, wgs_per_cu)) {
-        if (wgs_per_cu == 2 && fits(ns_cs, 1)) items_per_cu = 1;
-        else col_seams = false;
-    }
-    if (!col_seams && nl == 1 && row_seams && wgs_per_cu == 2) {
-        const int ns_halo = (width + FW - 5) / (FW - 4);
-        if (!fits(ns_halo, 2) && fits(ns_halo, 1)) items_per_cu = 1;
-    }
-    const Plan pl = make_plan(c, width, height, nl, 2, wgs_per_cu, col_seams ? 0 : -1);
-    out[0] = pl.n_strips * pl.n_segs * n_frames;      // over all launches of the batch
-    out[1] = pl.seg_rows;
-    out[2] = pl.n_strips;
-    out[3] = pl.n_segs;
-    if (nl == 1 || (f32_mfma(c) && n_frames < kItemBatchMax)) {   // explicit work items (plan_items), repeated per frame of a small batch
-        const std::vector<int> items =
-            plan_items(c->n_cu, pl.n_strips, 0, height, skew_percent(), items_per_cu,
-                       f32_mfma(c) && (seam_knob & 1)).items;
-        if (!items.empty()) {
-            out[0] = (int)items.size() / ITEM_INTS * n_frames;
-            out[1] = 0;
-            for (size_t i = 0; i < items.size(); i += ITEM_INTS) out[1] = std::max(out[1], items[i + 2] - items[i + 1]);
-            out[3] = ((int)items.size() / ITEM_INTS + pl.n_strips - 1) / pl.n_strips;
-        }
-    }
-    out[4] = (int)strip_lds_bytes(MODE_FUSED);
-    out[5] = NTHREADS;
+    StripGeometry g;
+    srcnn_ctx::ItemTable side;
+    if (int rc = strip_geometry(c, MODE_FUSED, width, height, 0, height, nl, &g, &side)) return rc;
+    geometry_report(g, MODE_FUSED, n_frames, out);
     return SRCNN_OK;
 }
 
 #ifdef SRCNN_TUNING_BUILD
 /* Undocumented test hook (not part of the ABI, needs no device): the work-item planner.  Fills `items`
  * (ITEM_INTS ints each) and `seams` (2 ints each) up to the given capacities; returns the item count, or
- * SRCNN_ERR_INVALID when a buffer is too small. */
+ * SRCNN_ERR_INVALID when a buffer is too small.  *n_seams: the seam count; a caller that adds 4096 to wgs_per_cu also gets
+ * 1 << 30 there when the plan keeps the seam windows of neighbouring strips apart (ItemPlan::separated). */
 int srcnn_debug_plan_items(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int wgs_per_cu,
                                       int want_seams, int *items, int max_items, int *seams, int max_seams,
                                       int *n_seams)
 {
-    // wgs_per_cu + 16 * extra_top + 256 * extra_bot: the planner's edge weights ride in the upper bits (old callers: 0)
+    // wgs_per_cu + 16 * extra_top + 256 * extra_bot [+ 4096]: the planner's edge weights ride in the upper bits (old callers: 0)
+    const bool report_separated = (wgs_per_cu & 4096) != 0;
     const int extra_top = (wgs_per_cu >> 4) & 15, extra_bot = (wgs_per_cu >> 8) & 15;
     wgs_per_cu &= 15;
     const ItemPlan plan = plan_items(n_cu, n_strips, row_begin, row_end, skew_pct, wgs_per_cu, want_seams != 0, extra_top, extra_bot);
@@ -613,8 +647,39 @@ int srcnn_debug_plan_items(int n_cu, int n_strips, int row_begin, int row_end, i
     // an empty vector's data() may be null, which memcpy must not be given even for 0 bytes (found by UBSan)
     if (!plan.items.empty()) std::memcpy(items, plan.items.data(), plan.items.size() * sizeof(int));
     if (!plan.seams.empty()) std::memcpy(seams, plan.seams.data(), plan.seams.size() * sizeof(int));
-    *n_seams = plan.n_seams();
+    *n_seams = plan.n_seams() | (report_separated && plan.separated && plan.n_seams() > 0 ? 1 << 30 : 0);
     return plan.count();
+}
+/* Undocumented test hook: the six srcnn_query_plan numbers of the geometry run_strip() last launched on the context (the
+ * workgroups of THAT launch), then the frames it held. */
+int srcnn_debug_last_launch_plan(srcnn_ctx *c, int out[7])
+{
+    if (!c || !out) return SRCNN_ERR_INVALID;
+    std::memcpy(out, c->last_launch, sizeof(c->last_launch));
+    return SRCNN_OK;
+}
+/* Undocumented test hook (needs no device): the geometry decision and its report for a context of n_cu compute units in
+ * ctx_mode (SRCNN_MODE_*), strip_mode 0 / 1 / 2 = fused / layers 1-2 / layer 3.  out[0..5]: the report; out[6..8]: items per
+ * frame, items per CU, column seams. */
+int srcnn_debug_strip_geometry(int n_cu, int ctx_mode, int strip_mode, int width, int height, int row_begin, int row_end, int n_frames,
+                               int out[9])
+{
+    if (n_cu <= 0 || width <= 0 || row_begin < 0 || row_begin >= row_end || row_end > height || n_frames <= 0 || !out ||
+        strip_mode < 0 || strip_mode > 2)
+        return SRCNN_ERR_INVALID;
+    std::unique_ptr<srcnn_ctx> c(new (std::nothrow) srcnn_ctx());
+    if (!c) return SRCNN_ERR_NOMEM;
+    c->n_cu = n_cu;
+    c->mode = ctx_mode;
+    const int mode = strip_mode == 0 ? MODE_FUSED : strip_mode == 1 ? MODE_L12 : MODE_L3;
+    StripGeometry g;
+    srcnn_ctx::ItemTable side;
+    if (int rc = strip_geometry(c.get(), mode, width, height, row_begin, row_end, n_frames, &g, &side)) return rc;
+    geometry_report(g, mode, n_frames, out);
+    out[6] = g.items;
+    out[7] = g.items_per_cu;
+    out[8] = g.col_seams ? 1 : 0;
+    return SRCNN_OK;
 }
 #endif
 

@@ -539,11 +539,11 @@ __global__ __launch_bounds__(NTHREADS, 1) void srcnn_split16_kernel(const StripP
 
 size_t split16_lds_bytes() { return (size_t)SP_RING_BYTES + sizeof(float) * 2 * 3 * 6 * FW; }
 
-hipError_t launch_split16(const StripParams &p, int n_frames, hipStream_t stream, size_t lds_pad)
+hipError_t launch_split16(const StripParams &p, int n_frames, hipStream_t stream)
 {
     const dim3 grid((unsigned)((long)p.n_strips * p.n_segs * n_frames));
     const dim3 block(NTHREADS);
-    const size_t lds = split16_lds_bytes() + lds_pad;
+    const size_t lds = split16_lds_bytes();
     if (p.flag) {
         if (p.pre) return hipErrorInvalidValue;     // (the API runs pre-clamp requests of that mode on the exact kernels)
         hipLaunchKernelGGL((srcnn_split16_kernel<false, false, true>), grid, block, lds, stream, p);

@@ -18,13 +18,13 @@ size_t split16_lds_bytes() { return 0; }
 hipError_t launch_seams(const StripParams &, int, const int *, hipStream_t) { return never(); }
 hipError_t launch_cseams(const StripParams &, int, hipStream_t) { return never(); }
 hipError_t launch_seams_merged(const StripParams &, int, const int *, const unsigned char *, int, hipStream_t) { return never(); }
-hipError_t launch_strip(int, const StripParams &, int, hipStream_t, size_t) { return never(); }
-hipError_t launch_strip_fold(const StripParams &, const FoldParams &, hipStream_t, size_t) { return never(); }
-hipError_t launch_strip_safe(int, const StripParams &, int, hipStream_t, size_t) { return never(); }
+hipError_t launch_strip(int, const StripParams &, int, hipStream_t) { return never(); }
+hipError_t launch_strip_fold(const StripParams &, const FoldParams &, hipStream_t) { return never(); }
+hipError_t launch_strip_safe(int, const StripParams &, int, hipStream_t) { return never(); }
 long interlock_probe_mismatches(int, hipStream_t) { return 0; }
 hipError_t launch_fixup(const FixParams &, int, bool, bool, hipStream_t) { return never(); }
 size_t fixup_list_entries(int, int, int, size_t *dense) { if (dense) *dense = 0; return 0; }
-hipError_t launch_split16(const StripParams &, int, hipStream_t, size_t) { return never(); }
+hipError_t launch_split16(const StripParams &, int, hipStream_t) { return never(); }
 hipError_t launch_conv99_exact(const uint8_t *, long, float *, long, int, int, const float *, float, hipStream_t) { return never(); }
 hipError_t launch_conv11_exact(const float *, long, long, float *, long, int, int, const float *, float, hipStream_t) { return never(); }
 hipError_t launch_conv99x11_exact(const uint8_t *, long, long, float *, long, long, long, int, int, int, const float *, hipStream_t) { return never(); }
@@ -45,6 +45,8 @@ hipError_t launch_split3(const uint8_t *, long, int, int, uint8_t *, long, hipSt
 extern "C" {
 int srcnn_debug_plan_items(int n_cu, int n_strips, int row_begin, int row_end, int skew_pct, int wgs_per_cu, int want_seams,
                            int *items, int max_items, int *seams, int max_seams, int *n_seams);
+int srcnn_debug_strip_geometry(int n_cu, int ctx_mode, int strip_mode, int width, int height, int row_begin, int row_end, int n_frames,
+                               int out[9]);
 int srcnn_debug_pack_fragments(const float *blob8129, float *frag, uint8_t *frag16, int *frag_floats, int *frag16_bytes);
 int srcnn_debug_cubic_table(int n_src, int n_dst, int *ofs, short *coef);
 int srcnn_debug_worker_pool(int n, int rounds);
@@ -99,6 +101,54 @@ int main(int argc, char **argv)
                                 }
                                 for (long cvr : covered) CHECK(cvr == rows);
                             }
+    // ---- the pinned plans (tests/golden/make_plan_items_pins.py: the same case list), exact-size buffers ----
+    {
+        struct PinCase { int n_strips, r0, r1, wpc, seams, extra; };
+        std::vector<PinCase> pinned;
+        for (int rows : {2160, 1080, 720, 576, 64})
+            for (int n_strips : {1, 5, 10, 11, 15, 16, 30, 31})
+                for (int wpc : {1, 2})
+                    for (int seams : {1, 0}) pinned.push_back({n_strips, 0, rows, wpc, seams, 0});
+        for (int r0 : {540, 0})
+            for (int n_strips : {60, 61})
+                for (int extra : {2, 0}) pinned.push_back({n_strips, r0, r0 + 540, 2, 1, extra});
+        pinned.push_back({257, 0, 2160, 2, 1, 0});
+        pinned.push_back({5, 0, 20, 2, 1, 0});
+        for (const PinCase &pc : pinned) {
+            int n_seams = -1;
+            const int cap = pc.wpc * 256;
+            std::vector<int> items((size_t)srcnn::ITEM_INTS * cap), sm((size_t)2 * cap);
+            const int n = srcnn_debug_plan_items(256, pc.n_strips, pc.r0, pc.r1, 10, pc.wpc + pc.extra * (16 + 256) + 4096, pc.seams, items.data(), cap,
+                                                 sm.data(), cap, &n_seams);
+            ++plans;
+            CHECK(n >= 0 && n <= cap && (n_seams & ((1 << 30) - 1)) <= cap);
+            if (n > 0) ++with_items;
+        }
+    }
+    // ---- the geometry decision run_strip() launches from and srcnn_query_plan reports from (strip_geometry, device-free):
+    //      the plane sizes of the pinned plans and the launch cases, every context mode, strip mode and batch class ----
+    {
+        long geometries = 0;
+        for (int n_cu : {64, 256, 304})
+            for (int ctx_mode : {0, 2, 3, 4})                                   // MFMA, SPLIT16, REFBYTES, REFBYTES16
+                for (int strip_mode : {0, 1, 2})
+                    for (int w : {1, 3, 124, 128, 130, 256, 576, 1280, 1920, 3840, 7680})
+                        for (int h : {1, 20, 64, 96, 576, 700, 720, 1080, 2160})
+                            for (int n_frames : {1, 2, 8, 31, 32, 64}) {
+                                if (n_frames > 2 && (long)w * h > 1920L * 1080) continue;
+                                for (int stripe = 0; stripe < (h >= 64 && n_frames == 1 ? 3 : 1); ++stripe) {
+                                    const int r0 = stripe == 0 ? 0 : stripe == 1 ? h / 4 : 0, r1 = stripe == 0 ? h : stripe == 1 ? h / 2 : h / 4;
+                                    int out[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+                                    CHECK(srcnn_debug_strip_geometry(n_cu, ctx_mode, strip_mode, w, h, r0, r1, n_frames, out) == 0);
+                                    ++geometries;
+                                    CHECK(out[0] > 0 && out[1] > 0 && out[1] <= r1 - r0 && out[2] > 0 && out[3] > 0 && out[5] == srcnn::NTHREADS);
+                                    CHECK(out[6] >= 0 && out[7] >= 0 && out[7] <= 2 && (out[8] == 0 || out[8] == 1));
+                                    CHECK(out[6] == 0 ? out[0] == out[2] * out[3] * n_frames : out[0] == out[6] * n_frames);
+                                }
+                            }
+        CHECK(srcnn_debug_strip_geometry(256, 0, 0, 64, 64, 10, 10, 1, nullptr) != 0);
+        std::printf("ok: %ld launch geometries\n", geometries);
+    }
     // ---- fragment packers: exact-size outputs, extreme but finite weights ----
     int nf = 0, nb = 0;
     srcnn_debug_pack_fragments(nullptr, nullptr, nullptr, &nf, &nb);

@@ -650,3 +650,34 @@ def test_launch_geometry_reported_by_query_plan(gpu_ctx):
     assert small["strips"] == 30 and small["workgroups"] == 8 * one["workgroups"]
     narrow = gpu_ctx.query_plan(130, 700, 1)        # last strip would hold 2 columns: halo columns instead
     assert narrow["strips"] == 2
+
+
+def test_query_plan_reports_what_was_launched():
+    """srcnn_query_plan and run_strip() take the launch geometry from one value (strip_geometry()).  For every case of
+    tests/golden/make_query_plan_pins.py -- six plane sizes in MODE_MFMA, MODE_REFBYTES and MODE_SPLIT16, 1920x1080 batches either
+    side of kItemBatchMax and of the per-frame launches, the two per-layer launches -- a child process bound to the tuning build
+    launches, reads the geometry of the last launch through srcnn_debug_last_launch_plan (six numbers, then the launch's
+    frames) and asks query_plan.  The launch is the one pinned from the library as it was before (query_plan_pins.json, taken
+    on 256 compute units); the report equals the launch (its workgroups are those of the whole batch); and the report equals
+    the pinned report except where the fixture lists a corrected one: the hand-kept mirror reported the float32 kernel's LDS
+    size in MODE_SPLIT16.  The per-layer launches have no report of their own: query_plan describes the fused pass."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    import torch
+    assert torch.cuda.get_device_properties(0).multi_processor_count == 256
+    golden = Path(__file__).resolve().parent / "golden"
+    r = subprocess.run([sys.executable, str(golden / "make_query_plan_pins.py"), "--print"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    want = json.loads((golden / "query_plan_pins.json").read_text())
+    assert got["n_cu"] == want["n_cu"] == 256 and len(got["cases"]) == len(want["cases"]) == 27
+    for g, w in zip(got["cases"], want["cases"]):
+        case = (w["call"], w["mode"], w["width"], w["height"], w["frames"])
+        assert case == (g["call"], g["mode"], g["width"], g["height"], g["frames"])
+        q, l = g["query_plan"], g["launch"]
+        assert l == w["launch"], (case, l, w["launch"])
+        assert q == w.get("corrected_query_plan", w["query_plan"]), (case, q, w)
+        if g["call"].startswith("forward_y"):
+            assert q[1:] == l[1:6] and q[0] * l[6] == l[0] * g["frames"], (case, q, l)

@@ -34,11 +34,34 @@ def plan(n_cu, n_strips, r0, r1, skew=10, per_cu=2, seams=True):
     items = (C.c_int * (ITEM_INTS * 4096))()
     seam = (C.c_int * (2 * 4096))()
     n_seams = C.c_int(0)
+    # per_cu is the hook's wgs_per_cu argument: workgroups per CU + 16 * extra_top + 256 * extra_bot (the edge rows weighed,
+    # test_open_ends_of_a_stripe_weigh_in_the_balance) + 4096 to get ItemPlan::separated in bit 30 of n_seams (only
+    # tests/golden/make_plan_items_pins.py asks for that; without it n_seams is the plain count)
     n = fn(n_cu, n_strips, r0, r1, skew, per_cu, int(seams), items, 4096, seam, 4096, C.byref(n_seams))
     assert n >= 0
     it = np.array(items[:ITEM_INTS * n], dtype=np.int64).reshape(n, ITEM_INTS)
     se = np.array(seam[:2 * n_seams.value], dtype=np.int64).reshape(n_seams.value, 2)
     return it, se
+
+
+def test_plans_are_the_pinned_ones():
+    """tests/golden/plan_items_pins.json (made by make_plan_items_pins.py before the experiment knobs left the planner): item
+    count, seam count, the separated flag -- bit 30 of the hook's n_seams output, for a caller that asks with wgs_per_cu +
+    4096 -- and a SHA-256 of the item and seam ints of every case; whole planes, a rank's stripes with and without their
+    edge rows weighed, and the two refusals."""
+    import importlib.util
+    import json
+    from pathlib import Path
+    golden = Path(__file__).resolve().parent / "golden"
+    spec = importlib.util.spec_from_file_location("make_plan_items_pins", golden / "make_plan_items_pins.py")
+    M = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(M)
+    want = json.loads((golden / "plan_items_pins.json").read_text())
+    assert want["n_cu"] == M.N_CU and want["skew_pct"] == M.SKEW and len(want["cases"]) == 170
+    got = M.pins(tuning_lib())
+    assert len(got) == len(want["cases"])
+    for g, w in zip(got, want["cases"]):
+        assert g == w, (g, w)
 
 
 GEOMETRIES = [(256, 5, 0, 360), (256, 4, 0, 400), (256, 2, 0, 75), (256, 30, 0, 2160), (256, 31, 0, 2160), (256, 15, 0, 1080), (256, 60, 0, 4320), (256, 62, 540, 1080),

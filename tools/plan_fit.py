@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Fit the work-item planner's model of a CU (cu_finish_estimate() in srcnn_cpp_amd/csrc/srcnn_plan.cpp) to the stamped production
-launch: tools/plan_fit_collect.sh writes, per CU, the rows of the first-dispatched workgroup and of the one that joined it and
-their exit times under several row splits.  Model: while both run, the first takes `fast` us per row and the second `slow`; the
-one left alone takes `alone`; each pays a fixed start.  Prints the least-squares rates (for SRCNN_DEBUG_RATES / the constants)
-and the residuals of the current constants.      usage: python tools/plan_fit.py gpurun_out/plan_fit.txt"""
+launch: the table holds, per CU, the rows of the first-dispatched workgroup and of the one that joined it and their exit times
+(the rows `DIAG_DUMP=file python tools/diag_light.py W H` appends; profiles/r03/planner_fit.txt was fitted to 16 such launches).
+Model: while both run, the first takes `fast` us per row and the second `slow`; the one left alone takes `alone`; each pays a
+fixed start.  Prints the least-squares rates (for the planner's constants) and the residuals of the current constants.
+usage: python tools/plan_fit.py table.txt"""
 import sys
 
 import numpy as np
