@@ -55,7 +55,9 @@ def test_resize_cubic_bit_exact(gpu_ctx, sw, sh, dw, dh):
 # (output widths that are multiples of four take the two fused launches around the conv path -- colour conversion inside the
 # resize kernels -- the others the three separate kernels: both forms are covered)
 @pytest.mark.parametrize("w,h,scale", [(40, 30, 2.0), (97, 61, 1.5), (33, 20, 3.0), (64, 48, 1.3), (320, 180, 2.0),
-                                       (200, 100, 2.4), (130, 70, 4.0)])
+                                       (200, 100, 2.4), (130, 70, 4.0),
+                                       # 1:1 and going down: the direct resize kernel, an output smaller than the input
+                                       (96, 64, 1.0), (96, 64, 0.75), (96, 64, 0.5), (96, 64, 0.3)])
 def test_whole_pipeline(gpu_ctx, weights_blob, w, h, scale):
     bgr = synth_bgr(w, h)
     assert S.scaled_size(w, h, scale) == oracle.scaled_size(w, h, scale)
@@ -103,6 +105,35 @@ def test_pipeline_device_entry_point(gpu_ctx, weights_blob):
     gpu_ctx.process_bgr_dev(d_in.data_ptr(), 3 * w, w, h, scale, d_out.data_ptr(), 3 * ow)
     gpu_ctx.synchronize()
     assert np.array_equal(d_out.cpu().numpy(), gpu_ctx.process_bgr(bgr, scale))
+
+
+def test_process_srcnn_from_a_cpp_host(tmp_path, weights_blob):
+    """srcnn::ProcessSRCNN (include/srcnn_amd.hpp), the buffer-level twin of the command-line tool's timed region, from a
+    plain C++ host (tests/helpers/process_srcnn_host.cpp: no HIP headers): the reference's example, then a 40x30 picture
+    at x2.0 from the same thread -- the thread-local Session again, at another geometry -- both bitwise the FMA-order
+    model; a null source and a scale that rounds a side to 0 return SRCNN_ERR_INVALID and leave `out` as it was."""
+    import subprocess
+    root = Path(__file__).resolve().parent.parent
+    exe = tmp_path / "process_srcnn_host"
+    subprocess.run(["g++", "-std=c++17", f"-I{root / 'include'}", str(root / "tests" / "helpers" / "process_srcnn_host.cpp"),
+                    f"-L{root / 'srcnn_cpp_amd'}", "-lsrcnn_amd", f"-Wl,-rpath,{root / 'srcnn_cpp_amd'}",
+                    "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)], check=True, timeout=600)
+    pictures = [(np.load(GOLD / "butterfly_bgr.npz")["src_bgr"], 1.5), (synth_bgr(40, 30), 2.0)]
+    jobs = []
+    for k, (bgr, scale) in enumerate(pictures):
+        bgr.tofile(tmp_path / f"in{k}.bgr")
+        jobs.append(f"{tmp_path / f'in{k}.bgr'}:{bgr.shape[1]}:{bgr.shape[0]}:{scale}")
+    jobs += ["NULL:40:30:2.0", f"{tmp_path / 'in1.bgr'}:3:3:0.2"]          # (int)(3 * 0.2) == 0
+    res = subprocess.run([str(exe), str(S._WEIGHTS_PATH), str(tmp_path / "out"), *jobs], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stdout + res.stderr
+    lines = res.stdout.splitlines()
+    for k, (bgr, scale) in enumerate(pictures):
+        ow, oh = oracle.scaled_size(bgr.shape[1], bgr.shape[0], scale)
+        assert lines[k] == f"job {k} rc=0 w={ow} h={oh} size={3 * ow * oh} untouched=0"
+        got = np.fromfile(tmp_path / f"out.{k}", np.uint8).reshape(oh, ow, 3)
+        assert np.array_equal(got, oracle.process_bgr(bgr, scale, weights_blob, y_path=oracle.gpuorder_forward_y))
+    assert lines[2:] == [f"job {k} rc={S.ERR_INVALID} w=12345 h=12345 size=5 untouched=1" for k in (2, 3)]
+    assert not (tmp_path / "out.2").exists() and not (tmp_path / "out.3").exists()
 
 
 def test_pipeline_error_paths(gpu_ctx):

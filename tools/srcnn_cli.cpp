@@ -125,10 +125,15 @@ bool load_weights(const Options &o, const char *argv0, std::vector<float> &blob)
     cand.push_back("srcnn_cpp_amd/data/srcnn915_weights.f32");
     // a 9-1-5, 9-3-5 or 9-5-5 blob (include/srcnn_amd.h, srcnn_set_model): 8,129 / 24,513 / 57,281 floats, or a colour one
     // (srcnn_set_model_color, channels in BGR order): 20,099 / 36,483 / 69,251 floats; a file of any other size named by
-    // --weights= is an error, not a reason to fall back on the shipped model
-    for (const auto &p : cand) {
-        FILE *f = std::fopen(p.c_str(), "rb");
-        if (!f) continue;
+    // --weights=, or one that cannot be opened, is an error, not a reason to fall back on the shipped model: the candidate that
+    // --weights= names (the first, where the option is given) ends the search whatever becomes of it
+    for (size_t i = 0; i < cand.size(); ++i) {
+        const bool named = i == 0 && !o.weights.empty();
+        FILE *f = std::fopen(cand[i].c_str(), "rb");
+        if (!f) {
+            if (named) return false;
+            continue;
+        }
         std::vector<float> buf(69251 + 1);
         const size_t n = std::fread(buf.data(), 4, buf.size(), f);
         std::fclose(f);
@@ -137,7 +142,7 @@ bool load_weights(const Options &o, const char *argv0, std::vector<float> &blob)
             blob.swap(buf);
             return true;
         }
-        if (p == o.weights) return false;
+        if (named) return false;
     }
     return false;
 }
