@@ -150,7 +150,18 @@ int srcnn_flush(srcnn_ctx *ctx);
 int srcnn_kernel_variant(const srcnn_ctx *ctx);
 /* Pin the form: 1 = the hazard-safe kernels whatever the probe said -- for a deployment that will not rest on a measured,
  * undocumented interlock: every wait state the ISA manual asks for is in the code the compiler emits, the bytes are the same, the
- * fused pass is ~3 % slower and seam deferral is not used; 0 = back to what the probe allows (the fast form only where it passed). */
+ * fused pass is ~3 % slower and seam deferral is not used; 0 = back to what the probe allows (the fast form only where it passed).
+ * The pin is the context's own (it survives srcnn_set_mode, srcnn_set_weights, srcnn_set_model, srcnn_set_padding,
+ * srcnn_set_seam_deferral and srcnn_set_stream, and touches no other context) and reaches the float32 MFMA strip kernels only:
+ * SRCNN_MODE_MFMA, SRCNN_MODE_REFBYTES, the per-layer calls, and layer 3 of the 1-channel replicate 9-3-5 / 9-5-5 byte models.
+ * SRCNN_MODE_SPLIT16 and SRCNN_MODE_REFBYTES16 launch the split-f16 kernel, which has ONE form: pinned or not they run the same
+ * code and return the same bytes, and pinning buys nothing there.  That kernel does not rest on the three dependencies the probe
+ * checks (its MFMAs are the compiler's builtins, so every operand an MFMA reads is padded for), but neither is it free of the
+ * question: its ReLU / split steps are inline asm that reads MFMA result registers directly, which the compiler's hazard
+ * recogniser does not look into.  The first such read of a row follows the MFMA that wrote the register by two further
+ * MFMAs and the row barrier (srcnn_split16.hip orders every step at least one MFMA behind its producer, for speed), so the
+ * distance is kept by the code's own instruction order, not by compiler-inserted wait states, and no check at srcnn_create
+ * covers it.  A deployment that will rest on documented wait states only uses SRCNN_MODE_MFMA / SRCNN_MODE_REFBYTES pinned. */
 int srcnn_set_kernel_variant(srcnn_ctx *ctx, int variant);
 
 /* ---- the reference call surface, host buffers ----------------------------- */

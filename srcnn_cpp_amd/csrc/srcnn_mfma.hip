@@ -71,7 +71,9 @@
 // the seam launchers -- and with the define -- the same strip kernels in namespace srcnn::safe behind launch_strip_safe().
 // srcnn_create() runs the row body's exact instruction sequences with and without wait states once per device
 // (srcnn_probe.hip) and the context launches the safe kernels if they ever disagree (srcnn_kernel_variant()).  Both forms
-// produce the same bytes (tests/test_gpu_hardening.py::test_safe_hazard_kernels_give_the_same_bytes).
+// produce the same bytes: tests/test_gpu_safe_variant.py runs every instantiation launch_strip_safe() can launch (but the stamped
+// DIAG = 2 one) against the CPU model of the kernels' summation order, bit for bit, as test_gpu_parity.py does for the fast form;
+// tests/test_gpu_hardening.py::test_safe_hazard_kernels_give_the_same_bytes compares the two forms on full-size planes.
 #ifndef SRCNN_SAFE_HAZARDS
 #define SRCNN_SAFE_HAZARDS 0
 #endif
