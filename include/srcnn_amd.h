@@ -313,6 +313,37 @@ int srcnn_set_model_color(srcnn_ctx *ctx, int f2,
                           const float *kernel3 /*[3][32][5][5]*/, const float *bias3 /*[3]*/);
 /* Channels of the loaded model: 3 after srcnn_set_model_color, else 1. */
 int srcnn_get_model_channels(const srcnn_ctx *ctx);
+
+/* Models of other widths (Dong et al., TPAMI 2016, section 4.3.1: the number of filters): a 9-f2-5 model of `channels` = 1 or 3
+ * channels with n1 filters in layer 1 and n2 in layer 2, 1 <= n1 <= 128, 1 <= n2 <= 64, f2 = 1, 3 or 5 (f1 = 9 and f3 = 5 as
+ * everywhere).  The tensors are PyTorch's convN.weight / convN.bias: kernel1 [n1][channels][9][9], bias1 [n1],
+ * kernel2 [n2][n1][f2][f2], bias2 [n2], kernel3 [channels][n2][5][5], bias3 [channels].  Any other value returns
+ * SRCNN_ERR_INVALID and the loaded model stays as it was.  Semantics as srcnn_set_model / srcnn_set_model_color.
+ *   - The widths are padded to n1p = 64 * ceil(n1 / 64) and n2p = 32 * ceil(n2 / 32): the library fills the channels beyond
+ *     n1 / n2 with zero weights and zero biases.  Such a channel is 0 after its ReLU and adds exact zeros to every sum
+ *     downstream, so the padding changes no result.
+ *   - A NARROW model (n1p = 64 and n2p = 32: 64 / 32 itself, the paper's small 32 / 16) is padded and handed to
+ *     srcnn_set_weights, srcnn_set_model or srcnn_set_model_color: the context then holds an ordinary model, and every mode and
+ *     entry point that runs such a model runs this one (the fused strip kernels for 9-1-5 included).
+ *   - A WIDE model (n1p = 128 or n2p = 64: the paper's 128 / 64) runs in SRCNN_MODE_MFMA only, under either padding, on the
+ *     banded path (summation order in srcnn_wide_kernels.hip: that of the 32-map kernels, continued), through the whole-image
+ *     entry points: srcnn_forward_y(_dev) with n_frames, pitches and d_preclamp, srcnn_forward_y_frames,
+ *     srcnn_forward_color(_dev), srcnn_process_bgr(_dev), srcnn_forward_f32(_dev), srcnn_process_f32(_dev),
+ *     srcnn_process_rgb_f32(_dev) and the four srcnn_*_image_dev calls.  Everything else -- every other mode,
+ *     SRCNN_MODE_BANDED16 included, row stripes and halo buffers, the striped, lanes and multi calls, the unfused and per-filter
+ *     _dev calls -- returns SRCNN_ERR_STATE, srcnn_last_error() names the widths, and the context stays usable.
+ *   - srcnn_set_weights, srcnn_set_model or srcnn_set_model_color replaces the model; a per-filter call that loads weights ends
+ *     it, as it ends any model.
+ *   - workspace: the two band maps hold n1p and n2p planes, 4 * (n1p + n2p) bytes per pixel of a band, within the 512 MiB of
+ *     srcnn_set_model (a wide model's bands are shorter).
+ *   - model blobs and the command-line tool hold 64 / 32 models only. */
+int srcnn_set_model_shape(srcnn_ctx *ctx, int channels, int n1, int f2, int n2,
+                          const float *kernel1 /*[n1][channels][9][9]*/, const float *bias1 /*[n1]*/,
+                          const float *kernel2 /*[n2][n1][f2][f2]*/, const float *bias2 /*[n2]*/,
+                          const float *kernel3 /*[channels][n2][5][5]*/, const float *bias3 /*[channels]*/);
+/* The loaded model's channels, filters as given to srcnn_set_model_shape (64 / 32 after any other loader) and f2; every pointer
+ * may be NULL. */
+int srcnn_get_model_shape(const srcnn_ctx *ctx, int *channels, int *n1, int *f2, int *n2);
 int srcnn_forward_color(srcnn_ctx *ctx, const uint8_t *src, size_t src_stride,
                         uint8_t *dst, size_t dst_stride, int width, int height,
                         float *preclamp /*may be NULL: [h][3w], preclamp_stride floats*/, size_t preclamp_stride);

@@ -122,6 +122,15 @@ public:
         check(srcnn_set_model_color(get(), f2, &kernel1[0][0][0][0], bias1, kernel2, bias2, &kernel3[0][0][0][0], bias3));
     }
     int model_channels() const { return srcnn_get_model_channels(get()); }
+    // A model of other widths (srcnn_set_model_shape): channels = 1 or 3, n1 <= 128 and n2 <= 64 filters, f2 = 1, 3, 5;
+    // kernel1 [n1][channels][9][9], kernel2 [n2][n1][f2][f2], kernel3 [channels][n2][5][5], bias3 [channels].  More than 64 / 32
+    // filters run whole images in SRCNN_MODE_MFMA only.
+    void set_model_shape(int channels, int n1, int f2, int n2, const float *kernel1, const float *bias1, const float *kernel2,
+                         const float *bias2, const float *kernel3, const float *bias3)
+    {
+        check(srcnn_set_model_shape(get(), channels, n1, f2, n2, kernel1, bias1, kernel2, bias2, kernel3, bias3));
+    }
+    void model_shape(int *channels, int *n1, int *f2, int *n2) const { check(srcnn_get_model_shape(get(), channels, n1, f2, n2)); }
     // Interleaved 3-byte pixels in and out (rows of 3 * width bytes); preclamp: [h][3w] floats, or null.
     void forward_color(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int width, int height,
                        float *preclamp = nullptr, size_t preclamp_stride = 0)

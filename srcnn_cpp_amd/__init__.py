@@ -60,6 +60,8 @@ PAD_ZERO = 1
 _PADDINGS = {"replicate": PAD_REPLICATE, "zero": PAD_ZERO}
 # 2 x (64*81 + 32*64 + 32*25) MAC per output pixel
 FLOP_PER_PIXEL = 16064
+# the widest model (srcnn_set_model_shape): filters of layer 1 and of layer 2
+MAX_N1, MAX_N2 = 128, 64
 # luma rows {w0, w1, w2, offset} of process_rgb_f32 (srcnn_process_rgb_f32) for planes in R, G, B order: BT.601 full range
 LUMA_BT601 = (0.299, 0.587, 0.114, 0.0)
 
@@ -149,6 +151,8 @@ def load_library() -> C.CDLL:
         "srcnn_get_padding": ([vp], i),
         "srcnn_set_model_color": ([vp, i, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p], i),
         "srcnn_get_model_channels": ([vp], i),
+        "srcnn_set_model_shape": ([vp, i, i, i, i, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p], i),
+        "srcnn_get_model_shape": ([vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)], i),
         "srcnn_forward_color": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_color_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
         "srcnn_forward_f32": ([vp, _f32p, sz, sz, _f32p, sz, sz, i, i], i),
@@ -247,6 +251,7 @@ ABI_SYMBOLS = (
     "srcnn_stripe_rows", "srcnn_forward_y_frames_multi", "srcnn_forward_y_lanes_dev", "srcnn_forward_y_striped", "srcnn_forward_y_striped_frames", "srcnn_forward_y_striped_dev",
     "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
+    "srcnn_set_model_shape", "srcnn_get_model_shape",
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
     "srcnn_cubic_f32_taps", "srcnn_resize_cubic_f32", "srcnn_resize_cubic_f32_dev", "srcnn_process_f32", "srcnn_process_f32_dev",
     "srcnn_luma_gain", "srcnn_process_rgb_f32", "srcnn_process_rgb_f32_dev",
@@ -314,7 +319,10 @@ def model_from_state_dict(sd, input_scale: float = 255.0, image_order: Optional[
     """A PyTorch SRCNN state dict -> (w1, b1, w2, b2, w3, b3) for Context.set_model.
 
     Reads conv1.weight (64,1,9,9), conv1.bias, conv2.weight (32,64,f2,f2) with f2 = 1, 3 or 5, conv2.bias,
-    conv3.weight (1,32,5,5) and conv3.bias.  The library runs on 0..255 luma; a model trained on [0, 1] inputs
+    conv3.weight (1,32,5,5) and conv3.bias.  Other widths -- conv1.weight (n1,C,9,9), conv2.weight (n2,n1,f2,f2),
+    conv3.weight (C,n2,5,5) with 1 <= n1 <= MAX_N1 = 128 and 1 <= n2 <= MAX_N2 = 64, the paper's 128 / 64 and 32 / 16 among them --
+    give shaped arrays of those widths (Context.set_model reads n1 and n2 from w2's shape); ValueError for widths out of range
+    and for a conv2.weight whose input count is not conv1's output count.  The library runs on 0..255 luma; a model trained on [0, 1] inputs
     (input_scale = 255, the default) gets its three biases multiplied by input_scale, which maps it exactly onto
     0..255 because ReLU is positively homogeneous (pass 1.0 for a model trained on 0..255).
 
@@ -342,11 +350,30 @@ def model_from_state_dict(sd, input_scale: float = 255.0, image_order: Optional[
             raise ValueError(f"{key}: shape {v.shape}, expected {shape}")
         return v
     w2 = arr("conv2.weight")
-    if w2.ndim != 4 or w2.shape[:2] != (32, 64) or w2.shape[2] != w2.shape[3] or w2.shape[2] not in (1, 3, 5):
-        raise ValueError(f"conv2.weight: shape {w2.shape}, expected (32, 64, f2, f2) with f2 in 1, 3, 5")
+    if w2.ndim != 4 or w2.shape[2] != w2.shape[3] or w2.shape[2] not in (1, 3, 5):
+        raise ValueError(f"conv2.weight: shape {w2.shape}, expected (32, 64, f2, f2) with f2 in 1, 3, 5 (or (n2, n1, f2, f2) with "
+                         f"n1 <= {MAX_N1}, n2 <= {MAX_N2})")
+    n2, n1 = w2.shape[:2]
+    if not (1 <= n1 <= MAX_N1 and 1 <= n2 <= MAX_N2):
+        raise ValueError(f"conv2.weight: shape {w2.shape}: {n1} / {n2} filters, expected 1 <= n1 <= {MAX_N1} and 1 <= n2 <= {MAX_N2}")
+    if arr("conv1.weight").shape[:1] != (n1,):
+        raise ValueError(f"conv1.weight: shape {arr('conv1.weight').shape} and conv2.weight: shape {w2.shape}: conv2 must read "
+                         "the channels conv1 writes")
     s = float(input_scale)
     f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
     c_in, c_out = arr("conv1.weight").shape[1:2], arr("conv3.weight").shape[:1]
+    if (n1, n2) != (64, 32):         # other widths: shaped arrays, 1 or 3 channels (Context.set_model -> srcnn_set_model_shape)
+        if c_in != c_out or c_in not in ((1,), (3,)):
+            raise ValueError(f"conv1 reads {c_in[0] if c_in else '?'} channels and conv3 writes {c_out[0] if c_out else '?'}: "
+                             "a model has 1 channel in and out, or 3")
+        ch = c_in[0]
+        if ch == 3 and image_order not in ("rgb", "bgr"):
+            raise ValueError(f"image_order={image_order!r}: a 3-channel model needs image_order='rgb' or 'bgr' (the channel "
+                             "order of the images it will run on)")
+        w1, w3, b3 = arr("conv1.weight", (n1, ch, 9, 9)), arr("conv3.weight", (ch, n2, 5, 5)), arr("conv3.bias", (ch,))
+        if ch == 3 and image_order == "bgr":
+            w1, w3, b3 = w1[:, ::-1], w3[::-1], b3[::-1]
+        return (f32(w1), f32(arr("conv1.bias", (n1,)) * s), f32(w2), f32(arr("conv2.bias", (n2,)) * s), f32(w3), f32(b3 * s))
     if c_in == (3,) or c_out == (3,):
         if c_in != c_out:
             raise ValueError(f"conv1 reads {c_in[0] if c_in else '?'} channels and conv3 writes {c_out[0] if c_out else '?'}: "
@@ -538,7 +565,14 @@ class Context:
         """A 9-1-5, 9-3-5 or 9-5-5 model (srcnn_set_model): f2 from w2's shape, (32, 64) or (32, 64, f2, f2).
         A colour model -- w1 (64, 3, 9, 9), w3 (3, 32, 5, 5), b3 of length 3 -- goes to srcnn_set_model_color.
         f2 = 3, 5 and colour models run in MODE_MFMA and, with layer 2 in split f16, in MODE_BANDED16; every other mode
-        refuses them."""
+        refuses them.
+        Other widths (srcnn_set_model_shape): shaped arrays w1 (n1, C, 9, 9), w2 (n2, n1, f2, f2) or (n2, n1), w3 (C, n2, 5, 5)
+        with n1 <= 128 and n2 <= 64 read from w2.shape[:2]; C = 1 or 3 from w1; b3 a number or C numbers.  A model padded to
+        64 / 32 (the paper's 32 / 16) is an ordinary model; a wider one (128 / 64) runs whole images in MODE_MFMA only.  Flat
+        arrays keep meaning 64 / 32."""
+        w2s = tuple(np.shape(w2))
+        if len(w2s) in (2, 4) and w2s[:2] != (32, 64):
+            return self._set_model_shape(w1, b1, w2, b2, w3, b3)
         if tuple(np.shape(w1)) == (64, 3, 9, 9) or tuple(np.shape(w3)) == (3, 32, 5, 5) or np.size(b3) == 3:
             return self._set_model_color(w1, b1, w2, b2, w3, b3)
         shape = tuple(np.shape(w2))
@@ -568,6 +602,34 @@ class Context:
         w2, b2 = _wt(w2, 2048 * f2 * f2, "kernel2"), _wt(b2, 32, "bias2")
         w3, b3 = _wt(w3, 2400, "kernel3"), _wt(b3, 3, "bias3")
         self._check(self._lib.srcnn_set_model_color(self._h, f2, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(w3), _fp(b3)))
+
+    def _set_model_shape(self, w1, b1, w2, b2, w3, b3):
+        shape = tuple(np.shape(w2))
+        if len(shape) == 2:
+            shape = shape + (1, 1)
+        n2, n1, f2 = shape[0], shape[1], shape[2]
+        if shape[2] != shape[3] or f2 not in (1, 3, 5):
+            raise ValueError(f"kernel2: shape {tuple(np.shape(w2))}, expected (n2, n1, f2, f2) with f2 in 1, 3, 5")
+        if not (1 <= n1 <= MAX_N1 and 1 <= n2 <= MAX_N2):
+            raise ValueError(f"kernel2: shape {tuple(np.shape(w2))}: {n1} / {n2} filters, expected 1 <= n1 <= {MAX_N1} and "
+                             f"1 <= n2 <= {MAX_N2}")
+        s1 = tuple(np.shape(w1))
+        ch = s1[1] if len(s1) == 4 else 1
+        if ch not in (1, 3) or s1 not in ((n1, ch, 9, 9), (n1, 9, 9)):
+            raise ValueError(f"kernel1: shape {s1}, expected ({n1}, C, 9, 9) with C = 1 or 3 (kernel2 reads {n1} channels)")
+        if tuple(np.shape(w3)) not in ((ch, n2, 5, 5),) + (((n2, 5, 5),) if ch == 1 else ()):
+            raise ValueError(f"kernel3: shape {tuple(np.shape(w3))}, expected ({ch}, {n2}, 5, 5)")
+        w1, b1 = _wt(w1, n1 * ch * 81, "kernel1"), _wt(b1, n1, "bias1")
+        w2, b2 = _wt(w2, n2 * n1 * f2 * f2, "kernel2"), _wt(b2, n2, "bias2")
+        w3, b3 = _wt(w3, ch * n2 * 25, "kernel3"), _wt(b3, ch, "bias3")
+        self._check(self._lib.srcnn_set_model_shape(self._h, ch, n1, f2, n2, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(w3), _fp(b3)))
+
+    def model_shape(self):
+        """(channels, n1, f2, n2) of the loaded model (srcnn_get_model_shape): the filters as given to set_model, 64 / 32 for
+        every model of those widths."""
+        v = [C.c_int(0) for _ in range(4)]
+        self._check(self._lib.srcnn_get_model_shape(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def set_model_blob(self, blob):
         self.set_model(*split_model(blob))

@@ -49,6 +49,8 @@ UNITS = [
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models, float planes and row stripes -- every form
     ("srcnn_spatial_kernels.hip", []),
+    # ... and layers 2 and 3 of the models of other widths (srcnn_set_model_shape: up to 128 / 64 filters), the spatial unit's flags
+    ("srcnn_wide_kernels.hip", []),
     # the metrics: float64 throughout; the SSIM formula and the luma as written, every product and sum rounded on its own (the
     # window sums use explicit fused multiply-adds), so identical pictures give exactly 1.0 per window
     ("srcnn_metrics.hip", ["-ffp-contract=off"]),

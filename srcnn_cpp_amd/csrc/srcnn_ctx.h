@@ -182,6 +182,11 @@ struct srcnn_ctx {
     // lanes -- wait before reusing them).
     int channels = 1;
     int f2 = 1;
+    // The widths of the loaded model (srcnn_set_model_shape): n1 / n2 filters as given, n1p / n2p padded with zero channels to a
+    // multiple of 64 / 32.  64 / 32 for every model the other loaders load.  A WIDE model (n1p = 128 or n2p = 64, wide_model())
+    // lives in sp_table alone, in the layout of wide_table_floats() (srcnn_kernels.h), and sp_map64 / sp_map32 hold n1p / n2p
+    // planes; it runs in SRCNN_MODE_MFMA through forward_banded() and nowhere else.
+    int n1 = 64, n2 = 32, n1p = 64, n2p = 32;
     srcnn::host::DevBuf sp_table, sp_map64, sp_map32;
     float sp_b3[3] = {0.f, 0.f, 0.f};
     int sp_f2 = 0;
@@ -388,9 +393,12 @@ inline bool has_model(const srcnn_ctx *c) { return c->has_l12 && c->has_l3; }
 // predicate; srcnn_forward_y_dev sends the other 1-channel models to the banded path and refuses a colour model.
 // SRCNN_MODE_BANDED16 runs every model on the banded path, so none of these entry points runs in it -- but for the per-filter
 // calls on host planes (srcnn_conv99x11, srcnn_conv55: per_filter is set while they run), which ignore every mode.
+// A wide model (srcnn_set_model_shape with more than 64 / 32 filters) runs on the banded path only.
+inline bool wide_model(const srcnn_ctx *c) { return c->n1p > 64 || c->n2p > 32; }
 inline bool luma_path_ok(const srcnn_ctx *c)
 {
-    return c->channels == 1 && c->f2 == 1 && c->padding != SRCNN_PAD_ZERO && (c->mode != SRCNN_MODE_BANDED16 || c->per_filter);
+    return c->channels == 1 && c->f2 == 1 && !wide_model(c) && c->padding != SRCNN_PAD_ZERO &&
+           (c->mode != SRCNN_MODE_BANDED16 || c->per_filter);
 }
 void drop_spatial_model(srcnn_ctx *c);
 

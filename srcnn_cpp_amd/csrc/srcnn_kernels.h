@@ -315,6 +315,35 @@ struct L3Output {
 // under replicate padding are not a form of this kernel (the MODE_L3 strip kernel runs them); floats of it are.
 hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
                              const float *frag, const float *b3, const L3Output &out, hipStream_t st);
+
+// ---- models of other widths (srcnn_wide_kernels.hip; srcnn_set_model_shape: n1 <= 128 and n2 <= 64 filters) ----
+// The widths are padded with zero channels to n1p = 64 or 128 and n2p = 32 or 64.  The fragment table of such a model, floats:
+// layer 1 [n1p / 64 groups][C channels][SPATIAL_NFRAG_L1][64] (group g: the table above for output channels 64g .. 64g + 63),
+// then layer 2 [n2p / 32 groups][n1p / 8 chunks][f2 * f2 taps][4 pairs][64] (group g, lane l: output channel 32g + (l & 31),
+// input channel 8 chunk + 2 pair + (l >> 5)) and b2 [n2p], then layer 3 [C output channels][n2p / 2 k-steps][64].  For
+// n1p = 64 and n2p = 32 this is the table above, float for float.
+__host__ __device__ constexpr size_t wide_l2_offset(int C, int n1p) { return (size_t)(n1p / 64) * C * SPATIAL_NFRAG_L1 * 64; }
+__host__ __device__ constexpr size_t wide_l2_floats(int f2, int n1p, int n2p) { return (size_t)(n2p / 32) * (n1p / 8) * f2 * f2 * 256; }
+__host__ __device__ constexpr size_t wide_l3_offset(int C, int f2, int n1p, int n2p) { return wide_l2_offset(C, n1p) + wide_l2_floats(f2, n1p, n2p) + n2p; }
+__host__ __device__ constexpr size_t wide_table_floats(int C, int f2, int n1p, int n2p) { return wide_l3_offset(C, f2, n1p, n2p) + (size_t)C * (n2p / 2) * 64; }
+// Layer 1 of such a model is n1p / 64 calls of launch_spatial_l1, each with its group's table and its 64 planes of the map.
+// Layers 2 and 3 are the wide unit's two launchers.  The host layer holds no reference to them: the unit hands them over when
+// the library is loaded (set_wide_launchers, srcnn_spatial.cpp), and the band loop calls them through wide_launchers().  So every
+// symbol the host units name is one every program that links them defines, and where no unit has handed its launchers over (the
+// host units linked against stand-ins for the kernel units) srcnn_set_model_shape refuses a wide model: nothing runs in its place.
+struct WideLaunchers {
+    // Layer 2: launch_spatial_l2's f32 form over n_chunks = n1p / 8 chunks of the map and n_groups = n2p / 32 groups of 32
+    // output planes (frag: the layer-2 part of the table, bias: the n2p floats behind it).
+    hipError_t (*l2)(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1, const float *frag,
+                     const float *bias, int n_chunks, int n_groups, float *out, long opitch, hipStream_t st);
+    // Layer 3 from 64 planar maps: launch_spatial_l3 with 32 k-steps, every form of it and bytes of 1 channel under replicate
+    // padding as well.  (A model with n2p = 32 keeps launch_spatial_l3 / MODE_L3.)
+    hipError_t (*l3)(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
+                     const float *frag, const float *b3, const L3Output &out, hipStream_t st);
+};
+void set_wide_launchers(const WideLaunchers &t);
+const WideLaunchers &wide_launchers();          // both null until a unit has called set_wide_launchers
+
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

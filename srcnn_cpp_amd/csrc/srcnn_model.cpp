@@ -217,6 +217,8 @@ int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float
     std::vector<uint8_t> frag16(S16_TABLE_BYTES);
     pack_fragments16(w1, b1, w2, b2, w3, frag16.data());
     c->sp_f2 = c->sp16_f2 = 0;   // the banded path's tables no longer hold the model (srcnn_spatial.cpp)
+    c->n1 = c->n1p = 64;         // ... and every model loaded through here has the plain widths (srcnn_set_model_shape sets
+    c->n2 = c->n2p = 32;         // its own afterwards)
     int rc;
     if ((rc = reserve(c, c->wfrag, frag.size() * 4))) return rc;
     if ((rc = reserve(c, c->wfrag16, frag16.size()))) return rc;
@@ -243,6 +245,12 @@ const char *const kNoModel = "the model is not loaded: srcnn_set_weights not cal
 // tables equal to the uploaded ones are not packed or uploaded again.
 int refuse_spatial(srcnn_ctx *c, const char *what, bool banded_entry)
 {
+    if (wide_model(c))
+        return fail(c, SRCNN_ERR_STATE, "%s does not run a model of %d / %d filters (srcnn_set_model_shape; padded to %d / %d): "
+                                        "such a model runs in SRCNN_MODE_MFMA through srcnn_forward_y(_dev) / srcnn_forward_y_frames / "
+                                        "srcnn_forward_color(_dev) / srcnn_process_bgr(_dev) / srcnn_forward_f32* / srcnn_process_f32* / "
+                                        "srcnn_process_rgb_f32* / the srcnn_*_image_dev calls",
+                    what, c->n1, c->n2, c->n1p, c->n2p);
     if (c->mode == SRCNN_MODE_BANDED16 && !banded_entry)
         return fail(c, SRCNN_ERR_STATE, "%s does not run in SRCNN_MODE_BANDED16 (that mode runs whole models on the banded path: "
                                         "srcnn_forward_y / srcnn_forward_y_dev / srcnn_forward_y_frames / srcnn_forward_color* / "
@@ -269,9 +277,15 @@ int refuse_spatial(srcnn_ctx *c, const char *what, bool banded_entry)
 // loaded all three layers).
 void drop_spatial_model(srcnn_ctx *c)
 {
-    if (c->f2 == 1 && c->channels == 1) return;
+    if (c->f2 == 1 && c->channels == 1 && !wide_model(c)) {
+        c->n1 = 64;      // (a narrow model of srcnn_set_model_shape lives on as the 9-1-5 tables it is)
+        c->n2 = 32;
+        return;
+    }
     c->f2 = 1;
     c->channels = 1;
+    c->n1 = c->n1p = 64;
+    c->n2 = c->n2p = 32;
     c->has_l12 = c->has_l3 = false;
     std::fill(c->host_raw.begin(), c->host_raw.end(), 0.f);
 }
@@ -316,10 +330,13 @@ int srcnn_set_weights(srcnn_ctx *c, const float *k99, const float *b99, const fl
     (void)rc;
     if (!k99 || !b99 || !k11 || !b11 || !k55) return fail(c, SRCNN_ERR_INVALID, "null weight table");
     c->f2 = 1;                  // back on the 9-1-5 path (srcnn_set_model)
-    if (c->channels != 1) {     // the end of a colour model: its zero 9-1-5 tables are replaced whatever the caller passes
+    // the end of a colour model or of a wide one: its zero 9-1-5 tables are replaced whatever the caller passes
+    if (c->channels != 1 || wide_model(c)) {
         c->channels = 1;
         c->has_l12 = c->has_l3 = false;
     }
+    c->n1 = c->n1p = 64;
+    c->n2 = c->n2p = 32;
     // a caller that passes its const tables on every call (the reference does, src/srcnn.cpp:609,627) packs and uploads once
     const float *hr = c->host_raw.data();
     if (c->has_l12 && c->has_l3 && hr[7328] == b55 && !std::memcmp(hr, b99, 64 * 4) && !std::memcmp(hr + 64, k99, 5184 * 4) &&

@@ -3,46 +3,64 @@
 // (srcnn_set_padding), f2 = 1 included, and the colour models (srcnn_set_model_color: 3 input and 3 output channels, 9-f2-5)
 // behind srcnn_forward_color(_dev) and srcnn_process_bgr(_dev); and the float image path, srcnn_forward_f32(_dev): every whole
 // model on float32 planes, the value before truncation out.  One weight table per model, one gate, one band loop.
+// Models of other widths (srcnn_set_model_shape: up to 128 / 64 filters, padded with zero channels to 64 or 128 and 32 or 64)
+// load here too: one that fits 64 / 32 as an ordinary model, a wider one into the same table and band loop with layers 2 and
+// 3 from srcnn_wide_kernels.hip.
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
 using namespace srcnn::host;
 
 namespace srcnn {
+
+// layers 2 and 3 of a wide model (srcnn_kernels.h): constant-initialised, so a unit may hand them over from its own initialiser
+static WideLaunchers g_wide_launchers = {nullptr, nullptr};
+void set_wide_launchers(const WideLaunchers &t) { g_wide_launchers = t; }
+const WideLaunchers &wide_launchers() { return g_wide_launchers; }
+
 namespace host {
 
-// The fragment table of srcnn_kernels.h (spatial_table_floats()) of a C-channel model.  w1 [64][C][9][9], w2 [32][64][f2][f2],
-// w3 [C][32][5][5] (PyTorch's conv weights).
-static void pack_spatial(int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
-                         float *out)
+// The fragment table of srcnn_kernels.h of a C-channel model of padded widths n1p (64 or 128) and n2p (32 or 64): for 64 / 32
+// spatial_table_floats() floats, the table the 32-map kernels read; else wide_table_floats() floats -- n1p / 64 layer-1 groups,
+// n1p / 8 layer-2 chunks x n2p / 32 groups, n2p / 2 layer-3 k-steps (the same loops: 64 / 32 gives the same floats in the same
+// places).  w1 [n1p][C][9][9], w2 [n2p][n1p][f2][f2], w3 [C][n2p][5][5] (PyTorch's conv weights, padded with zeros).
+static void pack_spatial(int C, int f2, int n1p, int n2p, const float *w1, const float *b1, const float *w2, const float *b2,
+                         const float *w3, float *out)
 {
-    for (int ch = 0; ch < C; ++ch)
-        for (int l = 0; l < 64; ++l) {
-            const int i = l & 31, kk = l >> 5;
-            for (int t = 0; t < 2; ++t)
-                for (int s = 0; s < 41; ++s) {
-                    const int tap = 2 * s + kk, k = 32 * t + i;
-                    out[((ch * 2 + t) * 41 + s) * 64 + l] = tap < 81 ? w1[(k * C + ch) * 81 + tap] : (ch == C - 1 ? b1[k] : 0.f);
-                }
-        }
-    const int taps = f2 * f2;
-    float *o2 = out + spatial_l2_offset(C);
-    for (int chunk = 0; chunk < 8; ++chunk)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int pp = 0; pp < 4; ++pp)
-                for (int l = 0; l < 64; ++l) {
-                    const int k = l & 31, ci = 8 * chunk + 2 * pp + (l >> 5);
-                    o2[(((size_t)chunk * taps + tap) * 4 + pp) * 64 + l] = w2[((size_t)k * 64 + ci) * taps + tap];
-                }
-    std::memcpy(o2 + (size_t)taps * 2048, b2, 32 * sizeof(float));
-    float *o3 = out + spatial_l3_offset(C, f2);
+    for (int g = 0; g < n1p / 64; ++g)
+        for (int ch = 0; ch < C; ++ch)
+            for (int l = 0; l < 64; ++l) {
+                const int i = l & 31, kk = l >> 5;
+                for (int t = 0; t < 2; ++t)
+                    for (int s = 0; s < 41; ++s) {
+                        const int tap = 2 * s + kk, k = 64 * g + 32 * t + i;
+                        out[(size_t)g * C * SPATIAL_NFRAG_L1 * 64 + ((ch * 2 + t) * 41 + s) * 64 + l] =
+                            tap < 81 ? w1[((size_t)k * C + ch) * 81 + tap] : (ch == C - 1 ? b1[k] : 0.f);
+                    }
+            }
+    const int taps = f2 * f2, chunks = n1p / 8;
+    float *o2 = out + wide_l2_offset(C, n1p);
+    for (int g = 0; g < n2p / 32; ++g)
+        for (int chunk = 0; chunk < chunks; ++chunk)
+            for (int tap = 0; tap < taps; ++tap)
+                for (int pp = 0; pp < 4; ++pp)
+                    for (int l = 0; l < 64; ++l) {
+                        const int k = 32 * g + (l & 31), ci = 8 * chunk + 2 * pp + (l >> 5);
+                        o2[((((size_t)g * chunks + chunk) * taps + tap) * 4 + pp) * 64 + l] = w2[((size_t)k * n1p + ci) * taps + tap];
+                    }
+    std::memcpy(o2 + wide_l2_floats(f2, n1p, n2p), b2, n2p * sizeof(float));
+    float *o3 = out + wide_l3_offset(C, f2, n1p, n2p);
+    const int ksteps = n2p / 2;
     for (int o = 0; o < C; ++o)
-        for (int s = 0; s < SPATIAL_NFRAG_L3; ++s)
+        for (int s = 0; s < ksteps; ++s)
             for (int l = 0; l < 64; ++l) {
                 const int tap = l3_row_tap(l & 31);
-                o3[((size_t)o * SPATIAL_NFRAG_L3 + s) * 64 + l] = tap < 0 ? 0.f : w3[(size_t)o * 800 + (2 * s + (l >> 5)) * 25 + tap];
+                o3[((size_t)o * ksteps + s) * 64 + l] = tap < 0 ? 0.f : w3[((size_t)o * n2p + 2 * s + (l >> 5)) * 25 + tap];
             }
 }
+static_assert(wide_l2_offset(3, 64) == spatial_l2_offset(3) && wide_l3_offset(3, 5, 64, 32) == spatial_l3_offset(3, 5) &&
+              wide_table_floats(3, 5, 64, 32) == spatial_table_floats(3, 5) && wide_table_floats(1, 1, 64, 32) == spatial_table_floats(1, 1),
+              "a 64 / 32 model keeps its table");
 
 // ---- SRCNN_MODE_BANDED16: exact power-of-two scales and the split W2 table (srcnn_spatial_kernels.hip, spatial_l2h_kernel) ----
 // sum |w1[k]| and |b1[k]| of the 64 layer-1 channels (doubles), what the bound below is made from; false when one is not finite
@@ -110,18 +128,21 @@ bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2)
     return true;
 }
 
-// The table and b3 of a C-channel 9-f2-5 model into sp_table / sp_b3 (pack_spatial's arguments)
+// The table and b3 of a C-channel 9-f2-5 model into sp_table / sp_b3 (pack_spatial's arguments).  A wide model (n1p = 128 or
+// n2p = 64) keeps nothing for SRCNN_MODE_BANDED16, which refuses it.
 static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2,
-                        const float *w3, const float *b3)
+                        const float *w3, const float *b3, int n1p = 64, int n2p = 32)
 {
-    std::vector<float> table(spatial_table_floats(C, f2));
-    pack_spatial(C, f2, w1, b1, w2, b2, w3, table.data());
+    std::vector<float> table(wide_table_floats(C, f2, n1p, n2p));
+    pack_spatial(C, f2, n1p, n2p, w1, b1, w2, b2, w3, table.data());
     int rc;
     if ((rc = reserve(c, c->sp_table, table.size() * sizeof(float)))) return rc;
     HIP_TRY(c, hipDeviceSynchronize());        // launches on any stream may still read the old table
     HIP_TRY(c, hipMemcpy(c->sp_table.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
     std::memcpy(c->sp_b3, b3, C * sizeof(float));
     c->sp_f2 = f2;
+    c->sp16_f2 = 0;
+    if (n1p != 64 || n2p != 32) return SRCNN_OK;
     // what SRCNN_MODE_BANDED16 makes its table and scales from, when a call first runs the model in that mode
     c->sp_w2.assign(w2, w2 + (size_t)2048 * f2 * f2);
     c->sp_l1_bound = l1_magnitudes(C, w1, b1, c->sp_l1_sum, c->sp_l1_absb) ? l1_bound(c->sp_l1_sum, c->sp_l1_absb, 255.0) : HUGE_VAL;
@@ -162,6 +183,10 @@ static int upload_table16(srcnn_ctx *c)
 static int banded_refusal(srcnn_ctx *c, bool f32 = false, bool rows = false)
 {
     const bool zero = c->padding == SRCNN_PAD_ZERO;
+    if (wide_model(c) && (c->mode != SRCNN_MODE_MFMA || rows))      // before the other gates: the message names the widths
+        return fail(c, SRCNN_ERR_STATE, "a model of %d / %d filters (srcnn_set_model_shape; padded to %d / %d) runs whole images in "
+                                        "SRCNN_MODE_MFMA only: %s", c->n1, c->n2, c->n1p, c->n2p,
+                    rows ? "row stripes and several GPUs are not built for it" : "this mode has no arithmetic for it");
     if (f32) {
         if (c->mode != SRCNN_MODE_MFMA && c->mode != SRCNN_MODE_BANDED16)
             return fail(c, SRCNN_ERR_STATE, "srcnn_forward_f32 runs in SRCNN_MODE_MFMA and SRCNN_MODE_BANDED16 only (mode %d has no "
@@ -246,7 +271,7 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     int rc;
     if ((rc = banded_refusal(c, io.f32, io.rows))) return rc;
     // (only a 9-1-5 model gets here unpacked: the others pack when they load)
-    if (c->sp_f2 != c->f2) {
+    if (c->sp_f2 != c->f2 && !wide_model(c)) {
         const float *hr = c->host_raw.data();
         if ((rc = upload_table(c, 1, 1, hr + 64, hr, hr + 5280, hr + 5248, hr + 7329, hr + 7328))) return rc;
     }
@@ -265,8 +290,11 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     const int C = c->channels, r2 = (c->f2 - 1) / 2;
     const bool zero = c->padding == SRCNN_PAD_ZERO;
     const long row_bytes = 4L * width;
-    const long cap = (long)(kSpatialWorkBytes / (size_t)row_bytes) - 64L * (4 + 2 * r2) - 32L * 4;
-    const int band_max = (int)std::max(16L, cap / 96);
+    // (n1p / n2p = 64 / 32 but for a model of srcnn_set_model_shape: 4 (n1p + n2p) bytes per pixel of a row)
+    const int n1p = c->n1p, n2p = c->n2p;
+    const bool wide = wide_model(c);
+    const long cap = (long)(kSpatialWorkBytes / (size_t)row_bytes) - (long)n1p * (4 + 2 * r2) - (long)n2p * 4;
+    const int band_max = (int)std::max(16L, cap / (n1p + n2p));
     const int row_begin = io.rows ? io.row_begin : 0, row_end = io.rows ? io.row_end : height;
     const int n_bands = (row_end - row_begin + band_max - 1) / band_max;
     const int band = (row_end - row_begin + n_bands - 1) / n_bands;
@@ -277,14 +305,14 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
                     io.rows ? (io.f32 ? "model_rows_f32_dev" : C == 1 ? "model_rows_dev" : "model_color_rows_dev")
                             : io.f32 ? "forward_f32_dev" : C == 1 ? "forward_y_dev" : "forward_color_dev",
                     C == 1 ? "" : "colour ", c->f2);
-    if ((rc = reserve(c, c->sp_map64, (size_t)64 * mpitch * sizeof(float)))) return rc;
-    if ((rc = reserve(c, c->sp_map32, (size_t)32 * opitch * sizeof(float)))) return rc;
+    if ((rc = reserve(c, c->sp_map64, (size_t)n1p * mpitch * sizeof(float)))) return rc;
+    if ((rc = reserve(c, c->sp_map32, (size_t)n2p * opitch * sizeof(float)))) return rc;
     if (!c->sp_done) HIP_TRY(c, hipEventCreateWithFlags(&c->sp_done, hipEventDisableTiming));
     // the maps were last used on another stream (the two lanes of srcnn_forward_y_frames): wait for that work
     if (c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
     const float *frag = static_cast<const float *>(c->sp_table.p);
-    const float *frag2 = frag + spatial_l2_offset(C), *bias2 = frag2 + (size_t)c->f2 * c->f2 * 2048;
-    const float *frag3 = frag + spatial_l3_offset(C, c->f2);
+    const float *frag2 = frag + wide_l2_offset(C, n1p), *bias2 = frag2 + wide_l2_floats(c->f2, n1p, n2p);
+    const float *frag3 = frag + wide_l3_offset(C, c->f2, n1p, n2p);
     float *map64 = static_cast<float *>(c->sp_map64.p), *map32 = static_cast<float *>(c->sp_map32.p);
     const size_t dst_stride = io.dst_stride;
     // where layer 1 reads the image (a stripe: the image's rows in src and the halo buffers) and what layer 3 writes (a stripe:
@@ -305,10 +333,24 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
             const int b1 = std::min(row_end, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
-            // split: the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
-            HIP_TRY(c, launch_spatial_l1(in, zero, split, scale1, width, height, m0, m1, frag, map64, mpitch, c->stream));
-            HIP_TRY(c, launch_spatial_l2(c->f2, zero, split, map64, mpitch, m0, m1, width, height, o0, o1,
-                                         split ? c->sp16_table.p : (const void *)frag2, bias2, unscale, map32, opitch, c->stream));
+            if (wide) {
+                // a wide model: layer 1 group by group (64 output channels each: its own table, its own planes of the map),
+                // layer 2 over n1p / 8 chunks and n2p / 32 output groups, layer 3 from 64 maps where there are 64
+                for (int g = 0; g < n1p / 64; ++g)
+                    HIP_TRY(c, launch_spatial_l1(in, zero, false, 1.f, width, height, m0, m1, frag + (size_t)g * C * SPATIAL_NFRAG_L1 * 64,
+                                                 map64 + (size_t)g * 64 * mpitch, mpitch, c->stream));
+                HIP_TRY(c, wide_launchers().l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, n1p / 8, n2p / 32,
+                                               map32, opitch, c->stream));
+                if (n2p > 32) {
+                    HIP_TRY(c, wide_launchers().l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, c->stream));
+                    continue;
+                }
+            } else {
+                // split: the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
+                HIP_TRY(c, launch_spatial_l1(in, zero, split, scale1, width, height, m0, m1, frag, map64, mpitch, c->stream));
+                HIP_TRY(c, launch_spatial_l2(c->f2, zero, split, map64, mpitch, m0, m1, width, height, o0, o1,
+                                             split ? c->sp16_table.p : (const void *)frag2, bias2, unscale, map32, opitch, c->stream));
+            }
             // float planes out, the 1-channel replicate model included (no float form of MODE_L3)
             if (io.f32 || C > 1 || zero) {
                 HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, c->stream));
@@ -394,6 +436,68 @@ int srcnn_set_model_color(srcnn_ctx *c, int f2, const float *k1, const float *b1
     c->f2 = f2;
     c->channels = 3;
     c->whole_model = true;
+    return SRCNN_OK;
+}
+
+int srcnn_set_model_shape(srcnn_ctx *c, int channels, int n1, int f2, int n2, const float *k1, const float *b1, const float *k2,
+                          const float *b2, const float *k3, const float *b3)
+{
+    BIND(c);
+    int rc;
+    if (!k1 || !b1 || !k2 || !b2 || !k3 || !b3) return fail(c, SRCNN_ERR_INVALID, "null weight table");
+    if ((channels != 1 && channels != 3) || (f2 != 1 && f2 != 3 && f2 != 5) || n1 < 1 || n1 > 128 || n2 < 1 || n2 > 64)
+        return fail(c, SRCNN_ERR_INVALID, "srcnn_set_model_shape: %d channel(s), n1 = %d, f2 = %d, n2 = %d (channels 1 or 3, "
+                                          "1 <= n1 <= 128, f2 = 1, 3 or 5, 1 <= n2 <= 64)", channels, n1, f2, n2);
+    const int C = channels, taps = f2 * f2, n1p = 64 * ((n1 + 63) / 64), n2p = 32 * ((n2 + 31) / 32);
+    // the padded tensors: zero weights and zero biases for the channels beyond n1 / n2
+    std::vector<float> w1((size_t)n1p * C * 81, 0.f), pb1((size_t)n1p, 0.f), w2((size_t)n2p * n1p * taps, 0.f), pb2((size_t)n2p, 0.f),
+        w3((size_t)C * n2p * 25, 0.f);
+    std::memcpy(w1.data(), k1, (size_t)n1 * C * 81 * sizeof(float));
+    std::memcpy(pb1.data(), b1, (size_t)n1 * sizeof(float));
+    for (int k = 0; k < n2; ++k)
+        std::memcpy(w2.data() + (size_t)k * n1p * taps, k2 + (size_t)k * n1 * taps, (size_t)n1 * taps * sizeof(float));
+    std::memcpy(pb2.data(), b2, (size_t)n2 * sizeof(float));
+    for (int o = 0; o < C; ++o) std::memcpy(w3.data() + (size_t)o * n2p * 25, k3 + (size_t)o * n2 * 25, (size_t)n2 * 25 * sizeof(float));
+    if (n1p == 64 && n2p == 32) {      // a narrow model is an ordinary model: every mode and entry point that runs one runs it
+        rc = C == 3 ? srcnn_set_model_color(c, f2, w1.data(), pb1.data(), w2.data(), pb2.data(), w3.data(), b3)
+                    : srcnn_set_model(c, f2, w1.data(), pb1.data(), w2.data(), pb2.data(), w3.data(), b3[0]);
+        if (rc) return rc;
+        c->n1 = n1;
+        c->n2 = n2;
+        return SRCNN_OK;
+    }
+    // (a missing kernel is an error, here and not at the first call that would run it; the library always holds the unit)
+    if (!wide_launchers().l2 || !wide_launchers().l3)
+        return fail(c, SRCNN_ERR_STATE, "srcnn_set_model_shape: n1 = %d, n2 = %d (padded to %d / %d) needs the kernels of "
+                                        "srcnn_wide_kernels.hip, which this build does not hold", n1, n2, n1p, n2p);
+    // A wide model lives in sp_table.  The 9-1-5 tables hold a zero model (and the has-model state) that no gate lets run -- but
+    // for layer 3 of a 1-channel model with n2p = 32, which MODE_L3 runs from them under replicate padding (as srcnn_set_model).
+    static const std::vector<float> zeros(5184, 0.f);
+    const bool l3_strip = C == 1 && n2p == 32;
+    c->f2 = 1;
+    c->channels = 1;
+    if ((rc = upload_weights(c, zeros.data(), zeros.data(), zeros.data(), zeros.data(), l3_strip ? w3.data() : zeros.data(),
+                             l3_strip ? b3[0] : 0.f)))
+        return rc;
+    c->has_l12 = c->has_l3 = true;
+    if ((rc = upload_table(c, C, f2, w1.data(), pb1.data(), w2.data(), pb2.data(), w3.data(), b3, n1p, n2p))) return rc;
+    c->f2 = f2;
+    c->channels = C;
+    c->whole_model = true;
+    c->n1 = n1;
+    c->n2 = n2;
+    c->n1p = n1p;
+    c->n2p = n2p;
+    return SRCNN_OK;
+}
+
+int srcnn_get_model_shape(const srcnn_ctx *c, int *channels, int *n1, int *f2, int *n2)
+{
+    if (!c) return SRCNN_ERR_INVALID;
+    if (channels) *channels = c->channels;
+    if (n1) *n1 = c->n1;
+    if (f2) *f2 = c->f2;
+    if (n2) *n2 = c->n2;
     return SRCNN_OK;
 }
 

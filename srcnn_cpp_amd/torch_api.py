@@ -367,7 +367,8 @@ def compile_module(module, device: int = 0, mode: int = MODE_MFMA, input_range: 
     with padding_mode "zeros" or "replicate") -> a callable on float32 CUDA tensors that computes module(x) with this library's
     HIP kernels.  mode: MODE_MFMA (float32 throughout) or MODE_BANDED16 (layer 2 in split f16, faster; input_range is then the
     largest |x| the tensors will hold, 1.0 for [0, 1] data).  The weights are read once, here: a module trained further needs a
-    new compile_module."""
+    new compile_module.  The filters: conv1 up to 128, conv2 up to 64 (64 / 32 is the classic model); more than 64 / 32 run in
+    MODE_MFMA only."""
     if mode not in (MODE_MFMA, MODE_BANDED16):
         raise ValueError(f"mode {mode}: the float image path runs in MODE_MFMA and MODE_BANDED16 only")
     conv1 = getattr(module, "conv1", None)
