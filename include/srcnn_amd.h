@@ -344,6 +344,21 @@ int srcnn_set_model_shape(srcnn_ctx *ctx, int channels, int n1, int f2, int n2,
 /* The loaded model's channels, filters as given to srcnn_set_model_shape (64 / 32 after any other loader) and f2; every pointer
  * may be NULL. */
 int srcnn_get_model_shape(const srcnn_ctx *ctx, int *channels, int *n1, int *f2, int *n2);
+/* Layer 2 of a WIDE model in split f16, a setting of the CONTEXT like the padding: off (0) by default, it survives every model
+ * load.  on = 1: when a wide model is loaded and the mode is SRCNN_MODE_MFMA, every call that runs the model (the whole-image
+ * entry points listed above) runs layer 2 with the arithmetic of SRCNN_MODE_BANDED16 -- layer 1 writes its map as f16 (hi, lo)
+ * pairs, layer 2 runs on the f16 matrix pipe over all n1p channels and n2p outputs (summation order in
+ * srcnn_wide16_kernels.hip), layer 3 is unchanged -- within the tolerance of the float32 form and several times faster for
+ * f2 = 3, 5.  The float calls scale by srcnn_set_input_range, the byte calls by 255, as in that mode.
+ *   - on = 0: the float32 kernels, the results of a context that never had the option on.
+ *   - A narrow model ignores the option in every mode; a wide model in any other mode or entry point is refused as before
+ *     (SRCNN_MODE_BANDED16 stays a mode of the 64 / 32 models).
+ *   - A wide model the split cannot scale (a weight or bias of layers 1-2 not finite, or magnitudes beyond float32's exponent
+ *     range) is refused at the first call with the option on: SRCNN_ERR_STATE, srcnn_last_error() names srcnn_set_wide_split16,
+ *     the context stays usable and the option off still runs the model.
+ * on other than 0 or 1 returns SRCNN_ERR_INVALID; srcnn_get_wide_split16 returns the setting. */
+int srcnn_set_wide_split16(srcnn_ctx *ctx, int on);
+int srcnn_get_wide_split16(const srcnn_ctx *ctx);
 int srcnn_forward_color(srcnn_ctx *ctx, const uint8_t *src, size_t src_stride,
                         uint8_t *dst, size_t dst_stride, int width, int height,
                         float *preclamp /*may be NULL: [h][3w], preclamp_stride floats*/, size_t preclamp_stride);

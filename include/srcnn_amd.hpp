@@ -131,6 +131,10 @@ public:
         check(srcnn_set_model_shape(get(), channels, n1, f2, n2, kernel1, bias1, kernel2, bias2, kernel3, bias3));
     }
     void model_shape(int *channels, int *n1, int *f2, int *n2) const { check(srcnn_get_model_shape(get(), channels, n1, f2, n2)); }
+    // Layer 2 of a model of more than 64 / 32 filters in split f16 (srcnn_set_wide_split16): off by default, a setting of the
+    // context; SRCNN_MODE_MFMA then runs such a model several times faster, within the same tolerance.
+    void set_wide_split16(bool on) { check(srcnn_set_wide_split16(get(), on ? 1 : 0)); }
+    bool wide_split16() const { return srcnn_get_wide_split16(get()) == 1; }
     // Interleaved 3-byte pixels in and out (rows of 3 * width bytes); preclamp: [h][3w] floats, or null.
     void forward_color(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int width, int height,
                        float *preclamp = nullptr, size_t preclamp_stride = 0)

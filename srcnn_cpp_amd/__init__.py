@@ -153,6 +153,8 @@ def load_library() -> C.CDLL:
         "srcnn_get_model_channels": ([vp], i),
         "srcnn_set_model_shape": ([vp, i, i, i, i, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p], i),
         "srcnn_get_model_shape": ([vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)], i),
+        "srcnn_set_wide_split16": ([vp, i], i),
+        "srcnn_get_wide_split16": ([vp], i),
         "srcnn_forward_color": ([vp, _u8p, sz, _u8p, sz, i, i, _f32p, sz], i),
         "srcnn_forward_color_dev": ([vp, vp, sz, sz, vp, sz, sz, i, i, i, vp], i),
         "srcnn_forward_f32": ([vp, _f32p, sz, sz, _f32p, sz, sz, i, i], i),
@@ -251,7 +253,7 @@ ABI_SYMBOLS = (
     "srcnn_stripe_rows", "srcnn_forward_y_frames_multi", "srcnn_forward_y_lanes_dev", "srcnn_forward_y_striped", "srcnn_forward_y_striped_frames", "srcnn_forward_y_striped_dev",
     "srcnn_set_model", "srcnn_get_model_f2", "srcnn_set_padding", "srcnn_get_padding",
     "srcnn_set_model_color", "srcnn_get_model_channels", "srcnn_forward_color", "srcnn_forward_color_dev",
-    "srcnn_set_model_shape", "srcnn_get_model_shape",
+    "srcnn_set_model_shape", "srcnn_get_model_shape", "srcnn_set_wide_split16", "srcnn_get_wide_split16",
     "srcnn_forward_f32", "srcnn_forward_f32_dev", "srcnn_set_input_range", "srcnn_get_input_range",
     "srcnn_cubic_f32_taps", "srcnn_resize_cubic_f32", "srcnn_resize_cubic_f32_dev", "srcnn_process_f32", "srcnn_process_f32_dev",
     "srcnn_luma_gain", "srcnn_process_rgb_f32", "srcnn_process_rgb_f32_dev",
@@ -568,8 +570,8 @@ class Context:
         refuses them.
         Other widths (srcnn_set_model_shape): shaped arrays w1 (n1, C, 9, 9), w2 (n2, n1, f2, f2) or (n2, n1), w3 (C, n2, 5, 5)
         with n1 <= 128 and n2 <= 64 read from w2.shape[:2]; C = 1 or 3 from w1; b3 a number or C numbers.  A model padded to
-        64 / 32 (the paper's 32 / 16) is an ordinary model; a wider one (128 / 64) runs whole images in MODE_MFMA only.  Flat
-        arrays keep meaning 64 / 32."""
+        64 / 32 (the paper's 32 / 16) is an ordinary model; a wider one (128 / 64) runs whole images in MODE_MFMA only (with
+        layer 2 in split f16 after set_wide_split16(True)).  Flat arrays keep meaning 64 / 32."""
         w2s = tuple(np.shape(w2))
         if len(w2s) in (2, 4) and w2s[:2] != (32, 64):
             return self._set_model_shape(w1, b1, w2, b2, w3, b3)
@@ -630,6 +632,19 @@ class Context:
         v = [C.c_int(0) for _ in range(4)]
         self._check(self._lib.srcnn_get_model_shape(self._h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def set_wide_split16(self, on: bool):
+        """Layer 2 of a model wider than 64 / 32 in split f16 (srcnn_set_wide_split16): off by default.  On, MODE_MFMA runs such a
+        model with the arithmetic MODE_BANDED16 gives the 64 / 32 models -- layer 1 writes f16 (hi, lo) pairs, layer 2 runs on the
+        f16 matrix pipe, layer 3 is unchanged -- within the tolerance of the float32 form and several times faster for f2 = 3, 5.
+        A setting of the context like the padding: it survives set_model, a narrow model ignores it, and every other mode still
+        refuses a wide model.  Float calls scale by set_input_range(), byte calls by 255.  A model the split cannot scale
+        (non-finite weights in layers 1-2) is refused at the first call with the option on, and runs with it off."""
+        self._check(self._lib.srcnn_set_wide_split16(self._h, 1 if on else 0))
+
+    def wide_split16(self) -> bool:
+        """srcnn_get_wide_split16."""
+        return int(self._lib.srcnn_get_wide_split16(self._h)) == 1
 
     def set_model_blob(self, blob):
         self.set_model(*split_model(blob))

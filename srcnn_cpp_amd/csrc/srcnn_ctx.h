@@ -187,13 +187,19 @@ struct srcnn_ctx {
     // lives in sp_table alone, in the layout of wide_table_floats() (srcnn_kernels.h), and sp_map64 / sp_map32 hold n1p / n2p
     // planes; it runs in SRCNN_MODE_MFMA through forward_banded() and nowhere else.
     int n1 = 64, n2 = 32, n1p = 64, n2p = 32;
+    // srcnn_set_wide_split16: a setting of the context like the padding (kept across model loads).  1: forward_banded() runs
+    // layer 2 of a WIDE model in split f16 (srcnn_wide16_kernels.hip), from the sp16_* state below made for n1p / n2p; a narrow
+    // model ignores it.
+    int wide_split16 = 0;
     srcnn::host::DevBuf sp_table, sp_map64, sp_map32;
     float sp_b3[3] = {0.f, 0.f, 0.f};
     int sp_f2 = 0;
     // SRCNN_MODE_BANDED16 (layer 2 in split f16): a host copy of W2 [32][64][sp_f2][sp_f2] and the bound of the layer-1 map for
     // 8-bit input, max_k (255 sum |w1[k]| + |b1[k]|), both kept by upload_table; the split W2 table (srcnn_kernels.h) and the
     // two power-of-two scales are made from them the first time a call in that mode runs the model (sp16_f2 = 0: not made since
-    // the model was loaded; -1: the model cannot be scaled, the mode refuses it)
+    // the model was loaded; -1: the model cannot be scaled, the mode refuses it).  A wide model keeps the same for
+    // srcnn_set_wide_split16: the padded W2 [n2p][n1p][sp_f2][sp_f2], the bound over its n1p channels, the table of
+    // wide_l2h_table_bytes().
     std::vector<float> sp_w2;
     double sp_l1_bound = 0.0;
     srcnn::host::DevBuf sp16_table;
@@ -204,7 +210,7 @@ struct srcnn_ctx {
     // sum |w1[k]| and |b1[k]| per layer-1 channel, upload_table16 the exponent of W2's scale, and a float call makes its two
     // scales from them.  The W2 table does not depend on the range; the byte entry points keep sp16_scale1 / sp16_unscale.
     float input_range = 255.f;
-    double sp_l1_sum[64] = {}, sp_l1_absb[64] = {};
+    double sp_l1_sum[128] = {}, sp_l1_absb[128] = {};      // (the first n1p of them)
     int sp16_e2 = 0;
     hipEvent_t sp_done = nullptr;
     hipStream_t sp_stream = nullptr;
@@ -380,9 +386,9 @@ void pack_fragments16(const float *w1, const float *b1, const float *w2, const f
 void split16(float w, float scale, uint16_t *hi, uint16_t *lo);     // f16 bits of hi = f16(w scale), lo = f16(w scale - hi)
 // SRCNN_MODE_BANDED16 (srcnn_spatial.cpp): the layer-1 bound for 8-bit input, the exponent that puts a bound in [2^14, 2^15),
 // and W2 times its power-of-two scale as the split A-operand table of spatial_l2h_kernel (false: the model cannot be scaled)
-double banded16_l1_bound(int C, const float *w1, const float *b1, double range = 255.0);
+double banded16_l1_bound(int C, const float *w1, const float *b1, double range = 255.0, int n1p = 64);
 bool banded16_exponent(double bound, int *e);
-bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2);
+bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2, int n1p = 64, int n2p = 32);
 bool split16_range_ok(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3);
 int upload_weights(srcnn_ctx *c, const float *k99, const float *b99, const float *k11, const float *b11, const float *k55, float b55);
 int use_layers12(srcnn_ctx *c, const float *kernel99, const float *bias99, const float *kernel11, const float *bias11);

@@ -344,6 +344,26 @@ struct WideLaunchers {
 void set_wide_launchers(const WideLaunchers &t);
 const WideLaunchers &wide_launchers();          // both null until a unit has called set_wide_launchers
 
+// ---- layer 2 of a wide model in split f16 (srcnn_wide16_kernels.hip; srcnn_set_wide_split16) ----
+// The split W2 table of a model of padded widths n1p / n2p: [n2p / 32 groups][n1p / 16 K steps][f2 * f2 taps][hi, lo][64 lanes]
+// [8 f16]; lane l of group g: output channel 32g + (l & 31), element e of step s: layer-1 channel
+// 64 (s >> 2) + spatial_l2h_channel(s & 3, l >> 5, e).  For n1p = 64 and n2p = 32 this is the table of SRCNN_MODE_BANDED16, byte
+// for byte.
+__host__ __device__ constexpr size_t wide_l2h_table_bytes(int f2, int n1p, int n2p) { return (size_t)(n2p / 32) * (n1p / 16) * f2 * f2 * 2 * 64 * 16; }
+// The kernel's dynamic LDS, that of spatial_l2h_kernel: four window planes [plane][hi, lo] of wide_l2h_ps() 16-byte words and
+// one K step's A fragments: 66 / 93 / 135 KiB for f2 = 1 / 3 / 5
+__host__ __device__ constexpr int wide_l2h_ps(int r2) { return (((16 + 2 * r2) * (64 + 2 * r2) + 7) / 8) * 8 + 4; }
+__host__ __device__ constexpr size_t wide_l2h_lds_bytes(int f2) { return ((size_t)4 * wide_l2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * 16; }
+// Layer 2: launch_spatial_l2's split form over n_steps = n1p / 16 K steps of the split map (layer 1's n1p / 64 launches with
+// split = true and one scale) and n_groups = n2p / 32 groups of 32 output planes (frag: the table above, bias: the n2p floats of
+// the fragment table, unscale = 1 / (layer 1's scale x the W2 scale)).  Handed over like the wide launchers: null until the unit
+// has called set_wide16_launcher, and then srcnn_set_wide_split16(ctx, 1) makes the first wide call fail, nothing runs in its place.
+typedef hipError_t (*Wide16Launcher)(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
+                                     const void *frag, const float *bias, float unscale, int n_steps, int n_groups, float *out,
+                                     long opitch, hipStream_t st);
+void set_wide16_launcher(Wide16Launcher l2h);
+Wide16Launcher wide16_launcher();
+
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);
 

@@ -17,6 +17,10 @@ namespace srcnn {
 static WideLaunchers g_wide_launchers = {nullptr, nullptr};
 void set_wide_launchers(const WideLaunchers &t) { g_wide_launchers = t; }
 const WideLaunchers &wide_launchers() { return g_wide_launchers; }
+// ... and layer 2 of a wide model in split f16 (srcnn_wide16_kernels.hip), the same way
+static Wide16Launcher g_wide16_launcher = nullptr;
+void set_wide16_launcher(Wide16Launcher l2h) { g_wide16_launcher = l2h; }
+Wide16Launcher wide16_launcher() { return g_wide16_launcher; }
 
 namespace host {
 
@@ -63,11 +67,11 @@ static_assert(wide_l2_offset(3, 64) == spatial_l2_offset(3) && wide_l3_offset(3,
               "a 64 / 32 model keeps its table");
 
 // ---- SRCNN_MODE_BANDED16: exact power-of-two scales and the split W2 table (srcnn_spatial_kernels.hip, spatial_l2h_kernel) ----
-// sum |w1[k]| and |b1[k]| of the 64 layer-1 channels (doubles), what the bound below is made from; false when one is not finite
-static bool l1_magnitudes(int C, const float *w1, const float *b1, double *sum, double *absb)
+// sum |w1[k]| and |b1[k]| of the n1p layer-1 channels (doubles), what the bound below is made from; false when one is not finite
+static bool l1_magnitudes(int C, int n1p, const float *w1, const float *b1, double *sum, double *absb)
 {
     bool finite = true;
-    for (int k = 0; k < 64; ++k) {
+    for (int k = 0; k < n1p; ++k) {
         sum[k] = 0.0;
         for (int i = 0; i < C * 81; ++i) sum[k] += std::fabs((double)w1[(size_t)k * C * 81 + i]);
         absb[k] = std::fabs((double)b1[k]);
@@ -76,20 +80,20 @@ static bool l1_magnitudes(int C, const float *w1, const float *b1, double *sum, 
     return finite;
 }
 
-// The largest value layer 1 can give for inputs of magnitude <= range: max over the 64 channels of range sum |w1[k]| + |b1[k]|
-static double l1_bound(const double *sum, const double *absb, double range)
+// The largest value layer 1 can give for inputs of magnitude <= range: max over the n1p channels of range sum |w1[k]| + |b1[k]|
+static double l1_bound(int n1p, const double *sum, const double *absb, double range)
 {
     double bound = 0.0;
-    for (int k = 0; k < 64; ++k) bound = std::max(bound, range * sum[k] + absb[k]);
+    for (int k = 0; k < n1p; ++k) bound = std::max(bound, range * sum[k] + absb[k]);
     return bound;
 }
 
 // ... for 8-bit input (range 255, what the byte entry points use), or the range of a float call (srcnn_set_input_range)
-double banded16_l1_bound(int C, const float *w1, const float *b1, double range)
+double banded16_l1_bound(int C, const float *w1, const float *b1, double range, int n1p)
 {
-    double sum[64], absb[64];
-    if (!l1_magnitudes(C, w1, b1, sum, absb)) return HUGE_VAL;
-    return l1_bound(sum, absb, range);
+    double sum[128], absb[128];
+    if (n1p < 1 || n1p > 128 || !l1_magnitudes(C, n1p, w1, b1, sum, absb)) return HUGE_VAL;
+    return l1_bound(n1p, sum, absb, range);
 }
 
 // e with bound * 2^e in [2^14, 2^15) (0 for a bound of 0); false when the bound is not finite
@@ -105,31 +109,33 @@ bool banded16_exponent(double bound, int *e)
     return true;
 }
 
-// W2 [32][64][f2][f2] times 2^e2 (max |W2| 2^e2 in [2^14, 2^15)) as f16 (hi, lo) pairs, round to nearest, in the A-operand order
-// of spatial_l2h_kernel (srcnn_kernels.h); false when a weight is not finite or the scaled weights leave float32's range
-bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2)
+// W2 [n2p][n1p][f2][f2] times 2^e2 (max |W2| 2^e2 in [2^14, 2^15)) as f16 (hi, lo) pairs, round to nearest, in the A-operand
+// order of spatial_l2h_kernel and wide_l2h_kernel (srcnn_kernels.h: n2p / 32 groups x n1p / 16 K steps; 64 / 32 is the one group
+// of 4 steps of SRCNN_MODE_BANDED16); false when a weight is not finite or the scaled weights leave float32's range
+bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2, int n1p, int n2p)
 {
-    const int taps = f2 * f2;
+    const int taps = f2 * f2, steps = n1p / 16;
     double wmax = 0.0;
-    for (size_t i = 0; i < (size_t)2048 * taps; ++i) {
+    for (size_t i = 0; i < (size_t)n2p * n1p * taps; ++i) {
         if (!std::isfinite(w2[i])) return false;
         wmax = std::max(wmax, std::fabs((double)w2[i]));
     }
     if (!banded16_exponent(wmax, e2) || std::abs(*e2) > 120) return false;
     const float scale = std::ldexp(1.f, *e2);
-    for (int s = 0; s < 4; ++s)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int k = l & 31, ci = spatial_l2h_channel(s, l >> 5, e);
-                    uint16_t *hi = table + ((((size_t)s * taps + tap) * 2) * 64 + l) * 8 + e;
-                    split16(w2[((size_t)k * 64 + ci) * taps + tap], scale, hi, hi + 64 * 8);
-                }
+    for (int g = 0; g < n2p / 32; ++g)
+        for (int s = 0; s < steps; ++s)
+            for (int tap = 0; tap < taps; ++tap)
+                for (int l = 0; l < 64; ++l)
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = 32 * g + (l & 31), ci = 64 * (s >> 2) + spatial_l2h_channel(s & 3, l >> 5, e);
+                        uint16_t *hi = table + (((((size_t)g * steps + s) * taps + tap) * 2) * 64 + l) * 8 + e;
+                        split16(w2[((size_t)k * n1p + ci) * taps + tap], scale, hi, hi + 64 * 8);
+                    }
     return true;
 }
 
 // The table and b3 of a C-channel 9-f2-5 model into sp_table / sp_b3 (pack_spatial's arguments).  A wide model (n1p = 128 or
-// n2p = 64) keeps nothing for SRCNN_MODE_BANDED16, which refuses it.
+// n2p = 64) keeps what the split needs too, for srcnn_set_wide_split16 (SRCNN_MODE_BANDED16 refuses it).
 static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2,
                         const float *w3, const float *b3, int n1p = 64, int n2p = 32)
 {
@@ -141,29 +147,33 @@ static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const floa
     HIP_TRY(c, hipMemcpy(c->sp_table.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
     std::memcpy(c->sp_b3, b3, C * sizeof(float));
     c->sp_f2 = f2;
-    c->sp16_f2 = 0;
-    if (n1p != 64 || n2p != 32) return SRCNN_OK;
-    // what SRCNN_MODE_BANDED16 makes its table and scales from, when a call first runs the model in that mode
-    c->sp_w2.assign(w2, w2 + (size_t)2048 * f2 * f2);
-    c->sp_l1_bound = l1_magnitudes(C, w1, b1, c->sp_l1_sum, c->sp_l1_absb) ? l1_bound(c->sp_l1_sum, c->sp_l1_absb, 255.0) : HUGE_VAL;
+    // what SRCNN_MODE_BANDED16 (a wide model: srcnn_set_wide_split16) makes its table and scales from, when a call first runs the
+    // model that way
+    c->sp_w2.assign(w2, w2 + (size_t)n2p * n1p * f2 * f2);
+    c->sp_l1_bound = l1_magnitudes(C, n1p, w1, b1, c->sp_l1_sum, c->sp_l1_absb) ? l1_bound(n1p, c->sp_l1_sum, c->sp_l1_absb, 255.0) : HUGE_VAL;
     c->sp16_f2 = 0;
     return SRCNN_OK;
 }
 
-// The split W2 table and the scales of SRCNN_MODE_BANDED16 for the model in sp_table, made once per loaded model
+// What refuses a model the split cannot scale: the mode, or for a wide model the option
+static const char *split_name(const srcnn_ctx *c) { return wide_model(c) ? "srcnn_set_wide_split16" : "SRCNN_MODE_BANDED16"; }
+static const char *split_way_out(const srcnn_ctx *c) { return wide_model(c) ? "switch the option off" : "use SRCNN_MODE_MFMA"; }
+
+// The split W2 table and the scales of SRCNN_MODE_BANDED16 (a wide model: of srcnn_set_wide_split16, for its n1p / n2p) for the
+// model in sp_table, made once per loaded model
 static int upload_table16(srcnn_ctx *c)
 {
     if (c->sp16_f2 == c->sp_f2) return SRCNN_OK;
-    const char *const refuse = "SRCNN_MODE_BANDED16 cannot scale this model into f16 (a weight or bias of layers 1-2 is not finite, "
-                               "or their magnitudes are beyond float32's exponent range); use SRCNN_MODE_MFMA";
-    if (c->sp16_f2 < 0) return fail(c, SRCNN_ERR_STATE, "%s", refuse);
-    const int f2 = c->sp_f2;
+    const char *const refuse = "%s cannot scale this model into f16 (a weight or bias of layers 1-2 is not finite, "
+                               "or their magnitudes are beyond float32's exponent range); %s";
+    if (c->sp16_f2 < 0) return fail(c, SRCNN_ERR_STATE, refuse, split_name(c), split_way_out(c));
+    const int f2 = c->sp_f2, n1p = c->n1p, n2p = c->n2p;
     int e1 = 0, e2 = 0;
-    std::vector<uint16_t> table(spatial_l2h_table_bytes(f2) / sizeof(uint16_t));
-    if (!banded16_exponent(c->sp_l1_bound, &e1) || !banded16_pack_w2(f2, c->sp_w2.data(), table.data(), &e2) ||
-        std::abs(e1 + e2) > 120) {
+    std::vector<uint16_t> table(wide_l2h_table_bytes(f2, n1p, n2p) / sizeof(uint16_t));
+    if (c->sp_w2.size() != (size_t)n2p * n1p * f2 * f2 || !banded16_exponent(c->sp_l1_bound, &e1) ||
+        !banded16_pack_w2(f2, c->sp_w2.data(), table.data(), &e2, n1p, n2p) || std::abs(e1 + e2) > 120) {
         c->sp16_f2 = -1;
-        return fail(c, SRCNN_ERR_STATE, "%s", refuse);
+        return fail(c, SRCNN_ERR_STATE, refuse, split_name(c), split_way_out(c));
     }
     int rc;
     if ((rc = reserve(c, c->sp16_table, table.size() * sizeof(uint16_t)))) return rc;
@@ -275,24 +285,28 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
         const float *hr = c->host_raw.data();
         if ((rc = upload_table(c, 1, 1, hr + 64, hr, hr + 5280, hr + 5248, hr + 7329, hr + 7328))) return rc;
     }
-    const bool split = c->mode == SRCNN_MODE_BANDED16;
+    // (n1p / n2p = 64 / 32 but for a model of srcnn_set_model_shape: 4 (n1p + n2p) bytes per pixel of a row)
+    const int n1p = c->n1p, n2p = c->n2p;
+    const bool wide = wide_model(c);
+    // layer 2 in split f16: the mode, or for a wide model (which the gate lets run in SRCNN_MODE_MFMA only) the option
+    const bool split = wide ? c->wide_split16 != 0 : c->mode == SRCNN_MODE_BANDED16;
+    if (split && wide && !wide16_launcher())       // (a missing kernel is an error; the library always holds the unit)
+        return fail(c, SRCNN_ERR_STATE, "srcnn_set_wide_split16: layer 2 of a wide model in split f16 needs the kernels of "
+                                        "srcnn_wide16_kernels.hip, which this build does not hold; switch the option off");
     if (split && (rc = upload_table16(c))) return rc;
     // a float call scales the layer-1 map by the bound for inputs up to input_range, not 255: the same W2 table, other scales
     float scale1 = c->sp16_scale1, unscale = c->sp16_unscale;
     if (split && io.f32) {
         int e1 = 0;
-        if (!banded16_exponent(l1_bound(c->sp_l1_sum, c->sp_l1_absb, (double)c->input_range), &e1) || std::abs(e1 + c->sp16_e2) > 120)
-            return fail(c, SRCNN_ERR_STATE, "SRCNN_MODE_BANDED16 cannot scale this model into f16 for inputs up to %g "
-                                            "(srcnn_set_input_range); use SRCNN_MODE_MFMA", (double)c->input_range);
+        if (!banded16_exponent(l1_bound(n1p, c->sp_l1_sum, c->sp_l1_absb, (double)c->input_range), &e1) || std::abs(e1 + c->sp16_e2) > 120)
+            return fail(c, SRCNN_ERR_STATE, "%s cannot scale this model into f16 for inputs up to %g "
+                                            "(srcnn_set_input_range); %s", split_name(c), (double)c->input_range, split_way_out(c));
         scale1 = std::ldexp(1.f, e1);
         unscale = std::ldexp(1.f, -(e1 + c->sp16_e2));
     }
     const int C = c->channels, r2 = (c->f2 - 1) / 2;
     const bool zero = c->padding == SRCNN_PAD_ZERO;
     const long row_bytes = 4L * width;
-    // (n1p / n2p = 64 / 32 but for a model of srcnn_set_model_shape: 4 (n1p + n2p) bytes per pixel of a row)
-    const int n1p = c->n1p, n2p = c->n2p;
-    const bool wide = wide_model(c);
     const long cap = (long)(kSpatialWorkBytes / (size_t)row_bytes) - (long)n1p * (4 + 2 * r2) - (long)n2p * 4;
     const int band_max = (int)std::max(16L, cap / (n1p + n2p));
     const int row_begin = io.rows ? io.row_begin : 0, row_end = io.rows ? io.row_end : height;
@@ -335,12 +349,19 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
             if (wide) {
                 // a wide model: layer 1 group by group (64 output channels each: its own table, its own planes of the map),
-                // layer 2 over n1p / 8 chunks and n2p / 32 output groups, layer 3 from 64 maps where there are 64
+                // layer 2 over n1p / 8 chunks and n2p / 32 output groups, layer 3 from 64 maps where there are 64.  split
+                // (srcnn_set_wide_split16): each group's 64 planes as 8 planes of f16 (hi, lo) pixels, all with the model's one
+                // scale, and layer 2 over n1p / 16 K steps on the f16 MFMA
                 for (int g = 0; g < n1p / 64; ++g)
-                    HIP_TRY(c, launch_spatial_l1(in, zero, false, 1.f, width, height, m0, m1, frag + (size_t)g * C * SPATIAL_NFRAG_L1 * 64,
-                                                 map64 + (size_t)g * 64 * mpitch, mpitch, c->stream));
-                HIP_TRY(c, wide_launchers().l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, n1p / 8, n2p / 32,
-                                               map32, opitch, c->stream));
+                    HIP_TRY(c, launch_spatial_l1(in, zero, split, split ? scale1 : 1.f, width, height, m0, m1,
+                                                 frag + (size_t)g * C * SPATIAL_NFRAG_L1 * 64, map64 + (size_t)g * 64 * mpitch, mpitch,
+                                                 c->stream));
+                if (split)
+                    HIP_TRY(c, wide16_launcher()(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, c->sp16_table.p, bias2, unscale,
+                                                 n1p / 16, n2p / 32, map32, opitch, c->stream));
+                else
+                    HIP_TRY(c, wide_launchers().l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, n1p / 8,
+                                                   n2p / 32, map32, opitch, c->stream));
                 if (n2p > 32) {
                     HIP_TRY(c, wide_launchers().l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, c->stream));
                     continue;
@@ -501,7 +522,41 @@ int srcnn_get_model_shape(const srcnn_ctx *c, int *channels, int *n1, int *f2, i
     return SRCNN_OK;
 }
 
+int srcnn_set_wide_split16(srcnn_ctx *c, int on)
+{
+    if (!c) return SRCNN_ERR_INVALID;
+    if (on != 0 && on != 1) return fail(c, SRCNN_ERR_INVALID, "srcnn_set_wide_split16: %d (0: layer 2 of a wide model in float32, 1: in split f16)", on);
+    c->wide_split16 = on;      // read when a call launches, like the padding; a model that cannot be scaled is refused there
+    return SRCNN_OK;
+}
+
+int srcnn_get_wide_split16(const srcnn_ctx *c) { return c ? c->wide_split16 : SRCNN_ERR_INVALID; }
+
 #ifdef SRCNN_TUNING_BUILD
+/* Undocumented test hook (not part of the ABI, needs no device): the host side of srcnn_set_wide_split16 for a model of `channels`
+ * channels padded to n1p (64 or 128) / n2p (32 or 64) filters: w1 [n1p][channels][9][9], b1 [n1p], w2 [n2p][n1p][f2][f2], `range`
+ * the largest |input| (255 for the byte entry points).  table: wide_l2h_table_bytes(f2, n1p, n2p) bytes or null; exps: {e1, e2}.
+ * Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the option refuses. */
+int srcnn_debug_wide16_tables(int channels, int n1p, int n2p, int f2, const float *w1, const float *b1, const float *w2, float range,
+                              uint16_t *table, int *exps)
+{
+    if ((channels != 1 && channels != 3) || (n1p != 64 && n1p != 128) || (n2p != 32 && n2p != 64) || (f2 != 1 && f2 != 3 && f2 != 5) ||
+        !w1 || !b1 || !w2 || !exps || !std::isfinite(range) || !(range > 0.f))
+        return SRCNN_ERR_INVALID;
+    std::vector<uint16_t> own;
+    if (!table) {
+        own.resize(wide_l2h_table_bytes(f2, n1p, n2p) / sizeof(uint16_t));
+        table = own.data();
+    }
+    if (!banded16_exponent(banded16_l1_bound(channels, w1, b1, (double)range, n1p), &exps[0]) ||
+        !banded16_pack_w2(f2, w2, table, &exps[1], n1p, n2p) || std::abs(exps[0] + exps[1]) > 120)
+        return SRCNN_ERR_STATE;
+    return (int)wide_l2h_table_bytes(f2, n1p, n2p);
+}
+
+/* ... and the dynamic LDS the launcher of wide_l2h_kernel asks for (wide_l2h_lds_bytes; the kernel asserts it is its layout's). */
+int srcnn_debug_wide16_lds_bytes(int f2) { return (f2 != 1 && f2 != 3 && f2 != 5) ? SRCNN_ERR_INVALID : (int)wide_l2h_lds_bytes(f2); }
+
 /* Undocumented test hook (not part of the ABI, needs no device): the host side of SRCNN_MODE_BANDED16 for a model of `channels`
  * channels.  table: spatial_l2h_table_bytes(f2) bytes or null; exps: {e1, e2}, the exponents of the layer-1 map's and W2's
  * scales.  Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the mode refuses. */

@@ -367,8 +367,9 @@ def compile_module(module, device: int = 0, mode: int = MODE_MFMA, input_range: 
     with padding_mode "zeros" or "replicate") -> a callable on float32 CUDA tensors that computes module(x) with this library's
     HIP kernels.  mode: MODE_MFMA (float32 throughout) or MODE_BANDED16 (layer 2 in split f16, faster; input_range is then the
     largest |x| the tensors will hold, 1.0 for [0, 1] data).  The weights are read once, here: a module trained further needs a
-    new compile_module.  The filters: conv1 up to 128, conv2 up to 64 (64 / 32 is the classic model); more than 64 / 32 run in
-    MODE_MFMA only."""
+    new compile_module.  The filters: conv1 up to 128, conv2 up to 64 (64 / 32 is the classic model).  MODE_BANDED16 is the
+    fast mode for every width: a module wider than 64 / 32 keeps its context in MODE_MFMA, the only mode that runs such a model,
+    with Context.set_wide_split16(True) -- the same split-f16 layer 2, the same input_range."""
     if mode not in (MODE_MFMA, MODE_BANDED16):
         raise ValueError(f"mode {mode}: the float image path runs in MODE_MFMA and MODE_BANDED16 only")
     conv1 = getattr(module, "conv1", None)
@@ -382,7 +383,12 @@ def compile_module(module, device: int = 0, mode: int = MODE_MFMA, input_range: 
     try:
         ctx.set_model(*model)
         ctx.set_padding(padding)
-        ctx.set_mode(mode)
+        _, n1, _, n2 = ctx.model_shape()
+        if mode == MODE_BANDED16 and (n1 > 64 or n2 > 32):
+            ctx.set_mode(MODE_MFMA)
+            ctx.set_wide_split16(True)
+        else:
+            ctx.set_mode(mode)
         ctx.set_input_range(input_range)
     except Exception:
         ctx.close()

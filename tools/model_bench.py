@@ -21,7 +21,9 @@ reports the float times beside the byte times with their ratio (f32 / u8) per mo
 --widths N1xN2 ... times models of those filter counts (srcnn_set_model_shape; default 64x32, the models of the other loaders).
 Each row then also carries the MFMAs per 32 pixels of the padded model, the FLOP they execute per pixel (128 per MFMA) and the
 fraction of the peak in EXECUTED FLOP, the figure to compare rows of different widths by.  Wide models (more than 64 / 32
-filters) run in SRCNN_MODE_MFMA only.
+filters) run in SRCNN_MODE_MFMA only: for them --mode banded16 / both times the OPTION srcnn_set_wide_split16 (layer 2 in split
+f16, the mode staying SRCNN_MODE_MFMA) instead of the mode, under the same keys (..._banded16, banded16_over_mfma), and the row
+says so in "split_form": "wide_split16".  Both forms of a configuration run in one process, the float32 form first.
 """
 import argparse
 import json
@@ -116,17 +118,22 @@ def main():
     args = ap.parse_args()
     paddings = ["replicate", "zero"] if args.padding == "both" else [args.padding]
     widths = [tuple(map(int, v.split("x"))) for v in args.widths]
-    if args.mode != "mfma" and any(n1 > 64 or n2 > 32 for n1, n2 in widths):
-        ap.error("models of more than 64 / 32 filters run in --mode mfma only")
     rows = []
+
+    def set_form(ctx, split, wide):
+        """Layer 2 in float32 or in split f16: the mode for a 64 / 32 model, the option (in SRCNN_MODE_MFMA) for a wide one."""
+        ctx.set_mode(S.MODE_BANDED16 if split and not wide else S.MODE_MFMA)
+        ctx.set_wide_split16(split and wide)
+
     with S.Context(0) as ctx:
         for channels, f2, (n1, n2) in ((c, f, v) for c in args.channels for f in args.f2 for v in widths):
             ctx.set_model(*(color_model(f2, 0, n1, n2) if channels == 3 else model(f2, 0, n1, n2)))
+            wide = n1 > 64 or n2 > 32
             for size in args.sizes:
                 w, h = map(int, size.split("x"))
                 for padding in paddings:
                     ctx.set_padding(padding)
-                    ctx.set_mode(S.MODE_BANDED16 if args.mode == "banded16" else S.MODE_MFMA)
+                    set_form(ctx, args.mode == "banded16", wide)
                     first = "u8" if "u8" in args.dtype else "f32"
                     med, best = time_plane(ctx, w, h, args.steps, args.warmup, channels, first)
                     px = w * h
@@ -150,16 +157,19 @@ def main():
                             row["fraction_of_peak_executed_f32"] = round(128 * n_mfma * px / (medf * 1e-3) / 1e12 / PEAK_TFLOPS, 3)
                     if args.mode != "mfma":
                         row["mode"] = "mfma" if args.mode == "both" else "banded16"
+                        if wide:
+                            row["split_form"] = "wide_split16"
                     if args.mode == "both":
-                        ctx.set_mode(S.MODE_BANDED16)
+                        set_form(ctx, True, wide)
                         med16, best16 = time_plane(ctx, w, h, args.steps, args.warmup, channels, first)
                         row.update(mode="both", ms_per_plane_banded16=round(med16, 3), ms_min_banded16=round(best16, 3),
                                    banded16_over_mfma=round(med16 / med, 3))
                         if both_dtypes:
                             med16f, best16f = time_plane(ctx, w, h, args.steps, args.warmup, channels, "f32")
                             row.update(ms_per_plane_banded16_f32=round(med16f, 3), ms_min_banded16_f32=round(best16f, 3),
-                                       banded16_f32_over_u8=round(med16f / med16, 3))
-                        ctx.set_mode(S.MODE_MFMA)
+                                       banded16_f32_over_u8=round(med16f / med16, 3),
+                                       banded16_over_mfma_f32=round(med16f / medf, 3))
+                        set_form(ctx, False, wide)
                     rows.append(row)
                     print(json.dumps(row), flush=True)
     if args.json:
