@@ -622,13 +622,53 @@ int srcnn_resize_cubic_aa_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int 
  *   - SRCNN_ERR_INVALID, with nothing launched and the context usable: a descriptor srcnn_image_check(.., is_dst = 0) refuses,
  *     channels other than 1 and 3, a luma with other than 3 channels, a non-finite luma, a data_range that is not finite or not
  *     > 0, a negative border, an empty region, SSIM on a region under 11 x 11, flags of 0 or with unknown bits, a null d_out.
- *   Out of scope: MS-SSIM and the uniform-window SSIM; rounding the luma to 8 bits as MATLAB's rgb2ycbcr does on uint8;
+ *   Out of scope: the uniform-window SSIM; rounding the luma to 8 bits as MATLAB's rgb2ycbcr does on uint8;
  *   host-memory forms; several GPUs; the command-line tool; returning an SSIM map. */
 enum { SRCNN_METRIC_SSE = 1, SRCNN_METRIC_SSIM = 2 };
 int srcnn_metrics_image_dev(srcnn_ctx *ctx, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
                             int n_frames, int border, const float *luma /* NULL or [4] */, double data_range, int flags,
                             double *d_out /* [n_frames][P][4] */);
 double srcnn_metric_psnr(double sse, double n_px, double data_range);
+
+/* MS-SSIM (Wang, Simoncelli and Bovik 2003) between two images as they are stored: per scale, the sum of the
+ * contrast-structure term and the sum of the SSIM over the valid windows -- raw sums per frame and scale, on the device,
+ * deterministic to the bit.  Everything srcnn_metrics_image_dev states about the inputs, the load, the luma, float64 and the
+ * window holds here; what follows is what differs.
+ *   - Inputs: a, b, width, height, channels (1 or 3), n_frames, luma (NULL or {w0, w1, w2, offset}, 3 channels only) and
+ *     data_range as srcnn_metrics_image_dev takes them.  P = results per frame (1 with a luma, else channels).
+ *   - border >= 0 is shaved off every side AT SCALE 0 ONLY.  The region is h' x w'.
+ *   - Scales: n_scales = S, 1 <= S <= 5.  Scale 0 is the region.  Scale j + 1 is scale j reduced by 2 x 2 means over blocks
+ *     that start at the region's origin,
+ *         out(y, x) = ((p(2y, 2x) + p(2y, 2x+1)) + (p(2y+1, 2x) + p(2y+1, 2x+1))) * 0.25      (float64, every sum rounded on its own)
+ *     with an odd last row or column paired with itself (the index is clamped), so scale j has ceil(h' / 2^j) x ceil(w' / 2^j)
+ *     pixels.  This is the ones(2)/4, 'symmetric', 1:2:end reduction of the authors' own implementation; an average pooling
+ *     that drops the odd row or column agrees with it at even sizes only.
+ *   - Per scale: the 11-tap window, the valid windows, the separable passes and the fma order of the SSIM above, and per window
+ *         cs   = (2 (E[ab] - mu_a mu_b) + C2) / (((E[a^2] - mu_a^2) + (E[b^2] - mu_b^2)) + C2)
+ *         ssim = ((2 mu_a mu_b + C1) (2 (E[ab] - mu_a mu_b) + C2))
+ *                / (((mu_a^2 + mu_b^2) + C1) (((E[a^2] - mu_a^2) + (E[b^2] - mu_b^2)) + C2)),
+ *     the second being the SSIM above, operation for operation.  Both are symmetric in a and b, and identical pictures give
+ *     exactly 1.0 per window for both.
+ *   - Output: d_out[((f P + p) S + s) 3 + k] = {cs_sum, ssim_sum, n_win} of scale s, n_win = (h_s - 10) (w_s - 10): raw sums
+ *     in float64 on the device; nothing is read back.  Sums of stripes or of several devices merge by addition per scale.
+ *   - Size rule: every scale needs 11 x 11, so h', w' >= 10 * 2^(S - 1) + 1: 161 for S = 5, 21 for S = 2.
+ *   - Determinism: no floating-point atomic.  One partial per workgroup into a workspace the context owns (it also holds the
+ *     float64 planes of the scales >= 1; grown on demand, freed with the context), added by a finishing kernel in a fixed
+ *     order.  Tiles and orders depend on h', w' and S only: the same call twice gives the same bits, a frame's sums do not
+ *     depend on its batch, and a and b swapped give the same bits.
+ *   - srcnn_msssim_image_dev is asynchronous on the context's stream, needs no model and runs in every mode.
+ *   - srcnn_metric_msssim: host only (no context, no GPU), from the [n_scales][3] sums of one result:
+ *         prod_{s < S-1} max(cs_sum_s / n_win_s, 0)^w_s  *  max(ssim_sum_{S-1} / n_win_{S-1}, 0)^w_{S-1}.
+ *     weights == NULL means the authors' (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) and requires n_scales == 5.  A mean that is
+ *     not positive contributes the factor 0, whatever its weight: a power of a negative number is never formed.  A NaN for a
+ *     null or NaN input, n_win <= 0, n_scales outside 1 .. 5, or NULL weights with another S.
+ *   - SRCNN_ERR_INVALID, with nothing launched and the context usable: what srcnn_metrics_image_dev refuses of the arguments the
+ *     two share, n_scales outside 1 .. 5, and a region smaller than the size rule allows (the message names S and the minimum).
+ *   Out of scope: MATLAB's 8-bit luma rounding; an SSIM map; host-memory forms; the command-line tool. */
+int srcnn_msssim_image_dev(srcnn_ctx *ctx, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
+                           int n_frames, int border, const float *luma /* NULL or [4] */, double data_range, int n_scales,
+                           double *d_out /* [n_frames][P][n_scales][3] */);
+double srcnn_metric_msssim(const double *sums /* [n_scales][3] */, int n_scales, const double *weights /* NULL or [n_scales] */);
 
 /* Convolution99x11 + Convolution55 in ONE fused kernel: u8 luma in, u8 luma
  * out, the 32-channel map never leaves the CU.  preclamp (optional, may be

@@ -71,6 +71,10 @@ ELEM_SIZE = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
 # what metrics_image_dev measures (SRCNN_METRIC_*): flags, and the fields of one result
 METRIC_SSE, METRIC_SSIM = 1, 2
 METRIC_FIELDS = ("sse", "n_px", "ssim_sum", "n_win")
+# what msssim_image_dev returns per scale, the most scales it takes, and the weights of Wang, Simoncelli and Bovik for five
+MSSSIM_FIELDS = ("cs_sum", "ssim_sum", "n_win")
+MSSSIM_MAX_SCALES = 5
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_NODEVICE, ERR_STATE = -1, -2, -3, -4, -5      # include/srcnn_amd.h
 _ERR = {-1: "invalid argument", -2: "HIP runtime error", -3: "out of memory",
@@ -168,6 +172,8 @@ def load_library() -> C.CDLL:
         "srcnn_resize_cubic_aa_image_dev": ([vp, imp, i, i, imp, i, i, i, i], i),
         "srcnn_metrics_image_dev": ([vp, imp, imp, i, i, i, i, i, _f32p, C.c_double, i, vp], i),
         "srcnn_metric_psnr": ([C.c_double, C.c_double, C.c_double], C.c_double),
+        "srcnn_msssim_image_dev": ([vp, imp, imp, i, i, i, i, i, _f32p, C.c_double, i, vp], i),
+        "srcnn_metric_msssim": ([C.POINTER(C.c_double), i, C.POINTER(C.c_double)], C.c_double),
         "srcnn_process_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i], i),
         "srcnn_process_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i], i),
         "srcnn_luma_gain": ([_f32p, _f32p], i),
@@ -260,7 +266,7 @@ ABI_SYMBOLS = (
     "srcnn_image_check", "srcnn_forward_image_dev", "srcnn_resize_cubic_image_dev", "srcnn_process_image_dev",
     "srcnn_process_rgb_image_dev",
     "srcnn_cubic_aa_f32_taps", "srcnn_resize_cubic_aa_f32", "srcnn_resize_cubic_aa_f32_dev", "srcnn_resize_cubic_aa_image_dev",
-    "srcnn_metrics_image_dev", "srcnn_metric_psnr",
+    "srcnn_metrics_image_dev", "srcnn_metric_psnr", "srcnn_msssim_image_dev", "srcnn_metric_msssim",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -822,6 +828,15 @@ class Context:
         self._check(self._lib.srcnn_metrics_image_dev(self._h, C.byref(ca), C.byref(cb), int(width), int(height), int(channels),
                                                       int(n_frames), int(border), luma4, float(data_range), int(flags), d_out))
 
+    def msssim_image_dev(self, a: "Image", b: "Image", width, height, channels, n_frames, border, luma, data_range, n_scales, d_out):
+        """srcnn_msssim_image_dev: {cs_sum, ssim_sum, n_win} per (frame, result, scale) of two stored images, float64 after the
+        load, into device memory at d_out (n_frames * P * n_scales * 3 doubles; P = 1 with a luma, else channels).  The border is
+        shaved at scale 0; scale j + 1 is the 2 x 2 mean of scale j; n_scales: 1 .. 5, and the region at least
+        10 * 2^(n_scales - 1) + 1 on a side.  Asynchronous on the context's stream; needs no model."""
+        luma4, ca, cb = _metric_luma4(luma), a.c(), b.c()      # refused here, before the library is reached
+        self._check(self._lib.srcnn_msssim_image_dev(self._h, C.byref(ca), C.byref(cb), int(width), int(height), int(channels),
+                                                     int(n_frames), int(border), luma4, float(data_range), int(n_scales), d_out))
+
     def process_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, n_frames=1):
         """srcnn_process_image_dev: process_f32_dev (resize + model) on stored images."""
         self._check(self._lib.srcnn_process_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
@@ -1291,6 +1306,22 @@ def metric_psnr(sse: float, n_px: float, data_range: float = 1.0) -> float:
     """10 log10(L^2 n_px / sse) from the sums metrics_image_dev returns (srcnn_metric_psnr; host only, needs no GPU): inf for
     sse == 0, nan for arguments that are no sums."""
     return float(load_library().srcnn_metric_psnr(float(sse), float(n_px), float(data_range)))
+
+
+def metric_msssim(sums, weights=None) -> float:
+    """MS-SSIM from the (n_scales, 3) sums msssim_image_dev returns for one result (srcnn_metric_msssim; host only, needs no
+    GPU): the product over the scales of max(mean, 0)^w, the mean of cs below the last scale and of ssim at it.  weights=None:
+    MSSSIM_WEIGHTS, which needs five scales.  nan for arguments that are no sums; 0 where a mean is not positive."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError(f"sums of shape {s.shape}: expected (n_scales, 3) rows of (cs_sum, ssim_sum, n_win)")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != s.shape[0]:
+            raise ValueError(f"{w.size} weights for {s.shape[0]} scales")
+    dp = C.POINTER(C.c_double)
+    return float(load_library().srcnn_metric_msssim(s.ctypes.data_as(dp), int(s.shape[0]), None if w is None else w.ctypes.data_as(dp)))
 
 
 def _clamp2(clamp):

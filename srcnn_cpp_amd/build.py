@@ -56,6 +56,8 @@ UNITS = [
     # the metrics: float64 throughout; the SSIM formula and the luma as written, every product and sum rounded on its own (the
     # window sums use explicit fused multiply-adds), so identical pictures give exactly 1.0 per window
     ("srcnn_metrics.hip", ["-ffp-contract=off"]),
+    # ... and MS-SSIM (srcnn_msssim_image_dev): the 2 x 2 means of its scales and the same window arithmetic, the same flag
+    ("srcnn_msssim.hip", ["-ffp-contract=off"]),
     ("srcnn_api.cpp", ["-x", "hip"]),
     ("srcnn_model.cpp", ["-x", "hip"]),
     ("srcnn_plan.cpp", ["-x", "hip"]),

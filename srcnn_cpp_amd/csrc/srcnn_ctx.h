@@ -252,6 +252,10 @@ struct srcnn_ctx {
     // last launch that wrote them
     srcnn::host::DevBuf metric_work;
     hipStream_t metric_stream = nullptr;
+    // MS-SSIM (srcnn_msssim_image_dev): the float64 planes of the scales >= 1 and the per-workgroup partial sums of one call, in
+    // one buffer (grown on demand), and the stream of the last launch that wrote it
+    srcnn::host::DevBuf msssim_work;
+    hipStream_t msssim_stream = nullptr;
     // second lane of the host-frame pipeline (srcnn_forward_y_frames)
     // explicit work items of single-round launches (build_items): a small cache of device tables, one per
     // launch geometry, so that a caller alternating between a few plane sizes never waits for an upload

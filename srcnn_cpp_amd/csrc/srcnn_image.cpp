@@ -253,7 +253,58 @@ int process_rgb_frames_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src
 }
 
 }  // namespace host
+
+static MsssimLauncher g_msssim_launcher = nullptr;
+void set_msssim_launcher(MsssimLauncher l) { g_msssim_launcher = l; }
+MsssimLauncher msssim_launcher() { return g_msssim_launcher; }
 }  // namespace srcnn
+
+namespace {
+
+// what srcnn_metrics_image_dev and srcnn_msssim_image_dev refuse alike, up to the region the border leaves: rw x rh
+int metric_args_refusal(srcnn_ctx *c, const char *what, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
+                        int n_frames, int border, const float *luma, double data_range, long *rw_out, long *rh_out)
+{
+    if (image_check(a, width, height, channels, n_frames, 0)) return fail(c, SRCNN_ERR_INVALID, "%s: bad image a (srcnn_image_check)", what);
+    if (image_check(b, width, height, channels, n_frames, 0)) return fail(c, SRCNN_ERR_INVALID, "%s: bad image b (srcnn_image_check)", what);
+    if (channels != 1 && channels != 3) return fail(c, SRCNN_ERR_INVALID, "%s: %d channels: expected 1 or 3", what, channels);
+    if (luma && channels != 3)
+        return fail(c, SRCNN_ERR_INVALID, "%s: a luma needs 3 channels, the images have %d (pass NULL to measure the plane itself)", what, channels);
+    if (luma && !(std::isfinite(luma[0]) && std::isfinite(luma[1]) && std::isfinite(luma[2]) && std::isfinite(luma[3])))
+        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset}", what);
+    if (!(std::isfinite(data_range) && data_range > 0.0))
+        return fail(c, SRCNN_ERR_INVALID, "%s: data_range %g: expected a finite number > 0", what, data_range);
+    if (border < 0) return fail(c, SRCNN_ERR_INVALID, "%s: border %d: expected >= 0", what, border);
+    const long rw = (long)width - 2L * border, rh = (long)height - 2L * border;
+    if (rw < 1 || rh < 1)
+        return fail(c, SRCNN_ERR_INVALID, "%s: a border of %d leaves nothing of a %d x %d image", what, border, width, height);
+    *rw_out = rw;
+    *rh_out = rh;
+    return SRCNN_OK;
+}
+
+// the region: the first pixel inside the border becomes element (0, 0)
+ImageRef metric_region(const srcnn_image *im, int width, int height, int channels, int n_frames, int border)
+{
+    ImageRef r = image_ref(im, width, height, channels, n_frames);
+    r.data = static_cast<char *>(r.data) + ((size_t)border * (size_t)r.stride + (size_t)border * (size_t)r.px_step) * elem_size(r.elem);
+    return r;
+}
+
+// the window in float64: exp(-(i - 5)^2 / 4.5), divided by the sum taken in ascending order; and C1, C2 of a data range
+void metric_constants(double data_range, double g[METRIC_WIN], double *c1, double *c2)
+{
+    double total = 0.0;
+    for (int k = 0; k < METRIC_WIN; ++k) {
+        g[k] = std::exp(-(double)((k - 5) * (k - 5)) / 4.5);
+        total += g[k];
+    }
+    for (int k = 0; k < METRIC_WIN; ++k) g[k] /= total;
+    *c1 = (0.01 * data_range) * (0.01 * data_range);
+    *c2 = (0.03 * data_range) * (0.03 * data_range);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -363,19 +414,8 @@ int srcnn_metrics_image_dev(srcnn_ctx *c, const srcnn_image *a, const srcnn_imag
     BIND(c);
     int rc;
     const char *what = "metrics_image_dev";
-    if (image_check(a, width, height, channels, n_frames, 0)) return fail(c, SRCNN_ERR_INVALID, "%s: bad image a (srcnn_image_check)", what);
-    if (image_check(b, width, height, channels, n_frames, 0)) return fail(c, SRCNN_ERR_INVALID, "%s: bad image b (srcnn_image_check)", what);
-    if (channels != 1 && channels != 3) return fail(c, SRCNN_ERR_INVALID, "%s: %d channels: expected 1 or 3", what, channels);
-    if (luma && channels != 3)
-        return fail(c, SRCNN_ERR_INVALID, "%s: a luma needs 3 channels, the images have %d (pass NULL to measure the plane itself)", what, channels);
-    if (luma && !(std::isfinite(luma[0]) && std::isfinite(luma[1]) && std::isfinite(luma[2]) && std::isfinite(luma[3])))
-        return fail(c, SRCNN_ERR_INVALID, "%s: luma must be four finite floats {w0, w1, w2, offset}", what);
-    if (!(std::isfinite(data_range) && data_range > 0.0))
-        return fail(c, SRCNN_ERR_INVALID, "%s: data_range %g: expected a finite number > 0", what, data_range);
-    if (border < 0) return fail(c, SRCNN_ERR_INVALID, "%s: border %d: expected >= 0", what, border);
-    const long rw = (long)width - 2L * border, rh = (long)height - 2L * border;
-    if (rw < 1 || rh < 1)
-        return fail(c, SRCNN_ERR_INVALID, "%s: a border of %d leaves nothing of a %d x %d image", what, border, width, height);
+    long rw, rh;
+    if ((rc = metric_args_refusal(c, what, a, b, width, height, channels, n_frames, border, luma, data_range, &rw, &rh))) return rc;
     if (!flags || (flags & ~(SRCNN_METRIC_SSE | SRCNN_METRIC_SSIM)))
         return fail(c, SRCNN_ERR_INVALID, "%s: flags %#x: expected SRCNN_METRIC_SSE, SRCNN_METRIC_SSIM or both", what, (unsigned)flags);
     if ((flags & SRCNN_METRIC_SSIM) && (rw < METRIC_WIN || rh < METRIC_WIN))
@@ -383,20 +423,9 @@ int srcnn_metrics_image_dev(srcnn_ctx *c, const srcnn_image *a, const srcnn_imag
     if (!d_out) return fail(c, SRCNN_ERR_INVALID, "%s: null output", what);
     const int per_frame = luma ? 1 : channels;
     if ((long)per_frame * n_frames > 0x7fffffffL) return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
-    // the region: the first pixel inside the border becomes element (0, 0)
-    auto region = [&](const srcnn_image *im) {
-        ImageRef r = image_ref(im, width, height, channels, n_frames);
-        r.data = static_cast<char *>(r.data) + ((size_t)border * (size_t)r.stride + (size_t)border * (size_t)r.px_step) * elem_size(r.elem);
-        return r;
-    };
-    // the window in float64: exp(-(i - 5)^2 / 4.5), divided by the sum taken in ascending order
-    double g[METRIC_WIN], total = 0.0;
-    for (int k = 0; k < METRIC_WIN; ++k) {
-        g[k] = std::exp(-(double)((k - 5) * (k - 5)) / 4.5);
-        total += g[k];
-    }
-    for (int k = 0; k < METRIC_WIN; ++k) g[k] /= total;
-    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+    auto region = [&](const srcnn_image *im) { return metric_region(im, width, height, channels, n_frames, border); };
+    double g[METRIC_WIN], c1, c2;
+    metric_constants(data_range, g, &c1, &c2);
     const unsigned __int128 doubles = (unsigned __int128)per_frame * n_frames *
                                       (size_t)(metric_sse_partials((int)rh) + metric_ssim_partials((int)rw, (int)rh));
     if (doubles > ((unsigned __int128)1 << 40)) return fail(c, SRCNN_ERR_NOMEM, "%s: the workspace of the partial sums is too large", what);
@@ -416,7 +445,72 @@ double srcnn_metric_psnr(double sse, double n_px, double data_range)
     return 10.0 * std::log10(data_range * data_range * n_px / sse);
 }
 
+/* ---- MS-SSIM: {cs_sum, ssim_sum, n_win} per (frame, result, scale), float64 after the load (srcnn_msssim.hip) ---- */
+int srcnn_msssim_image_dev(srcnn_ctx *c, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
+                           int n_frames, int border, const float *luma, double data_range, int n_scales, double *d_out)
+{
+    BIND(c);
+    int rc;
+    const char *what = "msssim_image_dev";
+    long rw, rh;
+    if ((rc = metric_args_refusal(c, what, a, b, width, height, channels, n_frames, border, luma, data_range, &rw, &rh))) return rc;
+    if (n_scales < 1 || n_scales > MSSSIM_MAX_SCALES)
+        return fail(c, SRCNN_ERR_INVALID, "%s: n_scales %d: expected 1 .. %d", what, n_scales, (int)MSSSIM_MAX_SCALES);
+    if (rw < msssim_min_side(n_scales) || rh < msssim_min_side(n_scales))
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d scales need a region of at least %d x %d (11 x 11 at the last scale), this one is %ld x %ld",
+                    what, n_scales, msssim_min_side(n_scales), msssim_min_side(n_scales), rw, rh);
+    if (!d_out) return fail(c, SRCNN_ERR_INVALID, "%s: null output", what);
+    const int per_frame = luma ? 1 : channels;
+    if ((long)per_frame * n_frames > 0x7fffffffL) return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    if (!msssim_launcher())
+        return fail(c, SRCNN_ERR_STATE, "%s: this library was linked without srcnn_msssim.hip, the unit that holds the MS-SSIM kernels", what);
+    MsssimPlan plan;
+    if (!msssim_plan((int)rw, (int)rh, n_scales, &plan)) return fail(c, SRCNN_ERR_INVALID, "%s: bad arguments", what);
+    double g[METRIC_WIN], c1, c2;
+    metric_constants(data_range, g, &c1, &c2);
+    // both pictures' planes of the scales >= 1, then the partials
+    const unsigned __int128 results = (unsigned __int128)per_frame * n_frames;
+    const unsigned __int128 plane_doubles = 2 * results * (unsigned __int128)plan.plane_doubles;
+    const unsigned __int128 doubles = plane_doubles + results * (unsigned __int128)plan.part_doubles;
+    if (doubles > ((unsigned __int128)1 << 40)) return fail(c, SRCNN_ERR_NOMEM, "%s: the workspace of the scales is too large", what);
+    // the workspace was last written on another stream: that work ends before this call overwrites it
+    if (c->msssim_stream && c->msssim_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->msssim_stream));
+    if ((rc = reserve(c, c->msssim_work, (size_t)doubles * sizeof(double)))) return rc;      // (growing waits for the device)
+    c->msssim_stream = c->stream;
+    double *work = static_cast<double *>(c->msssim_work.p);
+    HIP_TRY(c, msssim_launcher()(metric_region(a, width, height, channels, n_frames, border),
+                                 metric_region(b, width, height, channels, n_frames, border), (int)rw, (int)rh, channels, n_frames, luma,
+                                 g, c1, c2, n_scales, work, work + (size_t)plane_doubles, d_out, c->stream));
+    return SRCNN_OK;
+}
+
+double srcnn_metric_msssim(const double *sums, int n_scales, const double *weights)
+{
+    static const double kWang[MSSSIM_MAX_SCALES] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
+    if (!sums || n_scales < 1 || n_scales > MSSSIM_MAX_SCALES || (!weights && n_scales != MSSSIM_MAX_SCALES)) return std::nan("");
+    const double *w = weights ? weights : kWang;
+    double product = 1.0;
+    for (int s = 0; s < n_scales; ++s) {
+        const double cs = sums[3 * s], ssim = sums[3 * s + 1], n_win = sums[3 * s + 2];
+        if (std::isnan(cs) || std::isnan(ssim) || std::isnan(w[s]) || !(n_win > 0.0)) return std::nan("");
+        const double mean = (s == n_scales - 1 ? ssim : cs) / n_win;
+        product *= mean > 0.0 ? std::pow(mean, w[s]) : 0.0;      // never a power of a negative number
+    }
+    return product;
+}
+
 #ifdef SRCNN_TUNING_BUILD
+/* Undocumented test hook (tuning build only, not part of the ABI): MSSSIM_T (window columns of one workgroup of the MS-SSIM
+ * window kernel), MSSSIM_B0 and MSSSIM_B1 (its window rows at scale 0 and at the scales >= 1), MSSSIM_PYR_ROWS, and the LDS
+ * bytes of the window kernel. */
+int srcnn_debug_msssim_limits(int *out5)
+{
+    if (!out5) return SRCNN_ERR_INVALID;
+    const int v[5] = {MSSSIM_T, MSSSIM_B0, MSSSIM_B1, MSSSIM_PYR_ROWS, MSSSIM_LDS_BYTES};
+    for (int k = 0; k < 5; ++k) out5[k] = v[k];
+    return SRCNN_OK;
+}
+
 /* Undocumented test hook (tuning build only, not part of the ABI): METRIC_T, METRIC_B (window columns and rows of one SSIM
  * workgroup), METRIC_SSE_ROWS, and the LDS bytes of the SSIM kernel. */
 int srcnn_debug_metric_limits(int *out4)

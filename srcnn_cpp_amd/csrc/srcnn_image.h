@@ -122,6 +122,59 @@ inline long metric_ssim_partials(int rw, int rh)     // 0 where the region holds
 hipError_t launch_metrics(const ImageRef &a, const ImageRef &b, int rw, int rh, int channels, int n_frames, const float *luma,
                           const double gauss[METRIC_WIN], double c1, double c2, int flags, double *work, double *out, hipStream_t st);
 
+// ---- MS-SSIM (srcnn_msssim_image_dev; include/srcnn_amd.h has the semantics): srcnn_msssim.hip ------------------------------
+// Scale 0 is the region of the stored pictures; scale j + 1 is scale j reduced by 2 x 2 means, a packed float64 plane of
+// ceil(w_j / 2) x ceil(h_j / 2) in a workspace.  Three kernels, no floating-point atomic: msssim_pyramid_kernel makes the next
+// scale of both pictures (256 threads: MSSSIM_PYR_ROWS rows x 64 columns), msssim_window_kernel is metric_ssim_kernel's shape
+// (one wave, MSSSIM_T window columns x a band of window rows, 5 x 64 doubles of LDS) and writes one partial of the cs sum and one
+// of the SSIM sum per workgroup, msssim_finish_kernel adds a scale's partials in a fixed order and writes {cs_sum, ssim_sum,
+// n_win} per scale.  Every size below follows from (rw, rh, n_scales) alone.
+constexpr int MSSSIM_MAX_SCALES = 5;
+constexpr int MSSSIM_T = 64 - (METRIC_WIN - 1);      // window columns per workgroup: 54
+// window rows per workgroup: a wave walks its band's rows one after the other, so the band sets how long the launch of a small
+// scale lasts; scale 0 takes metric_ssim_kernel's band (10 / 64 of its rows read again), the scales >= 1 a short one
+constexpr int MSSSIM_B0 = 64;
+constexpr int MSSSIM_B1 = 16;
+inline int msssim_band(int s) { return s ? MSSSIM_B1 : MSSSIM_B0; }
+constexpr int MSSSIM_PYR_ROWS = 4;                   // rows of the next scale per workgroup of the pyramid kernel
+constexpr int MSSSIM_LDS_BYTES = 5 * 64 * 8;
+// the smallest region side n_scales scales fit in: 11 at the last scale, 10 * 2^(S - 1) + 1
+inline int msssim_min_side(int n_scales) { return 10 * (1 << (n_scales - 1)) + 1; }
+struct MsssimPlan {
+    int w[MSSSIM_MAX_SCALES], h[MSSSIM_MAX_SCALES];            // the size of scale s
+    long n_ct[MSSSIM_MAX_SCALES], n_bt[MSSSIM_MAX_SCALES];     // its column tiles and row bands
+    long plane_off[MSSSIM_MAX_SCALES];      // scale s >= 1 of one picture of one result begins here, in doubles
+    long plane_doubles;                     // ... and the scales 1 .. S - 1 of one picture of one result take this many
+    long part_off[MSSSIM_MAX_SCALES];       // the partials of scale s of one result begin here: n_ct n_bt of cs, then as many of ssim
+    long part_doubles;                      // ... and one result takes this many
+};
+inline bool msssim_plan(int rw, int rh, int n_scales, MsssimPlan *plan)      // false where a scale holds no window
+{
+    if (n_scales < 1 || n_scales > MSSSIM_MAX_SCALES || rw < msssim_min_side(n_scales) || rh < msssim_min_side(n_scales)) return false;
+    MsssimPlan p{};
+    for (int s = 0; s < n_scales; ++s) {
+        p.w[s] = s ? (p.w[s - 1] + 1) / 2 : rw;
+        p.h[s] = s ? (p.h[s - 1] + 1) / 2 : rh;
+        p.n_ct[s] = ((long)p.w[s] - METRIC_WIN + 1 + MSSSIM_T - 1) / MSSSIM_T;
+        p.n_bt[s] = ((long)p.h[s] - METRIC_WIN + 1 + msssim_band(s) - 1) / msssim_band(s);
+        p.plane_off[s] = p.plane_doubles;
+        if (s) p.plane_doubles += (long)p.w[s] * p.h[s];
+        p.part_off[s] = p.part_doubles;
+        p.part_doubles += 2 * p.n_ct[s] * p.n_bt[s];
+    }
+    *plan = p;
+    return true;
+}
+// a, b: the REGION of rw x rh, as launch_metrics takes it; planes: 2 * n_frames * P * plan.plane_doubles doubles (may be null
+// for one scale); parts: n_frames * P * plan.part_doubles doubles; out: n_frames * P * n_scales * 3 doubles.
+// srcnn_image.cpp names no symbol of srcnn_msssim.hip: that unit hands its launcher over from a constructor that runs when
+// the library is loaded, as the wide units do (srcnn_kernels.h), and where no unit has, the call is refused.
+typedef hipError_t (*MsssimLauncher)(const ImageRef &a, const ImageRef &b, int rw, int rh, int channels, int n_frames,
+                                     const float *luma, const double gauss[METRIC_WIN], double c1, double c2, int n_scales,
+                                     double *planes, double *parts, double *out, hipStream_t st);
+void set_msssim_launcher(MsssimLauncher l);
+MsssimLauncher msssim_launcher();               // null until a unit has called set_msssim_launcher
+
 namespace host {
 // What the _f32 entry points (srcnn_resize_f32.cpp) and the _image_dev ones (srcnn_image.cpp, where these live) share.  All take
 // checked arguments and device memory and run on the context's stream.

@@ -297,18 +297,12 @@ class CompiledModule:
                                 lambda *a: self.ctx.process_rgb_image_dev(*a[:-1], luma, clamp, a[-1]), check)
 
     # ---- full-reference metrics: the measurement at the end of an evaluation ----
-    def metrics(self, a, b, border=0, luma=None, data_range=1.0, ssim=True, in_scale=None):
-        """The raw sums behind PSNR and SSIM of two pictures as they are stored: a float64 CUDA tensor (N, P, 4) holding
-        (sse, n_px, ssim_sum, n_win) per frame and result.  a and b: (N, C, H, W) or (C, H, W) of the same shape with C = 1 or 3
-        (taken from the tensors, not from the module), each float32, float16, bfloat16 or uint8 with any positive strides;
-        they may differ in dtype and layout.  uint8 is read as byte * in_scale (default 1 / 255).  border rows and columns are
-        shaved off every side first.  luma = (w0, w1, w2, offset) measures the luma of 3-channel pictures (P = 1); None
-        measures every channel plane (P = C).  data_range is L of the SSIM constants, in loaded units.  ssim=False computes
-        the squared error only (the SSIM fields are then 0).  Float64 after the load, no atomics: the same bits every time.
-        Runs on the current stream, with no synchronisation."""
+    @staticmethod
+    def _metric_args(a, b, border, luma, data_range, in_scale, early=None):
+        """What metrics() and msssim_sums() check alike, in one order: -> (ia, ib, n, channels, h, w, rh, rw, data_range)"""
         import math
         import torch
-        from . import METRIC_SSE, METRIC_SSIM, _metric_luma4
+        from . import _metric_luma4
         if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor):
             raise ValueError(f"expected two torch.Tensors, got {type(a).__name__} and {type(b).__name__}")
         if a.dim() not in (3, 4) or tuple(a.shape) != tuple(b.shape):
@@ -318,8 +312,8 @@ class CompiledModule:
             raise ValueError(f"expected 1 or 3 channels, the tensors have {channels}: shape {tuple(a.shape)}")
         ia, n, h, w = describe_image(a, channels, in_scale)
         ib = describe_image(b, channels, in_scale)[0]
-        if not isinstance(ssim, bool):
-            raise ValueError(f"ssim {ssim!r}: expected True or False")
+        if early is not None:
+            early()
         if isinstance(border, bool) or not isinstance(border, int) or border < 0:
             raise ValueError(f"border {border!r}: expected an integer >= 0")
         if luma is not None and channels != 3:
@@ -334,6 +328,24 @@ class CompiledModule:
         rh, rw = h - 2 * border, w - 2 * border
         if rh < 1 or rw < 1:
             raise ValueError(f"a border of {border} leaves nothing of a {h} x {w} picture")
+        return ia, ib, n, channels, h, w, rh, rw, data_range
+
+    def metrics(self, a, b, border=0, luma=None, data_range=1.0, ssim=True, in_scale=None):
+        """The raw sums behind PSNR and SSIM of two pictures as they are stored: a float64 CUDA tensor (N, P, 4) holding
+        (sse, n_px, ssim_sum, n_win) per frame and result.  a and b: (N, C, H, W) or (C, H, W) of the same shape with C = 1 or 3
+        (taken from the tensors, not from the module), each float32, float16, bfloat16 or uint8 with any positive strides;
+        they may differ in dtype and layout.  uint8 is read as byte * in_scale (default 1 / 255).  border rows and columns are
+        shaved off every side first.  luma = (w0, w1, w2, offset) measures the luma of 3-channel pictures (P = 1); None
+        measures every channel plane (P = C).  data_range is L of the SSIM constants, in loaded units.  ssim=False computes
+        the squared error only (the SSIM fields are then 0).  Float64 after the load, no atomics: the same bits every time.
+        Runs on the current stream, with no synchronisation."""
+        import torch
+        from . import METRIC_SSE, METRIC_SSIM
+
+        def early():
+            if not isinstance(ssim, bool):
+                raise ValueError(f"ssim {ssim!r}: expected True or False")
+        ia, ib, n, channels, h, w, rh, rw, data_range = self._metric_args(a, b, border, luma, data_range, in_scale, early)
         if ssim and (rh < 11 or rw < 11):
             raise ValueError(f"SSIM needs a region of at least 11 x 11, this one is {rh} x {rw} (ssim=False measures the squared error alone)")
         check_image_device(a, self.device)
@@ -357,6 +369,54 @@ class CompiledModule:
         tensor (N, P)."""
         m = self.metrics(a, b, border=border, luma=luma, data_range=data_range, ssim=True, in_scale=in_scale)
         return m[..., 2] / m[..., 3]
+
+    def msssim_sums(self, a, b, border=0, luma=None, data_range=1.0, n_scales=5, in_scale=None):
+        """The raw sums behind MS-SSIM of two pictures as they are stored: a float64 CUDA tensor (N, P, n_scales, 3) holding
+        (cs_sum, ssim_sum, n_win) per frame, result and scale.  a, b, luma, data_range and in_scale as metrics() takes them.
+        border is shaved off at scale 0 only; scale j + 1 is the 2 x 2 mean of scale j, an odd last row or column paired with
+        itself.  n_scales: 1 .. 5; the region must be at least 10 * 2^(n_scales - 1) + 1 on a side (161 for five).  Float64
+        after the load, no atomics: the same bits every time.  Runs on the current stream, with no synchronisation."""
+        import torch
+        from . import MSSSIM_MAX_SCALES
+        ia, ib, n, channels, h, w, rh, rw, data_range = self._metric_args(a, b, border, luma, data_range, in_scale)
+        if isinstance(n_scales, bool) or not isinstance(n_scales, int) or not 1 <= n_scales <= MSSSIM_MAX_SCALES:
+            raise ValueError(f"n_scales {n_scales!r}: expected an integer 1 .. {MSSSIM_MAX_SCALES}")
+        least = 10 * 2 ** (n_scales - 1) + 1
+        if rh < least or rw < least:
+            raise ValueError(f"{n_scales} scales need a region of at least {least} x {least}, this one is {rh} x {rw}")
+        check_image_device(a, self.device)
+        check_image_device(b, self.device)
+        out = torch.empty((n, 1 if luma is not None else channels, n_scales, 3), dtype=torch.float64, device=a.device)
+        self._on_current_stream(a.device, lambda: self.ctx.msssim_image_dev(ia, ib, w, h, channels, n, border, luma, data_range, n_scales,
+                                                                            out.data_ptr()))
+        return out
+
+    def msssim(self, a, b, border=0, luma=None, data_range=1.0, n_scales=5, weights=None, in_scale=None):
+        """MS-SSIM per frame and result from msssim_sums(): a float64 CUDA tensor (N, P), the product over the scales of
+        max(mean, 0)^w with the mean of cs below the last scale and of ssim at it (0 where a mean is not positive).
+        weights=None: those of Wang, Simoncelli and Bovik, which needs n_scales=5.  Torch operations on the device, no
+        synchronisation."""
+        import math
+        import torch
+        from . import MSSSIM_WEIGHTS
+        if weights is None:
+            if n_scales != len(MSSSIM_WEIGHTS):
+                raise ValueError(f"weights=None means the five published weights: n_scales {n_scales!r} needs weights of its own")
+            weights = MSSSIM_WEIGHTS
+        try:
+            wl = [float(v) for v in weights]
+        except (TypeError, ValueError):
+            raise ValueError(f"weights {weights!r}: expected n_scales numbers") from None
+        if len(wl) != n_scales or any(math.isnan(v) for v in wl):
+            raise ValueError(f"weights {weights!r}: expected {n_scales!r} numbers, none a NaN")
+        m = self.msssim_sums(a, b, border=border, luma=luma, data_range=data_range, n_scales=n_scales, in_scale=in_scale)
+        mean = torch.cat((m[..., :-1, 0], m[..., -1:, 1]), dim=-1) / m[..., 2]
+        out = None
+        for s, ws in enumerate(wl):      # (the weights stay Python numbers: no copy to the device)
+            ms = mean[..., s]
+            factor = torch.where(ms > 0, ms.clamp_min(0.0).pow(ws), torch.zeros_like(ms))
+            out = factor if out is None else out * factor
+        return out
 
     def close(self):
         self.ctx.close()

@@ -13,6 +13,11 @@ H x W x 3 uint8 measured on the BT.601 luma; each for the squared error alone an
 Before a row is timed the library's result is checked against the same script in float64 (separable window sums on .double()
 tensors): relative error of the squared error <= (n + 4) 2^-53, mean SSIM within 1e-9.  Beside the times: the bytes of both pictures read once.  Run the same command twice and compare; per-kernel
 times come from a run of its own under rocprofv3 --kernel-trace --stats.
+--msssim times MS-SSIM instead (CompiledModule.msssim_sums, five scales; profiles/models/msssim_bench.json is its --json): the
+same three pictures, one row each, against (a) `torch`, the float32 script of the same metric (five
+rounds of the five conv2d, avg_pool2d(2) between them), and (b) `ssim`, the library's own metrics(ssim=True) of the same pair.
+Before a row is timed the sums are checked against the metric in float64 (the same separable sums, the 2 x 2 mean with an odd
+last row or column paired with itself): per-scale mean cs and mean SSIM within 1e-9.
 No GPU: the tool fails; there is no CPU timing."""
 import argparse
 import json
@@ -89,6 +94,82 @@ def script64(a, b, luma, border):
     return ((a - b) ** 2).sum(dim=(-2, -1)), m.mean(dim=(-2, -1))
 
 
+N_SCALES = 5
+
+
+def ms_script32(a, b, luma, border):
+    """The yardstick for MS-SSIM: float32 throughout, conv2d with the 2-D window, avg_pool2d between the scales"""
+    a, b = planes(a, luma, border, torch.float32), planes(b, luma, border, torch.float32)
+    c = a.shape[1]
+    g = window(torch.float32)
+    win = torch.outer(g, g)[None, None].repeat(c, 1, 1, 1)
+    blur = lambda t: F.conv2d(t, win, groups=c)
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    out = []
+    for s in range(N_SCALES):
+        ma, mb, eaa, ebb, eab = blur(a), blur(b), blur(a * a), blur(b * b), blur(a * b)
+        cs = (2 * (eab - ma * mb) + c2) / ((eaa - ma * ma) + (ebb - mb * mb) + c2)
+        out.append((cs.sum(dim=(-2, -1)), (cs * (2 * ma * mb + c1) / (ma * ma + mb * mb + c1)).sum(dim=(-2, -1))))
+        if s + 1 < N_SCALES:
+            a, b = F.avg_pool2d(a, 2), F.avg_pool2d(b, 2)
+    return out
+
+
+def ms_script64(a, b, luma, border):
+    """The check for MS-SSIM: float64 throughout, separable window sums, the library's reduction -> (N, P, S, 2) means"""
+    if a.dtype == torch.uint8:      # the library loads a byte as float32(b) * float32(1 / 255)
+        a, b = a.float() * (1.0 / 255.0), b.float() * (1.0 / 255.0)
+    a, b = planes(a, luma, border, torch.float64), planes(b, luma, border, torch.float64)
+    g = window(torch.float64)
+
+    def blur(t):
+        n = t.shape[-2] - 10
+        v = sum(g[j] * t[..., j:j + n, :] for j in range(11))
+        n = t.shape[-1] - 10
+        return sum(g[j] * v[..., j:j + n] for j in range(11))
+
+    def reduce2(t):      # an odd last row or column once more, then the 2 x 2 mean
+        t = F.pad(t, (0, t.shape[-1] % 2, 0, t.shape[-2] % 2), mode="replicate")
+        return ((t[..., 0::2, 0::2] + t[..., 0::2, 1::2]) + (t[..., 1::2, 0::2] + t[..., 1::2, 1::2])) * 0.25
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    out = []
+    for s in range(N_SCALES):
+        ma, mb, eaa, ebb, eab = blur(a), blur(b), blur(a * a), blur(b * b), blur(a * b)
+        cs = (2 * (eab - ma * mb) + c2) / ((eaa - ma * ma) + (ebb - mb * mb) + c2)
+        ssim = ((2 * ma * mb + c1) * (2 * (eab - ma * mb) + c2)) / ((ma * ma + mb * mb + c1) * ((eaa - ma * ma) + (ebb - mb * mb) + c2))
+        out.append(torch.stack((cs.mean(dim=(-2, -1)), ssim.mean(dim=(-2, -1))), dim=-1))
+        del ma, mb, eaa, ebb, eab, cs, ssim
+        if s + 1 < N_SCALES:
+            a, b = reduce2(a), reduce2(b)
+    return torch.stack(out, dim=-2)
+
+
+def msssim_rows(fast, args):
+    records = []
+    for stored in ("float32, 1 plane", "float32, 3 planes", "H x W x 3 uint8, BT.601 luma"):
+        a, b, luma, nbytes = pictures(stored)
+        got = fast.msssim_sums(a, b, border=args.border, luma=luma, n_scales=N_SCALES).cpu().numpy()
+        want = ms_script64(a, b, luma, args.border).cpu().numpy()
+        torch.cuda.empty_cache()
+        err = float(max(np.abs(got[..., 0] / got[..., 2] - want[..., 0]).max(), np.abs(got[..., 1] / got[..., 2] - want[..., 1]).max()))
+        if err > SSIM_TOL:
+            raise SystemExit(f"{stored}: per-scale means off by {err:.3g}: nothing timed")
+        calls = {"lib": lambda: fast.msssim_sums(a, b, border=args.border, luma=luma, n_scales=N_SCALES),
+                 "torch": lambda: ms_script32(a, b, luma, args.border),
+                 "ssim": lambda: fast.metrics(a, b, border=args.border, luma=luma, ssim=True)}
+        rec = dict(stored=stored, size=f"{SIZE[1]}x{SIZE[0]}", border=args.border, metric=f"MS-SSIM, {N_SCALES} scales",
+                   scale_means_err_vs_float64=err, bytes_read_once=nbytes, **bench(calls, args.rounds, args.warmup))
+        rec["lib_over_torch"] = rec["lib"]["ms_median"] / rec["torch"]["ms_median"]
+        rec["lib_over_ssim"] = rec["lib"]["ms_median"] / rec["ssim"]["ms_median"]
+        records.append(rec)
+        print(f"{stored}, {rec['metric']} ({nbytes / 1e6:.1f} MB): " +
+              ", ".join(f"{k} {rec[k]['ms_median']:.4f} ms (min {rec[k]['ms_min']:.4f}, {rec[k]['spread']:.1%})" for k in calls) +
+              f"; lib / torch {rec['lib_over_torch']:.3f}, lib / ssim {rec['lib_over_ssim']:.3f}; |scale means - float64| {err:.3g}", flush=True)
+        del a, b
+        torch.cuda.empty_cache()
+    return records
+
+
 def pictures(stored):
     h, w = SIZE
     rng = np.random.default_rng(len(stored))
@@ -124,13 +205,16 @@ def main():
     ap.add_argument("--border", type=int, default=2)
     ap.add_argument("--json", default=None)
     ap.add_argument("--lib", default=None, help="another build of the library")
+    ap.add_argument("--msssim", action="store_true", help="time MS-SSIM (five scales) instead of the squared error and SSIM")
     args = ap.parse_args()
     if args.lib:
         S.use_library(args.lib)
     fast = compile_module(SRCNN().eval())          # raises without a gfx950 GPU
     records = []
     try:
-        for stored in ("float32, 1 plane", "float32, 3 planes", "H x W x 3 uint8, BT.601 luma"):
+        if args.msssim:
+            records = msssim_rows(fast, args)
+        for stored in () if args.msssim else ("float32, 1 plane", "float32, 3 planes", "H x W x 3 uint8, BT.601 luma"):
             a, b, luma, nbytes = pictures(stored)
             got = fast.metrics(a, b, border=args.border, luma=luma).cpu().numpy()
             sse64, ssim64 = (t.cpu().numpy() for t in script64(a, b, luma, args.border))
@@ -162,7 +246,10 @@ def main():
     if args.json:
         Path(args.json).parent.mkdir(parents=True, exist_ok=True)
         Path(args.json).write_text(json.dumps(result, indent=1) + "\n")
-    print(json.dumps({"lib_over_torch": [r["lib_over_torch"] for r in records]}))
+    summary = {"lib_over_torch": [r["lib_over_torch"] for r in records]}
+    if args.msssim:
+        summary["lib_over_ssim"] = [r["lib_over_ssim"] for r in records]
+    print(json.dumps(summary))
 
 
 if __name__ == "__main__":
