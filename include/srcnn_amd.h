@@ -326,7 +326,7 @@ int srcnn_get_model_channels(const srcnn_ctx *ctx);
  *     srcnn_set_weights, srcnn_set_model or srcnn_set_model_color: the context then holds an ordinary model, and every mode and
  *     entry point that runs such a model runs this one (the fused strip kernels for 9-1-5 included).
  *   - A WIDE model (n1p = 128 or n2p = 64: the paper's 128 / 64) runs in SRCNN_MODE_MFMA only, under either padding, on the
- *     banded path (summation order in srcnn_wide_kernels.hip: that of the 32-map kernels, continued), through the whole-image
+ *     banded path (summation order in srcnn_spatial_kernels.hip: that of a 64 / 32 model, continued), through the whole-image
  *     entry points: srcnn_forward_y(_dev) with n_frames, pitches and d_preclamp, srcnn_forward_y_frames,
  *     srcnn_forward_color(_dev), srcnn_process_bgr(_dev), srcnn_forward_f32(_dev), srcnn_process_f32(_dev),
  *     srcnn_process_rgb_f32(_dev) and the four srcnn_*_image_dev calls.  Everything else -- every other mode,
@@ -348,7 +348,7 @@ int srcnn_get_model_shape(const srcnn_ctx *ctx, int *channels, int *n1, int *f2,
  * load.  on = 1: when a wide model is loaded and the mode is SRCNN_MODE_MFMA, every call that runs the model (the whole-image
  * entry points listed above) runs layer 2 with the arithmetic of SRCNN_MODE_BANDED16 -- layer 1 writes its map as f16 (hi, lo)
  * pairs, layer 2 runs on the f16 matrix pipe over all n1p channels and n2p outputs (summation order in
- * srcnn_wide16_kernels.hip), layer 3 is unchanged -- within the tolerance of the float32 form and several times faster for
+ * srcnn_spatial_kernels.hip), layer 3 is unchanged -- within the tolerance of the float32 form and several times faster for
  * f2 = 3, 5.  The float calls scale by srcnn_set_input_range, the byte calls by 255, as in that mode.
  *   - on = 0: the float32 kernels, the results of a context that never had the option on.
  *   - A narrow model ignores the option in every mode; a wide model in any other mode or entry point is refused as before

@@ -47,12 +47,10 @@ UNITS = [
     # the resize's vertical pass is OpenCV's float32 multiply-then-add (every product and sum rounded on its own):
     # __fmul_rn / __fadd_rn are plain * and + in HIP's headers, so contraction must be off here too
     ("srcnn_pipeline.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
-    # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models, float planes and row stripes -- every form
+    # the banded path: the 9-3-5 / 9-5-5 models, zero padding, the colour models, float planes and row stripes -- every form,
+    # the wide forms of layers 2 and 3 for the models of other widths (srcnn_set_model_shape: up to 128 / 64 filters) and of
+    # layer 2 in split f16 (srcnn_set_wide_split16) among them
     ("srcnn_spatial_kernels.hip", []),
-    # ... and layers 2 and 3 of the models of other widths (srcnn_set_model_shape: up to 128 / 64 filters), the spatial unit's flags
-    ("srcnn_wide_kernels.hip", []),
-    # ... and layer 2 of those models in split f16 (srcnn_set_wide_split16), a unit of its own with the same flags
-    ("srcnn_wide16_kernels.hip", []),
     # the metrics: float64 throughout; the SSIM formula and the luma as written, every product and sum rounded on its own (the
     # window sums use explicit fused multiply-adds), so identical pictures give exactly 1.0 per window
     ("srcnn_metrics.hip", ["-ffp-contract=off"]),

@@ -184,11 +184,11 @@ struct srcnn_ctx {
     int f2 = 1;
     // The widths of the loaded model (srcnn_set_model_shape): n1 / n2 filters as given, n1p / n2p padded with zero channels to a
     // multiple of 64 / 32.  64 / 32 for every model the other loaders load.  A WIDE model (n1p = 128 or n2p = 64, wide_model())
-    // lives in sp_table alone, in the layout of wide_table_floats() (srcnn_kernels.h), and sp_map64 / sp_map32 hold n1p / n2p
+    // lives in sp_table alone, spatial_table_floats() of its widths (srcnn_kernels.h), and sp_map64 / sp_map32 hold n1p / n2p
     // planes; it runs in SRCNN_MODE_MFMA through forward_banded() and nowhere else.
     int n1 = 64, n2 = 32, n1p = 64, n2p = 32;
     // srcnn_set_wide_split16: a setting of the context like the padding (kept across model loads).  1: forward_banded() runs
-    // layer 2 of a WIDE model in split f16 (srcnn_wide16_kernels.hip), from the sp16_* state below made for n1p / n2p; a narrow
+    // layer 2 of a WIDE model in split f16 (spatial_l2h_kernel's wide forms), from the sp16_* state below made for n1p / n2p; a narrow
     // model ignores it.
     int wide_split16 = 0;
     srcnn::host::DevBuf sp_table, sp_map64, sp_map32;
@@ -199,7 +199,7 @@ struct srcnn_ctx {
     // two power-of-two scales are made from them the first time a call in that mode runs the model (sp16_f2 = 0: not made since
     // the model was loaded; -1: the model cannot be scaled, the mode refuses it).  A wide model keeps the same for
     // srcnn_set_wide_split16: the padded W2 [n2p][n1p][sp_f2][sp_f2], the bound over its n1p channels, the table of
-    // wide_l2h_table_bytes().
+    // spatial_l2h_table_bytes() for its widths.
     std::vector<float> sp_w2;
     double sp_l1_bound = 0.0;
     srcnn::host::DevBuf sp16_table;

@@ -251,21 +251,40 @@ hipError_t launch_conv55_exact(const float *planes, long stride, long pitch, lon
                                int w, int h, int n_frames, const float *d_kernel800, float bias,
                                hipStream_t st);
 
-// ---- the banded path (srcnn_spatial_kernels.hip): 9-3-5 / 9-5-5 models, every model under zero padding, colour models ----
-// Fragment table of a model of C = 1 or 3 channels, floats: layer 1 [C channels][SPATIAL_NFRAG_L1][64] (per input channel c:
-// fragment t * 41 + s, lane l: output channel 32t + (l & 31), tap 2s + (l >> 5); tap 81: b1 on the last channel, else 0), then
-// layer 2 [8 chunks][f2 * f2 taps][4 pairs][64] (lane l: output channel l & 31, input channel 8 chunk + 2 pair + (l >> 5)) and
-// b2 [32], then layer 3 [C output channels][SPATIAL_NFRAG_L3][64] (per output channel o, k-step s, lane l: W3[o][2s + (l >> 5)]
+// ---- the banded path (srcnn_spatial_kernels.hip): 9-3-5 / 9-5-5 models, every model under zero padding, colour models, and
+// models of other widths (srcnn_set_model_shape: n1 <= 128 and n2 <= 64 filters) ----
+// The widths of a model are padded with zero channels to n1p = 64 or 128 and n2p = 32 or 64; every model but one of
+// srcnn_set_model_shape has 64 / 32, the defaults below.  Fragment table of a model of C = 1 or 3 channels, floats: layer 1
+// [n1p / 64 groups][C channels][SPATIAL_NFRAG_L1][64] (group g, per input channel c: fragment t * 41 + s, lane l: output channel
+// 64g + 32t + (l & 31), tap 2s + (l >> 5); tap 81: b1 on the last channel, else 0), then layer 2 [n2p / 32 groups][n1p / 8 chunks]
+// [f2 * f2 taps][4 pairs][64] (group g, lane l: output channel 32g + (l & 31), input channel 8 chunk + 2 pair + (l >> 5)) and
+// b2 [n2p], then layer 3 [C output channels][n2p / 2 k-steps][64] (per output channel o, k-step s, lane l: W3[o][2s + (l >> 5)]
 // at the tap of l3_row_tap(l & 31), 0 for the unused rows).  Unscaled: the maps hold the model's own values.
-constexpr int SPATIAL_NFRAG_L1 = 82, SPATIAL_NFRAG_L3 = 16;
-__host__ __device__ constexpr size_t spatial_l2_offset(int C) { return (size_t)C * SPATIAL_NFRAG_L1 * 64; }
-__host__ __device__ constexpr size_t spatial_l3_offset(int C, int f2) { return spatial_l2_offset(C) + (size_t)f2 * f2 * 2048 + 32; }
-__host__ __device__ constexpr size_t spatial_table_floats(int C, int f2) { return spatial_l3_offset(C, f2) + (size_t)C * SPATIAL_NFRAG_L3 * 64; }
+constexpr int SPATIAL_NFRAG_L1 = 82;
+__host__ __device__ constexpr size_t spatial_l2_offset(int C, int n1p = 64) { return (size_t)(n1p / 64) * C * SPATIAL_NFRAG_L1 * 64; }
+__host__ __device__ constexpr size_t spatial_l2_floats(int f2, int n1p = 64, int n2p = 32) { return (size_t)(n2p / 32) * (n1p / 8) * f2 * f2 * 256; }
+__host__ __device__ constexpr size_t spatial_l3_offset(int C, int f2, int n1p = 64, int n2p = 32)
+{
+    return spatial_l2_offset(C, n1p) + spatial_l2_floats(f2, n1p, n2p) + n2p;
+}
+__host__ __device__ constexpr size_t spatial_table_floats(int C, int f2, int n1p = 64, int n2p = 32)
+{
+    return spatial_l3_offset(C, f2, n1p, n2p) + (size_t)C * (n2p / 2) * 64;
+}
 size_t spatial_l2_lds_bytes(int f2);
-// The split W2 table of SRCNN_MODE_BANDED16 (spatial_l2h_table_bytes(f2): [4 K steps][f2 * f2 taps][hi, lo][64 lanes][8 f16],
-// lane l: output channel l & 31, element e: layer-1 channel spatial_l2h_channel(step, l >> 5, e))
+// The split W2 table of SRCNN_MODE_BANDED16 and srcnn_set_wide_split16 (spatial_l2h_table_bytes(f2, n1p, n2p)): [n2p / 32 groups]
+// [n1p / 16 K steps][f2 * f2 taps][hi, lo][64 lanes][8 f16]; lane l of group g: output channel 32g + (l & 31), element e of step s:
+// layer-1 channel 64 (s >> 2) + spatial_l2h_channel(s & 3, l >> 5, e)
 __host__ __device__ constexpr int spatial_l2h_channel(int step, int h, int e) { return 32 * (step >> 1) + acc_row(8 * (step & 1) + e, h); }
-__host__ __device__ constexpr size_t spatial_l2h_table_bytes(int f2) { return (size_t)4 * f2 * f2 * 2 * 64 * 16; }
+__host__ __device__ constexpr size_t spatial_l2h_table_bytes(int f2, int n1p = 64, int n2p = 32)
+{
+    return (size_t)(n2p / 32) * (n1p / 16) * f2 * f2 * 2 * 64 * 16;
+}
+// The dynamic LDS of spatial_l2h_kernel: four window planes [plane][hi, lo] of spatial_l2h_ps() 16-byte words (a (16 + 2 r2) x
+// (64 + 2 r2) window, = 4 mod 8) and one K step's A fragments: 66 / 93 / 135 KiB for f2 = 1 / 3 / 5.  The kernel asserts that this
+// is its layout's size, and the launcher asks for it.
+__host__ __device__ constexpr int spatial_l2h_ps(int r2) { return (((16 + 2 * r2) * (64 + 2 * r2) + 7) / 8) * 8 + 4; }
+__host__ __device__ constexpr size_t spatial_l2h_lds_bytes(int f2) { return ((size_t)4 * spatial_l2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * 16; }
 // One launcher per layer; each picks the kernel form from what it is given and returns hipErrorInvalidValue where there is none.
 // Every form of a layer does the same arithmetic in the same order.
 //
@@ -292,15 +311,19 @@ struct L1Input {
 // refers to the image (0, H - 1, 0, W - 1), never to a stripe.  split (SRCNN_MODE_BANDED16): `map` holds 8 planes of 32-byte
 // pixels, every activation times `scale` (a power of two) as an f16 (hi, lo) pair; else 64 planar f32 maps (plane pitch mpitch,
 // row stride W; the same bytes) and `scale` is unused.  A stripe reads no input row outside [max(0, m0 - 4), min(H, m1 + 4)) and
-// no column beyond W - 1.
+// no column beyond W - 1.  Layer 1 of a model with n1p = 128 is two calls, each with its group's table and its 64 planes of the
+// map (split: all with the model's one scale).
 hipError_t launch_spatial_l1(const L1Input &in, bool zero, bool split, float scale, int W, int H, int m0, int m1, const float *frag,
                              void *map, long mpitch, hipStream_t st);
-// Layer 2 (f2 = 1, 3, 5): 32 planar f32 maps (row stride W) of rows [o0, o1) from the layer-1 map of rows [m0, m1) (which must
-// hold rows o0 - r2 .. o1 + r2 - 1, clamped to the image); zero: the map outside the image is 0, else replicated.  split: the
-// f16 pair map, frag = the split W2 table above and unscale = 1 / (layer 1's scale x the W2 scale), on the f16 MFMA
-// (spatial_l2h_kernel); else the f32 maps, frag = the layer-2 part of the fragment table, unscale unused.
+// Layer 2 (f2 = 1, 3, 5): n2p planar f32 maps (row stride W) of rows [o0, o1) from the layer-1 map of n1p channels and rows
+// [m0, m1) (which must hold rows o0 - r2 .. o1 + r2 - 1, clamped to the image); zero: the map outside the image is 0, else
+// replicated.  split: the f16 pair map, frag = the split W2 table above and unscale = 1 / (layer 1's scale x the W2 scale), on
+// the f16 MFMA (spatial_l2h_kernel); else the f32 maps, frag = the layer-2 part of the fragment table, unscale unused.  bias: the
+// n2p floats of the fragment table.  n1p = 64 and n2p = 32: the kernels with compile-time loop counts; else (n1p 64 or 128, n2p
+// 32 or 64) the forms with the count as an argument, one group of 32 output planes per grid z.
 hipError_t launch_spatial_l2(int f2, bool zero, bool split, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                             const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st);
+                             const void *frag, const float *bias, float unscale, float *out, long opitch, int n1p, int n2p,
+                             hipStream_t st);
 // What layer 3 writes: pixels of `channels` bytes (row stride dstride; pre: the values before truncation at the same element
 // offsets, or null), or (f32) the value before truncation to `channels` float planes, dst[y * dstride + x + o * ch_pitch], and
 // no byte.
@@ -310,59 +333,12 @@ struct L3Output {
     long dstride, ch_pitch;
     float *pre;
 };
-// Layer 3: rows [b0, b1) of the output from the 32 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch), which must
-// hold every image row of [b0 - 2, b1 + 2).  frag: the layer-3 part of the table above, b3: `channels` floats.  Bytes of 1 channel
-// under replicate padding are not a form of this kernel (the MODE_L3 strip kernel runs them); floats of it are.
+// Layer 3: rows [b0, b1) of the output from the n2p = 32 or 64 planar maps of rows [o0, o1) (row stride W, plane pitch mpitch),
+// which must hold every image row of [b0 - 2, b1 + 2).  frag: the layer-3 part of the table above, b3: `channels` floats.  From 32
+// maps, bytes of 1 channel under replicate padding are not a form of this kernel (the MODE_L3 strip kernel runs them); floats of
+// it are, and from 64 maps every form is.
 hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                             const float *frag, const float *b3, const L3Output &out, hipStream_t st);
-
-// ---- models of other widths (srcnn_wide_kernels.hip; srcnn_set_model_shape: n1 <= 128 and n2 <= 64 filters) ----
-// The widths are padded with zero channels to n1p = 64 or 128 and n2p = 32 or 64.  The fragment table of such a model, floats:
-// layer 1 [n1p / 64 groups][C channels][SPATIAL_NFRAG_L1][64] (group g: the table above for output channels 64g .. 64g + 63),
-// then layer 2 [n2p / 32 groups][n1p / 8 chunks][f2 * f2 taps][4 pairs][64] (group g, lane l: output channel 32g + (l & 31),
-// input channel 8 chunk + 2 pair + (l >> 5)) and b2 [n2p], then layer 3 [C output channels][n2p / 2 k-steps][64].  For
-// n1p = 64 and n2p = 32 this is the table above, float for float.
-__host__ __device__ constexpr size_t wide_l2_offset(int C, int n1p) { return (size_t)(n1p / 64) * C * SPATIAL_NFRAG_L1 * 64; }
-__host__ __device__ constexpr size_t wide_l2_floats(int f2, int n1p, int n2p) { return (size_t)(n2p / 32) * (n1p / 8) * f2 * f2 * 256; }
-__host__ __device__ constexpr size_t wide_l3_offset(int C, int f2, int n1p, int n2p) { return wide_l2_offset(C, n1p) + wide_l2_floats(f2, n1p, n2p) + n2p; }
-__host__ __device__ constexpr size_t wide_table_floats(int C, int f2, int n1p, int n2p) { return wide_l3_offset(C, f2, n1p, n2p) + (size_t)C * (n2p / 2) * 64; }
-// Layer 1 of such a model is n1p / 64 calls of launch_spatial_l1, each with its group's table and its 64 planes of the map.
-// Layers 2 and 3 are the wide unit's two launchers.  The host layer holds no reference to them: the unit hands them over when
-// the library is loaded (set_wide_launchers, srcnn_spatial.cpp), and the band loop calls them through wide_launchers().  So every
-// symbol the host units name is one every program that links them defines, and where no unit has handed its launchers over (the
-// host units linked against stand-ins for the kernel units) srcnn_set_model_shape refuses a wide model: nothing runs in its place.
-struct WideLaunchers {
-    // Layer 2: launch_spatial_l2's f32 form over n_chunks = n1p / 8 chunks of the map and n_groups = n2p / 32 groups of 32
-    // output planes (frag: the layer-2 part of the table, bias: the n2p floats behind it).
-    hipError_t (*l2)(int f2, bool zero, const float *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1, const float *frag,
-                     const float *bias, int n_chunks, int n_groups, float *out, long opitch, hipStream_t st);
-    // Layer 3 from 64 planar maps: launch_spatial_l3 with 32 k-steps, every form of it and bytes of 1 channel under replicate
-    // padding as well.  (A model with n2p = 32 keeps launch_spatial_l3 / MODE_L3.)
-    hipError_t (*l3)(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                     const float *frag, const float *b3, const L3Output &out, hipStream_t st);
-};
-void set_wide_launchers(const WideLaunchers &t);
-const WideLaunchers &wide_launchers();          // both null until a unit has called set_wide_launchers
-
-// ---- layer 2 of a wide model in split f16 (srcnn_wide16_kernels.hip; srcnn_set_wide_split16) ----
-// The split W2 table of a model of padded widths n1p / n2p: [n2p / 32 groups][n1p / 16 K steps][f2 * f2 taps][hi, lo][64 lanes]
-// [8 f16]; lane l of group g: output channel 32g + (l & 31), element e of step s: layer-1 channel
-// 64 (s >> 2) + spatial_l2h_channel(s & 3, l >> 5, e).  For n1p = 64 and n2p = 32 this is the table of SRCNN_MODE_BANDED16, byte
-// for byte.
-__host__ __device__ constexpr size_t wide_l2h_table_bytes(int f2, int n1p, int n2p) { return (size_t)(n2p / 32) * (n1p / 16) * f2 * f2 * 2 * 64 * 16; }
-// The kernel's dynamic LDS, that of spatial_l2h_kernel: four window planes [plane][hi, lo] of wide_l2h_ps() 16-byte words and
-// one K step's A fragments: 66 / 93 / 135 KiB for f2 = 1 / 3 / 5
-__host__ __device__ constexpr int wide_l2h_ps(int r2) { return (((16 + 2 * r2) * (64 + 2 * r2) + 7) / 8) * 8 + 4; }
-__host__ __device__ constexpr size_t wide_l2h_lds_bytes(int f2) { return ((size_t)4 * wide_l2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * 16; }
-// Layer 2: launch_spatial_l2's split form over n_steps = n1p / 16 K steps of the split map (layer 1's n1p / 64 launches with
-// split = true and one scale) and n_groups = n2p / 32 groups of 32 output planes (frag: the table above, bias: the n2p floats of
-// the fragment table, unscale = 1 / (layer 1's scale x the W2 scale)).  Handed over like the wide launchers: null until the unit
-// has called set_wide16_launcher, and then srcnn_set_wide_split16(ctx, 1) makes the first wide call fail, nothing runs in its place.
-typedef hipError_t (*Wide16Launcher)(int f2, bool zero, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                                     const void *frag, const float *bias, float unscale, int n_steps, int n_groups, float *out,
-                                     long opitch, hipStream_t st);
-void set_wide16_launcher(Wide16Launcher l2h);
-Wide16Launcher wide16_launcher();
+                             const float *frag, const float *b3, const L3Output &out, int n2p, hipStream_t st);
 
 // interleaved 3-byte pixels -> three planes (row stride W, plane pitch ppitch)
 hipError_t launch_split3(const uint8_t *src, long sstride, int W, int H, uint8_t *planes, long ppitch, hipStream_t st);

@@ -4,30 +4,19 @@
 // behind srcnn_forward_color(_dev) and srcnn_process_bgr(_dev); and the float image path, srcnn_forward_f32(_dev): every whole
 // model on float32 planes, the value before truncation out.  One weight table per model, one gate, one band loop.
 // Models of other widths (srcnn_set_model_shape: up to 128 / 64 filters, padded with zero channels to 64 or 128 and 32 or 64)
-// load here too: one that fits 64 / 32 as an ordinary model, a wider one into the same table and band loop with layers 2 and
-// 3 from srcnn_wide_kernels.hip.
+// load here too: one that fits 64 / 32 as an ordinary model, a wider one into the same table and band loop, where the launchers
+// of layers 2 and 3 pick the forms for its widths.
 #include "srcnn_ctx.h"
 
 using namespace srcnn;
 using namespace srcnn::host;
 
 namespace srcnn {
-
-// layers 2 and 3 of a wide model (srcnn_kernels.h): constant-initialised, so a unit may hand them over from its own initialiser
-static WideLaunchers g_wide_launchers = {nullptr, nullptr};
-void set_wide_launchers(const WideLaunchers &t) { g_wide_launchers = t; }
-const WideLaunchers &wide_launchers() { return g_wide_launchers; }
-// ... and layer 2 of a wide model in split f16 (srcnn_wide16_kernels.hip), the same way
-static Wide16Launcher g_wide16_launcher = nullptr;
-void set_wide16_launcher(Wide16Launcher l2h) { g_wide16_launcher = l2h; }
-Wide16Launcher wide16_launcher() { return g_wide16_launcher; }
-
 namespace host {
 
-// The fragment table of srcnn_kernels.h of a C-channel model of padded widths n1p (64 or 128) and n2p (32 or 64): for 64 / 32
-// spatial_table_floats() floats, the table the 32-map kernels read; else wide_table_floats() floats -- n1p / 64 layer-1 groups,
-// n1p / 8 layer-2 chunks x n2p / 32 groups, n2p / 2 layer-3 k-steps (the same loops: 64 / 32 gives the same floats in the same
-// places).  w1 [n1p][C][9][9], w2 [n2p][n1p][f2][f2], w3 [C][n2p][5][5] (PyTorch's conv weights, padded with zeros).
+// The fragment table of srcnn_kernels.h of a C-channel model of padded widths n1p (64 or 128) and n2p (32 or 64),
+// spatial_table_floats(C, f2, n1p, n2p) floats: n1p / 64 layer-1 groups, n1p / 8 layer-2 chunks x n2p / 32 groups, n2p / 2
+// layer-3 k-steps.  w1 [n1p][C][9][9], w2 [n2p][n1p][f2][f2], w3 [C][n2p][5][5] (PyTorch's conv weights, padded with zeros).
 static void pack_spatial(int C, int f2, int n1p, int n2p, const float *w1, const float *b1, const float *w2, const float *b2,
                          const float *w3, float *out)
 {
@@ -43,7 +32,7 @@ static void pack_spatial(int C, int f2, int n1p, int n2p, const float *w1, const
                     }
             }
     const int taps = f2 * f2, chunks = n1p / 8;
-    float *o2 = out + wide_l2_offset(C, n1p);
+    float *o2 = out + spatial_l2_offset(C, n1p);
     for (int g = 0; g < n2p / 32; ++g)
         for (int chunk = 0; chunk < chunks; ++chunk)
             for (int tap = 0; tap < taps; ++tap)
@@ -52,8 +41,8 @@ static void pack_spatial(int C, int f2, int n1p, int n2p, const float *w1, const
                         const int k = 32 * g + (l & 31), ci = 8 * chunk + 2 * pp + (l >> 5);
                         o2[((((size_t)g * chunks + chunk) * taps + tap) * 4 + pp) * 64 + l] = w2[((size_t)k * n1p + ci) * taps + tap];
                     }
-    std::memcpy(o2 + wide_l2_floats(f2, n1p, n2p), b2, n2p * sizeof(float));
-    float *o3 = out + wide_l3_offset(C, f2, n1p, n2p);
+    std::memcpy(o2 + spatial_l2_floats(f2, n1p, n2p), b2, n2p * sizeof(float));
+    float *o3 = out + spatial_l3_offset(C, f2, n1p, n2p);
     const int ksteps = n2p / 2;
     for (int o = 0; o < C; ++o)
         for (int s = 0; s < ksteps; ++s)
@@ -62,8 +51,9 @@ static void pack_spatial(int C, int f2, int n1p, int n2p, const float *w1, const
                 o3[((size_t)o * ksteps + s) * 64 + l] = tap < 0 ? 0.f : w3[((size_t)o * n2p + 2 * s + (l >> 5)) * 25 + tap];
             }
 }
-static_assert(wide_l2_offset(3, 64) == spatial_l2_offset(3) && wide_l3_offset(3, 5, 64, 32) == spatial_l3_offset(3, 5) &&
-              wide_table_floats(3, 5, 64, 32) == spatial_table_floats(3, 5) && wide_table_floats(1, 1, 64, 32) == spatial_table_floats(1, 1),
+// (the geometry of a 64 / 32 model, spelled out: the table the kernels with compile-time counts have always read)
+static_assert(spatial_l2_offset(3) == 3 * 82 * 64 && spatial_l3_offset(3, 5) == spatial_l2_offset(3) + 25 * 2048 + 32 &&
+              spatial_table_floats(3, 5) == spatial_l3_offset(3, 5) + 3 * 16 * 64 && spatial_table_floats(1, 1) == 82 * 64 + 2048 + 32 + 16 * 64,
               "a 64 / 32 model keeps its table");
 
 // ---- SRCNN_MODE_BANDED16: exact power-of-two scales and the split W2 table (srcnn_spatial_kernels.hip, spatial_l2h_kernel) ----
@@ -110,8 +100,8 @@ bool banded16_exponent(double bound, int *e)
 }
 
 // W2 [n2p][n1p][f2][f2] times 2^e2 (max |W2| 2^e2 in [2^14, 2^15)) as f16 (hi, lo) pairs, round to nearest, in the A-operand
-// order of spatial_l2h_kernel and wide_l2h_kernel (srcnn_kernels.h: n2p / 32 groups x n1p / 16 K steps; 64 / 32 is the one group
-// of 4 steps of SRCNN_MODE_BANDED16); false when a weight is not finite or the scaled weights leave float32's range
+// order of spatial_l2h_kernel (srcnn_kernels.h: n2p / 32 groups x n1p / 16 K steps; 64 / 32 is the one group of 4 steps of
+// SRCNN_MODE_BANDED16); false when a weight is not finite or the scaled weights leave float32's range
 bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2, int n1p, int n2p)
 {
     const int taps = f2 * f2, steps = n1p / 16;
@@ -139,7 +129,7 @@ bool banded16_pack_w2(int f2, const float *w2, uint16_t *table, int *e2, int n1p
 static int upload_table(srcnn_ctx *c, int C, int f2, const float *w1, const float *b1, const float *w2, const float *b2,
                         const float *w3, const float *b3, int n1p = 64, int n2p = 32)
 {
-    std::vector<float> table(wide_table_floats(C, f2, n1p, n2p));
+    std::vector<float> table(spatial_table_floats(C, f2, n1p, n2p));
     pack_spatial(C, f2, n1p, n2p, w1, b1, w2, b2, w3, table.data());
     int rc;
     if ((rc = reserve(c, c->sp_table, table.size() * sizeof(float)))) return rc;
@@ -169,7 +159,7 @@ static int upload_table16(srcnn_ctx *c)
     if (c->sp16_f2 < 0) return fail(c, SRCNN_ERR_STATE, refuse, split_name(c), split_way_out(c));
     const int f2 = c->sp_f2, n1p = c->n1p, n2p = c->n2p;
     int e1 = 0, e2 = 0;
-    std::vector<uint16_t> table(wide_l2h_table_bytes(f2, n1p, n2p) / sizeof(uint16_t));
+    std::vector<uint16_t> table(spatial_l2h_table_bytes(f2, n1p, n2p) / sizeof(uint16_t));
     if (c->sp_w2.size() != (size_t)n2p * n1p * f2 * f2 || !banded16_exponent(c->sp_l1_bound, &e1) ||
         !banded16_pack_w2(f2, c->sp_w2.data(), table.data(), &e2, n1p, n2p) || std::abs(e1 + e2) > 120) {
         c->sp16_f2 = -1;
@@ -290,9 +280,6 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     const bool wide = wide_model(c);
     // layer 2 in split f16: the mode, or for a wide model (which the gate lets run in SRCNN_MODE_MFMA only) the option
     const bool split = wide ? c->wide_split16 != 0 : c->mode == SRCNN_MODE_BANDED16;
-    if (split && wide && !wide16_launcher())       // (a missing kernel is an error; the library always holds the unit)
-        return fail(c, SRCNN_ERR_STATE, "srcnn_set_wide_split16: layer 2 of a wide model in split f16 needs the kernels of "
-                                        "srcnn_wide16_kernels.hip, which this build does not hold; switch the option off");
     if (split && (rc = upload_table16(c))) return rc;
     // a float call scales the layer-1 map by the bound for inputs up to input_range, not 255: the same W2 table, other scales
     float scale1 = c->sp16_scale1, unscale = c->sp16_unscale;
@@ -325,8 +312,8 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
     // the maps were last used on another stream (the two lanes of srcnn_forward_y_frames): wait for that work
     if (c->sp_stream && c->sp_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sp_done, 0));
     const float *frag = static_cast<const float *>(c->sp_table.p);
-    const float *frag2 = frag + wide_l2_offset(C, n1p), *bias2 = frag2 + wide_l2_floats(c->f2, n1p, n2p);
-    const float *frag3 = frag + wide_l3_offset(C, c->f2, n1p, n2p);
+    const float *frag2 = frag + spatial_l2_offset(C, n1p), *bias2 = frag2 + spatial_l2_floats(c->f2, n1p, n2p);
+    const float *frag3 = frag + spatial_l3_offset(C, c->f2, n1p, n2p);
     float *map64 = static_cast<float *>(c->sp_map64.p), *map32 = static_cast<float *>(c->sp_map32.p);
     const size_t dst_stride = io.dst_stride;
     // where layer 1 reads the image (a stripe: the image's rows in src and the halo buffers) and what layer 3 writes (a stripe:
@@ -347,34 +334,18 @@ int forward_banded(srcnn_ctx *c, const BandedPlanes &io, int width, int height, 
             const int b1 = std::min(row_end, b0 + band);
             const int o0 = std::max(0, b0 - 2), o1 = std::min(height, b1 + 2);
             const int m0 = std::max(0, o0 - r2), m1 = std::min(height, o1 + r2);
-            if (wide) {
-                // a wide model: layer 1 group by group (64 output channels each: its own table, its own planes of the map),
-                // layer 2 over n1p / 8 chunks and n2p / 32 output groups, layer 3 from 64 maps where there are 64.  split
-                // (srcnn_set_wide_split16): each group's 64 planes as 8 planes of f16 (hi, lo) pixels, all with the model's one
-                // scale, and layer 2 over n1p / 16 K steps on the f16 MFMA
-                for (int g = 0; g < n1p / 64; ++g)
-                    HIP_TRY(c, launch_spatial_l1(in, zero, split, split ? scale1 : 1.f, width, height, m0, m1,
-                                                 frag + (size_t)g * C * SPATIAL_NFRAG_L1 * 64, map64 + (size_t)g * 64 * mpitch, mpitch,
-                                                 c->stream));
-                if (split)
-                    HIP_TRY(c, wide16_launcher()(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, c->sp16_table.p, bias2, unscale,
-                                                 n1p / 16, n2p / 32, map32, opitch, c->stream));
-                else
-                    HIP_TRY(c, wide_launchers().l2(c->f2, zero, map64, mpitch, m0, m1, width, height, o0, o1, frag2, bias2, n1p / 8,
-                                                   n2p / 32, map32, opitch, c->stream));
-                if (n2p > 32) {
-                    HIP_TRY(c, wide_launchers().l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, c->stream));
-                    continue;
-                }
-            } else {
-                // split: the same bytes of map64 as 8 planes of f16 (hi, lo) pixels, layer 2 on the f16 MFMA
-                HIP_TRY(c, launch_spatial_l1(in, zero, split, scale1, width, height, m0, m1, frag, map64, mpitch, c->stream));
-                HIP_TRY(c, launch_spatial_l2(c->f2, zero, split, map64, mpitch, m0, m1, width, height, o0, o1,
-                                             split ? c->sp16_table.p : (const void *)frag2, bias2, unscale, map32, opitch, c->stream));
-            }
-            // float planes out, the 1-channel replicate model included (no float form of MODE_L3)
-            if (io.f32 || C > 1 || zero) {
-                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, c->stream));
+            // layer 1 group by group (64 output channels each: its own table, its own planes of the map; one group but for a
+            // wide model); split: each group's 64 planes, the same bytes, as 8 planes of f16 (hi, lo) pixels, all with the model's
+            // one scale, and layer 2 on the f16 MFMA
+            for (int g = 0; g < n1p / 64; ++g)
+                HIP_TRY(c, launch_spatial_l1(in, zero, split, scale1, width, height, m0, m1, frag + (size_t)g * C * SPATIAL_NFRAG_L1 * 64,
+                                             map64 + (size_t)g * 64 * mpitch, mpitch, c->stream));
+            HIP_TRY(c, launch_spatial_l2(c->f2, zero, split, map64, mpitch, m0, m1, width, height, o0, o1,
+                                         split ? c->sp16_table.p : (const void *)frag2, bias2, unscale, map32, opitch, n1p, n2p, c->stream));
+            // float planes out, the 1-channel replicate model included (MODE_L3 has no float form), and every form from 64 maps
+            // (MODE_L3 reads 32)
+            if (io.f32 || C > 1 || zero || n2p > 32) {
+                HIP_TRY(c, launch_spatial_l3(C, zero, map32, opitch, o0, o1, width, height, b0, b1, frag3, c->sp_b3, out, n2p, c->stream));
                 continue;
             }
             StripParams q{};
@@ -487,10 +458,6 @@ int srcnn_set_model_shape(srcnn_ctx *c, int channels, int n1, int f2, int n2, co
         c->n2 = n2;
         return SRCNN_OK;
     }
-    // (a missing kernel is an error, here and not at the first call that would run it; the library always holds the unit)
-    if (!wide_launchers().l2 || !wide_launchers().l3)
-        return fail(c, SRCNN_ERR_STATE, "srcnn_set_model_shape: n1 = %d, n2 = %d (padded to %d / %d) needs the kernels of "
-                                        "srcnn_wide_kernels.hip, which this build does not hold", n1, n2, n1p, n2p);
     // A wide model lives in sp_table.  The 9-1-5 tables hold a zero model (and the has-model state) that no gate lets run -- but
     // for layer 3 of a 1-channel model with n2p = 32, which MODE_L3 runs from them under replicate padding (as srcnn_set_model).
     static const std::vector<float> zeros(5184, 0.f);
@@ -535,7 +502,7 @@ int srcnn_get_wide_split16(const srcnn_ctx *c) { return c ? c->wide_split16 : SR
 #ifdef SRCNN_TUNING_BUILD
 /* Undocumented test hook (not part of the ABI, needs no device): the host side of srcnn_set_wide_split16 for a model of `channels`
  * channels padded to n1p (64 or 128) / n2p (32 or 64) filters: w1 [n1p][channels][9][9], b1 [n1p], w2 [n2p][n1p][f2][f2], `range`
- * the largest |input| (255 for the byte entry points).  table: wide_l2h_table_bytes(f2, n1p, n2p) bytes or null; exps: {e1, e2}.
+ * the largest |input| (255 for the byte entry points).  table: spatial_l2h_table_bytes(f2, n1p, n2p) bytes or null; exps: {e1, e2}.
  * Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the option refuses. */
 int srcnn_debug_wide16_tables(int channels, int n1p, int n2p, int f2, const float *w1, const float *b1, const float *w2, float range,
                               uint16_t *table, int *exps)
@@ -545,44 +512,30 @@ int srcnn_debug_wide16_tables(int channels, int n1p, int n2p, int f2, const floa
         return SRCNN_ERR_INVALID;
     std::vector<uint16_t> own;
     if (!table) {
-        own.resize(wide_l2h_table_bytes(f2, n1p, n2p) / sizeof(uint16_t));
+        own.resize(spatial_l2h_table_bytes(f2, n1p, n2p) / sizeof(uint16_t));
         table = own.data();
     }
     if (!banded16_exponent(banded16_l1_bound(channels, w1, b1, (double)range, n1p), &exps[0]) ||
         !banded16_pack_w2(f2, w2, table, &exps[1], n1p, n2p) || std::abs(exps[0] + exps[1]) > 120)
         return SRCNN_ERR_STATE;
-    return (int)wide_l2h_table_bytes(f2, n1p, n2p);
+    return (int)spatial_l2h_table_bytes(f2, n1p, n2p);
 }
 
-/* ... and the dynamic LDS the launcher of wide_l2h_kernel asks for (wide_l2h_lds_bytes; the kernel asserts it is its layout's). */
-int srcnn_debug_wide16_lds_bytes(int f2) { return (f2 != 1 && f2 != 3 && f2 != 5) ? SRCNN_ERR_INVALID : (int)wide_l2h_lds_bytes(f2); }
+/* ... and the dynamic LDS the launcher of spatial_l2h_kernel asks for (spatial_l2h_lds_bytes; the kernel asserts it is its layout's). */
+int srcnn_debug_wide16_lds_bytes(int f2) { return (f2 != 1 && f2 != 3 && f2 != 5) ? SRCNN_ERR_INVALID : (int)spatial_l2h_lds_bytes(f2); }
 
-/* Undocumented test hook (not part of the ABI, needs no device): the host side of SRCNN_MODE_BANDED16 for a model of `channels`
- * channels.  table: spatial_l2h_table_bytes(f2) bytes or null; exps: {e1, e2}, the exponents of the layer-1 map's and W2's
- * scales.  Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the mode refuses. */
-int srcnn_debug_banded16_tables_range(int channels, int f2, const float *w1, const float *b1, const float *w2, float range,
-                                      uint16_t *table, int *exps);
-int srcnn_debug_banded16_tables(int channels, int f2, const float *w1, const float *b1, const float *w2, uint16_t *table, int *exps)
-{
-    return srcnn_debug_banded16_tables_range(channels, f2, w1, b1, w2, 255.f, table, exps);
-}
-
-/* ... for a float call with srcnn_set_input_range(range): e1 follows the range, the table and e2 do not. */
+/* Undocumented test hooks (not part of the ABI, need no device): the host side of SRCNN_MODE_BANDED16 for a model of `channels`
+ * channels, the 64 / 32 case of srcnn_debug_wide16_tables.  table: spatial_l2h_table_bytes(f2) bytes or null; exps: {e1, e2}, the
+ * exponents of the layer-1 map's and W2's scales.  Returns the table's size in bytes, or SRCNN_ERR_STATE for a model the mode
+ * refuses.  _range: for a float call with srcnn_set_input_range(range): e1 follows the range, the table and e2 do not. */
 int srcnn_debug_banded16_tables_range(int channels, int f2, const float *w1, const float *b1, const float *w2, float range,
                                       uint16_t *table, int *exps)
 {
-    if ((channels != 1 && channels != 3) || (f2 != 1 && f2 != 3 && f2 != 5) || !w1 || !b1 || !w2 || !exps || !std::isfinite(range) ||
-        !(range > 0.f))
-        return SRCNN_ERR_INVALID;
-    std::vector<uint16_t> own;
-    if (!table) {
-        own.resize(spatial_l2h_table_bytes(f2) / sizeof(uint16_t));
-        table = own.data();
-    }
-    if (!banded16_exponent(banded16_l1_bound(channels, w1, b1, (double)range), &exps[0]) || !banded16_pack_w2(f2, w2, table, &exps[1]) ||
-        std::abs(exps[0] + exps[1]) > 120)
-        return SRCNN_ERR_STATE;
-    return (int)spatial_l2h_table_bytes(f2);
+    return srcnn_debug_wide16_tables(channels, 64, 32, f2, w1, b1, w2, range, table, exps);
+}
+int srcnn_debug_banded16_tables(int channels, int f2, const float *w1, const float *b1, const float *w2, uint16_t *table, int *exps)
+{
+    return srcnn_debug_banded16_tables_range(channels, f2, w1, b1, w2, 255.f, table, exps);
 }
 
 /* srcnn_set_input_range on a context that is bound to no device (the call touches none): its return code, and in *after the

@@ -23,6 +23,23 @@
 // layer-1 map as f16 (hi, lo) pairs (the same bytes), spatial_l2h_kernel reads it on v_mfma_f32_32x32x16_f16 and writes the same
 // 32 planar f32 maps, layer 3 is unchanged.
 //
+// Models of other widths (srcnn_set_model_shape: n1 <= 128 filters in layer 1, n2 <= 64 in layer 2) run the same kernels.  The
+// host pads the widths to n1p = 64 or 128 and n2p = 32 or 64 with zero weights and zero biases (srcnn_spatial.cpp); 64 / 32 is
+// an ordinary model.  Layer 1 needs no form of its own: its output channels are independent, so n1p / 64 launches of
+// spatial_l1_kernel, each with its own fragment table and its own 64 planes of the map, write the n1p maps (split: 8 planes of
+// 32-byte pixels per launch, all with the model's one scale).  Layers 2 and 3 have WIDE forms, the same bodies over more maps:
+//
+//   spatial_l2_kernel<F2, ZERO, int>    n1p maps -> n2p planar f32 maps: the chunk loop over n1p / 8 chunks (a kernel argument
+//                                       instead of the compile-time 8), one group of 32 output channels per blockIdx.z
+//   spatial_l2h_kernel<F2, ZERO, int>   the split map of n1p channels -> n2p planar f32 maps (srcnn_set_wide_split16): n1p / 16
+//                                       K steps (a kernel argument) instead of 4, one group of 32 output channels per blockIdx.z
+//   spatial_l3_kernel<C, 32, ...>       64 maps -> C channels: 32 k-steps instead of 16; bytes (with or without the pre-clamp
+//                                       floats) or float planes, C = 1 under replicate padding included (from 32 maps those
+//                                       bytes are left to the MODE_L3 strip kernel)
+//
+// A padded channel is 0 after its ReLU (split: both halves of its pair are 0) and carries zero weights downstream: every term it
+// adds is an exact 0, so a 64 / 32 model embedded in wider tensors gives the floats of the forms with compile-time counts.
+//
 // Row stripes (srcnn_model_rows_dev, srcnn_model_rows_halo_dev, srcnn_model_striped*) run the same launches on a row range of
 // the image with one more compile-time form of layer 1, spatial_l1_kernel<1, ZERO, Scale, uint8_t, L1Rows>: the image's rows
 // come from up to three buffers, and no row outside the ones the launch's map rows need is read.  Layers 2 and 3 read the
@@ -30,8 +47,9 @@
 // (srcnn_model_color_rows*_dev, srcnn_model_rows*_f32_dev, srcnn_model_color_striped*, srcnn_model_striped_f32*) are the same
 // with the forms spatial_l1_kernel<C, ZERO, Scale, In, L1RowsCF> for 3 interleaved byte channels and for 1 or 3 float planes.
 //
-// Every form lives in this one translation unit, 55 kernels behind the three launchers at its end (srcnn_kernels.h), which
-// choose the form from what they are given.
+// Every form lives in this one translation unit, 79 kernels behind the three launchers at its end (srcnn_kernels.h), which
+// choose the form from what they are given.  Every load goes through a clamped, always valid address; every store is guarded by
+// the image and band bounds.
 //
 // The input is read at src[y * sstride + x * px_step + c * ch_step]: px_step = 3, ch_step = 1 for interleaved 3-byte pixels
 // (srcnn_forward_color*), px_step = 1, ch_step = plane pitch for the three resized planes of srcnn_process_bgr, and a plain
@@ -49,10 +67,11 @@
 //   layer 1, channel k:  0 + sum over c = 0 .. C - 1 of (w1[k][c][0] x0 + ... + w1[k][c][80] x80 + t_c), taps row-major,
 //                        where t_c = 0 * 1 (a zero tap) for c < C - 1 and t_{C-1} = b1[k] * 1 (the bias tap); for C = 1:
 //                        0 + w1[k][0] y0 + w1[k][1] y1 + ... + w1[k][80] y80 + b1[k]
-//   layer 2, channel k:  b2[k], then the input channels in chunks of 8 (ascending); inside a chunk the taps (kh, kw)
-//                        row-major, inside a tap the channel pairs ascending, channel 2p before 2p + 1.
-//   layer 3, channel o:  per map pixel the tap partials T[tap] = sum_c w3[o][c][tap] F_c (channel pairs ascending), summed
-//                        down the 5 tap rows (m ascending), then ((((V_0 + V_1) + V_2) + V_3) + V_4) + b3[o]
+//   layer 2, channel k:  b2[k], then the input channels in chunks of 8 (ascending, n1p / 8 of them); inside a chunk the taps
+//                        (kh, kw) row-major, inside a tap the channel pairs ascending, channel 2p before 2p + 1.
+//   layer 3, channel o:  per map pixel the tap partials T[tap] = sum_c w3[o][c][tap] F_c (channel pairs ascending, n2p / 2 of
+//                        them), summed down the 5 tap rows (m ascending), then ((((V_0 + V_1) + V_2) + V_3) + V_4) + b3[o]
+// (layer 2 in split f16: the order stated above spatial_l2h_kernel.)  The wide forms continue the order of a 64 / 32 model.
 #include "srcnn_kernels.h"
 
 #include <type_traits>
@@ -76,7 +95,8 @@ constexpr size_t SL1_LDS3 = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 
 constexpr size_t SL1_LDS3F = (size_t)3 * SPATIAL_NFRAG_L1 * 64 * sizeof(float) + 3 * SL1_YC * sizeof(float);
 
 // Kernel arguments are passed as they always were, so that each form compiles to the instructions it had: layer 1 takes the
-// steps of the input (int px_step, long ch_step) for 3 channels and none for 1, layer 3 takes its C biases as C floats.
+// steps of the input (int px_step, long ch_step) for 3 channels and none for 1, layer 3 takes its C biases as C floats (from 64
+// maps: always three, of which it reads C), the wide forms of layer 2 their loop count between the bias and the output.
 // Channel c of input pixel (y, x) (a byte, or a float of the float image path), without and with steps:
 template <typename In>
 __device__ __forceinline__ In l1_at(const In *p, long stride, int y, int x, int) { return p[(long)y * stride + x]; }
@@ -304,11 +324,18 @@ __global__ __launch_bounds__(256) void spatial_l1_kernel(const In *__restrict__ 
 }
 
 // ---- layer 2 ----------------------------------------------------------------------------------------------------------
+// The loop count of a layer-2 kernel: the compile-time count of a 64 / 32 model, or the one kernel argument of a wide form
+__device__ __forceinline__ constexpr int wide_count(int narrow) { return narrow; }
+__device__ __forceinline__ constexpr int wide_count(int, int wide) { return wide; }
+
 // Workgroup: 4 waves, a tile of SL2_COLS = 64 columns x SL2_ROWS = 16 output rows.  Wave w owns rows 4w .. 4w + 3 and both
 // 32-column units of each: 8 accumulators, so every A fragment read from LDS feeds 8 MFMAs.  The K loop walks the 64 input
 // channels in chunks of SL2_CC = 8: per chunk the 8 channels' (16 + 2 r2) x (64 + 2 r2) window (replicate-clamped at the image
 // edges) and the chunk's f2 x f2 x 4 A fragments are staged in LDS, then 8 x f2^2 x 4 MFMAs run per wave.
 // A channel plane of the window is SL2_PS floats, = 32 mod 64: the two lane-halves (channels 2p, 2p + 1) read disjoint banks.
+// A wide form (Wide = int, the chunk count n1p / 8): blockIdx.z = g computes output channels 32g .. 32g + 31, whose fragments
+// [n_chunks][f2 x f2][4][64] start at frag + g * n_chunks * NA, biases at bias + 32g and planes at out + 32g * opitch; the window
+// is staged once per output group.
 constexpr int SL2_COLS = 64, SL2_ROWS = 16, SL2_CC = 8, SL2_XP = 72;
 __host__ __device__ constexpr int sl2_ps(int r2) { return ((((SL2_ROWS + 2 * r2) * SL2_XP) + 31) / 64) * 64 + 32; }
 size_t spatial_l2_lds_bytes(int f2)
@@ -316,11 +343,13 @@ size_t spatial_l2_lds_bytes(int f2)
     return ((size_t)SL2_CC * sl2_ps((f2 - 1) / 2) + (size_t)f2 * f2 * (SL2_CC / 2) * 64) * sizeof(float);
 }
 
-template <int F2, bool ZERO>
+template <int F2, bool ZERO, typename... Wide>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void spatial_l2_kernel(const float *__restrict__ map, long mpitch, int m0, int m1,
                                                          int W, int H, int o0, int o1, const float *__restrict__ frag,
-                                                         const float *__restrict__ bias, float *__restrict__ out, long opitch)
+                                                         const float *__restrict__ bias, Wide... wide, float *__restrict__ out,
+                                                         long opitch)
 {
+    static_assert(sizeof...(Wide) <= 1, "nothing, or the chunk count of a wide model");
     constexpr int R = (F2 - 1) / 2, PS = sl2_ps(R), WR = SL2_ROWS + 2 * R, WC = SL2_COLS + 2 * R;
     constexpr int NA = F2 * F2 * (SL2_CC / 2) * 64;          // A floats per chunk
     extern __shared__ float lds[];
@@ -328,6 +357,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, kk = lane >> 5;
     const int x0 = blockIdx.x * SL2_COLS, y0 = o0 + blockIdx.y * SL2_ROWS;
+    const int n_chunks = wide_count(64 / SL2_CC, wide...);
+    if constexpr (sizeof...(Wide) > 0) {
+        const int group = blockIdx.z;
+        frag += (size_t)group * n_chunks * NA;
+        bias += 32 * group;
+        out += (long)(32 * group) * opitch;
+    }
     f32x16 acc[8];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -335,7 +371,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc[u][q] = b;
     }
-    for (int chunk = 0; chunk < 64 / SL2_CC; ++chunk) {
+    for (int chunk = 0; chunk < n_chunks; ++chunk) {
         __syncthreads();
         for (int e = tid; e < SL2_CC * WR * WC; e += 256) {
             const int c = e / (WR * WC), rem = e - c * (WR * WC), rr = rem / WC, cc = rem - rr * WC;
@@ -386,8 +422,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
 // max(fma(acc, 2^-(e1 + e2), b2[k]), 0), and the output is the 32 planar f32 maps of spatial_l2_kernel.  The power-of-two
 // scales (per model, exact) put the largest layer-1 activation any 8-bit input can give and max |W2| in [2^14, 2^15), so the hi
 // parts of all but vanishing values are normal f16 numbers.
-// Summation order: the input channels in 4 steps of 16 (ascending); inside a step the taps (kh, kw) row-major; per tap three
-// MFMAs, hi hi, then lo hi, then hi lo.  The order of the 16 products inside one MFMA is the hardware's (not documented), so
+// Summation order: the input channels in n1p / 16 steps of 16 (ascending; 4 for a 64 / 32 model; step s: layer-1 channels
+// 64 (s >> 2) + spatial_l2h_channel(s & 3, h, e)); inside a step the taps (kh, kw) row-major; per tap three MFMAs, hi hi, then
+// lo hi, then hi lo.  The order of the 16 products inside one MFMA is the hardware's (not documented), so
 // there is no bitwise CPU model of this kernel: it is held to the tolerance of the f32 path.
 // Workgroup and tile as spatial_l2_kernel: 4 waves, 64 columns x 16 rows, wave w rows 4w .. 4w + 3 and both 32-column units, so
 // each A fragment pair (w_hi, w_lo: 2 x 16 B per lane) feeds 24 MFMAs, with 16 B-operand reads: 18 ds_read_b128 per 24 MFMAs.
@@ -395,29 +432,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
 // 32 (s >> 1) + acc_row(8 (s & 1) + e, h); the A table is packed in that order: [4 steps][f2 x f2 taps][hi, lo][64 lanes][8 f16],
 // lane l: output channel l & 31, K slots 8 (l >> 5) ...  Per step the two planes' (16 + 2 r2) x (64 + 2 r2) window is staged as
 // four LDS planes [plane][hi, lo] of 16-byte words, so the 16 lanes the LDS serves together read 256 consecutive bytes (no bank
-// conflict), and the step's A fragments beside it: 66 / 93 / 135 KiB for f2 = 1 / 3 / 5, one workgroup per CU for f2 = 3, 5.
+// conflict), and the step's A fragments beside it: spatial_l2h_lds_bytes(f2) (srcnn_kernels.h), 66 / 93 / 135 KiB for f2 = 1 / 3 /
+// 5, one workgroup per CU for f2 = 3, 5.  Plane p of the whole map is plane p % 8 of layer-1 group p / 8, at map + 2 p mpitch
+// words.  A wide form (Wide = int, the step count): blockIdx.z = g computes output channels 32g .. 32g + 31, whose fragments
+// [n_steps][f2 x f2][hi, lo][64] start at frag + g * n_steps * NA, biases at bias + 32g and planes at out + 32g * opitch; the
+// window is staged once per output group.
 // With one wave per SIMD nothing else hides the global loads, so step s + 1 is fetched into registers while step s computes.
-constexpr int SL2H_STEPS = 4;
-__host__ __device__ constexpr int sl2h_ps(int r2) { return (((SL2_ROWS + 2 * r2) * (SL2_COLS + 2 * r2) + 7) / 8) * 8 + 4; }
-static size_t spatial_l2h_lds_bytes(int f2) { return ((size_t)4 * sl2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * sizeof(uint4); }
 #define HMFMA(a, b, c) \
     __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, (a)), __builtin_bit_cast(f16x8, (b)), (c), 0, 0, 0)
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-template <int F2, bool ZERO>
+template <int F2, bool ZERO, typename... Wide>
 __global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restrict__ map_, long mpitch, int m0, int m1, int W, int H,
                                                           int o0, int o1, const uint4 *__restrict__ frag_,
-                                                          const float *__restrict__ bias, float unscale, float *__restrict__ out,
-                                                          long opitch)
+                                                          const float *__restrict__ bias, float unscale, Wide... wide,
+                                                          float *__restrict__ out, long opitch)
 {
-    constexpr int R = (F2 - 1) / 2, PS = sl2h_ps(R), WR = SL2_ROWS + 2 * R, WC = SL2_COLS + 2 * R;
+    static_assert(sizeof...(Wide) <= 1, "nothing, or the K-step count of a wide model");
+    constexpr int R = (F2 - 1) / 2, PS = spatial_l2h_ps(R), WR = SL2_ROWS + 2 * R, WC = SL2_COLS + 2 * R;
     constexpr int NA = F2 * F2 * 2 * 64, NAK = (NA + 255) / 256;     // A words (16 B) per step, and per thread
     // a window LINE is one row of one plane, 2 WC words [column][hi, lo] as the map has them; wave w stages lines w, w + 4, ..
     constexpr int LW = 2 * WC, NK = (LW + 63) / 64, NL = 2 * WR / 4;
     static_assert(2 * WR % 4 == 0, "the lines divide among the 4 waves");
+    static_assert(PS >= WR * WC && ((size_t)4 * PS + NA) * sizeof(uint4) == spatial_l2h_lds_bytes(F2),
+                  "the header's plane holds this tile's window, and the launcher's LDS size is this layout's");
     extern __shared__ uint4 lds16[];
+    const int n_steps = wide_count(4, wide...);
     const u32x4 *map = reinterpret_cast<const u32x4 *>(map_), *frag = reinterpret_cast<const u32x4 *>(frag_);
+    if constexpr (sizeof...(Wide) > 0) {
+        const int group = blockIdx.z;
+        frag += (size_t)group * n_steps * NA;
+        bias += 32 * group;
+        out += (long)(32 * group) * opitch;
+    }
     u32x4 *xs = reinterpret_cast<u32x4 *>(lds16), *as = xs + 4 * PS;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, kk = lane >> 5;
@@ -455,7 +503,7 @@ __global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restric
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc[u] = (f32x16){0};
     fetch(0);
-    for (int s = 0; s < SL2H_STEPS; ++s) {
+    for (int s = 0; s < n_steps; ++s) {
         __syncthreads();
 #pragma unroll
         for (int n = 0; n < NL; ++n) {
@@ -470,7 +518,7 @@ __global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restric
 #pragma unroll
         for (int i = 0; i < NAK; ++i) as[min(tid + 256 * i, NA - 1)] = areg[i];
         __syncthreads();
-        if (s + 1 < SL2H_STEPS) fetch(s + 1);
+        if (s + 1 < n_steps) fetch(s + 1);
         const u32x4 *xb = xs + 2 * kk * PS + (4 * wave) * WC + j;
         for (int kh = 0; kh < F2; ++kh) {
 #pragma unroll 1
@@ -510,8 +558,9 @@ __global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restric
 // ---- layer 3 ----------------------------------------------------------------------------------------------------------
 // Workgroup: 4 waves, a strip of SL3_COLS = 128 map columns (image columns 124 bx - 2 ..), of which the middle SL3_OUT = 124
 // are output, and a segment of SL3_SEG output rows; wave w owns map columns 32w .. 32w + 31 and walks the map rows
-// y0 - 2 .. y1 + 1.  Per map row C x 16 MFMAs give the C x 25 tap partials T[tap] = sum_c W3[o][c][tap] F_c (A set o: W3[o]
-// with the rows of l3_row_tap(); B: the 32 channels of the lane's pixel), so register 5s + m of lane-half h holds tap (m, n = s
+// y0 - 2 .. y1 + 1.  Per map row C x K MFMAs (K = 16 k-steps over 32 maps, 32 over the 64 of a wide model; k-step s: channels 2s
+// and 2s + 1 on the two lane-halves) give the C x 25 tap partials T[tap] = sum_c W3[o][c][tap] F_c (A set o: W3[o]
+// with the rows of l3_row_tap(); B: the channels of the lane's pixel), so register 5s + m of lane-half h holds tap (m, n = s
 // (h = 0) or 3 + s (h = 1)).  The loads are clamped to the band's rows and the image's columns, which is replicate padding;
 // ZERO sets the partials of a map pixel outside the image to 0 (a feature outside the image contributes nothing, so the sums
 // need no clamp).  Each wave keeps sl3_ahead(C) map rows of loads in flight: the 1-channel kernel is bound by the 128 B per
@@ -523,19 +572,19 @@ __global__ __launch_bounds__(256) void spatial_l2h_kernel(const uint4 *__restric
 // tiles are handed out XCD by XCD (block b runs on XCD b % 8), so horizontally neighbouring strips share their halo columns in
 // one L2.
 constexpr int SL3_COLS = 128, SL3_OUT = SL3_COLS - 4, SL3_SEG = 16, SL3_XCDS = 8;
-__host__ __device__ constexpr int sl3_ahead(int C) { return C == 1 ? 4 : 2; }   // a ring of sl3_ahead x 16 registers
+__host__ __device__ constexpr int sl3_ahead(int C) { return C == 1 ? 4 : 2; }   // a ring of sl3_ahead x K registers
 
 // Out = float (the float image path): the last argument is the channel pitch of C float planes, and a finished value goes to
 // dst[y * dstride + x + o * ch_pitch] as it is -- no truncation, no clamp, no byte.
 typedef float *__restrict__ l3_pre_ptr;
 template <typename Out> using l3_last_arg = std::conditional_t<std::is_same_v<Out, float>, long, l3_pre_ptr>;
 
-template <int C, bool PRE, bool ZERO, typename Out, typename... B3>
+template <int C, int K, bool PRE, bool ZERO, typename Out, typename... B3>
 __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict__ map, long mpitch, int o0, int o1, int W, int H,
                                                          int b0, int b1, int nx, int n_tiles, const float *__restrict__ frag,
                                                          B3... b3, Out *__restrict__ dst, long dstride, l3_last_arg<Out> pre)
 {
-    static_assert(sizeof...(B3) == C, "one bias per output channel");
+    static_assert((K == 16 || K == 32) && sizeof...(B3) >= C, "k-steps over 32 or 64 maps; a bias per output channel");
     static_assert(!(std::is_same_v<Out, float> && PRE), "the float form has no second output");
     constexpr int AHEAD = sl3_ahead(C);
     __shared__ float vt[2][C][5][SL3_COLS];
@@ -547,20 +596,20 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
     const int c = 32 * wave + j, x = tx * SL3_OUT - 2 + c;
     const int y0 = b0 + ty * SL3_SEG, y1 = min(b1, y0 + SL3_SEG), r_end = y1 + 2;
     const bool col_ok = x >= 0 && x < W;
-    const float bias[C] = {b3...};
-    float a[C][16];
+    const float bias[] = {b3...};
+    float a[C][K];
 #pragma unroll
     for (int o = 0; o < C; ++o)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) a[o][s] = frag[(o * 16 + s) * 64 + lane];
+        for (int s = 0; s < K; ++s) a[o][s] = frag[(o * K + s) * 64 + lane];
     // channels 2s + kk of map row r at the lane's column, from a clamped (always valid) address: no branch between the loads
     const float *colp = map + (long)kk * mpitch + sclamp(x, 0, W - 1);
     auto load = [&](int r, float *v) {
         const float *p = colp + (long)(sclamp(r, o0, o1 - 1) - o0) * W;
 #pragma unroll
-        for (int s = 0; s < 16; ++s) v[s] = p[(long)(2 * s) * mpitch];
+        for (int s = 0; s < K; ++s) v[s] = p[(long)(2 * s) * mpitch];
     };
-    float xr[AHEAD][16], chn[C][3][4];
+    float xr[AHEAD][K], chn[C][3][4];
 #pragma unroll
     for (int o = 0; o < C; ++o)
 #pragma unroll
@@ -579,7 +628,7 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
 #pragma unroll
             for (int o = 0; o < C; ++o) t[o] = (f32x16){0};
 #pragma unroll
-            for (int s = 0; s < 16; ++s)
+            for (int s = 0; s < K; ++s)
 #pragma unroll
                 for (int o = 0; o < C; ++o) t[o] = SMFMA(a[o][s], xr[d][s], t[o]);
             if (r + AHEAD < r_end) load(r + AHEAD, xr[d]);
@@ -606,27 +655,27 @@ __global__ __launch_bounds__(256) void spatial_l3_kernel(const float *__restrict
                         if (n < 5) vr[(o * 5 + n) * SL3_COLS + c] = v[o][s];
                     }
                 __syncthreads();
-                if constexpr (std::is_same_v<Out, float>) {
-                    if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
-                        const long ob = (long)y * dstride + x;
-#pragma unroll
-                        for (int o = 0; o < C; ++o) {
-                            const float *vo = vr + o * 5 * SL3_COLS;
-                            const float sum = (((vo[c - 2] + vo[SL3_COLS + c - 1]) + vo[2 * SL3_COLS + c]) + vo[3 * SL3_COLS + c + 1]) +
-                                              vo[4 * SL3_COLS + c + 2];
-                            dst[ob + o * pre] = sum + bias[o];
-                        }
-                    }
-                } else if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
-                    const long ob = (long)y * dstride + (long)C * x;
+                if (kk == 0 && c >= 2 && c < SL3_COLS - 2 && x < W) {
+                    constexpr bool F32 = std::is_same_v<Out, float>;
+                    // (one offset, formed per family where each kernel had it: before the sums from 32 maps, after each sum from 64.
+                    // Either writing alone leaves the other family's listing reordered around the epilogue, and timed on the GPU
+                    // some rows of the reordered family fell outside the run-to-run gap of the parent: DESIGN.md 4.6)
+                    const long row = K == 16 ? (long)y * dstride + (F32 ? x : (long)C * x) : 0;
 #pragma unroll
                     for (int o = 0; o < C; ++o) {
                         const float *vo = vr + o * 5 * SL3_COLS;
                         const float sum = (((vo[c - 2] + vo[SL3_COLS + c - 1]) + vo[2 * SL3_COLS + c]) + vo[3 * SL3_COLS + c + 1]) +
                                           vo[4 * SL3_COLS + c + 2];
                         const float val = sum + bias[o];
-                        dst[ob + o] = (uint8_t)sclamp((int)val, 0, 255);
-                        if constexpr (PRE) pre[ob + o] = val;
+                        long ob;
+                        if constexpr (F32) ob = K == 16 ? row + o * pre : (long)y * dstride + x + o * pre;
+                        else ob = K == 16 ? row + o : (long)y * dstride + (long)C * x + o;
+                        if constexpr (F32) {
+                            dst[ob] = val;
+                        } else {
+                            dst[ob] = (uint8_t)sclamp((int)val, 0, 255);
+                            if constexpr (PRE) pre[ob] = val;
+                        }
                     }
                 }
             }
@@ -686,51 +735,68 @@ hipError_t launch_spatial_l1(const L1Input &in, bool zero, bool split, float sca
 }
 
 hipError_t launch_spatial_l2(int f2, bool zero, bool split, const void *map, long mpitch, int m0, int m1, int W, int H, int o0, int o1,
-                             const void *frag, const float *bias, float unscale, float *out, long opitch, hipStream_t st)
+                             const void *frag, const float *bias, float unscale, float *out, long opitch, int n1p, int n2p,
+                             hipStream_t st)
 {
-    const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS));
-    // (f2 = 1 under replicate padding: the colour 9-1-5 model; the 1-channel one runs on the strip kernels)
+    if ((n1p != 64 && n1p != 128) || (n2p != 32 && n2p != 64)) return hipErrorInvalidValue;
+    const bool wide = n1p != 64 || n2p != 32;      // the count as an argument, a group of 32 output planes per grid z
+    const dim3 grid((unsigned)((W + SL2_COLS - 1) / SL2_COLS), (unsigned)((o1 - o0 + SL2_ROWS - 1) / SL2_ROWS), (unsigned)(n2p / 32));
+    // (f2 = 1 under replicate padding: the colour 9-1-5 model and the wide ones; the 1-channel one runs on the strip kernels)
     return with_form<1, 3, 5>(f2, zero, [&](auto F2, auto ZERO) {
         // (the 9-5-5 kernel's 70 KB and every split form exceed the default dynamic-LDS limit; set per call: the attribute is
         // per device)
-        if (split) {
-            auto *kernel = spatial_l2h_kernel<decltype(F2)::value, decltype(ZERO)::value>;
-            const size_t lds = spatial_l2h_lds_bytes(F2);
+        auto launch = [&](auto *kernel, size_t lds, auto... args) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, static_cast<const uint4 *>(map), mpitch, m0, m1, W, H, o0, o1,
-                               static_cast<const uint4 *>(frag), bias, unscale, out, opitch);
-        } else {
-            auto *kernel = spatial_l2_kernel<decltype(F2)::value, decltype(ZERO)::value>;
-            const size_t lds = spatial_l2_lds_bytes(F2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, static_cast<const float *>(map), mpitch, m0, m1, W, H, o0, o1,
-                               static_cast<const float *>(frag), bias, out, opitch);
-        }
-        return hipGetLastError();
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, args...);
+            return hipGetLastError();
+        };
+        // one form: the kernel with `count...` (nothing, or the K steps or chunks of a wide model) between its bias and its output
+        constexpr int f = decltype(F2)::value;
+        constexpr bool z = decltype(ZERO)::value;
+        auto f16 = [&](auto... count) {
+            const size_t lds = spatial_l2h_lds_bytes(f);
+            return launch(spatial_l2h_kernel<f, z, decltype(count)...>, lds, static_cast<const uint4 *>(map), mpitch, m0, m1, W, H, o0, o1,
+                          static_cast<const uint4 *>(frag), bias, unscale, count..., out, opitch);
+        };
+        auto f32 = [&](auto... count) {
+            const size_t lds = spatial_l2_lds_bytes(f);
+            return launch(spatial_l2_kernel<f, z, decltype(count)...>, lds, static_cast<const float *>(map), mpitch, m0, m1, W, H, o0, o1,
+                          static_cast<const float *>(frag), bias, count..., out, opitch);
+        };
+        if (split) return wide ? f16(n1p / 16) : f16();
+        return wide ? f32(n1p / 8) : f32();
     });
 }
 
 hipError_t launch_spatial_l3(int channels, bool zero, const float *map, long mpitch, int o0, int o1, int W, int H, int b0, int b1,
-                             const float *frag, const float *b3, const L3Output &out, hipStream_t st)
+                             const float *frag, const float *b3, const L3Output &out, int n2p, hipStream_t st)
 {
+    if (n2p != 32 && n2p != 64) return hipErrorInvalidValue;
     const int nx = (W + SL3_OUT - 1) / SL3_OUT, ny = (b1 - b0 + SL3_SEG - 1) / SL3_SEG, n_tiles = nx * ny;
     const dim3 grid((unsigned)(SL3_XCDS * ((n_tiles + SL3_XCDS - 1) / SL3_XCDS)));
-    // one form: spatial_l3_kernel<C, PRE, ZERO, Out, float x C> by the type of dst; last: the kernel's last argument
-    auto launch = [&](auto C, auto ZERO, auto PRE, auto *dst, auto last, auto... b) {
+    // one form: spatial_l3_kernel<C, K, PRE, ZERO, Out, float...> by the type of dst; last: the kernel's last argument
+    auto launch = [&](auto C, auto K, auto ZERO, auto PRE, auto *dst, auto last, auto... b) {
         using Out = std::remove_pointer_t<decltype(dst)>;
-        hipLaunchKernelGGL((spatial_l3_kernel<decltype(C)::value, decltype(PRE)::value, decltype(ZERO)::value, Out, decltype(b)...>), grid,
-                           dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, b..., dst, out.dstride, last);
+        hipLaunchKernelGGL((spatial_l3_kernel<decltype(C)::value, decltype(K)::value, decltype(PRE)::value, decltype(ZERO)::value, Out,
+                                              decltype(b)...>),
+                           grid, dim3(256), 0, st, map, mpitch, o0, o1, W, H, b0, b1, nx, n_tiles, frag, b..., dst, out.dstride, last);
         return hipGetLastError();
     };
     return with_form<1, 3>(channels, zero, [&](auto C, auto ZERO) -> hipError_t {
-        auto biases = [&](auto PRE, auto *dst, auto last) {
-            if constexpr (decltype(C)::value == 1) return launch(C, ZERO, PRE, dst, last, b3[0]);
-            else return launch(C, ZERO, PRE, dst, last, b3[0], b3[1], b3[2]);
+        constexpr int c = decltype(C)::value;
+        // the kernel from 32 maps takes its C biases, the one from 64 maps always three (as each always did)
+        auto biases = [&](auto K, auto PRE, auto *dst, auto last) {
+            if constexpr (decltype(K)::value == 32) return launch(C, K, ZERO, PRE, dst, last, b3[0], c == 3 ? b3[1] : 0.f, c == 3 ? b3[2] : 0.f);
+            else if constexpr (c == 1) return launch(C, K, ZERO, PRE, dst, last, b3[0]);
+            else return launch(C, K, ZERO, PRE, dst, last, b3[0], b3[1], b3[2]);
         };
-        if (out.f32) return biases(std::false_type{}, static_cast<float *>(out.dst), out.ch_pitch);
-        if constexpr (decltype(C)::value == 1 && !decltype(ZERO)::value) return hipErrorInvalidValue;      // (MODE_L3 runs it)
-        else if (out.pre) return biases(std::true_type{}, static_cast<uint8_t *>(out.dst), out.pre);
-        else return biases(std::false_type{}, static_cast<uint8_t *>(out.dst), out.pre);
+        auto output = [&](auto K) -> hipError_t {
+            if (out.f32) return biases(K, std::false_type{}, static_cast<float *>(out.dst), out.ch_pitch);
+            if constexpr (decltype(K)::value == 16 && c == 1 && !decltype(ZERO)::value) return hipErrorInvalidValue;      // (MODE_L3 runs it)
+            else if (out.pre) return biases(K, std::true_type{}, static_cast<uint8_t *>(out.dst), out.pre);
+            else return biases(K, std::false_type{}, static_cast<uint8_t *>(out.dst), out.pre);
+        };
+        return n2p == 64 ? output(std::integral_constant<int, 32>{}) : output(std::integral_constant<int, 16>{});
     });
 }
 

@@ -37,8 +37,8 @@ bool fused_pipeline_ok(int, int, int, int, const void *, long, const void *, lon
 hipError_t launch_bgr_to_y_resized(const uint8_t *, long, int, int, uint8_t *, long, int, int, const int *, const short *, const int *, const short *, hipStream_t) { return never(); }
 hipError_t launch_resize_merge(const uint8_t *, long, int, int, const uint8_t *, long, uint8_t *, long, int, int, const int *, const short *, const int *, const short *, hipStream_t) { return never(); }
 hipError_t launch_spatial_l1(const L1Input &, bool, bool, float, int, int, int, int, const float *, void *, long, hipStream_t) { return never(); }
-hipError_t launch_spatial_l2(int, bool, bool, const void *, long, int, int, int, int, int, int, const void *, const float *, float, float *, long, hipStream_t) { return never(); }
-hipError_t launch_spatial_l3(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, const L3Output &, hipStream_t) { return never(); }
+hipError_t launch_spatial_l2(int, bool, bool, const void *, long, int, int, int, int, int, int, const void *, const float *, float, float *, long, int, int, hipStream_t) { return never(); }
+hipError_t launch_spatial_l3(int, bool, const float *, long, int, int, int, int, int, int, const float *, const float *, const L3Output &, int, hipStream_t) { return never(); }
 hipError_t launch_split3(const uint8_t *, long, int, int, uint8_t *, long, hipStream_t) { return never(); }
 }  // namespace srcnn
 

@@ -12,7 +12,12 @@ UNIT = "srcnn_spatial_kernels.hip"
 # families of layer-1 forms by what the mangled name says of Scale (NoScale or f), In (h: bytes, f: floats) and Steps...
 L1 = r"spatial_l1_kernelILi\dELb[01]E(?:NS_7NoScaleE|f)"
 L1_BYTES, L1_FLOATS, L1_ROWS, L1_ROWS_CF = L1 + r"hJ(?:il)?E", L1 + r"fJ(?:il)?E", L1 + r"hJNS_6L1RowsE", L1 + r"[hf]JNS_8L1RowsCFE"
-L3_BYTES, L3_FLOATS = r"spatial_l3_kernelILi\dELb[01]ELb[01]EhJ", r"spatial_l3_kernelILi\dELb0ELb[01]EfJ"
+# layers 2 and 3: the forms of a 64 / 32 model (an empty pack, 16 k-steps) and the wide forms of a model of other widths (a pack of
+# one int: the chunk or K-step count as a kernel argument; 32 k-steps)
+L2, L2H = r"spatial_l2_kernelILi\dELb[01]EJEE", r"spatial_l2h_kernelILi\dELb[01]EJEE"
+L2_WIDE, L2H_WIDE = r"spatial_l2_kernelILi(\d)ELb([01])EJiEE", r"spatial_l2h_kernelILi(\d)ELb([01])EJiEE"
+L3_BYTES, L3_FLOATS = r"spatial_l3_kernelILi\dELi16ELb[01]ELb[01]EhJ", r"spatial_l3_kernelILi\dELi16ELb0ELb[01]EfJ"
+L3_WIDE = r"spatial_l3_kernelILi(\d)ELi32ELb([01])ELb([01])E([hf])JfffEE"
 
 
 @functools.lru_cache(maxsize=None)

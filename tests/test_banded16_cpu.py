@@ -187,14 +187,14 @@ def test_split_arithmetic_meets_the_mfma_tolerance_colour(f2, padding):
 
 # ---- the device code ----------------------------------------------------------------------------------------------------------
 def test_no_kernel_of_the_unit_uses_scratch_memory():
-    assert len(L.kernels("spatial_l2h_kernel")) == 6                # f2 = 1, 3, 5 x replicate, zero
+    assert len(L.kernels(L.L2H)) == 6                               # f2 = 1, 3, 5 x replicate, zero (a 64 / 32 model's forms)
     assert len(L.kernels(L.L1_BYTES)) == 8                          # 1, 3 channels x replicate, zero x f32, split output
     for name, desc, _ in L.kernels():
         assert L.private_bytes(desc) == 0, name
 
 
 def test_layer2_kernel_runs_on_the_f16_mfma_only():
-    found = L.kernels("spatial_l2h_kernel")
+    found = L.kernels(L.L2H)
     assert len(found) == 6
     for name, _, body in found:
         assert "v_mfma_f32_32x32x16_f16" in body, name

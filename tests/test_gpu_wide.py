@@ -1,4 +1,4 @@
-"""Models of other widths on the GPU (srcnn_set_model_shape: up to 128 / 64 filters; srcnn_wide_kernels.hip): float64 references
+"""Models of other widths on the GPU (srcnn_set_model_shape: up to 128 / 64 filters; the wide forms of srcnn_spatial_kernels.hip): float64 references
 at the tile edges of all three layers, three bitwise links to the 64 / 32 path (zero-embedded models, one-hot hidden channels,
 integer-valued input through both paths), the band seams of a 1024 x 768 plane, batches with padded strides and guard
 elements, a 128 / 64 nn.Module through compile_module, the narrow models, the refusals and model replacement.
@@ -177,7 +177,7 @@ def test_one_hot_channels_equal_the_pair_moved_to_0_0(wctx, channels, f2, paddin
                          [(128, 32, 1, "zero"), (128, 32, 3, "replicate"), (128, 32, 3, "zero"), (64, 64, 1, "replicate")])
 @pytest.mark.parametrize("f2", [1, 3, 5])
 def test_bitwise_equal_to_the_byte_paths_preclamp(wctx, n1, n2, channels, padding, f2):
-    """Wherever layer 3 runs a kernel of the new unit (n2p = 64) or spatial_l3_kernel (n2p = 32, but for bytes of 1 channel
+    """Wherever layer 3 runs a wide form (n2p = 64) or spatial_l3_kernel (n2p = 32, but for bytes of 1 channel
     under replicate padding, which MODE_L3 runs): the same arithmetic in the same order on both paths."""
     wctx.set_model(*random_wide_model(channels, n1, f2, n2, 5))
     wctx.set_padding(padding)

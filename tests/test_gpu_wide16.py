@@ -1,4 +1,4 @@
-"""Layer 2 of a wide model in split f16 on the GPU (srcnn_set_wide_split16; srcnn_wide16_kernels.hip): float64 references at the
+"""Layer 2 of a wide model in split f16 on the GPU (srcnn_set_wide_split16; spatial_l2h_kernel's wide forms): float64 references at the
 tile edges of all three layers, two bitwise links to what already runs (a 64 / 32 model zero-embedded in wider tensors gives
 SRCNN_MODE_BANDED16's bytes and floats; one-hot hidden channels), the band seam of a 1024 x 768 plane, the float path's input
 range and compile_module(mode=MODE_BANDED16) on a 128 / 64 module, and that nothing else moves: narrow models, the refusals, the

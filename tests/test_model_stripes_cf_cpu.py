@@ -207,12 +207,13 @@ def test_the_new_kernels_run_on_the_f32_mfma_only():
 
 
 def test_one_unit_holds_every_form_and_no_launcher_is_weak():
-    """What the side units and the weak launchers stood for: the kernel set of the banded path is exactly the one it was, and
-    the host layer depends on no optional symbol (tests/checks/san_host.cpp links it against three stubs)."""
+    """What the side units, the weak launchers and the launchers handed over by constructors stood for: the kernel set of the
+    banded path is exactly the one it was, the wide forms of layers 2 and 3 included, and the host layer depends on no optional
+    symbol (tests/checks/san_host.cpp links it against three stubs)."""
     names = [n for n, _, _ in L.kernels()]
-    assert len(names) == 55 and len(set(names)) == 55, names
+    assert len(names) == 79 and len(set(names)) == 79, names
     families = [("split3_kernel", 1), (L.L1_BYTES, 8), (L.L1_ROWS, 4), (L.L1_ROWS_CF, 12), (L.L1_FLOATS, 8),
-                ("spatial_l2_kernel", 6), ("spatial_l2h_kernel", 6), (L.L3_BYTES, 6), (L.L3_FLOATS, 4)]
+                (L.L2, 6), (L.L2H, 6), (L.L3_BYTES, 6), (L.L3_FLOATS, 4), (L.L2_WIDE, 6), (L.L2H_WIDE, 6), (L.L3_WIDE, 12)]
     picked = []
     for pattern, count in families:
         family = [n for n, _, _ in L.kernels(pattern)]
@@ -221,8 +222,11 @@ def test_one_unit_holds_every_form_and_no_launcher_is_weak():
     assert sorted(picked) == sorted(names)                     # every kernel is in exactly one family
     header = (B.CSRC / "srcnn_kernels.h").read_text()
     assert "weak" not in header
+    assert not re.search(r"set_\w*launcher", header) and "Launchers" not in header       # nothing is handed over at load time
+    assert "__attribute__((constructor))" not in (B.CSRC / L.UNIT).read_text()
     assert len(re.findall(r"^hipError_t launch_spatial_\w+\(", header, re.M)) == 3
     units = [u[0] for u in B.UNITS]
     assert units.count(L.UNIT) == 1
-    for gone in ("srcnn_spatial_f32.hip", "srcnn_spatial_rows.hip", "srcnn_spatial_rows_cf.hip"):
+    for gone in ("srcnn_spatial_f32.hip", "srcnn_spatial_rows.hip", "srcnn_spatial_rows_cf.hip", "srcnn_wide_kernels.hip",
+                 "srcnn_wide16_kernels.hip"):
         assert gone not in units and not (B.CSRC / gone).exists()

@@ -1,6 +1,6 @@
-"""Layer 2 of a wide model in split f16 (srcnn_set_wide_split16, srcnn_wide16_kernels.hip) without a GPU: the ABI, the host side of
+"""Layer 2 of a wide model in split f16 (srcnn_set_wide_split16) without a GPU: the ABI, the host side of
 the split for padded widths n1p / n2p (scales and the W2 table, through the tuning library's hook), a numpy model of the split
-arithmetic against the float64 restatement, and the device code of the new kernel unit.
+arithmetic against the float64 restatement, and the device code of the wide forms of spatial_l2h_kernel.
 
 The numpy model is tests/test_banded16_cpu.py's split_model for any widths: layer 1 in float32, every activation times 2^e1
 split into a_hi = rtz_f16(a), a_lo = f16(a - a_hi), W2 times 2^e2 split round-to-nearest (the library's own table, decoded),
@@ -11,7 +11,6 @@ import ctypes as C
 import functools
 import re
 import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -22,6 +21,7 @@ import torch.nn.functional as F
 import srcnn_cpp_amd as S
 from srcnn_cpp_amd import build as B
 from srcnn_cpp_amd.synth import synth_luma
+import spatial_listing as L
 from color_reference import synth_color
 from spatial_reference import as_model, pre_tolerance, random_model
 from wide_reference import embed, forward, padded_widths, random_wide_model
@@ -55,11 +55,10 @@ def test_header_declares_and_library_exports_the_option(lib):
     assert callable(S.Context.set_wide_split16) and callable(S.Context.wide_split16)
 
 
-def test_null_context_and_the_unit_is_in_the_build(lib):
+def test_null_context_and_the_unit_is_gone_from_the_build_and_from_disk(lib):
     assert lib.srcnn_set_wide_split16(None, 1) == S.ERR_INVALID
     assert lib.srcnn_get_wide_split16(None) == S.ERR_INVALID
-    flags = {u[0]: u[1] for u in B.UNITS if len(u) == 2}
-    assert flags[UNIT] == flags["srcnn_spatial_kernels.hip"] == flags["srcnn_wide_kernels.hip"]
+    assert UNIT not in [u[0] for u in B.UNITS] and not (B.CSRC / UNIT).exists()
 
 
 # ---- 2: the host side: exponents and the split W2 table -------------------------------------------------------------------
@@ -289,51 +288,31 @@ def test_the_numpy_model_restates_the_one_of_banded16_at_64_32():
     assert np.array_equal(got, want)
 
 
-# ---- 4: the device code of the new unit -----------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def listing():
-    """The unit's gfx950 assembly, compiled with the build's flags for it."""
-    flags = [u[1] for u in B.UNITS if u[0] == UNIT and len(u) == 2][0]
-    with tempfile.TemporaryDirectory() as d:
-        out = Path(d) / "unit.s"
-        subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, f"-I{B.CSRC}", "-S", "--cuda-device-only",
-                        "-o", str(out), str(B.CSRC / UNIT)], check=True, stderr=subprocess.DEVNULL)
-        return out.read_text()
-
-
-def kernels():
-    text = listing()
-    found = []
-    for name, desc in re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-        body = re.search(rf"^{re.escape(name)}:(.*?)^\.Lfunc_end", text, re.S | re.M).group(1)
-        found.append((name, desc, body))
-    return found
-
-
+# ---- 4: the device code of the wide forms (srcnn_spatial_kernels.hip) -----------------------------------------------------
 def l2h_lds_bytes(f2):
-    """spatial_l2h_lds_bytes(f2) (srcnn_spatial_kernels.hip): four window planes [plane][hi, lo] and one step's A fragments."""
+    """spatial_l2h_lds_bytes(f2) (srcnn_kernels.h): four window planes [plane][hi, lo] and one step's A fragments."""
     r = (f2 - 1) // 2
     ps = ((16 + 2 * r) * (64 + 2 * r) + 7) // 8 * 8 + 4
     return (4 * ps + f2 * f2 * 2 * 64) * 16
 
 
 def test_the_units_kernels():
-    ks = kernels()
+    ks = L.kernels(L.L2H_WIDE)
     assert len(ks) == 6 and len({k[0] for k in ks}) == 6
-    forms = sorted(re.search(r"wide_l2h_kernelILi(\d)ELb([01])E", k[0]).groups() for k in ks)
+    forms = sorted(re.search(L.L2H_WIDE, k[0]).groups() for k in ks)
     assert forms == sorted((f, z) for f in "135" for z in "01")          # f2 = 1, 3, 5 x replicate, zero
     for name, desc, body in ks:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, f"{name} has a private segment"
+        assert L.private_bytes(desc) == 0, f"{name} has a private segment"
         assert "scratch_" not in body, name
-        assert set(re.findall(r"\b(v_mfma_\w+)", body)) == {"v_mfma_f32_32x32x16_f16"}, name
+        assert L.mfma_kinds(body) == {"v_mfma_f32_32x32x16_f16"}, name
         assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 512
         # all LDS is dynamic: the launcher's constant below is the whole of it
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", desc).group(1)) == 0
+        assert L.static_lds_bytes(desc) == 0
 
 
 def test_the_launchers_lds_sizes_are_those_of_spatial_l2h_kernel():
-    """The launcher asks for wide_l2h_lds_bytes(f2) (srcnn_kernels.h; the kernel static_asserts that this is its layout's size):
-    spatial_l2h_lds_bytes(f2), 66 / 93 / 135 KiB, inside the 160 KiB of a gfx950 CU."""
+    """The launcher asks for spatial_l2h_lds_bytes(f2) (srcnn_kernels.h; the kernel static_asserts that this is its layout's size):
+    66 / 93 / 135 KiB, inside the 160 KiB of a gfx950 CU.  One function, used by the one kernel and the one launcher."""
     lib = C.CDLL(str(S.tuning_library_path()))
     lib.srcnn_debug_wide16_lds_bytes.restype = C.c_int
     lib.srcnn_debug_wide16_lds_bytes.argtypes = [C.c_int]
@@ -341,9 +320,11 @@ def test_the_launchers_lds_sizes_are_those_of_spatial_l2h_kernel():
     assert got == [l2h_lds_bytes(f2) for f2 in (1, 3, 5)]
     assert [round(b / 1024) for b in got] == [66, 93, 135] and max(got) <= 160 * 1024
     assert lib.srcnn_debug_wide16_lds_bytes(7) == S.ERR_INVALID
-    src = (B.CSRC / UNIT).read_text()
-    assert "const size_t lds = wide_l2h_lds_bytes(F2);" in src and "== wide_l2h_lds_bytes(F2)" in src
-    # the same figures from the kernel unit whose layout this is
-    spatial = (B.CSRC / "srcnn_spatial_kernels.hip").read_text()
-    assert "(((SL2_ROWS + 2 * r2) * (SL2_COLS + 2 * r2) + 7) / 8) * 8 + 4" in spatial
-    assert "((size_t)4 * sl2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * sizeof(uint4)" in spatial
+    src, header = (B.CSRC / L.UNIT).read_text(), (B.CSRC / "srcnn_kernels.h").read_text()
+    assert "const size_t lds = spatial_l2h_lds_bytes(f);" in src and "== spatial_l2h_lds_bytes(F2)" in src
+    # the figures are the header's one pair of functions, for the tile the kernel unit states
+    assert "(((16 + 2 * r2) * (64 + 2 * r2) + 7) / 8) * 8 + 4" in header
+    assert "((size_t)4 * spatial_l2h_ps((f2 - 1) / 2) + (size_t)f2 * f2 * 2 * 64) * 16" in header
+    for fn in (r"\w+_l2h_ps\(int", r"\w+_l2h_lds_bytes\(int"):
+        assert len(re.findall(fn, header + src)) == 1, fn
+    assert "constexpr int SL2_COLS = 64, SL2_ROWS = 16," in src and "PS >= WR * WC" in src

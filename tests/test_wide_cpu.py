@@ -1,10 +1,8 @@
 """Models of other widths (srcnn_set_model_shape, srcnn_get_model_shape) without a GPU: the ABI, the loaders' acceptance and
 refusals, what Context.set_model hands to the library (on a context without a device), the references' own consistency, and
-the device code of the new kernel unit."""
-import functools
+the device code of the wide forms of layers 2 and 3."""
 import re
 import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -13,6 +11,7 @@ import torch
 
 import srcnn_cpp_amd as S
 from srcnn_cpp_amd import build as B
+import spatial_listing as L
 from color_reference import random_color_model, torch_forward_color
 from spatial_reference import band_seams as band_seams_64_32
 from spatial_reference import random_model, torch_forward
@@ -222,46 +221,25 @@ def test_band_seams_formula():
     assert len(band_seams(3840, 2160, 5, 128, 64)) > len(band_seams_64_32(3840, 2160, 5))
 
 
-# ---- the device code of the new unit --------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def listing():
-    """The unit's gfx950 assembly, compiled with the build's flags for it."""
-    flags = [u[1] for u in B.UNITS if u[0] == UNIT and len(u) == 2][0]
-    with tempfile.TemporaryDirectory() as d:
-        out = Path(d) / "unit.s"
-        subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, f"-I{B.CSRC}", "-S", "--cuda-device-only",
-                        "-o", str(out), str(B.CSRC / UNIT)], check=True, stderr=subprocess.DEVNULL)
-        return out.read_text()
-
-
-def kernels():
-    text = listing()
-    found = []
-    for name, desc in re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-        body = re.search(rf"^{re.escape(name)}:(.*?)^\.Lfunc_end", text, re.S | re.M).group(1)
-        found.append((name, desc, body))
-    return found
-
-
-def test_the_unit_is_built_with_the_spatial_units_flags():
-    flags = {u[0]: u[1] for u in B.UNITS if len(u) == 2}
-    assert flags[UNIT] == flags["srcnn_spatial_kernels.hip"]
+# ---- the device code of the wide forms (srcnn_spatial_kernels.hip) -----------------------------------------------------------
+def test_the_unit_is_gone_from_the_build_and_from_disk():
+    assert UNIT not in [u[0] for u in B.UNITS] and not (B.CSRC / UNIT).exists()
 
 
 def test_the_units_kernels():
-    ks = kernels()
-    l2 = [k for k in ks if "wide_l2_kernel" in k[0]]
-    l3 = [k for k in ks if "wide_l3_kernel" in k[0]]
+    l2, l3 = L.kernels(L.L2_WIDE), L.kernels(L.L3_WIDE)
+    ks = l2 + l3
     assert len(l2) == 6 and len(l3) == 12 and len(ks) == 18
     assert len({k[0] for k in ks}) == 18
+    assert sorted(re.search(L.L2_WIDE, k[0]).groups() for k in l2) == sorted((f2, z) for f2 in "135" for z in "01")
     # layer 3: C = 1, 3 x replicate, zero x {bytes, bytes + pre-clamp, floats}
-    forms = sorted(re.search(r"wide_l3_kernelILi(\d)ELb([01])ELb([01])E([hf])", k[0]).groups() for k in l3)
+    forms = sorted(re.search(L.L3_WIDE, k[0]).groups() for k in l3)
     assert forms == sorted((c, pre, z, t) for c in "13" for z in "01" for pre, t in (("0", "h"), ("1", "h"), ("0", "f")))
     for name, desc, body in ks:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, f"{name} has a private segment"
+        assert L.private_bytes(desc) == 0, f"{name} has a private segment"
         assert "scratch_" not in body, name
-        assert set(re.findall(r"\b(v_mfma_\w+)", body)) == {"v_mfma_f32_32x32x2_f32"}, name
+        assert L.mfma_kinds(body) == {"v_mfma_f32_32x32x2_f32"}, name
         assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 512
     for name, desc, body in l3:     # the LDS row of the strip: 2 x C x 5 x 128 floats, nothing else
-        c = int(re.search(r"wide_l3_kernelILi(\d)", name).group(1))
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", desc).group(1)) == 2 * c * 5 * 128 * 4
+        c = int(re.search(L.L3_WIDE, name).group(1))
+        assert L.static_lds_bytes(desc) == 2 * c * 5 * 128 * 4

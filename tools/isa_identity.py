@@ -18,6 +18,13 @@ kernel sets are then the same, one for one.  How the four units of the banded pa
 
     python tools/isa_identity.py srcnn_spatial_kernels.hip --rev <parent> --exact \
         --old-units srcnn_spatial_kernels.hip srcnn_spatial_f32.hip srcnn_spatial_rows.hip srcnn_spatial_rows_cf.hip
+
+and how the two units of the wide forms (models of other widths) joined it with
+
+    python tools/isa_identity.py srcnn_spatial_kernels.hip --rev <parent> --exact \
+        --old-units srcnn_spatial_kernels.hip srcnn_wide_kernels.hip srcnn_wide16_kernels.hip
+
+(79 of 79 identical; DESIGN.md 4.6 says which three lines of the layer-3 epilogue that takes).
 """
 import argparse
 import hashlib
