@@ -6,7 +6,10 @@ The numpy model restates what the kernels compute: layer 1 in float32, every act
 a_hi = rtz_f16(a), a_lo = f16(a - a_hi), W2 times 2^e2 split round-to-nearest (the library's own table, decoded), layer 2 as the
 three products hi*hi + lo*hi + hi*lo (each exact; summed here in float64), one multiply by 2^-(e1 + e2) and the bias in float32,
 layer 3 in float32.  The same model with the lo parts dropped -- plain f16 operands -- must MISS the tolerance on the 9-3-5 and
-9-5-5 cases: the test can tell the split from a single f16 product."""
+9-5-5 cases: the test can tell the split from a single f16 product.
+
+split_model also takes one seeded defect (DEFECTS): tests/test_banded_error_level_cpu.py shows that the float32 error level of
+tests/error_level.py, which the GPU tests apply to the kernels, passes the intact model and rejects every defect."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -107,14 +110,27 @@ def rtz_f16(a):
     return np.where(over, np.nextafter(h, np.float16(0)), h)
 
 
-def split_model(x, model, padding, terms):
-    """x [C, h, w] u8 -> the values before truncation [C, h, w] (float32 layers 1 and 3, split layer 2; terms = 1: hi * hi only)."""
+DEFECTS = ("a_lo_one_k_step", "w_lo_one_tap", "w_lo", "a_lo", "lo_right_unit")
+
+
+def split_model(x, model, padding, terms, defect=None, tables=None):
+    """x [C, h, w] u8 -> the values before truncation [C, h, w] (float32 layers 1 and 3, split layer 2; terms = 1: hi * hi only).
+    defect: None, or one of DEFECTS -- a seeded loss of lo parts, as a kernel could have it: a_lo dropped in K step 1 of 4 (its 16
+    channels from l2h_channel), w_lo dropped on tap (0, 0), w_lo or a_lo dropped everywhere, both lo terms dropped in columns
+    32 .. 63 of every 64-column tile (the right 32-column MFMA unit of spatial_l2h_kernel).  tables: host_tables(model), to
+    decode the library's table once for many images."""
+    assert defect is None or (defect in DEFECTS and terms == 3)
     w1, b1, w2, b2, w3, b3 = model
     w1, w3 = np.asarray(w1, np.float32), np.asarray(w3, np.float32)
     chans = x.shape[0]
     f2 = 1 if np.ndim(w2) == 2 else w2.shape[2]
     r2 = (f2 - 1) // 2
-    e1, e2, wh, wl = host_tables(model)
+    e1, e2, wh, wl = host_tables(model) if tables is None else tables
+    if defect == "w_lo":
+        wl = np.zeros_like(wl)
+    elif defect == "w_lo_one_tap":
+        wl = wl.copy()
+        wl[:, :, 0, 0] = 0
 
     def pad(t, r):
         return t if r == 0 else F.pad(t, (r,) * 4, mode="replicate" if padding == "replicate" else "constant")
@@ -127,10 +143,17 @@ def split_model(x, model, padding, terms):
     a_hi = rtz_f16(a)
     a_lo = (a - a_hi.astype(np.float32)).astype(np.float16)
     assert (a_lo >= 0).all() and np.isfinite(a_lo).all()
+    if defect == "a_lo":
+        a_lo = np.zeros_like(a_lo)
+    elif defect == "a_lo_one_k_step":
+        a_lo = a_lo.copy()
+        a_lo[[l2h_channel(1, h, e) for h in range(2) for e in range(8)]] = 0
     conv = lambda act, w: F.conv2d(pad(t64(act.astype(np.float64))[None], r2), t64(w))[0].numpy()
     acc = conv(a_hi, wh)
     if terms == 3:
-        acc = acc + conv(a_hi, wl) + conv(a_lo, wh)
+        # (1 or 0 per column: the intact model multiplies by 1, which changes no bit)
+        keep = np.where(np.arange(x.shape[2]) % 64 >= 32, 0.0, 1.0) if defect == "lo_right_unit" else np.ones(x.shape[2])
+        acc = acc + conv(a_hi, wl) * keep + conv(a_lo, wh) * keep
     m2 = np.maximum(acc.astype(np.float32).astype(np.float64) * 2.0 ** -(e1 + e2) + np.asarray(b2, np.float64)[:, None, None], 0)
     pre = F.conv2d(pad(t32(m2)[None], 2), t32(w3.reshape(chans, 32, 5, 5)), t32(np.atleast_1d(np.asarray(b3, np.float32))))
     return pre[0].numpy().astype(np.float64)

@@ -1,6 +1,9 @@
 """SRCNN_MODE_BANDED16 on the GPU: every whole model on the banded path with layer 2 in split f16 (spatial_l2h_kernel), held to the
 tolerance of SRCNN_MODE_MFMA against the float64 restatements; an error at the float32 level; exact structure (batches, frames,
-the pipeline, one-hot taps, mode switches); and the refusals."""
+the pipeline, one-hot taps, mode switches); and the refusals.
+
+The tight numerical bound of the mode (and of SRCNN_MODE_MFMA's banded kernels) is in tests/test_gpu_banded_error_level.py: every
+kernel form at the tile bounds of the three kernels, within 4 x the error of a plain float32 evaluation (tests/error_level.py)."""
 import numpy as np
 import pytest
 import torch

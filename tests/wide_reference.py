@@ -9,8 +9,8 @@ import torch
 import torch.nn.functional as F
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+def _t(a, dtype=torch.float64):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
 
 
 def _conv(x, w, b, padding):
@@ -25,13 +25,14 @@ def padded_widths(n1, n2):
     return 64 * ((n1 + 63) // 64), 32 * ((n2 + 31) // 32)
 
 
-def forward(x, model, padding="replicate"):
-    """x [C, h, w] -> the values before truncation, [C, h, w] float64."""
+def forward(x, model, padding="replicate", dtype=torch.float64):
+    """x [C, h, w] -> the values before truncation, [C, h, w], evaluated by torch on the CPU in `dtype` (float64: the reference;
+    float32: the yardstick of tests/error_level.py) and returned in it."""
     w1, b1, w2, b2, w3, b3 = model
-    t = _t(np.asarray(x, np.float64))[None]
-    t = F.relu(_conv(t, _t(w1), _t(b1), padding))
-    t = F.relu(_conv(t, _t(w2), _t(b2), padding))
-    return _conv(t, _t(w3), _t(b3), padding)[0].numpy()
+    t = _t(np.asarray(x), dtype)[None]
+    t = F.relu(_conv(t, _t(w1, dtype), _t(b1, dtype), padding))
+    t = F.relu(_conv(t, _t(w2, dtype), _t(b2, dtype), padding))
+    return _conv(t, _t(w3, dtype), _t(b3, dtype), padding)[0].numpy()
 
 
 def forward_rows(x, model, r0, r1, padding="replicate"):
