@@ -608,6 +608,64 @@ int srcnn_resize_cubic_aa_f32(srcnn_ctx *ctx, const float *src, size_t src_strid
 int srcnn_resize_cubic_aa_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
                                     const srcnn_image *dst, int dst_w, int dst_h, int channels, int n_frames);
 
+/* Pillow's resize of uint8 images, byte for byte: Image.resize(size, Image.BILINEAR or Image.BICUBIC) of a uint8 picture, the
+ * resize behind the training pairs and the test inputs of the PyTorch SRCNN scripts.  It is not one of the float resizes
+ * rounded at the end: it runs on integer coefficients with 22 fractional bits and rounds and saturates to uint8 after the
+ * horizontal pass and again after the vertical one.  Pillow's Resample.c defines the result; where this text and Pillow
+ * disagree, Pillow wins.
+ *   - Arithmetic, per axis with s source and n output samples and S = 1 (bilinear) or 2 (bicubic); everything in float64 on the
+ *     host, in exactly this order of operations, nothing contracted ((int) truncates toward zero):
+ *         scale = s / n;   fs = scale < 1 ? 1 : scale;   support = S * fs;
+ *         for output d:   center = (d + 0.5) * scale
+ *                         xmin = (int)(center - support + 0.5);   if xmin < 0: xmin = 0
+ *                         xmax = (int)(center + support + 0.5);   if xmax > s: xmax = s;   count = xmax - xmin
+ *                         w_j = k((j + xmin - center + 0.5) * (1 / fs)),   j = 0 .. count - 1
+ *                         ww = ((w_0 + w_1) + w_2) + ...;   if ww != 0: w_j = w_j / ww
+ *                         c_j = w_j < 0 ? (int)(-0.5 + w_j * 4194304) : (int)(0.5 + w_j * 4194304)        (4194304 = 2^22)
+ *         bicubic, a = -0.5:   x = |x|;   x < 1: ((a + 2) * x - (a + 3)) * x * x + 1;   x < 2: (((x - 5) * x + 8) * x - 4) * a;   else 0
+ *         bilinear:            x = |x|;   x < 1: 1 - x;   else 0
+ *     (the operations of srcnn_cubic_aa_f32_taps up to w_j / ww, but for the multiplication by 1 / fs; new is the integer c_j).
+ *   - A pass, for every output sample, in int32:
+ *         acc = 1 << 21;   acc += (int)src[xmin + j] * c_j for j ascending;   out = min(max(acc >> 22, 0), 255)   (arithmetic shift)
+ *     No index is clamped: xmin >= 0 and xmin + count <= s by construction.  sum |c_j| of an output sample stays below 2^23 (at
+ *     most 1.27 * 2^22 over every geometry tried), so |acc| <= 2^21 + 255 (2^23 - 1) < 2^31; tables beyond that bound are refused.
+ *   - Two passes: the horizontal one first, into a UINT8 intermediate of src_h x dst_w; the vertical one reads it.  A pass whose
+ *     axis keeps its length is skipped, the bytes go through untouched; the same size on both axes is a copy.  Channels are
+ *     independent: an RGB picture is three planes with the same tables.
+ *   - srcnn_pil_taps: the table of one axis, host only (no context, no GPU), with the conventions of srcnn_cubic_aa_f32_taps:
+ *     returns the largest count; coef == NULL sizes the table; first[d] = xmin, count[d], coef[d * max_taps + j] = c_j, zero for
+ *     j >= count[d].  SRCNN_ERR_INVALID for sizes <= 0, an unknown filter, a null first or count beside a coef, max_taps below
+ *     the largest count.  It gives the table of an axis that keeps its length too (which the resize skips).  Lanczos, Hamming and
+ *     box are out of scope: Lanczos coefficients go through sin(), so a bitwise claim would rest on the host's libm.
+ *   - srcnn_resize_pil_image_dev: src and dst are SRCNN_ELEM_U8 descriptors under the address rule of every image call (any
+ *     px_step, stride, ch_pitch and frame_pitch: H x W x C pixels are read and written where they lie); their scale is ignored.
+ *     Any sizes, up, down or the same; channels >= 1; needs no model, runs in every mode, asynchronous on the context's stream.
+ *     SRCNN_ERR_INVALID for what srcnn_resize_cubic_aa_image_dev refuses, a descriptor that is not U8, an unknown filter, a
+ *     destination that overlaps the source.
+ *   - Two kernel forms give the same bytes.  Up to a ratio of 4 per axis (and 17 taps) -- every up-scale -- one launch keeps a
+ *     tile's rounded horizontal results in on-chip memory as bytes; beyond it a horizontal launch writes a uint8 plane of src_h x
+ *     dst_w per channel and frame into a workspace the context owns (grown on demand, freed with it) and a vertical launch
+ *     reads it.  The tables of one geometry and filter are cached in the context and rebuilt when either changes.
+ *   - srcnn_process_pil_image_dev: the resize of the loaded model's channels (1 or 3) into a planar uint8 image of the context
+ *     that carries src->scale, then srcnn_forward_image_dev from that image into dst (any element kind): it equals the two calls
+ *     made separately, bit for bit.  Gate: that of srcnn_process_image_dev, a U8 source, a known filter, and no shrinking.
+ *   - srcnn_process_rgb_pil_image_dev: the same resize of 3 channels, then srcnn_process_rgb_image_dev at the same size on the
+ *     result; equals those two calls bit for bit.  Gate and refusals: those of srcnn_process_rgb_image_dev, a U8 source, a known
+ *     filter.
+ *   - A refused call launches nothing and leaves the context usable.
+ *   Out of scope: Pillow's "F" and 16-bit modes, box= and reducing_gap=, Lanczos, Hamming, box and nearest, Pillow's colour
+ *   conversions, row stripes and several GPUs, host-memory forms, the command-line tool. */
+enum { SRCNN_PIL_BILINEAR = 2, SRCNN_PIL_BICUBIC = 3 };      /* Pillow's own numbers (Image.Resampling) */
+int srcnn_pil_taps(int src_n, int dst_n, int filter, int *first /*[dst_n]*/, int *count /*[dst_n]*/,
+                   int32_t *coef /*[dst_n][max_taps] or NULL*/, int max_taps);
+int srcnn_resize_pil_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                               const srcnn_image *dst, int dst_w, int dst_h, int channels, int n_frames, int filter);
+int srcnn_process_pil_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                                const srcnn_image *dst, int dst_w, int dst_h, int n_frames, int filter);
+int srcnn_process_rgb_pil_image_dev(srcnn_ctx *ctx, const srcnn_image *src, int src_w, int src_h,
+                                    const srcnn_image *dst, int dst_w, int dst_h,
+                                    const float luma[4], const float *clamp /* NULL or {lo, hi} */, int n_frames, int filter);
+
 /* Full-reference quality metrics: the measurement at the end of an evaluation.  The sum of squared errors (for PSNR) and the
  * Gaussian-window SSIM of Wang et al. 2004 between two images as they are stored, on the channel planes or on a luma, with a
  * border shaved off -- raw sums per frame, on the device, deterministic to the bit.

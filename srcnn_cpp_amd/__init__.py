@@ -38,6 +38,7 @@ __all__ = [
     "cubic_f32_taps", "cubic_aa_f32_taps", "luma_gain", "luma_for_order", "luma_bt601_studio", "LUMA_BT601",
     "ELEM_F32", "ELEM_F16", "ELEM_BF16", "ELEM_U8", "ELEM_SIZE", "Image", "image_check",
     "ChromaGrid", "chroma_grid", "chroma_taps",
+    "PIL_BILINEAR", "PIL_BICUBIC", "pil_taps",
 ]
 
 _PKG = Path(__file__).resolve().parent
@@ -69,6 +70,9 @@ LUMA_BT601 = (0.299, 0.587, 0.114, 0.0)
 # element kinds of an Image (SRCNN_ELEM_*) and their sizes in bytes
 ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = 0, 1, 2, 3
 ELEM_SIZE = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
+# the filters of Pillow's resize (SRCNN_PIL_*: Pillow's own numbers, Image.Resampling) and the names the torch methods take
+PIL_BILINEAR, PIL_BICUBIC = 2, 3
+PIL_FILTERS = {"bilinear": PIL_BILINEAR, "bicubic": PIL_BICUBIC}
 # what metrics_image_dev measures (SRCNN_METRIC_*): flags, and the fields of one result
 METRIC_SSE, METRIC_SSIM = 1, 2
 METRIC_FIELDS = ("sse", "n_px", "ssim_sum", "n_win")
@@ -171,6 +175,10 @@ def load_library() -> C.CDLL:
         "srcnn_resize_cubic_aa_f32": ([vp, _f32p, sz, sz, i, i, _f32p, sz, sz, i, i, i], i),
         "srcnn_resize_cubic_aa_f32_dev": ([vp, vp, sz, sz, sz, i, i, vp, sz, sz, sz, i, i, i, i], i),
         "srcnn_resize_cubic_aa_image_dev": ([vp, imp, i, i, imp, i, i, i, i], i),
+        "srcnn_pil_taps": ([i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_int32), i], i),
+        "srcnn_resize_pil_image_dev": ([vp, imp, i, i, imp, i, i, i, i, i], i),
+        "srcnn_process_pil_image_dev": ([vp, imp, i, i, imp, i, i, i, i], i),
+        "srcnn_process_rgb_pil_image_dev": ([vp, imp, i, i, imp, i, i, _f32p, _f32p, i, i], i),
         "srcnn_metrics_image_dev": ([vp, imp, imp, i, i, i, i, i, _f32p, C.c_double, i, vp], i),
         "srcnn_metric_psnr": ([C.c_double, C.c_double, C.c_double], C.c_double),
         "srcnn_msssim_image_dev": ([vp, imp, imp, i, i, i, i, i, _f32p, C.c_double, i, vp], i),
@@ -270,6 +278,7 @@ ABI_SYMBOLS = (
     "srcnn_chroma_taps",
     "srcnn_cubic_aa_f32_taps", "srcnn_resize_cubic_aa_f32", "srcnn_resize_cubic_aa_f32_dev", "srcnn_resize_cubic_aa_image_dev",
     "srcnn_metrics_image_dev", "srcnn_metric_psnr", "srcnn_msssim_image_dev", "srcnn_metric_msssim",
+    "srcnn_pil_taps", "srcnn_resize_pil_image_dev", "srcnn_process_pil_image_dev", "srcnn_process_rgb_pil_image_dev",
     "srcnn_model_halo_rows", "srcnn_model_rows_dev", "srcnn_model_rows_halo_dev", "srcnn_model_striped", "srcnn_model_striped_dev",
     "srcnn_model_color_rows_dev", "srcnn_model_color_rows_halo_dev", "srcnn_model_color_striped", "srcnn_model_color_striped_dev",
     "srcnn_model_rows_f32_dev", "srcnn_model_rows_halo_f32_dev", "srcnn_model_striped_f32", "srcnn_model_striped_f32_dev",
@@ -823,6 +832,26 @@ class Context:
         self._check(self._lib.srcnn_resize_cubic_aa_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w,
                                                               dst_h, channels, n_frames))
 
+    def resize_pil_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, channels, n_frames=1, filter=PIL_BICUBIC):
+        """srcnn_resize_pil_image_dev: Pillow's Image.resize of uint8 pictures, byte for byte (filter: PIL_BILINEAR or
+        PIL_BICUBIC), on two ELEM_U8 images where they lie; any sizes, no model needed, asynchronous on the context's stream."""
+        self._check(self._lib.srcnn_resize_pil_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
+                                                         channels, n_frames, int(filter)))
+
+    def process_pil_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, n_frames=1, filter=PIL_BICUBIC):
+        """srcnn_process_pil_image_dev: resize_pil_image_dev of the model's channels into a uint8 image of the context that
+        carries src's scale, then forward_image_dev from it into dst (any element kind); never shrinks."""
+        self._check(self._lib.srcnn_process_pil_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w, dst_h,
+                                                          n_frames, int(filter)))
+
+    def process_rgb_pil_image_dev(self, src: "Image", src_w, src_h, dst: "Image", dst_w, dst_h, luma=LUMA_BT601, clamp=None,
+                                  n_frames=1, filter=PIL_BICUBIC):
+        """srcnn_process_rgb_pil_image_dev: resize_pil_image_dev of 3 channels, then process_rgb_image_dev at the same size."""
+        _not_shrinking(src_w, src_h, dst_w, dst_h)
+        luma4, clamp2 = _luma4(luma), _clamp2(clamp)
+        self._check(self._lib.srcnn_process_rgb_pil_image_dev(self._h, C.byref(src.c()), src_w, src_h, C.byref(dst.c()), dst_w,
+                                                              dst_h, luma4, clamp2, n_frames, int(filter)))
+
     def metrics_image_dev(self, a: "Image", b: "Image", width, height, channels, n_frames, border, luma, data_range, flags, d_out):
         """srcnn_metrics_image_dev: {sse, n_px, ssim_sum, n_win} per (frame, result) of two stored images, float64 after the
         load, into device memory at d_out (n_frames * P * 4 doubles; P = 1 with a luma, else channels).  luma: None or
@@ -1327,6 +1356,28 @@ def cubic_aa_f32_taps(src_n: int, dst_n: int):
     rc = lib.srcnn_cubic_aa_f32_taps(int(src_n), int(dst_n), first.ctypes.data_as(ip), count.ctypes.data_as(ip), _fp(coef), k)
     if rc != k:
         raise SrcnnError(rc, "cubic_aa_f32_taps")
+    return first, count, coef
+
+
+def pil_taps(src_n: int, dst_n: int, filter: int = PIL_BICUBIC):
+    """Pillow's table of one axis for uint8 pictures (srcnn_pil_taps; host only, needs no GPU): (first, count, coef) with
+    first[d] the first source sample of output d, count[d] its tap count and coef[d, :count[d]] its int32 coefficients with 22
+    fractional bits, zero beyond; coef has as many columns as the largest count.  filter: PIL_BILINEAR or PIL_BICUBIC."""
+    if src_n <= 0 or dst_n <= 0:
+        raise ValueError(f"pil_taps: sizes {src_n} -> {dst_n} (both must be positive)")
+    if filter not in (PIL_BILINEAR, PIL_BICUBIC):
+        raise ValueError(f"pil_taps: filter {filter!r}: expected PIL_BILINEAR (2) or PIL_BICUBIC (3)")
+    lib = load_library()
+    k = lib.srcnn_pil_taps(int(src_n), int(dst_n), int(filter), None, None, None, 0)
+    if k <= 0:
+        raise SrcnnError(k, "pil_taps")
+    first, count = np.empty(dst_n, np.int32), np.empty(dst_n, np.int32)
+    coef = np.empty((dst_n, k), np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = lib.srcnn_pil_taps(int(src_n), int(dst_n), int(filter), first.ctypes.data_as(ip), count.ctypes.data_as(ip),
+                            coef.ctypes.data_as(C.POINTER(C.c_int32)), k)
+    if rc != k:
+        raise SrcnnError(rc, "pil_taps")
     return first, count, coef
 
 

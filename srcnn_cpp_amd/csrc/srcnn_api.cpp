@@ -132,7 +132,8 @@ void srcnn_destroy(srcnn_ctx *c)
     for (DevBuf *b : {&c->wfrag, &c->wraw, &c->in_u8, &c->out_u8, &c->pre_f32, &c->planes, &c->plane1, &c->kern, &c->sink,
                       &c->bgr_in, &c->bgr_out, &c->ycc_lo, &c->ycc_hi, &c->y_sr, &c->tables, &c->wfrag16,
                       &c->band_top, &c->band_bot, &c->stripe_ext, &c->sp_table, &c->sp16_table, &c->sp_map64, &c->sp_map32,
-                      &c->f32_tables, &c->f32_lo, &c->f32_hi, &c->f32_work, &c->aa_tables, &c->aa_work, &c->metric_work, &c->msssim_work})
+                      &c->f32_tables, &c->f32_lo, &c->f32_hi, &c->f32_work, &c->aa_tables, &c->aa_work, &c->metric_work, &c->msssim_work,
+                      &c->pil_tables, &c->pil_work, &c->pil_image})
         release(*b);
     if (c->sp_done) (void)hipEventDestroy(c->sp_done);
     for (int k = 0; k < srcnn_ctx::kHaloSets; ++k) {

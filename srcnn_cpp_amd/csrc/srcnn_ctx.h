@@ -248,6 +248,13 @@ struct srcnn_ctx {
     srcnn::host::DevBuf aa_tables, aa_work;
     int atab_sw = 0, atab_sh = 0, atab_dw = 0, atab_dh = 0, atab_kx = 0, atab_ky = 0;
     hipStream_t aa_stream = nullptr;
+    // Pillow's resize of uint8 images (srcnn_resize_pil_image_dev): a cache slot of its own -- the int32 tables of one geometry
+    // and filter with their largest tap counts and the rows a tile spans, the byte workspace of the general form (n_planes x
+    // src_h x dst_w, grown on demand), the planar uint8 image the process calls resize into (srcnn_process_pil_image_dev), and
+    // the stream of the last launch that used any of them (ensure_tables_pil, resample_pil_dev)
+    srcnn::host::DevBuf pil_tables, pil_work, pil_image;
+    int ptab_sw = 0, ptab_sh = 0, ptab_dw = 0, ptab_dh = 0, ptab_filter = 0, ptab_kx = 0, ptab_ky = 0, ptab_span = 0;
+    hipStream_t pil_stream = nullptr;
     // The metrics (srcnn_metrics_image_dev): the per-workgroup partial sums of one call (grown on demand) and the stream of the
     // last launch that wrote them
     srcnn::host::DevBuf metric_work;
@@ -528,6 +535,9 @@ int ensure_tables_f32(srcnn_ctx *c, int sw, int sh, int dw, int dh, ResizeTables
 // the largest count of the axis; coef null: that and nothing else; else first[d], count[d], coef[d * max_taps + j] (zero beyond
 // count[d]), SRCNN_ERR_INVALID for max_taps below the largest count.  (The device tables and the launch: srcnn_image.h.)
 int cubic_aa_f32_taps(int n_src, int n_dst, int *first, int *count, float *coef, int max_taps);
+// Pillow's table of one axis for uint8 pictures (also srcnn_pil_taps): the same conventions, int32 coefficients with 22
+// fractional bits; filter: SRCNN_PIL_BILINEAR or SRCNN_PIL_BICUBIC (checked by the caller)
+int pil_taps(int n_src, int n_dst, int filter, int *first, int *count, int32_t *coef, int max_taps);
 
 // ---- srcnn_host.cpp ----
 void cubic_table(int n_src, int n_dst, int *ofs, short *coef);

@@ -407,6 +407,86 @@ int srcnn_process_rgb_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w,
     return process_rgb_frames_dev(c, s, src_w, src_h, d, dst_w, dst_h, luma, g, clamp, n_frames);
 }
 
+/* ---- Pillow's resize of uint8 images (tables and launch: resample_pil_dev of srcnn_resize_f32.cpp) ---- */
+static bool pil_filter_known(int filter) { return filter == SRCNN_PIL_BILINEAR || filter == SRCNN_PIL_BICUBIC; }
+static const char *const kPilBytes = "Pillow's resize works on the bytes of SRCNN_ELEM_U8 images";
+static const char *const kPilFilter = "expected SRCNN_PIL_BILINEAR (2) or SRCNN_PIL_BICUBIC (3)";
+
+int srcnn_resize_pil_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w, int dst_h,
+                               int channels, int n_frames, int filter)
+{
+    BIND(c);
+    int rc;
+    const char *what = "resize_pil_image_dev";
+    // the scale of a descriptor is not read: the check sees a valid one in its place
+    srcnn_image s8{}, d8{};
+    if (src) { s8 = *src; s8.scale = 1.f; }
+    if (dst) { d8 = *dst; d8.scale = 1.f; }
+    if ((rc = images_refusal(c, what, src ? &s8 : nullptr, src_w, src_h, dst ? &d8 : nullptr, dst_w, dst_h, channels, n_frames))) return rc;
+    if (s8.elem != SRCNN_ELEM_U8 || d8.elem != SRCNN_ELEM_U8)
+        return fail(c, SRCNN_ERR_INVALID, "%s: elem %d -> %d: %s", what, s8.elem, d8.elem, kPilBytes);
+    if (!pil_filter_known(filter)) return fail(c, SRCNN_ERR_INVALID, "%s: filter %d: %s", what, filter, kPilFilter);
+    return resample_pil_dev(c, image_ref(&s8, src_w, src_h, channels, n_frames), src_w, src_h,
+                            image_ref(&d8, dst_w, dst_h, channels, n_frames), dst_w, dst_h, channels, n_frames, filter);
+}
+
+// what the two process calls ask of the source beyond their counterparts' gates; then the resize into the context's planar
+// uint8 image, which carries the source's scale: *mid describes it
+static int pil_front_refusal(srcnn_ctx *c, const char *what, const srcnn_image *src, int src_w, int src_h, int dst_w, int dst_h, int filter)
+{
+    if (src->elem != SRCNN_ELEM_U8) return fail(c, SRCNN_ERR_INVALID, "%s: source elem %d: %s", what, src->elem, kPilBytes);
+    if (!pil_filter_known(filter)) return fail(c, SRCNN_ERR_INVALID, "%s: filter %d: %s", what, filter, kPilFilter);
+    if (dst_w < src_w || dst_h < src_h)
+        return fail(c, SRCNN_ERR_INVALID, "%s: %d x %d -> %d x %d shrinks the image (a super-resolution call resizes up or not at all)",
+                    what, src_w, src_h, dst_w, dst_h);
+    return SRCNN_OK;
+}
+static int pil_front_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, int dst_w, int dst_h, int channels, int n_frames,
+                         int filter, srcnn_image *mid)
+{
+    int rc;
+    void *p = nullptr;
+    if ((rc = pil_workspace_image(c, dst_w, dst_h, channels, n_frames, &p))) return rc;
+    const size_t plane = (size_t)dst_w * dst_h;
+    *mid = srcnn_image{p, SRCNN_ELEM_U8, src->scale, 1, (size_t)dst_w, plane, (size_t)channels * plane};
+    return resample_pil_dev(c, image_ref(src, src_w, src_h, channels, n_frames), src_w, src_h,
+                            image_ref(mid, dst_w, dst_h, channels, n_frames), dst_w, dst_h, channels, n_frames, filter);
+}
+
+int srcnn_process_pil_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w, int dst_h,
+                                int n_frames, int filter)
+{
+    BIND(c);
+    int rc;
+    const char *what = "process_pil_image_dev";
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    const int C = c->channels;
+    if ((rc = images_refusal(c, what, src, src_w, src_h, dst, dst_w, dst_h, C, n_frames))) return rc;
+    if ((rc = pil_front_refusal(c, what, src, src_w, src_h, dst_w, dst_h, filter))) return rc;
+    if ((rc = forward_f32_refusal(c))) return rc;      // the gate of srcnn_forward_f32, before anything is launched
+    srcnn_image mid;
+    if ((rc = pil_front_dev(c, src, src_w, src_h, dst_w, dst_h, C, n_frames, filter, &mid))) return rc;
+    return srcnn_forward_image_dev(c, &mid, dst, dst_w, dst_h, n_frames);
+}
+
+int srcnn_process_rgb_pil_image_dev(srcnn_ctx *c, const srcnn_image *src, int src_w, int src_h, const srcnn_image *dst, int dst_w,
+                                    int dst_h, const float *luma, const float *clamp, int n_frames, int filter)
+{
+    BIND(c);
+    int rc;
+    const char *what = "process_rgb_pil_image_dev";
+    if (!has_model(c)) return fail(c, SRCNN_ERR_STATE, "%s", kNoModel);
+    if ((rc = images_refusal(c, what, src, src_w, src_h, dst, dst_w, dst_h, 3, n_frames))) return rc;
+    float g = 0.f;
+    if ((rc = process_rgb_refusal(c, what, "srcnn_process_pil_image_dev runs on the three channels", src_w, src_h, dst_w, dst_h, luma,
+                                  clamp, &g)))
+        return rc;
+    if ((rc = pil_front_refusal(c, what, src, src_w, src_h, dst_w, dst_h, filter))) return rc;
+    srcnn_image mid;
+    if ((rc = pil_front_dev(c, src, src_w, src_h, dst_w, dst_h, 3, n_frames, filter, &mid))) return rc;
+    return srcnn_process_rgb_image_dev(c, &mid, dst_w, dst_h, dst, dst_w, dst_h, luma, clamp, n_frames);
+}
+
 /* ---- full-reference metrics: {sse, n_px, ssim_sum, n_win} per (frame, result), float64 after the load (srcnn_metrics.hip) ---- */
 int srcnn_metrics_image_dev(srcnn_ctx *c, const srcnn_image *a, const srcnn_image *b, int width, int height, int channels,
                             int n_frames, int border, const float *luma, double data_range, int flags, double *d_out)

@@ -94,6 +94,41 @@ struct ResampleAaTables {
 hipError_t launch_resample_aa(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
                               const ResampleAaTables &t, int variant, float *work, hipStream_t st);
 
+// ---- Pillow's resize of uint8 images (srcnn_resize_pil_image_dev; include/srcnn_amd.h has the arithmetic) -------------------
+// The antialiased resize's two forms on integers, the same bytes from both.  tiled: one launch; a workgroup of 256 threads
+// produces PIL_TR output rows x PIL_TC columns, the ROUNDED horizontal results of the source rows the tile spans stay in LDS as
+// bytes (hbuf[PIL_RMAX][PIL_TC] = 5,120 bytes).  general: two launches of PIL_HC threads per workgroup, the horizontal pass
+// into a uint8 workspace of sh x dw per plane, the vertical pass out of it -- any ratio and any tap count.
+constexpr int PIL_TR = 16;        // output rows per workgroup (tiled form)
+constexpr int PIL_TC = 64;        // output columns per workgroup (tiled form): one per lane of a wave
+constexpr int PIL_HC = 256;       // output columns per workgroup (general form, both launches)
+constexpr int PIL_RATIO = 4;      // the tiled form takes source sizes up to PIL_RATIO x the destination's, per axis
+constexpr int PIL_KMAX = 17;      // ... and tables of at most this many taps per output sample
+constexpr int PIL_RMAX = PIL_RATIO * (PIL_TR - 1) + 1 + PIL_KMAX + 2;      // source rows a tile may span: 80
+constexpr int PIL_BITS = 22;      // fractional bits of a coefficient
+constexpr long PIL_COEF_SUM_MAX = (1L << 23) - 1;      // sum |c_j| of one output sample: 24-bit products, an int32 sum
+enum { RESAMPLE_PIL_GENERAL = 0, RESAMPLE_PIL_TILED = 1 };
+// The tables of one geometry and filter on the device (srcnn_pil_taps per axis; the identity for an axis that keeps its length).
+// xcoef is TAP-major, [kx][dw]; ycoef is [dh][ky].  tile_span: the most source rows a tile of PIL_TR output rows reads, walked
+// over yfirst / ycount on the host when the tables were made (INT_MAX where yfirst is not ascending).
+struct ResamplePilTables {
+    const int *xfirst, *xcount, *yfirst, *ycount;
+    const int *xcoef, *ycoef;
+    int kx, ky, tile_span;
+};
+// Which form runs a geometry with these tables: the tiled one inside the antialiased tiled form's range, and only where the
+// TABLES keep every tile inside hbuf
+inline int resample_pil_variant(int sw, int sh, int dw, int dh, const ResamplePilTables &t)
+{
+    if ((long)sw > (long)PIL_RATIO * dw || (long)sh > (long)PIL_RATIO * dh || t.kx > PIL_KMAX || t.ky > PIL_KMAX) return RESAMPLE_PIL_GENERAL;
+    return t.tile_span > 0 && t.tile_span <= PIL_RMAX ? RESAMPLE_PIL_TILED : RESAMPLE_PIL_GENERAL;
+}
+// Both descriptors ELEM_U8 (their scale is not read).  variant: resample_pil_variant(), or RESAMPLE_PIL_GENERAL for any
+// geometry; work: sh * dw bytes per plane (general form only).  hipErrorInvalidValue for RESAMPLE_PIL_TILED with tables whose
+// tile_span does not fit hbuf.
+hipError_t launch_resample_pil(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
+                               const ResamplePilTables &t, int variant, uint8_t *work, hipStream_t st);
+
 // ---- full-reference metrics (srcnn_metrics_image_dev; include/srcnn_amd.h has the semantics): srcnn_metrics.hip -------------
 // Everything after the load is float64.  Three kernels, no floating-point atomic: metric_sse_kernel and metric_ssim_kernel write
 // one partial sum per workgroup into a workspace, metric_finish_kernel adds the partials of a plane in a fixed order and writes
@@ -194,6 +229,14 @@ int process_rgb_frames_dev(srcnn_ctx *c, const ImageRef &src, int src_w, int src
 // The launch behind every antialiased resize (srcnn_resize_f32.cpp): checked arguments, device memory, the context's stream;
 // tables cached per geometry, the form chosen by resample_aa_variant(), the general form's workspace grown on demand.
 int resample_aa_dev(srcnn_ctx *c, const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames);
+// The launch behind every Pillow resize (srcnn_resize_f32.cpp): checked arguments, two ELEM_U8 descriptors in device memory, a
+// known filter, the context's stream; tables cached per geometry and filter, the form chosen by resample_pil_variant(), the
+// general form's byte workspace grown on demand.
+int resample_pil_dev(srcnn_ctx *c, const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
+                     int filter);
+// The context's planar uint8 image of `channels` x n_frames planes of width x height (srcnn_process_pil_image_dev and
+// srcnn_process_rgb_pil_image_dev resize into it), grown on demand
+int pil_workspace_image(srcnn_ctx *c, int width, int height, int channels, int n_frames, void **data);
 }  // namespace host
 
 }  // namespace srcnn

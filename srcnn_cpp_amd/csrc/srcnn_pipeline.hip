@@ -1417,4 +1417,153 @@ hipError_t launch_resample_aa(const ImageRef &src, int sw, int sh, const ImageRe
     return hipGetLastError();
 }
 
+// ---- Pillow's resize of uint8 images (srcnn_resize_pil_image_dev): resample_pil_* kernels -----------------------------------
+// The resample_aa_* kernels' shape on integers.  Per axis a table gives every output sample its first source sample, its tap
+// count and its int32 coefficients with PIL_BITS fractional bits (srcnn_pil_taps; an axis that keeps its length has the identity
+// table, one tap of 1 << PIL_BITS, which returns the byte untouched: (b << 22 + (1 << 21)) >> 22 = b).  A pass computes
+// acc = 1 << 21, acc += byte * c_j for j ascending, out = min(max(acc >> 22, 0), 255): a uint8 after the horizontal pass (in LDS
+// or in the workspace) and again after the vertical one.  The host has checked sum |c_j| < 2^23 for every output sample of the
+// tables it hands over, so every |c_j| fits the signed 24-bit multiply and |acc| <= 2^21 + 255 (2^23 - 1) < 2^31.
+// Both sides are SRCNN_ELEM_U8 descriptors whose scale is not read; lanes, loads and the tap-major x table are resample_aa's.
+struct PilArgs {
+    ImageRef src, dst;
+    int sw, sh, dw, dh, channels, n_planes;
+    ResamplePilTables t;
+    uint8_t *work;      // general form: n_planes x sh x dw bytes
+};
+
+__device__ __forceinline__ int pil_clip8(int acc) { return min(max(acc >> PIL_BITS, 0), 255); }
+constexpr int kPilHalf = 1 << (PIL_BITS - 1);
+
+// Horizontal pass of a tile: source rows [r_lo, r_lo + nrow) of the plane at element offset s, output column dxc (the lane's,
+// clamped to the plane) -> hbuf[row][lane], a byte.  Wave w takes rows w, w + 4, ...; four of them share a coefficient load.
+__device__ __forceinline__ void pil_tile_hpass(uint8_t (*hbuf)[PIL_TC], const PilArgs &a, long s, int r_lo, int nrow, int dxc)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint8_t *p = static_cast<const uint8_t *>(a.src.data);
+    const int cnt = a.t.xcount[dxc];
+    const int *coef = a.t.xcoef + dxc;
+    const long col = s + (long)a.t.xfirst[dxc] * a.src.px_step;
+    for (int r0 = w; r0 < nrow; r0 += 16) {
+        long row[4];
+        int acc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            row[k] = col + (long)min(r_lo + r0 + 4 * k, a.sh - 1) * a.src.stride;      // (rows beyond the tile: computed, not kept)
+            acc[k] = kPilHalf;
+        }
+        for (int j = 0; j < cnt; ++j) {
+            const int cj = coef[(long)j * a.dw];
+            const long o = (long)j * a.src.px_step;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] += __mul24((int)p[row[k] + o], cj);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (r0 + 4 * k < nrow) hbuf[r0 + 4 * k][lane] = (uint8_t)pil_clip8(acc[k]);
+    }
+}
+
+// Vertical pass of a tile: output rows [dy0, dy1), wave w takes dy0 + w, dy0 + w + 4, ...; column dx of the plane at element
+// offset d of the destination
+__device__ __forceinline__ void pil_tile_vpass(const uint8_t (*hbuf)[PIL_TC], const PilArgs &a, long d, int dy0, int dy1, int r_lo, int dx)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint8_t *q = static_cast<uint8_t *>(a.dst.data);
+    for (int dy = dy0 + w; dy < dy1; dy += 4) {
+        const int j0 = a.t.yfirst[dy] - r_lo, cnt = a.t.ycount[dy];
+        const int *coef = a.t.ycoef + (long)dy * a.t.ky;
+        int acc = kPilHalf;
+        for (int j = 0; j < cnt; ++j) acc += __mul24((int)hbuf[j0 + j][lane], coef[j]);
+        if (dx < a.dw) q[d + (long)dy * a.dst.stride + (long)dx * a.dst.px_step] = (uint8_t)pil_clip8(acc);
+    }
+}
+
+__global__ __launch_bounds__(256) void resample_pil_tiled_kernel(const PilArgs a)
+{
+    __shared__ uint8_t hbuf[PIL_RMAX][PIL_TC];
+    const int dx = blockIdx.x * PIL_TC + (threadIdx.x & 63);
+    const int dxc = min(dx, a.dw - 1);
+    const int n_row_tiles = (a.dh + PIL_TR - 1) / PIL_TR;
+    for (int z = blockIdx.z; z < a.n_planes; z += gridDim.z) {
+        const int frame = z / a.channels, ch = z - frame * a.channels;
+        const long s = frame * a.src.frame_pitch + ch * a.src.ch_pitch;
+        const long d = frame * a.dst.frame_pitch + ch * a.dst.ch_pitch;
+        for (int rt = blockIdx.y; rt < n_row_tiles; rt += gridDim.y) {
+            const int dy0 = rt * PIL_TR, dy1 = min(dy0 + PIL_TR, a.dh);
+            const int r_lo = a.t.yfirst[dy0];
+            const int nrow = a.t.yfirst[dy1 - 1] + a.t.ycount[dy1 - 1] - r_lo;      // <= t.tile_span <= PIL_RMAX: launch_resample_pil()
+            pil_tile_hpass(hbuf, a, s, r_lo, nrow, dxc);
+            __syncthreads();
+            pil_tile_vpass(hbuf, a, d, dy0, dy1, r_lo, dx);
+            __syncthreads();      // the next tile's horizontal pass overwrites what this vertical pass reads
+        }
+    }
+}
+
+// General form, first launch: the horizontal pass of every source row into the byte workspace (thread = output column)
+__global__ __launch_bounds__(PIL_HC) void resample_pil_h_kernel(const PilArgs a)
+{
+    const int dx = blockIdx.x * PIL_HC + threadIdx.x;
+    if (dx >= a.dw) return;
+    const uint8_t *p = static_cast<const uint8_t *>(a.src.data);
+    const int cnt = a.t.xcount[dx];
+    const int *coef = a.t.xcoef + dx;
+    const long col = (long)a.t.xfirst[dx] * a.src.px_step;
+    for (int z = blockIdx.z; z < a.n_planes; z += gridDim.z) {
+        const int frame = z / a.channels, ch = z - frame * a.channels;
+        const long s = frame * a.src.frame_pitch + ch * a.src.ch_pitch + col;
+        uint8_t *o = a.work + (long)z * a.sh * a.dw + dx;
+        for (int y = blockIdx.y; y < a.sh; y += gridDim.y) {
+            const long row = s + (long)y * a.src.stride;
+            int acc = kPilHalf;
+            for (int j = 0; j < cnt; ++j) acc += __mul24((int)p[row + (long)j * a.src.px_step], coef[(long)j * a.dw]);
+            o[(long)y * a.dw] = (uint8_t)pil_clip8(acc);
+        }
+    }
+}
+
+// ... second launch: the vertical pass out of the workspace (thread = output column, a block's row is blockIdx.y's)
+__global__ __launch_bounds__(PIL_HC) void resample_pil_v_kernel(const PilArgs a)
+{
+    const int dx = blockIdx.x * PIL_HC + threadIdx.x;
+    if (dx >= a.dw) return;
+    uint8_t *q = static_cast<uint8_t *>(a.dst.data);
+    for (int z = blockIdx.z; z < a.n_planes; z += gridDim.z) {
+        const int frame = z / a.channels, ch = z - frame * a.channels;
+        const uint8_t *h = a.work + (long)z * a.sh * a.dw + dx;
+        const long d = frame * a.dst.frame_pitch + ch * a.dst.ch_pitch + (long)dx * a.dst.px_step;
+        for (int dy = blockIdx.y; dy < a.dh; dy += gridDim.y) {
+            const int cnt = a.t.ycount[dy];
+            const int *coef = a.t.ycoef + (long)dy * a.t.ky;
+            const uint8_t *r = h + (long)a.t.yfirst[dy] * a.dw;
+            int acc = kPilHalf;
+            for (int j = 0; j < cnt; ++j) acc += __mul24((int)r[(long)j * a.dw], coef[j]);
+            q[d + (long)dy * a.dst.stride] = (uint8_t)pil_clip8(acc);
+        }
+    }
+}
+
+hipError_t launch_resample_pil(const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
+                               const ResamplePilTables &t, int variant, uint8_t *work, hipStream_t st)
+{
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels <= 0 || n_frames <= 0 || (long)channels * n_frames > 0x7fffffffL ||
+        t.kx <= 0 || t.ky <= 0 || src.elem != ELEM_U8 || dst.elem != ELEM_U8)
+        return hipErrorInvalidValue;
+    const PilArgs a{src, dst, sw, sh, dw, dh, channels, channels * n_frames, t, work};
+    const unsigned gz = grid_cap(a.n_planes);
+    if (variant == RESAMPLE_PIL_TILED) {
+        // the rows a tile spans, as the tables themselves have them (t.tile_span: the host's walk over yfirst / ycount)
+        if (t.tile_span <= 0 || t.tile_span > PIL_RMAX) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(resample_pil_tiled_kernel, dim3((dw + PIL_TC - 1) / PIL_TC, grid_cap((dh + PIL_TR - 1) / PIL_TR), gz),
+                           dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
+    if (!work) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resample_pil_h_kernel, dim3((dw + PIL_HC - 1) / PIL_HC, grid_cap(sh), gz), dim3(PIL_HC), 0, st, a);
+    hipLaunchKernelGGL(resample_pil_v_kernel, dim3((dw + PIL_HC - 1) / PIL_HC, grid_cap(dh), gz), dim3(PIL_HC), 0, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace srcnn

@@ -6,8 +6,12 @@
 // srcnn_*_image_dev calls run (srcnn_image.cpp; launchers and kernels: srcnn_image.h, srcnn_pipeline.hip).
 // The antialiased down-scaling resize lives here too (srcnn_cubic_aa_f32_taps, srcnn_resize_cubic_aa_f32*, and resample_aa_dev,
 // the launch srcnn_resize_cubic_aa_image_dev shares): its tables have a tap count per output sample; kernels resample_aa_*.
+// And Pillow's resize of uint8 images (srcnn_pil_taps, and resample_pil_dev, the launch behind srcnn_resize_pil_image_dev and
+// the two process calls of srcnn_image.cpp): the same tables with int32 coefficients of 22 fractional bits; kernels resample_pil_*.
 #include "srcnn_ctx.h"
 #include "srcnn_image.h"
+
+#include <climits>
 
 using namespace srcnn;
 using namespace srcnn::host;
@@ -206,6 +210,186 @@ int resample_aa_dev(srcnn_ctx *c, const ImageRef &src, int sw, int sh, const Ima
     return SRCNN_OK;
 }
 
+// ---- Pillow's resize of uint8 images (srcnn_pil_taps, resample_pil_dev; include/srcnn_amd.h has the arithmetic) ----
+// the filter of Pillow's Resample.c: bilinear (support 1) or bicubic with a = -0.5 (support 2), the operations as written there
+static double pil_filter(int filter, double x)
+{
+    x = std::fabs(x);
+    if (filter == SRCNN_PIL_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+    const double a = -0.5;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+// One axis of Image.resize on a uint8 picture (precompute_coeffs and normalize_coeffs_8bpc), float64 in the header's order, each
+// coefficient an int32 with PIL_BITS fractional bits.  The conventions of cubic_aa_f32_taps.
+int pil_taps(int n_src, int n_dst, int filter, int *first, int *count, int32_t *coef, int max_taps)
+{
+    const double scale = (double)n_src / (double)n_dst, fs = scale < 1.0 ? 1.0 : scale;
+    const double support = (filter == SRCNN_PIL_BILINEAR ? 1.0 : 2.0) * fs, ss = 1.0 / fs;
+    int kmax = 0;
+    for (int d = 0; d < n_dst; ++d) {
+        int xmin, cnt;
+        aa_span((d + 0.5) * scale, support, n_src, &xmin, &cnt);
+        kmax = std::max(kmax, cnt);
+    }
+    if (!coef) return kmax;
+    if (max_taps < kmax) return SRCNN_ERR_INVALID;
+    std::vector<double> w((size_t)kmax);
+    for (int d = 0; d < n_dst; ++d) {
+        const double center = (d + 0.5) * scale;
+        int xmin, cnt;
+        aa_span(center, support, n_src, &xmin, &cnt);
+        double ww = 0.0;
+        for (int j = 0; j < cnt; ++j) {
+            w[(size_t)j] = pil_filter(filter, ((double)(j + xmin) - center + 0.5) * ss);
+            ww += w[(size_t)j];
+        }
+        int32_t *row = coef + (size_t)d * (size_t)max_taps;
+        for (int j = 0; j < max_taps; ++j) {
+            if (j >= cnt) { row[j] = 0; continue; }
+            const double v = ww != 0.0 ? w[(size_t)j] / ww : w[(size_t)j];
+            row[j] = v < 0.0 ? (int32_t)(-0.5 + v * (double)(1 << PIL_BITS)) : (int32_t)(0.5 + v * (double)(1 << PIL_BITS));
+        }
+        first[d] = xmin;
+        count[d] = cnt;
+    }
+    return kmax;
+}
+
+// The table of one axis as the kernels take it: the identity (one tap of 1 << PIL_BITS, which returns the byte untouched) where
+// the axis keeps its length -- Pillow skips that pass -- and pil_taps otherwise.  False where an output sample's sum |c_j|
+// exceeds PIL_COEF_SUM_MAX (no geometry found does: DESIGN.md 4.22), which the kernels' 24-bit products and int32 sums rest on.
+static bool pil_axis(int n_src, int n_dst, int filter, std::vector<int> *first, std::vector<int> *count, std::vector<int32_t> *coef,
+                     int *k)
+{
+    first->assign((size_t)n_dst, 0);
+    count->assign((size_t)n_dst, 1);
+    if (n_src == n_dst) {
+        *k = 1;
+        coef->assign((size_t)n_dst, 1 << PIL_BITS);
+        for (int d = 0; d < n_dst; ++d) (*first)[(size_t)d] = d;
+        return true;
+    }
+    *k = pil_taps(n_src, n_dst, filter, nullptr, nullptr, nullptr, 0);
+    coef->assign((size_t)*k * n_dst, 0);
+    pil_taps(n_src, n_dst, filter, first->data(), count->data(), coef->data(), *k);
+    for (int d = 0; d < n_dst; ++d) {
+        long sum = 0;
+        for (int j = 0; j < *k; ++j) sum += std::labs((long)(*coef)[(size_t)d * *k + j]);
+        if (sum > PIL_COEF_SUM_MAX) return false;
+    }
+    return true;
+}
+
+// The most source rows a tile of PIL_TR output rows reads, from the tables themselves: rows yfirst[dy0] .. max(yfirst + ycount) - 1
+static int pil_tile_span(const std::vector<int> &yfirst, const std::vector<int> &ycount)
+{
+    const int dh = (int)yfirst.size();
+    long span = 0;
+    for (int dy0 = 0; dy0 < dh; dy0 += PIL_TR) {
+        const int dy1 = std::min(dy0 + PIL_TR, dh);
+        long end = 0;
+        for (int dy = dy0; dy < dy1; ++dy) {
+            if (yfirst[(size_t)dy] < yfirst[(size_t)dy0] || ycount[(size_t)dy] <= 0) return INT_MAX;
+            end = std::max(end, (long)yfirst[(size_t)dy] + ycount[(size_t)dy]);
+        }
+        // (the kernel takes the tile's end from its last row: the two must agree)
+        if (end != (long)yfirst[(size_t)dy1 - 1] + ycount[(size_t)dy1 - 1]) return INT_MAX;
+        span = std::max(span, end - yfirst[(size_t)dy0]);
+    }
+    return span > INT_MAX ? INT_MAX : (int)span;
+}
+
+// The Pillow tables of a (sw x sh) -> (dw x dh) resize with `filter` on the device, a cache slot of their own.  Layout, all
+// int32: xcoef[kx][dw] (tap-major), ycoef[dh][ky], xfirst[dw], xcount[dw], yfirst[dh], ycount[dh].
+static int ensure_tables_pil(srcnn_ctx *c, int sw, int sh, int dw, int dh, int filter, ResamplePilTables *t)
+{
+    if (!(c->pil_tables.p && c->ptab_sw == sw && c->ptab_sh == sh && c->ptab_dw == dw && c->ptab_dh == dh && c->ptab_filter == filter)) {
+        std::vector<int> xfirst, xcount, yfirst, ycount;
+        std::vector<int32_t> xrows, ycoef;
+        int kx = 0, ky = 0;
+        if (!pil_axis(sw, dw, filter, &xfirst, &xcount, &xrows, &kx) || !pil_axis(sh, dh, filter, &yfirst, &ycount, &ycoef, &ky))
+            return fail(c, SRCNN_ERR_INVALID, "Pillow resize %d x %d -> %d x %d: a coefficient sum leaves the int32 accumulator's range",
+                        sw, sh, dw, dh);
+        const size_t nx = (size_t)kx * dw, ny = (size_t)ky * dh;
+        std::vector<int32_t> all(nx + ny + 2 * ((size_t)dw + dh));
+        for (int d = 0; d < dw; ++d)
+            for (int j = 0; j < kx; ++j) all[(size_t)j * dw + d] = xrows[(size_t)d * kx + j];
+        std::copy(ycoef.begin(), ycoef.end(), all.begin() + nx);
+        int32_t *ints = all.data() + nx + ny;
+        std::copy(xfirst.begin(), xfirst.end(), ints);
+        std::copy(xcount.begin(), xcount.end(), ints + dw);
+        std::copy(yfirst.begin(), yfirst.end(), ints + 2 * (size_t)dw);
+        std::copy(ycount.begin(), ycount.end(), ints + 2 * (size_t)dw + dh);
+        // an earlier launch on this stream may still read the old tables (one on another stream: resample_pil_dev has waited)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->ptab_sw = 0;
+        int rc;
+        if ((rc = reserve(c, c->pil_tables, all.size() * 4))) return rc;
+        HIP_TRY(c, hipMemcpy(c->pil_tables.p, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+        c->ptab_sw = sw; c->ptab_sh = sh; c->ptab_dw = dw; c->ptab_dh = dh; c->ptab_filter = filter;
+        c->ptab_kx = kx; c->ptab_ky = ky; c->ptab_span = pil_tile_span(yfirst, ycount);
+    }
+    const size_t nx = (size_t)c->ptab_kx * dw, ny = (size_t)c->ptab_ky * dh;
+    t->xcoef = static_cast<const int *>(c->pil_tables.p);
+    t->ycoef = t->xcoef + nx;
+    t->xfirst = t->ycoef + ny;
+    t->xcount = t->xfirst + dw;
+    t->yfirst = t->xcount + dw;
+    t->ycount = t->yfirst + dh;
+    t->kx = c->ptab_kx;
+    t->ky = c->ptab_ky;
+    t->tile_span = c->ptab_span;
+    return SRCNN_OK;
+}
+
+#ifdef SRCNN_TUNING_BUILD
+static int g_pil_force_general = 0, g_pil_last_form = -1;      // srcnn_debug_resample_pil_form / _last_form
+#endif
+
+int resample_pil_dev(srcnn_ctx *c, const ImageRef &src, int sw, int sh, const ImageRef &dst, int dw, int dh, int channels, int n_frames,
+                     int filter)
+{
+    ResamplePilTables t;
+    int rc;
+    // tables and workspace were last used on another stream: that work ends before this call replaces or overwrites them
+    if (c->pil_stream && c->pil_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->pil_stream));
+    if ((rc = ensure_tables_pil(c, sw, sh, dw, dh, filter, &t))) return rc;
+    int variant = resample_pil_variant(sw, sh, dw, dh, t);
+#ifdef SRCNN_TUNING_BUILD
+    if (g_pil_force_general) variant = RESAMPLE_PIL_GENERAL;
+    g_pil_last_form = variant;
+#endif
+    uint8_t *work = nullptr;
+    if (variant == RESAMPLE_PIL_GENERAL) {
+        const unsigned __int128 bytes = (unsigned __int128)channels * n_frames * (size_t)sh * (size_t)dw;
+        if (bytes > ((unsigned __int128)1 << 46))
+            return fail(c, SRCNN_ERR_NOMEM, "Pillow resize: the workspace of the two-launch form (%d planes of %d x %d bytes) is too large",
+                        channels * n_frames, dw, sh);
+        if ((rc = reserve(c, c->pil_work, (size_t)bytes))) return rc;      // (growing waits for the device)
+        work = static_cast<uint8_t *>(c->pil_work.p);
+    }
+    c->pil_stream = c->stream;
+    HIP_TRY(c, launch_resample_pil(src, sw, sh, dst, dw, dh, channels, n_frames, t, variant, work, c->stream));
+    return SRCNN_OK;
+}
+
+int pil_workspace_image(srcnn_ctx *c, int width, int height, int channels, int n_frames, void **data)
+{
+    const unsigned __int128 bytes = (unsigned __int128)channels * n_frames * (size_t)width * (size_t)height;
+    if (bytes > ((unsigned __int128)1 << 46))
+        return fail(c, SRCNN_ERR_NOMEM, "Pillow resize: the resized image (%d planes of %d x %d bytes) is too large", channels * n_frames,
+                    width, height);
+    // the image was last read on another stream: that work ends before this call overwrites it
+    if (c->pil_stream && c->pil_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->pil_stream));
+    int rc;
+    if ((rc = reserve(c, c->pil_image, (size_t)bytes))) return rc;      // (growing waits for the device)
+    *data = c->pil_image.p;
+    return SRCNN_OK;
+}
+
 }  // namespace host
 }  // namespace srcnn
 
@@ -323,6 +507,14 @@ int srcnn_cubic_aa_f32_taps(int src_n, int dst_n, int *first, int *count, float 
     if (!coef) return cubic_aa_f32_taps(src_n, dst_n, nullptr, nullptr, nullptr, 0);
     if (!first || !count) return SRCNN_ERR_INVALID;
     return cubic_aa_f32_taps(src_n, dst_n, first, count, coef, max_taps);
+}
+
+int srcnn_pil_taps(int src_n, int dst_n, int filter, int *first, int *count, int32_t *coef, int max_taps)
+{
+    if (src_n <= 0 || dst_n <= 0 || (filter != SRCNN_PIL_BILINEAR && filter != SRCNN_PIL_BICUBIC)) return SRCNN_ERR_INVALID;
+    if (!coef) return pil_taps(src_n, dst_n, filter, nullptr, nullptr, nullptr, 0);
+    if (!first || !count) return SRCNN_ERR_INVALID;
+    return pil_taps(src_n, dst_n, filter, first, count, coef, max_taps);
 }
 
 int srcnn_resize_cubic_aa_f32_dev(srcnn_ctx *c, const float *d_src, size_t src_stride, size_t src_ch_pitch, size_t src_frame_pitch,
@@ -444,6 +636,24 @@ int srcnn_debug_resample_aa_limits(int *out5)
     if (!out5) return SRCNN_ERR_INVALID;
     const int v[5] = {AA_TR, AA_TC, AA_RATIO, AA_KMAX, AA_RMAX};
     for (int k = 0; k < 5; ++k) out5[k] = v[k];
+    return SRCNN_OK;
+}
+
+/* ... and of Pillow's resize, the same three: _form (0: the general form for every later call, else the library's choice),
+ * _last_form (1 tiled, 0 general, -1 none yet), _limits: PIL_TR, PIL_TC, PIL_HC, PIL_RATIO, PIL_KMAX, PIL_RMAX. */
+int srcnn_debug_resample_pil_form(int form)
+{
+    g_pil_force_general = form == 0;
+    return SRCNN_OK;
+}
+
+int srcnn_debug_resample_pil_last_form(void) { return g_pil_last_form; }
+
+int srcnn_debug_resample_pil_limits(int *out6)
+{
+    if (!out6) return SRCNN_ERR_INVALID;
+    const int v[6] = {PIL_TR, PIL_TC, PIL_HC, PIL_RATIO, PIL_KMAX, PIL_RMAX};
+    for (int k = 0; k < 6; ++k) out6[k] = v[k];
     return SRCNN_OK;
 }
 #endif  /* SRCNN_TUNING_BUILD */

@@ -296,6 +296,64 @@ class CompiledModule:
         return self._image_call(x, 3, target, out_dtype, out_channels_last, in_scale, out_scale,
                                 lambda *a: self.ctx.process_rgb_image_dev(*a[:-1], luma, clamp, a[-1]), check)
 
+    # ---- Pillow's resize of uint8 tensors, byte for byte ----
+    @staticmethod
+    def _pil_filter(name, x, filter):
+        """The SRCNN_PIL_* number of filter ("bilinear" or "bicubic"); TypeError for a tensor that is not uint8"""
+        import torch
+        from . import PIL_FILTERS
+        if isinstance(x, torch.Tensor) and x.dtype != torch.uint8:
+            raise TypeError(f"{name} takes a uint8 tensor, as Pillow's Image.resize takes an 8-bit picture; this one is {x.dtype}: "
+                            "a float tensor is resized by resize(..., antialias=True)")
+        if not isinstance(filter, str) or filter not in PIL_FILTERS:
+            raise ValueError(f"filter {filter!r}: expected one of {sorted(PIL_FILTERS)}")
+        return PIL_FILTERS[filter]
+
+    def resize_pil(self, x, size, filter="bicubic"):
+        """Image.resize((W, H), Image.BICUBIC or Image.BILINEAR) of Pillow on a uint8 tensor, byte for byte: the picture a
+        Pillow-based training or test script makes, up, down or at the same size.  x: uint8 (N, C, H, W) or (C, H, W) on the
+        module's GPU with any number of channels and any positive strides (channels_last, a permuted H x W x C view), read
+        where it lies; size = (H, W).  Returns uint8 in the same memory format.  Runs on the current stream."""
+        import torch
+        f = self._pil_filter("resize_pil", x, filter)
+        if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4):
+            raise ValueError(f"expected a uint8 tensor of shape (N, C, H, W) or (C, H, W), got {getattr(x, 'shape', type(x).__name__)}")
+        channels = int(x.shape[-3])
+        dh, dw = check_size(size)
+        return self._image_call(x, channels, lambda h, w: (dh, dw), None, None, None, None,
+                                lambda s, w, h, d, dw, dh, n: self.ctx.resize_pil_image_dev(s, w, h, d, dw, dh, channels, n, f))
+
+    def upscale_pil(self, x, scale=None, size=None, filter="bicubic", out_dtype=None, out_channels_last=None, in_scale=None,
+                    out_scale=None):
+        """The module on Pillow's resize of a uint8 tensor: forward_image(resize_pil(x, size, filter)) in one call, bit for
+        bit -- what a script does that builds its input with Image.resize and ToTensor.  x: uint8 with the module's channels;
+        the resized bytes are read as byte * in_scale (default 1 / 255); out_dtype (default uint8), out_channels_last and
+        out_scale as forward_image takes them.  Never shrinks."""
+        f = self._pil_filter("upscale_pil", x, filter)
+
+        def check(h, w, dh, dw):
+            if dh < h or dw < w:
+                raise ValueError(f"size {(dh, dw)} is smaller than the tensor's {(h, w)}: upscale_pil resizes up or not at all")
+        return self._image_call(x, self.channels, self._target("upscale_pil", scale, size), out_dtype, out_channels_last, in_scale,
+                                out_scale, lambda *a: self.ctx.process_pil_image_dev(*a, f), check)
+
+    def upscale_rgb_pil(self, x, scale=None, size=None, luma=LUMA_BT601, clamp=None, out_dtype=None, out_channels_last=None,
+                        in_scale=None, out_scale=None, filter="bicubic"):
+        """upscale_rgb_image(resize_pil(x, size, filter), size=size) in one call, bit for bit: a 1-channel module on the luma of
+        a uint8 RGB tensor that Pillow's resize has brought to the target size.  The arguments of upscale_rgb_image, and filter."""
+        f = self._pil_filter("upscale_rgb_pil", x, filter)
+        if self.channels != 1:
+            raise ValueError(f"upscale_rgb_pil runs a 1-channel module on the luma of the tensor: this module has {self.channels} "
+                             "channels (upscale_pil runs it on the channels themselves)")
+        target = self._target("upscale_rgb_pil", scale, size)
+
+        def check(h, w, dh, dw):
+            if dh < h or dw < w:
+                raise ValueError(f"size {(dh, dw)} is smaller than the tensor's {(h, w)}: upscale_rgb_pil resizes up or not at all")
+            _luma4(luma), _clamp2(clamp)
+        return self._image_call(x, 3, target, out_dtype, out_channels_last, in_scale, out_scale,
+                                lambda *a: self.ctx.process_rgb_pil_image_dev(*a[:-1], luma, clamp, a[-1], f), check)
+
     # ---- full-reference metrics: the measurement at the end of an evaluation ----
     @staticmethod
     def _metric_args(a, b, border, luma, data_range, in_scale, early=None):
